@@ -41,7 +41,42 @@ def parse():
                     help="(internal) the probe job of choose_exchange(): two eager + two replayed steps with the stream-ordered RCCL exchange")
     ap.add_argument("--check-launch", action="store_true",
                     help="rendezvous + one all-reduce only (gloo when there is no GPU): tests the --gpus N self-launch path on CPU")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, a fixed sample of the updated weights, the running "
+                         "mIoU confusion matrix) as DIR/<name>.npy, for comparing two builds output for output")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_WEIGHT_SAMPLE = 1 << 22      # fp32 master weights written by --dump-outputs: 16 MB of the ~135 MB flat vector
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, trainer, losses):
+    """--dump-outputs: the arrays a caller of the timed step receives after its last call -- the per-output losses (float64), the fp32 master
+    weights the optimizer left behind (a fixed, seeded sample of the parameter elements, in the parameters' order, float32) and every running
+    mIoU confusion matrix (float64: the counts pass 2^24).  Same arguments -> same inputs, same indices: two builds compare array for array."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), np.array([float(v.detach()) for v in losses], dtype=np.float64))
+    store = trainer.store
+    offs = np.array([o for _, o, _ in store.segments], dtype=np.int64)
+    sizes = np.array([n for _, _, n in store.segments], dtype=np.int64)
+    starts = np.concatenate([[0], np.cumsum(sizes)[:-1]])
+    total = int(sizes.sum())
+    k = min(DUMP_WEIGHT_SAMPLE, total)
+    pos = np.sort(np.random.default_rng(DUMP_SEED).choice(total, size=k, replace=False)) if k < total else np.arange(total, dtype=np.int64)
+    seg = np.searchsorted(starts, pos, side="right") - 1
+    flat = torch.from_numpy(offs[seg] + pos - starts[seg]).to(store.flat_w.device)
+    np.save(os.path.join(out_dir, "weights_sample.npy"), store.flat_w[flat].cpu().numpy().astype(np.float32))
+    for i in range(len(losses)):
+        for j, m in enumerate(trainer._metrics_for(i)):
+            cm = getattr(getattr(m, "metric", m), "total_cm", None)
+            if cm is not None:
+                np.save(os.path.join(out_dir, f"confusion_matrix_output_{i + 1}_{j}.npy"), cm.cpu().numpy().astype(np.float64))
 
 
 def visible_gpu_count():
@@ -786,6 +821,8 @@ def main():
     loss_val = float(losses[0])
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, trainer, losses)
     ips = args.batch * world * args.steps / elapsed
     res = {
         "metric": "train_images_per_sec (ConvNeXt-T+ASPP 512x512 crop, fwd+bwd+AdamW, whole job)",

@@ -1,5 +1,5 @@
-import sys, traceback, collections, torch
-sys.path.insert(0, "/root/repo")
+import os, sys, traceback, collections, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 from iseg_amd import functional as F
 seen = collections.Counter()

@@ -1,7 +1,7 @@
 """the depthwise 7 x 7 forward / data-gradient / weight-gradient launches of the four ConvNeXt-T stages (16 images), a few launches each:
 run under tools/ktrace.sh (kernel-only times) or tools/ktraffic.sh (HBM-side bytes per launch)"""
 import os, sys, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from iseg_amd import kernels as K
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 5
 flush = os.environ.get("KB_FLUSH", "1") == "1"      # 0: back-to-back launches on cache-warm tensors

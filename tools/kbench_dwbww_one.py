@@ -1,5 +1,5 @@
 import os, sys, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from iseg_amd import kernels as K
 S, C = 128, 96
 x = torch.randn(16, S, S, C, device="cuda").to(torch.bfloat16)

@@ -1,6 +1,6 @@
 """LayerNorm forward / backward micro-benchmark at the four ConvNeXt-T stage shapes (16 images)"""
 import os, sys, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from iseg_amd import kernels as K
 def timeit(fn, n=20):
     for _ in range(3): fn()

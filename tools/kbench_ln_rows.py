@@ -1,6 +1,6 @@
 """LayerNorm backward / forward at growing row counts (fixed cost vs streaming rate); run under rocprofv3 --kernel-trace --stats for kernel-only times"""
 import os, sys, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from iseg_amd import kernels as K
 def timeit(fn, n=20):
     for _ in range(3): fn()
