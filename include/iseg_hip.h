@@ -257,6 +257,39 @@ int iseg_bn_relu_upsample_add(const void* z, const float* mean, const float* rst
 int iseg_rsqrt_eps(const float* var, float eps, float* out, int n, iseg_stream_t stream); /* inference: rstd of moving var */
 
 /* ---------------------------------------------------------------------------------------------------------
+ * EfficientNet MBConv tail (backbones/efficientnet.py:214-255): dwconv_bn -> swish -> squeeze-excite (mean over H*W, se_reduce,
+ * swish, se_expand, sigmoid) -> gate, on the depthwise output x [N, HW, C] (NHWC).  z = (x-mean)*rstd*gamma+beta, a = swish(z),
+ * m = mean_hw a [N, C], hpre = W1^T m + b1 [N, Cse], g = sigmoid(W2^T swish(hpre) + b2) [N, C], out = a*g; the un-gated a is never
+ * stored.  W1 [C, Cse], W2 [Cse, C] (Keras 1x1 kernels), biases and statistics fp32; x / out / dO / dx fp32 or bf16 (dtype).
+ * Training statistics: mean / rstd from iseg_bn_stats + (all-reduce) + iseg_bn_finalize; moving statistics: moving_mean and
+ * iseg_rsqrt_eps(moving_variance).  Partial sums go to caller-owned buffers and are summed in a fixed order (no float atomics).
+ *   fwd: iseg_bn_swish_se_squeeze (x -> partials) ; iseg_se_excite_fwd (partials -> m, hpre, g) ; iseg_bn_swish_gate_fwd (x, g -> out)
+ *   bwd: iseg_bn_swish_gate_bwd_reduce (dO, x -> partials of S1 = sum dO*a, S2 = sum dO*s', S3 = sum dO*s'*xhat, S4 = sum s',
+ *        S5 = sum s'*xhat per (n, c), s' = swish'(z), xhat = (x-mean)*rstd) ; iseg_se_excite_bwd (-> dW1, db1, dW2, db2 (accumulate
+ *        flag; any may be NULL), dmh = dm/HW [N, C], sums [2C] = (sum dz, sum dz*xhat) with dz = (dO*g + dmh)*s': iseg_bn_bwd_reduce's
+ *        message layout, (caller) all-reduce) ; iseg_bn_swish_gate_bwd_apply (dx = gamma*rstd*(dz - sums0*inv_n - xhat*sums1*inv_n) when
+ *        train, gamma*rstd*dz otherwise; dbeta += sums[0:C], dgamma += sums[C:2C] when non-NULL, only while sums are this replica's own).
+ * C % 8 == 0, any HW, any Cse >= 1, (C + Cse) * 4 <= 64 KiB, 16-byte aligned tensors; anything else returns ISEG_ERR_UNSUPPORTED.
+ * --------------------------------------------------------------------------------------------------------- */
+int iseg_mbconv_supported(int N, int HW, int C, int Cse);
+size_t iseg_mbconv_partials_bytes(int N, int HW, int C, int backward);
+size_t iseg_se_excite_bwd_workspace_bytes(int N, int C, int Cse);
+int iseg_bn_swish_se_squeeze(const void* x, const float* mean, const float* rstd, const float* gamma, const float* beta, float* partials,
+                             size_t partials_bytes, int N, int HW, int C, int dtype, iseg_stream_t stream);
+int iseg_se_excite_fwd(const float* partials, int N, int HW, int C, int Cse, const float* W1, const float* b1, const float* W2, const float* b2,
+                       float* m, float* hpre, float* g, iseg_stream_t stream);
+int iseg_bn_swish_gate_fwd(const void* x, const float* mean, const float* rstd, const float* gamma, const float* beta, const float* g, void* out,
+                           int N, int HW, int C, int dtype, iseg_stream_t stream);
+int iseg_bn_swish_gate_bwd_reduce(const void* dO, const void* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                                  float* partials, size_t partials_bytes, int N, int HW, int C, int dtype, iseg_stream_t stream);
+int iseg_se_excite_bwd(const float* partials, int N, int HW, int C, int Cse, const float* W1, const float* W2, const float* m, const float* hpre,
+                       const float* g, float* dW1, float* db1, float* dW2, float* db2, int accumulate, float* dmh, float* sums, void* ws,
+                       size_t ws_bytes, iseg_stream_t stream);
+int iseg_bn_swish_gate_bwd_apply(const void* dO, const void* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                                 const float* g, const float* dmh, const float* sums, float inv_n, int train, void* dx, float* dgamma,
+                                 float* dbeta, int N, int HW, int C, int dtype, iseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Exchange step of the data-parallel path: distribution/distribution_utils.py:158-169 all_reduce_values -> ReplicaContext.all_reduce(SUM)
  * (SyncBN statistics layers/keras3/bn.py:60-117, gradient sums), over RCCL on xGMI.  One process per GPU: rank 0 creates the 128-byte id
  * and hands it to the other ranks through the host program; every rank then calls iseg_comm_init.  iseg_allreduce_sum works in place and is

@@ -98,6 +98,15 @@ SIGNATURES = {
     "iseg_bn_bwd_apply_remask": (_i, [_p, _l, _p, _l, _p, _p, _p, _p, _p, _f, _p, _l, _p, _p, _l, _i, _i, _p]),
     "iseg_bn_relu_upsample_add": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "iseg_rsqrt_eps": (_i, [_p, _f, _p, _i, _p]),
+    "iseg_mbconv_supported": (_i, [_i, _i, _i, _i]),
+    "iseg_mbconv_partials_bytes": (_z, [_i, _i, _i, _i]),
+    "iseg_se_excite_bwd_workspace_bytes": (_z, [_i, _i, _i]),
+    "iseg_bn_swish_se_squeeze": (_i, [_p, _p, _p, _p, _p, _p, _z, _i, _i, _i, _i, _p]),
+    "iseg_se_excite_fwd": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "iseg_bn_swish_gate_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "iseg_bn_swish_gate_bwd_reduce": (_i, [_p, _p, _p, _p, _p, _p, _p, _z, _i, _i, _i, _i, _p]),
+    "iseg_se_excite_bwd": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p, _z, _p]),
+    "iseg_bn_swish_gate_bwd_apply": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _f, _i, _p, _p, _p, _i, _i, _i, _i, _p]),
     "iseg_cast": (_i, [_p, _i, _p, _i, _l, _p]),
     "iseg_deferred_begin": (_i, [_p, _z, _p, _z, _p]),
     "iseg_deferred_flush": (_i, [_p]),

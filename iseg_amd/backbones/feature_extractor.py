@@ -7,6 +7,8 @@ from .. import static_strings as ss
 from .backbone_registry import backbone_registry_dict
 from .convnext import build_dilated_convnext, convnext_large, convnext_tiny, convnext_xlarge, convnext_xxlarge
 from .convnext_v2 import convnext_v2_huge, convnext_v2_large, convnext_v2_nano, convnext_v2_tiny
+from .efficientnet import (EfficientNetB0, EfficientNetB1, EfficientNetB2, EfficientNetB3, EfficientNetB4, EfficientNetB5, EfficientNetB6,
+                           EfficientNetB7, EfficientNetL2, build_dilated_efficientnet)
 from .hrnet import HRNetW32, HRNetW48
 from .mobilenetv2_common import MobileNetV2, build_atrous_mobilenetv2
 from .resnet_common import apply_multi_grid, build_atrous_resnet, resnet50, resnet101, resnet152
@@ -22,6 +24,15 @@ def _builtin_backbones():
         ss.CONVNEXT_V2_TINY: convnext_v2_tiny,
         ss.CONVNEXT_V2_LARGE: convnext_v2_large,
         ss.CONVNEXT_V2_HUGE: convnext_v2_huge,
+        ss.EFFICIENTNETB0: EfficientNetB0,      # (feature_extractor.py:87-95)
+        ss.EFFICIENTNETB1: EfficientNetB1,
+        ss.EFFICIENTNETB2: EfficientNetB2,
+        ss.EFFICIENTNETB3: EfficientNetB3,
+        ss.EFFICIENTNETB4: EfficientNetB4,
+        ss.EFFICIENTNETB5: EfficientNetB5,
+        ss.EFFICIENTNETB6: EfficientNetB6,
+        ss.EFFICIENTNETB7: EfficientNetB7,
+        ss.EFFICIENTNETL2: EfficientNetL2,
         ss.MOBILENETV2: MobileNetV2,
         ss.HRNET_W48: HRNetW48,
         ss.HRNET_W32: HRNetW32,
@@ -54,6 +65,8 @@ def get_backbone(name=ss.RESNET50, custom_backbone_fn=None, output_stride=32, re
                  efficientnet_use_top=True, moat_use_pos_encoding=False):
     name = name.lower()
     general_kwargs = {"return_endpoints": return_endpoints}
+    if ss.EFFICIENTNET in name:      # :68-71
+        general_kwargs.update({"use_top": efficientnet_use_top})
     if ss.MOAT in name:      # :73-76
         general_kwargs.update({"use_pos_emb": moat_use_pos_encoding})
     if ss.RESNET in name:      # :58-66
@@ -70,6 +83,8 @@ def get_backbone(name=ss.RESNET50, custom_backbone_fn=None, output_stride=32, re
     if ss.RESNET in name:
         build_atrous_resnet(backbone, output_stride=output_stride)
         apply_multi_grid(backbone, block_index=-1, grids=resnet_multi_grids)
+    elif ss.EFFICIENTNET in name:      # :144-145
+        build_dilated_efficientnet(backbone, output_stride=output_stride)
     elif name == ss.MOBILENETV2:
         build_atrous_mobilenetv2(backbone, output_stride=output_stride)
     elif ss.CONVNEXT in name:

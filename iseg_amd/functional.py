@@ -850,6 +850,111 @@ def batch_norm(x, gamma, beta, moving_mean, moving_var, eps, momentum, training,
 
 
 # ---------------------------------------------------------------------------------------------------------
+# EfficientNet MBConv tail (backbones/efficientnet.py:214-255): (Sync)BN -> swish -> squeeze-excite -> gate as one tape node
+# (csrc/mbconv.hip).  The un-gated activation is never written; statistics and their all-reduce messages are _BatchNormTrainFn's.
+# ---------------------------------------------------------------------------------------------------------
+def _se_params(W1, b1, W2, b2):
+    C, Cse = W1.shape[-2], W1.shape[-1]
+    return W1.data.reshape(C, Cse), b1.data, W2.data.reshape(Cse, C), b2.data
+
+
+def _se_grads(W1, b1, W2, b2):
+    C, Cse = W1.shape[-2], W1.shape[-1]
+    return ((_grad(W1).reshape(C, Cse) if W1.requires_grad else None), (_grad(b1) if b1.requires_grad else None),
+            (_grad(W2).reshape(Cse, C) if W2.requires_grad else None), (_grad(b2) if b2.requires_grad else None))
+
+
+class _BnSwishSETrainFn(Function):
+    @staticmethod
+    def forward(ctx, x, gamma, beta, moving_mean, moving_var, W1, b1, W2, b2, eps, momentum, sync):
+        C = x.shape[-1]
+        xc = _c(x)
+        x2 = xc.reshape(-1, C)
+        packed = K.bn_stats(x2, C, x2.shape[0], C)
+        if sync:
+            dist.all_reduce_sum(packed)          # the packed [2C+1] statistics message of _BatchNormTrainFn
+        mean, rstd = K.bn_finalize(packed, C, eps, momentum, moving_mean, moving_var)
+        out, m, hpre, g = K.bn_swish_se_fwd(xc, mean, rstd, gamma.data, beta.data, *_se_params(W1, b1, W2, b2))
+        ctx.params, ctx.sync = (gamma, beta, W1, b1, W2, b2), sync
+        ctx.save_for_backward(xc, mean, rstd, m, hpre, g)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        xc, mean, rstd, m, hpre, g = ctx.saved_tensors
+        gamma, beta, W1, b1, W2, b2 = ctx.params
+        rows, C = xc.numel() // xc.shape[-1], xc.shape[-1]
+        dO = _c(dout)
+        W1d, _, W2d, _ = _se_params(W1, b1, W2, b2)
+        sums, dmh = K.bn_swish_se_bwd_sums(dO, xc, mean, rstd, gamma.data, beta.data, W1d, W2d, m, hpre, g, *_se_grads(W1, b1, W2, b2))
+        dist.grads_ready(W1, b1, W2, b2)
+        dbeta = _grad(beta) if beta.requires_grad else None
+        dgamma = _grad(gamma) if gamma.requires_grad else None
+        if ctx.sync and dist.active():
+            K.accumulate_pair(sums, C, dbeta, dgamma)
+            dist.grads_ready(gamma, beta)
+            sums = sums.clone()
+            dist.all_reduce_sum(sums)           # the [2C] sums message of _BatchNormTrainFn's backward
+            dx = K.bn_swish_gate_bwd_apply(dO, xc, mean, rstd, gamma.data, beta.data, g, dmh, sums, 1.0 / (rows * dist.world_size()), True)
+        else:
+            dx = K.bn_swish_gate_bwd_apply(dO, xc, mean, rstd, gamma.data, beta.data, g, dmh, sums, 1.0 / rows, True, dgamma=dgamma, dbeta=dbeta)
+            dist.grads_ready(gamma, beta)
+        return dx, None, None, None, None, None, None, None, None, None, None, None
+
+
+class _BnSwishSEInferFn(Function):
+    @staticmethod
+    def forward(ctx, x, gamma, beta, moving_mean, moving_var, W1, b1, W2, b2, eps):
+        xc = _c(x)
+        rstd = K.rsqrt_eps(moving_var, eps)
+        mean = moving_mean.clone()      # the backward reads the statistics of THIS call: a later training-mode call updates the buffer in place
+        out, m, hpre, g = K.bn_swish_se_fwd(xc, mean, rstd, gamma.data, beta.data, *_se_params(W1, b1, W2, b2))
+        ctx.params = (gamma, beta, W1, b1, W2, b2)
+        ctx.save_for_backward(xc, mean, rstd, m, hpre, g)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        xc, mean, rstd, m, hpre, g = ctx.saved_tensors
+        gamma, beta, W1, b1, W2, b2 = ctx.params
+        dO = _c(dout)
+        W1d, _, W2d, _ = _se_params(W1, b1, W2, b2)
+        sums, dmh = K.bn_swish_se_bwd_sums(dO, xc, mean, rstd, gamma.data, beta.data, W1d, W2d, m, hpre, g, *_se_grads(W1, b1, W2, b2))
+        dist.grads_ready(W1, b1, W2, b2)
+        dx = K.bn_swish_gate_bwd_apply(dO, xc, mean, rstd, gamma.data, beta.data, g, dmh, sums, 0.0, False,
+                                       dgamma=_grad(gamma) if gamma.requires_grad else None, dbeta=_grad(beta) if beta.requires_grad else None)
+        dist.grads_ready(gamma, beta)
+        return dx, None, None, None, None, None, None, None, None, None
+
+
+def mbconv_fused_enabled():
+    """ISEG_MBCONV_FUSED=0 routes the MBConv tail through the composed kernels (the A/B baseline)"""
+    return os.environ.get("ISEG_MBCONV_FUSED", "1") != "0"
+
+
+def bn_swish_se_supported(x, se_filters, *vectors):
+    """the shape rules of csrc/mbconv.hip, and the 16-byte alignment its vector accesses need: of x when it is passed as is (a non-contiguous
+    x is copied into a fresh, aligned buffer first) and of the per-channel vectors (gamma, beta, moving statistics) it reads directly"""
+    N, H, W, C = x.shape
+    if x.is_contiguous() and x.data_ptr() % 16:
+        return False
+    if any(v.data_ptr() % 16 or not v.is_contiguous() for v in vectors):
+        return False
+    return K.mbconv_supported(N, H * W, C, se_filters)
+
+
+def bn_swish_se(x, gamma, beta, moving_mean, moving_var, eps, momentum, training, W1, b1, W2, b2, sync=True):
+    """x * g with x <- swish(batch_norm(x)), g = sigmoid(conv1x1(swish(conv1x1(mean_hw x, W1, b1)), W2, b2)) per (sample, channel): the
+    MBConv tail as one tape node.  W1 [1, 1, C, Cse], W2 [1, 1, Cse, C] (Keras kernels).  Shapes bn_swish_se_supported refuses raise."""
+    _check_act_dtype(x)
+    if nn.dry_run():
+        return _dry(x.shape, x)
+    if training:
+        return _BnSwishSETrainFn.apply(x, gamma, beta, moving_mean, moving_var, W1, b1, W2, b2, float(eps), float(momentum), bool(sync))
+    return _BnSwishSEInferFn.apply(x, gamma, beta, moving_mean, moving_var, W1, b1, W2, b2, float(eps))
+
+
+# ---------------------------------------------------------------------------------------------------------
 # activations, add, dropout, drop-path
 # ---------------------------------------------------------------------------------------------------------
 class _ActFn(Function):

@@ -578,6 +578,62 @@ def rsqrt_eps(var, eps):
 
 
 # ---------------------------------------------------------------------------------------------------------
+# EfficientNet MBConv tail: BN -> swish -> squeeze-excite -> gate (csrc/mbconv.hip)
+# ---------------------------------------------------------------------------------------------------------
+def mbconv_supported(N, HW, Cc, Cse):
+    return bool(_hip.lib().iseg_mbconv_supported(int(N), int(HW), int(Cc), int(Cse)))
+
+
+def _mb_partials(N, HW, Cc, backward, device):
+    nbytes = _hip.lib().iseg_mbconv_partials_bytes(N, HW, Cc, int(backward))
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=device), nbytes
+
+
+def bn_swish_se_fwd(x, mean, rstd, gamma, beta, W1, b1, W2, b2):
+    """out = swish(bn(x)) * sigmoid(W2^T swish(W1^T mean_hw swish(bn(x)) + b1) + b2); x [N, H, W, C]; W1 [C, Cse], W2 [Cse, C] fp32.
+    Returns (out, m [N, C], hpre [N, Cse], g [N, C]) -- the last three are what the backward reads."""
+    _require_cuda(x, W1, W2)
+    N, H, W, Cc = x.shape
+    HW, Cse = H * W, W1.shape[-1]
+    part, pbytes = _mb_partials(N, HW, Cc, False, x.device)
+    _hip.call("iseg_bn_swish_se_squeeze", ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(part), pbytes, N, HW, Cc, dt(x), stream())
+    m = torch.empty((N, Cc), dtype=torch.float32, device=x.device)
+    hpre = torch.empty((N, Cse), dtype=torch.float32, device=x.device)
+    g = torch.empty((N, Cc), dtype=torch.float32, device=x.device)
+    _hip.call("iseg_se_excite_fwd", ptr(part), N, HW, Cc, Cse, ptr(W1), ptr(b1), ptr(W2), ptr(b2), ptr(m), ptr(hpre), ptr(g), stream())
+    out = torch.empty_like(x)
+    _hip.call("iseg_bn_swish_gate_fwd", ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(g), ptr(out), N, HW, Cc, dt(x), stream())
+    return out, m, hpre, g
+
+
+def bn_swish_se_bwd_sums(dO, x, mean, rstd, gamma, beta, W1, W2, m, hpre, g, dW1, db1, dW2, db2, accumulate=True):
+    """reduce pass + excite backward: books dW1 / db1 / dW2 / db2 ((+)=, None skipped); returns (sums [2C] = (sum dz, sum dz*xhat),
+    dmh [N, C] = dm / HW)"""
+    _require_cuda(dO, x)
+    N, H, W, Cc = x.shape
+    HW, Cse = H * W, W1.shape[-1]
+    part, pbytes = _mb_partials(N, HW, Cc, True, x.device)
+    _hip.call("iseg_bn_swish_gate_bwd_reduce", ptr(dO), ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(part), pbytes, N, HW, Cc, dt(x),
+              stream())
+    wsb = _hip.lib().iseg_se_excite_bwd_workspace_bytes(N, Cc, Cse)
+    ws = torch.empty(wsb // 4, dtype=torch.float32, device=x.device)
+    dmh = torch.empty((N, Cc), dtype=torch.float32, device=x.device)
+    sums = torch.empty(2 * Cc, dtype=torch.float32, device=x.device)
+    _hip.call("iseg_se_excite_bwd", ptr(part), N, HW, Cc, Cse, ptr(W1), ptr(W2), ptr(m), ptr(hpre), ptr(g), ptr(dW1), ptr(db1), ptr(dW2), ptr(db2),
+              int(accumulate), ptr(dmh), ptr(sums), ptr(ws), wsb, stream())
+    return sums, dmh
+
+
+def bn_swish_gate_bwd_apply(dO, x, mean, rstd, gamma, beta, g, dmh, sums, inv_n, train, dgamma=None, dbeta=None):
+    """dx of the tail; dgamma / dbeta (+)= the sums by the same launch -- only while `sums` are this replica's own"""
+    N, H, W, Cc = x.shape
+    dx = torch.empty_like(x)
+    _hip.call("iseg_bn_swish_gate_bwd_apply", ptr(dO), ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(g), ptr(dmh), ptr(sums),
+              float(inv_n), int(train), ptr(dx), ptr(dgamma), ptr(dbeta), N, H * W, Cc, dt(x), stream())
+    return dx
+
+
+# ---------------------------------------------------------------------------------------------------------
 # depthwise conv
 # ---------------------------------------------------------------------------------------------------------
 def dwconv2d(x, w, bias, K, dil, pad_t, pad_l, *, flip=False, add=None):
