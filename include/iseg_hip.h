@@ -290,6 +290,38 @@ int iseg_bn_swish_gate_bwd_apply(const void* dO, const void* x, const float* mea
                                  float* dbeta, int N, int HW, int C, int dtype, iseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Xception separable unit, activation=False (backbones/xception_common.py:14-78): relu -> DepthwiseConv2D(3, strides, dilation_rate,
+ * padding="same") -> BN -> Conv2D(filters, 1), the pointwise BN left to the SyncBN kernels.  x, z [N, H, W, C] / [N, Ho, Wo, C] NHWC fp32 or
+ * bf16 (dtype), w [9][C] fp32 (the Keras depthwise kernel), pointwise kernel W [Cin][Cout] fp32, statistics fp32.  With a = gamma*rstd and
+ * c = beta - a*mean the BN is folded into the GEMM: v = z (diag(a) W) + c^T W; relu(x) and the BN output are never written.
+ *   iseg_relu_dwconv3_stats   z = dw3x3(relu(x)); packed != NULL: iseg_bn_stats' message [sum z | sum z^2 | count] of the stored z, from
+ *                             fixed-order per-tile partials in ws (iseg_relu_dwconv3_stats_workspace_bytes); packed == NULL: z only
+ *   iseg_sepconv_fold         Wt [Cout][Cin] = (diag(a) W)^T and Wn [Cin][Cout] = diag(a) W in dtype (either may be NULL, not both), bias [Cout] = c^T W fp32
+ *   iseg_sepconv_fold_bwd     G = z^T dV [Cin][Cout] fp32, S = colsum(dV) [Cout]: dW += diag(a) G + c S^T (dW may be NULL);
+ *                             sums [2Cin] = [dbeta | dgamma], dbeta = W S, dgamma = rstd (rowsum(W o G) - mean dbeta): iseg_bn_bwd_reduce's
+ *                             layout, so the SyncBN all-reduce carries it; the same launch adds this replica's own sums into dgamma / dbeta
+ *                             when non-NULL (booked before that all-reduce, as _BatchNormTrainFn books them)
+ *   iseg_bnfold_dwconv3_relu_bwd  D = dV Wn^T [N, Ho, Wo, C] (dtype): dz = D + alpha + beta' z staged in LDS (train: the BN backward of the
+ *                             all-reduced sums with inv_n = 1 / global count; train == 0: dz = D); dx = [x > 0] dw3x3^T(dz),
+ *                             dw [9][C] += sum relu(x) dz per tap (fixed-order per-tile partials in ws).
+ * The two depthwise kernels stage a pixel tile plus its halo in LDS once per workgroup (relu(x) forward, dz backward) and read every tap there.
+ * K = 3, stride 1 or 2 (stride 2: dilation 1), dilation <= 8, C % 8 == 0, N <= 65535, 16-byte aligned activations and w; anything else
+ * returns ISEG_ERR_UNSUPPORTED.
+ * --------------------------------------------------------------------------------------------------------- */
+int iseg_sepconv_supported(int N, int H, int W, int C, int stride, int dil, int dtype);
+size_t iseg_relu_dwconv3_stats_workspace_bytes(int N, int H, int W, int C, int stride, int dil);
+int iseg_relu_dwconv3_stats(const void* x, const float* w, void* z, float* packed, int N, int H, int W, int C, int stride, int dil, int dtype,
+                            void* ws, size_t ws_bytes, iseg_stream_t stream);
+int iseg_sepconv_fold(const float* W, const float* mean, const float* rstd, const float* gamma, const float* beta, void* Wt, void* Wn, float* bias,
+                      int Cin, int Cout, int dtype, iseg_stream_t stream);
+int iseg_sepconv_fold_bwd(const float* G, const float* S, const float* W, const float* mean, const float* rstd, const float* gamma,
+                          const float* beta, float* dW, float* sums, float* dgamma, float* dbeta, int Cin, int Cout, iseg_stream_t stream);
+size_t iseg_bnfold_dwconv3_relu_bwd_workspace_bytes(int N, int H, int W, int C, int stride, int dil);
+int iseg_bnfold_dwconv3_relu_bwd(const void* D, const void* z, const void* x, const float* w, const float* mean, const float* rstd,
+                                 const float* gamma, const float* sums, float inv_n, int train, void* dx, float* dw, int N, int H, int W, int C,
+                                 int stride, int dil, int dtype, void* ws, size_t ws_bytes, iseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Exchange step of the data-parallel path: distribution/distribution_utils.py:158-169 all_reduce_values -> ReplicaContext.all_reduce(SUM)
  * (SyncBN statistics layers/keras3/bn.py:60-117, gradient sums), over RCCL on xGMI.  One process per GPU: rank 0 creates the 128-byte id
  * and hands it to the other ranks through the host program; every rank then calls iseg_comm_init.  iseg_allreduce_sum works in place and is

@@ -12,6 +12,7 @@ from .efficientnet import (EfficientNetB0, EfficientNetB1, EfficientNetB2, Effic
 from .hrnet import HRNetW32, HRNetW48
 from .mobilenetv2_common import MobileNetV2, build_atrous_mobilenetv2
 from .resnet_common import apply_multi_grid, build_atrous_resnet, resnet50, resnet101, resnet152
+from .xception import build_atrous_xception, xception65
 
 
 def _builtin_backbones():
@@ -33,6 +34,7 @@ def _builtin_backbones():
         ss.EFFICIENTNETB6: EfficientNetB6,
         ss.EFFICIENTNETB7: EfficientNetB7,
         ss.EFFICIENTNETL2: EfficientNetL2,
+        ss.XCEPTION65: xception65,      # (feature_extractor.py:86)
         ss.MOBILENETV2: MobileNetV2,
         ss.HRNET_W48: HRNetW48,
         ss.HRNET_W32: HRNetW32,
@@ -83,6 +85,8 @@ def get_backbone(name=ss.RESNET50, custom_backbone_fn=None, output_stride=32, re
     if ss.RESNET in name:
         build_atrous_resnet(backbone, output_stride=output_stride)
         apply_multi_grid(backbone, block_index=-1, grids=resnet_multi_grids)
+    elif ss.XCEPTION in name:      # :142-143
+        build_atrous_xception(backbone, output_stride=output_stride)
     elif ss.EFFICIENTNET in name:      # :144-145
         build_dilated_efficientnet(backbone, output_stride=output_stride)
     elif name == ss.MOBILENETV2:

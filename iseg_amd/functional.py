@@ -955,6 +955,131 @@ def bn_swish_se(x, gamma, beta, moving_mean, moving_var, eps, momentum, training
 
 
 # ---------------------------------------------------------------------------------------------------------
+# Xception separable unit, activation=False (backbones/xception_common.py:14-78): relu -> depthwise 3x3 -> (Sync)BN -> pointwise 1x1 as one
+# tape node (csrc/sepconv.hip).  The BN is folded into the pointwise GEMM (v = z diag(a) W + c^T W), so neither relu(x) nor the BN output is
+# written; the statistics and gradient-sum messages are _BatchNormTrainFn's, so the SyncBN all-reduces carry them unchanged.
+# ---------------------------------------------------------------------------------------------------------
+def _sepconv_pointwise(z2, pwk, mean, rstd, gamma, beta, need_grad):
+    """fold the BN into the pointwise kernel and run the GEMM; returns (v, Wn) -- Wn [Cin, Cout], the data gradient's operand, only when
+    need_grad (else None).  The forward reads the K-contiguous copy where the LDS-DMA GEMM takes the product (as _kcontig_kernel routes a 1x1
+    conv), else Wn; the fold writes only the layouts that will be read."""
+    Cin, Cout = pwk.shape[-2], pwk.shape[-1]
+    kcontig = (_FWD_KCONTIG and z2.dtype == torch.bfloat16 and Cin % 8 == 0 and Cin >= _DMA_MIN_K and Cout % 8 == 0 and Cout >= 64
+               and z2.shape[0] >= 64)
+    Wt, Wn, bias = K.sepconv_fold(pwk.data.reshape(Cin, Cout), mean, rstd, gamma.data, beta.data, z2.dtype, want_t=kcontig,
+                                  want_n=need_grad or not kcontig)
+    v = K.dense_fwd_t(z2, Wt, bias) if kcontig else K.dense_fwd(z2, Wn, bias)
+    return v, Wn
+
+
+def _sepconv_backward(ctx, dv, train, inv_n):
+    """wgrad GEMM + colsum -> fold_bwd -> (all-reduce of the BN sums) -> dgrad GEMM -> fused depthwise / BN / ReLU backward"""
+    xc, z, mean, rstd, Wn = ctx.saved_tensors
+    dwk, gamma, beta, pwk = ctx.params
+    C, Cout = Wn.shape
+    dv2 = _c(dv).reshape(-1, Cout)
+    z2 = z.reshape(-1, C)
+    G = torch.empty((C, Cout), dtype=torch.float32, device=dv.device)
+    S = torch.empty(Cout, dtype=torch.float32, device=dv.device)
+    if z2.dtype == torch.bfloat16 and C % 8 == 0:
+        # S rides the weight-gradient GEMM as its ones-row at every width here: at Cin = 64 / 128 / 256 (where dense_wgrad runs a separate
+        # column-sum pass) that measured 90 / 102 / 41 us against 93 / 142 / 60 us for the Xception shapes of a 16 x 512^2 batch
+        M = z2.shape[0]
+        K.gemm(z2, dv2, G, C, Cout, M, lda=C, ldb=Cout, ldd=Cout, a_kcontig=0, b_kcontig=0, accumulate=False, colsum_out=S, colsum_accumulate=False)
+    else:
+        K.dense_wgrad(z2, dv2, G, accumulate=False, bias_grad=S)
+    # this replica's dgamma / dbeta are booked by the same launch, before the sums go to the all-reduce (as _BatchNormTrainFn books them)
+    sums = K.sepconv_fold_bwd(G, S, pwk.data.reshape(C, Cout), mean, rstd, gamma.data, beta.data,
+                              dW=_grad(pwk).reshape(C, Cout) if pwk.requires_grad else None,
+                              dgamma=_grad(gamma) if gamma.requires_grad else None, dbeta=_grad(beta) if beta.requires_grad else None)
+    dist.grads_ready(pwk, gamma, beta)
+    if train and ctx.sync and dist.active():
+        sums = sums.clone()
+        dist.all_reduce_sum(sums)           # the [2C] sums message of _BatchNormTrainFn's backward
+    D = K.dense_dgrad(dv2, Wn).reshape(z.shape)
+    dw = _grad(dwk).reshape(9, C) if dwk.requires_grad else torch.zeros((9, C), dtype=torch.float32, device=dv.device)
+    dx = K.bnfold_dwconv3_relu_bwd(D, z, xc, dwk.data.reshape(9, C), mean, rstd, gamma.data, sums, inv_n, train, dw, ctx.stride, ctx.dil)
+    dist.grads_ready(dwk)
+    return dx
+
+
+class _SepConvTrainFn(Function):
+    @staticmethod
+    def forward(ctx, x, dwk, gamma, beta, pwk, moving_mean, moving_var, eps, momentum, stride, dil, sync):
+        C, Cout = x.shape[-1], pwk.shape[-1]
+        xc = _c(x)
+        z, packed = K.relu_dwconv3_stats(xc, dwk.data.reshape(9, C), stride, dil, stats=True)
+        if sync:
+            dist.all_reduce_sum(packed)          # the packed [2C+1] statistics message of _BatchNormTrainFn
+        mean, rstd = K.bn_finalize(packed, C, eps, momentum, moving_mean, moving_var)
+        v, Wn = _sepconv_pointwise(z.reshape(-1, C), pwk, mean, rstd, gamma, beta, any(ctx.needs_input_grad))
+        ctx.params, ctx.sync, ctx.stride, ctx.dil = (dwk, gamma, beta, pwk), sync, stride, dil
+        ctx.save_for_backward(xc, z, mean, rstd, Wn)
+        return v.reshape(*z.shape[:-1], Cout)
+
+    @staticmethod
+    def backward(ctx, dv):
+        z = ctx.saved_tensors[1]
+        rows = z.numel() // z.shape[-1]
+        world = dist.world_size() if ctx.sync and dist.active() else 1
+        return (_sepconv_backward(ctx, dv, True, 1.0 / (rows * world)),) + (None,) * 11
+
+
+class _SepConvInferFn(Function):
+    @staticmethod
+    def forward(ctx, x, dwk, gamma, beta, pwk, moving_mean, moving_var, eps, stride, dil):
+        C, Cout = x.shape[-1], pwk.shape[-1]
+        xc = _c(x)
+        z, _ = K.relu_dwconv3_stats(xc, dwk.data.reshape(9, C), stride, dil, stats=False)
+        rstd = K.rsqrt_eps(moving_var, eps)
+        mean = moving_mean.clone()      # the backward reads the statistics of THIS call: a later training-mode call updates the buffer in place
+        v, Wn = _sepconv_pointwise(z.reshape(-1, C), pwk, mean, rstd, gamma, beta, any(ctx.needs_input_grad))
+        ctx.params, ctx.sync, ctx.stride, ctx.dil = (dwk, gamma, beta, pwk), False, stride, dil
+        ctx.save_for_backward(xc, z, mean, rstd, Wn)
+        return v.reshape(*z.shape[:-1], Cout)
+
+    @staticmethod
+    def backward(ctx, dv):
+        return (_sepconv_backward(ctx, dv, False, 0.0),) + (None,) * 9
+
+
+def sepconv_fused_enabled():
+    """ISEG_SEPCONV_FUSED=0 routes the Xception separable unit through the composed operators (the A/B baseline)"""
+    return os.environ.get("ISEG_SEPCONV_FUSED", "1") != "0"
+
+
+def sepconv_supported(x, dw_kernel, bn, pw_kernel, strides=1, dilation=1):
+    """the shape rules of csrc/sepconv.hip, and the 16-byte alignment its vector accesses need: of x when it is passed as is (a non-contiguous
+    x is copied into a fresh, aligned buffer first) and of the vectors and kernels it reads directly"""
+    N, H, W, C = x.shape
+    if tuple(dw_kernel.shape) != (3, 3, C, 1) or pw_kernel.shape[-2] != C or pw_kernel.dim() != 4 or tuple(pw_kernel.shape[:2]) != (1, 1):
+        return False
+    if x.is_contiguous() and x.data_ptr() % 16:
+        return False
+    vectors = (dw_kernel, pw_kernel, bn.gamma, bn.beta, bn.moving_mean, bn.moving_variance)
+    if any(v.data_ptr() % 16 or not v.is_contiguous() for v in vectors):
+        return False
+    return K.sepconv_supported(N, H, W, C, int(strides), int(dilation), x.dtype)
+
+
+def sepconv_unit(x, dw_kernel, bn, pw_kernel, training, strides=1, dilation=1):
+    """conv1x1(bn(depthwise_conv2d(relu(x), dw_kernel, dilation, strides)), pw_kernel) -- the pointwise output before its BN.  dw_kernel
+    [3, 3, C, 1], pw_kernel [1, 1, C, Cout] (Keras kernels), bn the depthwise BatchNormalization layer (built).  Fused unless
+    ISEG_SEPCONV_FUSED=0 or sepconv_supported refuses the shape or tensors; then the composed operators run."""
+    _check_act_dtype(x)
+    s, d = int(strides), int(dilation)
+    bn_training = bool(training) and bn.trainable
+    if nn.dry_run() or not sepconv_fused_enabled() or not sepconv_supported(x, dw_kernel, bn, pw_kernel, s, d):
+        z = depthwise_conv2d(relu(x), dw_kernel, None, dilation=d, strides=s)
+        u = batch_norm(z, bn.gamma, bn.beta, bn.moving_mean, bn.moving_variance, bn.epsilon, bn.momentum, bn_training, sync=bn.synchronized)
+        return conv2d(u, pw_kernel, None, (1, 1), (1, 1), "same")
+    if bn_training:
+        return _SepConvTrainFn.apply(x, dw_kernel, bn.gamma, bn.beta, pw_kernel, bn.moving_mean, bn.moving_variance, float(bn.epsilon),
+                                     float(bn.momentum), s, d, bool(bn.synchronized))
+    return _SepConvInferFn.apply(x, dw_kernel, bn.gamma, bn.beta, pw_kernel, bn.moving_mean, bn.moving_variance, float(bn.epsilon), s, d)
+
+
+# ---------------------------------------------------------------------------------------------------------
 # activations, add, dropout, drop-path
 # ---------------------------------------------------------------------------------------------------------
 class _ActFn(Function):

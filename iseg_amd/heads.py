@@ -118,6 +118,12 @@ def efficientnet_b0_aspp(num_class=21, output_stride=32, build_input_size=(512, 
                     build_input_size)
 
 
+def xception65_aspp(num_class=21, output_stride=16, build_input_size=(512, 512), dropout_rate=0.1):
+    """Xception-65 (backbones/xception.py) + ASPP: the DeepLabV3 configuration"""
+    return _managed("xception65", ASPPHead(256, output_stride=output_stride, dropout_rate=dropout_rate), num_class, output_stride,
+                    build_input_size)
+
+
 def swin_tiny_fapn(num_class=21, build_input_size=(512, 512)):
     """Swin-T + the FaPN decoder (layers/fapn.py)"""
     return _managed("swin_tiny_224", FaPNHead(top_filters=768), num_class, 32, build_input_size)

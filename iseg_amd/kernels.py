@@ -634,6 +634,59 @@ def bn_swish_gate_bwd_apply(dO, x, mean, rstd, gamma, beta, g, dmh, sums, inv_n,
 
 
 # ---------------------------------------------------------------------------------------------------------
+# Xception separable unit: relu -> depthwise 3x3 -> BN folded into the pointwise GEMM (csrc/sepconv.hip)
+# ---------------------------------------------------------------------------------------------------------
+def sepconv_supported(N, H, W, Cc, stride, dil, dtype):
+    return bool(_hip.lib().iseg_sepconv_supported(int(N), int(H), int(W), int(Cc), int(stride), int(dil), dt(dtype)))
+
+
+def relu_dwconv3_stats(x, w, stride, dil, stats=True):
+    """z = dw3x3(relu(x)) (TF 'same'), and with stats the packed [2C+1] message of bn_stats over z; x [N,H,W,C], w [9, C] fp32"""
+    _require_cuda(x, w)
+    N, H, W, Cc = x.shape
+    Ho, _ = same_pad(H, 3, stride, dil)
+    Wo, _ = same_pad(W, 3, stride, dil)
+    z = torch.empty((N, Ho, Wo, Cc), dtype=x.dtype, device=x.device)
+    packed, ws, wsb = None, None, 0
+    if stats:
+        packed = torch.empty(2 * Cc + 1, dtype=torch.float32, device=x.device)
+        ws, wsb = workspace(_hip.lib().iseg_relu_dwconv3_stats_workspace_bytes(N, H, W, Cc, stride, dil), x.device)
+    _hip.call("iseg_relu_dwconv3_stats", ptr(x), ptr(w), ptr(z), ptr(packed), N, H, W, Cc, int(stride), int(dil), dt(x), ptr(ws), wsb, stream())
+    return z, packed
+
+
+def sepconv_fold(W, mean, rstd, gamma, beta, dtype, want_t=True, want_n=True):
+    """(Wt [Cout, Cin], Wn [Cin, Cout]) = diag(a) W in the operand dtype (None where not wanted), bias [Cout] = c^T W fp32; a = gamma*rstd,
+    c = beta - a*mean"""
+    Cin, Cout = W.shape
+    Wt = torch.empty((Cout, Cin), dtype=dtype, device=W.device) if want_t else None
+    Wn = torch.empty((Cin, Cout), dtype=dtype, device=W.device) if want_n else None
+    bias = torch.empty(Cout, dtype=torch.float32, device=W.device)
+    _hip.call("iseg_sepconv_fold", ptr(W), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(Wt), ptr(Wn), ptr(bias), Cin, Cout, dt(dtype), stream())
+    return Wt, Wn, bias
+
+
+def sepconv_fold_bwd(G, S, W, mean, rstd, gamma, beta, dW=None, dgamma=None, dbeta=None):
+    """dW (+)= diag(a) G + c S^T; returns sums [2Cin] = [dbeta | dgamma], which the same launch adds into dgamma / dbeta (None: skipped)"""
+    Cin, Cout = W.shape
+    sums = torch.empty(2 * Cin, dtype=torch.float32, device=W.device)
+    _hip.call("iseg_sepconv_fold_bwd", ptr(G), ptr(S), ptr(W), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(dW), ptr(sums), ptr(dgamma),
+              ptr(dbeta), Cin, Cout, stream())
+    return sums
+
+
+def bnfold_dwconv3_relu_bwd(D, z, x, w, mean, rstd, gamma, sums, inv_n, train, dw, stride, dil):
+    """dx = [x > 0] dw3x3^T(dz), dw [9, C] += sum relu(x) dz; dz = D + alpha + beta' z (training statistics) or D"""
+    _require_cuda(D, z, x, w, dw)
+    N, H, W, Cc = x.shape
+    dx = torch.empty_like(x)
+    ws, wsb = workspace(_hip.lib().iseg_bnfold_dwconv3_relu_bwd_workspace_bytes(N, H, W, Cc, stride, dil), x.device)
+    _hip.call("iseg_bnfold_dwconv3_relu_bwd", ptr(D), ptr(z), ptr(x), ptr(w), ptr(mean), ptr(rstd), ptr(gamma), ptr(sums), float(inv_n), int(train),
+              ptr(dx), ptr(dw), N, H, W, Cc, int(stride), int(dil), dt(x), ptr(ws), wsb, stream())
+    return dx
+
+
+# ---------------------------------------------------------------------------------------------------------
 # depthwise conv
 # ---------------------------------------------------------------------------------------------------------
 def dwconv2d(x, w, bias, K, dil, pad_t, pad_l, *, flip=False, add=None):
