@@ -24,7 +24,7 @@ int iseg_check_launch(const char* what) {
     return ISEG_OK;
 }
 
-extern "C" int iseg_version(void) { return 100; }
+extern "C" int iseg_version(void) { return 101; }
 
 extern "C" size_t iseg_last_error(char* buf_h, size_t n) {
     const size_t len = strlen(g_err);

@@ -80,14 +80,13 @@ class _CastFn(Function):
 # ---------------------------------------------------------------------------------------------------------
 # Dense / 1x1 conv:  y = act(x @ W + b)         keras.layers.Dense, Conv2D(1x1)
 # ---------------------------------------------------------------------------------------------------------
-_FWD_KCONTIG = os.environ.get("ISEG_FWD_KCONTIG", "1") != "0"      # experiment knob: 0 = forward products read the Keras [K][N] kernels
 _DMA_MIN_K = max(16, int(os.environ.get("ISEG_GEMM_DMA_MIN_K", "32")))      # the same knob csrc/gemm.hip reads (dma_min_k)
 
 
 def _kcontig_kernel(W, x2, Kd, N):
     """the [N][K] copy of a forward product's kernel (nn.wt) when the LDS-DMA GEMM can take the product (csrc/gemm_dma.h dma_eligible: bf16,
     K a multiple of 8 and >= 32, N a multiple of 8 and >= 64, M >= 64), else None: the register-staged kernel reads [K][N] as it lies"""
-    if not _FWD_KCONTIG or x2.dtype != torch.bfloat16 or Kd % 8 or Kd < _DMA_MIN_K or N % 8 or N < 64 or x2.shape[0] < 64:
+    if x2.dtype != torch.bfloat16 or Kd % 8 or Kd < _DMA_MIN_K or N % 8 or N < 64 or x2.shape[0] < 64:
         return None
     return nn.wt(W, (Kd, N))
 
@@ -346,9 +345,6 @@ def _conv_geometry(H, W, kh, kw, strides, dilation, padding):
     return Ho, Wo, pt, pl
 
 
-_IGEMM_PHASES = os.environ.get("ISEG_IGEMM_PHASES", "1") != "0"      # experiment knob: 0 = strided data gradients through GEMM + col2im
-
-
 class _Conv2dFn(Function):
     """Three routes: (1) 1x1 / stride 1 / one group on the activation as it lies = a plain GEMM; (2) bf16 storage with channels per
     group that are multiples of 8 = implicit GEMM on the matrix cores (csrc/conv_igemm.hip: the patch matrix is gathered while the
@@ -378,7 +374,7 @@ class _Conv2dFn(Function):
                        bias=(b.data if b is not None else None))
         elif igemm:
             Wt = None
-            if _FWD_KCONTIG and K.conv2d_igemm_fwd_kt_supported(geom, cdt):      # LDS-DMA form on the K-contiguous kernel copy
+            if K.conv2d_igemm_fwd_kt_supported(geom, cdt):      # LDS-DMA form on the K-contiguous kernel copy
                 Wt = nn.wt(W, (kh * kw * Cin, Cout))
             if Wt is not None:
                 y = K.conv2d_igemm_fwd_kt(xc, Wt, b.data if b is not None else None, geom)
@@ -431,7 +427,7 @@ class _Conv2dFn(Function):
             if W.requires_grad:
                 K.conv2d_igemm_bwd_weight(xc, dy4, _grad(W), g_, accumulate=True)
             patchify = (kh, kw) == st      # kernel == stride: the column buffer IS dx up to a permutation, one plain GEMM fills it
-            if need_dx and (st == (1, 1) or (di == (1, 1) and st[0] * st[1] <= 16 and _IGEMM_PHASES and not patchify)):
+            if need_dx and (st == (1, 1) or (di == (1, 1) and st[0] * st[1] <= 16 and not patchify)):
                 # stride 1: one gather over dy; strided and undilated: one stride-1 gather per stride phase, all phases in one launch, rows
                 # scattered to their pixels by the epilogue (csrc/conv_igemm.hip pass 3) -- no zero products, no column buffer, no col2im
                 # (ResNet's 3x3 / s2 at 64x64x128: 23 us against 40 us for GEMM + col2im)
@@ -964,7 +960,7 @@ def _sepconv_pointwise(z2, pwk, mean, rstd, gamma, beta, need_grad):
     need_grad (else None).  The forward reads the K-contiguous copy where the LDS-DMA GEMM takes the product (as _kcontig_kernel routes a 1x1
     conv), else Wn; the fold writes only the layouts that will be read."""
     Cin, Cout = pwk.shape[-2], pwk.shape[-1]
-    kcontig = (_FWD_KCONTIG and z2.dtype == torch.bfloat16 and Cin % 8 == 0 and Cin >= _DMA_MIN_K and Cout % 8 == 0 and Cout >= 64
+    kcontig = (z2.dtype == torch.bfloat16 and Cin % 8 == 0 and Cin >= _DMA_MIN_K and Cout % 8 == 0 and Cout >= 64
                and z2.shape[0] >= 64)
     Wt, Wn, bias = K.sepconv_fold(pwk.data.reshape(Cin, Cout), mean, rstd, gamma.data, beta.data, z2.dtype, want_t=kcontig,
                                   want_n=need_grad or not kcontig)
@@ -1416,20 +1412,6 @@ def concat(xs):
 # ---------------------------------------------------------------------------------------------------------
 # ConvNeXt block, fused:  x + drop_path(gamma * pw2(gelu(pw1(LN(dw7x7(x))))))     backbones/convnext.py:47-63
 # ---------------------------------------------------------------------------------------------------------
-_BATCHED_PREP = os.environ.get("ISEG_BATCHED_PREP", "1") == "1"      # 0: per-block prep launches (A/B measurements)
-_MLP_LN_ON_LOAD = os.environ.get("ISEG_MLP_LN_ON_LOAD", "1") == "1"      # 0: LayerNorm of the fused stages as its own kernel (A/B measurements)
-_WGRAD_PAIR = os.environ.get("ISEG_WGRAD_PAIR", "1") == "1"      # 0: the two weight-gradient products of an un-fused block as two launches (A/B measurements)
-_LAYERSCALE_FROM_SLABS = os.environ.get("ISEG_LAYERSCALE_FROM_SLABS", "1") == "1"      # 0: slab sum + Z tensor + layer-scale kernel (A/B measurements)
-_MLP_LN_BWD_FUSED = os.environ.get("ISEG_MLP_LN_BWD_FUSED", "1") == "1"      # 0: LayerNorm backward of the fused stages as its own kernel (A/B measurements)
-# 1: the drop-path factor rides the saved activation of the un-fused stages and rowscale_kernel disappears (round 6, see _ConvNeXtBlockFn.forward).
-# Measured on the flagship, interleaved on one box: 8.196 / 8.210 / 8.227 ms without, 8.225 / 8.237 / 8.256 ms with it -- the 12 row-scale passes it
-# removes (25 MB each) come back as the row-sum job's read of dout, two wider epilogues and wider partial rows.  Off by default; kept for the
-# launch count (11 instead of 12 per stage-2 block) and tested (tests/test_blocks_gpu.py, tests/test_kernels_gpu.py).
-_DP_FOLDED = os.environ.get("ISEG_DP_FOLDED", "0") == "1"
-_SLAB_REDUCE_MERGED = os.environ.get("ISEG_SLAB_REDUCE_MERGED", "1") == "1"      # 0: slab sum of dW1 as its own launch (A/B measurements)
-_MLP_BWD_NO_HIDDEN = os.environ.get("ISEG_MLP_BWD_NO_HIDDEN", "1") == "1"      # 0: the round-2 backward route of the fused stages (A/B measurements)
-
-
 class _ConvNeXtBlockFn(Function):
     @staticmethod
     def forward(ctx, x, dw_kernel, dw_bias, ln_gamma, ln_beta, w1, b1, w2, b2, gamma, dil, eps, dp_mask):
@@ -1444,10 +1426,10 @@ class _ConvNeXtBlockFn(Function):
         y1 = K.dwconv2d(xc, p.dw_kernel.data.reshape(Kk * Kk, C), p.dw_bias.data, Kk, dil, pad, pad)
         M = N * H * W
         ctx.fused = K.convnext_mlp_supported(C, xc.dtype)
-        ctx.dp_folded = False
         # round 3: on the fused stages LayerNorm rides the MLP kernels' row loads (forward: statistics + normalisation, backward: normalisation
-        # from the saved statistics), so y2 is never written or read -- needs the backward route that keeps nothing [M, 4C]-shaped either
-        ctx.ln_on_load = ctx.fused and _MLP_LN_ON_LOAD and _MLP_BWD_NO_HIDDEN and (dp_mask is None or (H * W) % 64 == 0)
+        # from the saved statistics), so y2 is never written or read -- needs the backward route that keeps nothing [M, 4C]-shaped either, which
+        # takes a drop-path mask only when H * W is a multiple of 64
+        ctx.ln_on_load = ctx.fused and (dp_mask is None or (H * W) % 64 == 0)
         if ctx.ln_on_load:
             y2 = mean = rstd = None
         else:
@@ -1462,10 +1444,7 @@ class _ConvNeXtBlockFn(Function):
         if ctx.fused:
             # wide stages (C = 96 / 192, bf16): the [M, 4C] hidden tile stays on the CU (csrc/mlp_fused.hip) and the backward pass
             # recomputes it, so nothing [M, 4C]-shaped is kept; `bw` holds the tiled weight images the backward chain streams
-            if _BATCHED_PREP:      # one launch per weight update for every block of the model (nn.mlp_tiled)
-                fw, bw = nn.mlp_tiled(p.w1, p.w2, p.gamma)
-            else:
-                fw, bw = K.convnext_mlp_prep(p.w1.data, p.w2.data, gam, backward=grad)
+            fw, bw = nn.mlp_tiled(p.w1, p.w2, p.gamma)      # one launch per weight update for every block of the model
             if ctx.ln_on_load:
                 out, mean, rstd = K.convnext_mlp_fwd_ln(y1.reshape(M, C), p.ln_gamma.data, p.ln_beta.data, eps, fw, p.b1.data, p.b2.data, gam,
                                                         dp_mask, H * W, xc.reshape(M, C))
@@ -1475,17 +1454,7 @@ class _ConvNeXtBlockFn(Function):
         else:
             h = torch.empty((M, 4 * C), dtype=xc.dtype, device=xc.device) if grad else None
             w1t, w2t = (nn.wt(p.w1), nn.wt(p.w2)) if xc.dtype == torch.bfloat16 else (None, None)
-            # round 6: the drop-path factor s rides the SAVED activation.  x + s gamma (g W2 + b2) = x + gamma ((s g) W2 + s b2): the pwconv1 epilogue
-            # writes s g (gelu' stays unscaled), pwconv2 scales its bias row-wise instead of its result, and the backward pass then works on the
-            # UNSCALED dout -- the row factor goes into the x-aux epilogue of dH, Z = (s g)^T dout needs no scaled operand, and the column sums
-            # S = colsum(s dout) are formed inside the layer-scale launch: rowscale_kernel (one pass over [M, C] per block) disappears.
-            ctx.dp_folded = bool(_DP_FOLDED and grad and dp_mask is not None and w1t is not None and w2t is not None and p.gamma is not None and
-                                 p.b1 is not None and _WGRAD_PAIR and _LAYERSCALE_FROM_SLABS and 4 * C >= 768 and C % 8 == 0)
-            if ctx.dp_folded:
-                g = K.dense_fwd_t(y2, w1t, p.b1.data, act=K.ACT_GELU, pre_out=h, pre_deriv=True, rowscale=dp_mask, rows_per_group=H * W)
-                out = K.dense_fwd_t(g, w2t, p.b2.data, colscale=gam, rowscale=dp_mask, rows_per_group=H * W, residual=xc.reshape(M, C),
-                                    bias_rowscaled=True)
-            elif w1t is not None and w2t is not None:
+            if w1t is not None and w2t is not None:
                 # K-contiguous kernel copies: the forward products run on the LDS-DMA GEMM like the data gradients (256 x 128 tiles)
                 g = K.dense_fwd_t(y2, w1t, p.b1.data, act=K.ACT_GELU, pre_out=h, pre_deriv=grad)
                 out = K.dense_fwd_t(g, w2t, p.b2.data, colscale=gam, rowscale=dp_mask, rows_per_group=H * W, residual=xc.reshape(M, C))
@@ -1498,10 +1467,9 @@ class _ConvNeXtBlockFn(Function):
 
     @staticmethod
     def backward(ctx, dout):
-        """Two queues.  The data-gradient chain (dbr -> dh -> dy2 -> LayerNorm -> depthwise data gradient) is what the next block waits
-        for; everything that only feeds the optimizer (column sums, the two weight-gradient GEMMs, layer-scale gradients, the depthwise
-        weight gradient) goes to a side HIP stream behind events, so the short kernels of the narrow stages overlap instead of queueing
-        (_SideQueue; opt-in with ISEG_SIDE_STREAM=1 -- measured slower than one queue on one GPU, see _side_enabled).  Both queues meet before the gradients are announced to the reducer."""
+        """The data-gradient chain (dbr -> dh -> dy2 -> LayerNorm -> depthwise data gradient) and the parameter gradients (column sums, the
+        weight-gradient products, layer-scale gradients, the depthwise weight gradient) all run on the current stream; the gradients are
+        announced to the reducer once the block's last kernel is enqueued."""
         xc, y1, y2, mean, rstd, h, g, dp_mask = ctx.saved_tensors
         p, dil, pad = ctx.p, ctx.dil, ctx.pad
         N, H, W, C = xc.shape
@@ -1509,67 +1477,35 @@ class _ConvNeXtBlockFn(Function):
         Kk = p.dw_kernel.shape[0]
         do2 = _c(dout).reshape(M, C)
         cdt = xc.dtype
-        side = _SideQueue(xc.device)
-        if ctx.fused and _MLP_BWD_NO_HIDDEN and (dp_mask is None or (H * W) % 64 == 0):
+        if ctx.ln_on_load:
             # round 3: nothing [M, 4C]-shaped reaches HBM in the backward pass either.  One kernel carries the data gradient through the
-            # recomputed hidden tile; a second one (workgroups own 128 hidden units and a chunk of rows) recomputes it again and contracts
-            # over the rows for every parameter gradient of the MLP; the drop-path row factor and the column sums of dbr ride both
-            # (csrc/mlp_wgrad.hip) -- replaces rowscale + colsum + chain + two weight-gradient GEMMs + their split-K sums + layerscale_grads
-            bw = h
-            yop, ln = (y1.reshape(M, C), (mean, rstd, p.ln_gamma.data, p.ln_beta.data)) if ctx.ln_on_load else (y2, None)
-            dy1 = dy2 = None
-            if ln is not None and _MLP_LN_BWD_FUSED:      # the chain kernel's epilogue carries the rows through the LayerNorm backward too
-                dy1 = K.convnext_mlp_bwd_data_ln(yop, do2, bw, p.b1.data, ln, _grad(p.ln_gamma), _grad(p.ln_beta), dp_mask, H * W)
-            else:
-                dy2 = K.convnext_mlp_bwd_data(yop, do2, bw, p.b1.data, dp_mask, H * W, ln=ln)
-            side.run(lambda: K.convnext_mlp_wgrad(yop, do2, bw, p.b1.data, p.w2.data, p.b2.data, p.gamma.data if p.gamma is not None else None,
-                                                  _grad(p.w1), _grad(p.b1), _grad(p.w2), _grad(p.b2),
-                                                  _grad(p.gamma) if p.gamma is not None else None, dp_mask, H * W, ln=ln), yop, do2)
-            del h, bw
+            # recomputed hidden tile and, in its epilogue, through the LayerNorm backward; a second one (workgroups own 128 hidden units and a
+            # chunk of rows) recomputes it again and contracts over the rows for every parameter gradient of the MLP; the drop-path row factor
+            # and the column sums of dbr ride both (csrc/mlp_wgrad.hip) -- replaces rowscale + colsum + chain + two weight-gradient GEMMs + their
+            # split-K sums + layerscale_grads
+            y1m, ln = y1.reshape(M, C), (mean, rstd, p.ln_gamma.data, p.ln_beta.data)
+            dy1 = K.convnext_mlp_bwd_data_ln(y1m, do2, h, p.b1.data, ln, _grad(p.ln_gamma), _grad(p.ln_beta), dp_mask, H * W)
+            K.convnext_mlp_wgrad(y1m, do2, h, p.b1.data, p.w2.data, p.b2.data, p.gamma.data if p.gamma is not None else None,
+                                 _grad(p.w1), _grad(p.b1), _grad(p.w2), _grad(p.b2), _grad(p.gamma) if p.gamma is not None else None, dp_mask,
+                                 H * W, ln=ln)
+            del h
         else:
-            dy1 = None
-            dy2 = _ConvNeXtBlockFn._mlp_backward_with_hidden(ctx, p, do2, y2, h, g, dp_mask, side, H, W, C, M, cdt, xc)
+            dy2 = _ConvNeXtBlockFn._mlp_backward_with_hidden(ctx, p, do2, y2, h, g, dp_mask, H, W, C, M, cdt, xc)
             del h, g
-        if dy1 is None:
             dy1 = K.layernorm_bwd(dy2, y1.reshape(M, C), p.ln_gamma.data, mean, rstd, _grad(p.ln_gamma), _grad(p.ln_beta))
         dy1 = dy1.reshape(N, H, W, C)
-        side.run(lambda: K.dwconv2d_bwd_weight(xc, dy1, _grad(p.dw_kernel).reshape(Kk * Kk, C), _grad(p.dw_bias), Kk, dil, pad, pad), xc, dy1)
+        K.dwconv2d_bwd_weight(xc, dy1, _grad(p.dw_kernel).reshape(Kk * Kk, C), _grad(p.dw_bias), Kk, dil, pad, pad)
         dx = None
         if ctx.needs_input_grad[0]:
             padb = (Kk - 1) * dil - pad
             dx = K.dwconv2d(dy1, p.dw_kernel.data.reshape(Kk * Kk, C), None, Kk, dil, padb, padb, flip=True, add=_c(dout))
-        side.join()
         dist.grads_ready(p.dw_kernel, p.dw_bias, p.ln_gamma, p.ln_beta, p.w1, p.b1, p.w2, p.b2, p.gamma)
         return (dx,) + (None,) * 12
 
     @staticmethod
-    def _mlp_backward_with_hidden(ctx, p, do2, y2, h, g, dp_mask, side, H, W, C, M, cdt, xc):
-        """the round-2 route: g / dh materialised ([M, 4C] each), two weight-gradient GEMMs; still the path of the un-fused stages (C >= 384)"""
-        if ctx.dp_folded:      # (forward: g = s gelu(h) was saved; see there)
-            w2eff = nn.w_colscaled(p.w2, p.gamma) if _BATCHED_PREP else K.scale_cols_cast(p.w2.data, p.gamma.data, cdt)
-            dh = K.dense_dgrad(do2, w2eff, act=K.ACT_MUL_AUX, aux=h, rowscale=dp_mask, rows_per_group=H * W)      # s (dout W2g^T) gelu'(pre)
-            del h
-
-            def folded_param_grads():
-                srow = (do2, dp_mask, H * W)
-                sl = K.dense_wgrad_pair(g, do2, y2, dh, _grad(p.w1), _grad(p.b1), defer_second=_SLAB_REDUCE_MERGED, ones_first=False)
-                if sl is not None:      # stage 2: both weight gradients in one launch, every slab sum + S in the layer-scale launch
-                    K.layerscale_grads_slabs(sl[0], sl[1], p.w2.data, p.b2.data, p.gamma.data, _grad(p.w2), _grad(p.gamma), _grad(p.b2),
-                                             extra=sl[2] if len(sl) > 2 else None, srow=srow)
-                    return
-                slz = K.dense_wgrad_slabs(g, do2, ones_row=False)      # stage 3 (the two products do not pair): Z = (s g)^T dout, no ones-row
-                if slz is not None:
-                    K.layerscale_grads_slabs(slz[0], slz[1], p.w2.data, p.b2.data, p.gamma.data, _grad(p.w2), _grad(p.gamma), _grad(p.b2), srow=srow)
-                else:      # (not split: the tensor form, with S from a scaled copy after all)
-                    Z = torch.empty((4 * C, C), dtype=torch.float32, device=xc.device)
-                    K.dense_wgrad(g, do2, Z, accumulate=False)
-                    S_ = torch.empty(C, dtype=torch.float32, device=xc.device)
-                    K.colsum(K.rowscale(do2, dp_mask, H * W), C, 0, 1, M, C, S_)
-                    K.layerscale_grads(Z, p.w2.data, p.b2.data, p.gamma.data, S_, _grad(p.w2), _grad(p.gamma), _grad(p.b2))
-                K.dense_wgrad(y2, dh, _grad(p.w1), bias_grad=_grad(p.b1))
-
-            side.run(folded_param_grads, do2, g, dh, y2)
-            return K.dense_dgrad(dh, nn.w(p.w1))
+    def _mlp_backward_with_hidden(ctx, p, do2, y2, h, g, dp_mask, H, W, C, M, cdt, xc):
+        """the round-2 route: g / dh materialised ([M, 4C] each), two weight-gradient products; the path of the un-fused stages (C >= 384),
+        and of the fused stages when a drop-path mask meets a plane that is not a multiple of 64 pixels"""
         dbr = K.rowscale(do2, dp_mask, H * W) if dp_mask is not None else do2
         S = torch.empty(C, dtype=torch.float32, device=xc.device)      # column sums of dbr (layer-scale and bias gradients)
         s_on_gemm = p.gamma is not None and (ctx.fused or g is not None) and xc.dtype == torch.bfloat16 and 4 * C >= 768      # rides Z = g^T dbr below
@@ -1582,44 +1518,36 @@ class _ConvNeXtBlockFn(Function):
         else:
             if p.gamma is None:
                 w2eff = nn.w(p.w2)
-            elif _BATCHED_PREP and cdt == torch.bfloat16:
+            elif cdt == torch.bfloat16:
                 w2eff = nn.w_colscaled(p.w2, p.gamma)
             else:
                 w2eff = K.scale_cols_cast(p.w2.data, p.gamma.data, cdt)
             dh = K.dense_dgrad(dbr, w2eff, act=K.ACT_MUL_AUX, aux=h)          # [M,4C] = (dbr @ W2g^T) * gelu'(pre), h = gelu'(pre)
         del h
 
-        # --- side: pw2 + layer scale from Z = g^T dbr and S = colsum(dbr) (no pass over [M,C] for gamma), then dW1 (+ db1)
-        def param_grads():
-            if p.gamma is not None:
-                if s_on_gemm and _LAYERSCALE_FROM_SLABS and _WGRAD_PAIR and p.b1 is not None:
-                    # round 5: both weight-gradient products of the block as ONE launch (36 tiles x 7 splits instead of 2 x 18 x 13): Z stops at its
-                    # slabs for the layer-scale kernel, dW1 / db1 are summed by the generic slab reduce
-                    # (round 6: the slab sum of dW1 / db1 rides the layer-scale launch -- _SLAB_REDUCE_MERGED=0 keeps the two launches)
-                    sl = K.dense_wgrad_pair(g, dbr, y2, dh, _grad(p.w1), _grad(p.b1), defer_second=_SLAB_REDUCE_MERGED)
-                    if sl is not None:
-                        K.layerscale_grads_slabs(sl[0], sl[1], p.w2.data, p.b2.data, p.gamma.data, _grad(p.w2), _grad(p.gamma), _grad(p.b2),
-                                                 extra=sl[2] if len(sl) > 2 else None)
-                        return
-                sl = K.dense_wgrad_slabs(g, dbr) if (s_on_gemm and _LAYERSCALE_FROM_SLABS) else None
-                if sl is not None:      # the layer-scale kernel sums the split-K slabs of Z (and its ones-row S) while it reads them
-                    K.layerscale_grads_slabs(sl[0], sl[1], p.w2.data, p.b2.data, p.gamma.data, _grad(p.w2), _grad(p.gamma), _grad(p.b2))
-                else:
-                    Z = torch.empty((4 * C, C), dtype=torch.float32, device=xc.device)
-                    K.dense_wgrad(g, dbr, Z, accumulate=False, bias_grad=S if s_on_gemm else None)      # Z = gelu(h)^T dbr (+ S from its ones-row)
-                    K.layerscale_grads(Z, p.w2.data, p.b2.data, p.gamma.data, S, _grad(p.w2), _grad(p.gamma), _grad(p.b2))
+        # pw2 + layer scale from Z = g^T dbr and S = colsum(dbr) (no pass over [M,C] for gamma), then dW1 (+ db1)
+        pair = None
+        if p.gamma is not None:
+            if s_on_gemm and p.b1 is not None:
+                # round 5: both weight-gradient products of the block as ONE launch (36 tiles x 7 splits instead of 2 x 18 x 13): Z stops at its
+                # slabs for the layer-scale kernel; round 6: the slab sum of dW1 / db1 rides the layer-scale launch too
+                pair = K.dense_wgrad_pair(g, dbr, y2, dh, _grad(p.w1), _grad(p.b1), defer_second=True)
+            sl = pair if pair is not None else (K.dense_wgrad_slabs(g, dbr) if s_on_gemm else None)
+            if sl is not None:      # the layer-scale kernel sums the split-K slabs of Z (and its ones-row S) while it reads them
+                K.layerscale_grads_slabs(sl[0], sl[1], p.w2.data, p.b2.data, p.gamma.data, _grad(p.w2), _grad(p.gamma), _grad(p.b2),
+                                         extra=sl[2] if len(sl) > 2 else None)
             else:
-                K.dense_wgrad(g, dbr, _grad(p.w2))
-                K.axpby(S, _grad(p.b2), 1.0, 1.0, out=_grad(p.b2))
+                Z = torch.empty((4 * C, C), dtype=torch.float32, device=xc.device)
+                K.dense_wgrad(g, dbr, Z, accumulate=False, bias_grad=S if s_on_gemm else None)      # Z = gelu(h)^T dbr (+ S from its ones-row)
+                K.layerscale_grads(Z, p.w2.data, p.b2.data, p.gamma.data, S, _grad(p.w2), _grad(p.gamma), _grad(p.b2))
+        else:
+            K.dense_wgrad(g, dbr, _grad(p.w2))
+            K.axpby(S, _grad(p.b2), 1.0, 1.0, out=_grad(p.b2))
+        if pair is None:
             K.dense_wgrad(y2, dh, _grad(p.w1), bias_grad=_grad(p.b1))      # db1 rides the wgrad GEMM (virtual ones-row) when C % 128 != 0
-
-        side.run(param_grads, dbr, g, dh, y2)
         if not ctx.fused:
             dy2 = K.dense_dgrad(dh, nn.w(p.w1))                                # [M,C]
         return dy2
-
-
-_GRN_FOLD_RATIO = int(os.environ.get("ISEG_V2_GRN_FOLD_RATIO", "1"))      # experiments: fold from HW * ratio >= 2 * (4C) on
 
 
 class _ConvNeXtV2BlockFn(Function):
@@ -1652,7 +1580,7 @@ class _ConvNeXtV2BlockFn(Function):
         # Wide planes (at least two activation rows per kernel row and sample): the normalisation is folded into the second product --
         # per-sample kernels diag(gamma*nx_n + 1) W2 and the bias b2 + beta W2 -- so grn(g) is never written (csrc/grn.hip, "folded")
         HW = H * W
-        ctx.fold = (w2t is not None and HW % 256 == 0 and HW * _GRN_FOLD_RATIO >= 8 * C and C >= 64 and C % 16 == 0      # (the LDS-DMA GEMM's own conditions)
+        ctx.fold = (w2t is not None and HW % 256 == 0 and HW >= 8 * C and C >= 64 and C % 16 == 0      # (the LDS-DMA GEMM's own conditions)
                     and os.environ.get("ISEG_V2_GRN_FOLD", "1") == "1")
         if ctx.fold:
             nx, gx = K.grn_stats(g.reshape(N, HW, 4 * C), grn_eps)
@@ -1732,90 +1660,6 @@ def convnext_v2_block(x, params, dilation, eps, grn_eps, dp_mask):
     p = params
     return _ConvNeXtV2BlockFn.apply(x, p.dw_kernel, p.dw_bias, p.ln_gamma, p.ln_beta, p.w1, p.b1, p.grn_gamma, p.grn_beta, p.w2, p.b2,
                                     int(dilation), float(eps), float(grn_eps), dp_mask)
-
-
-# ---------------------------------------------------------------------------------------------------------
-# side queue for work that only feeds the optimizer
-# ---------------------------------------------------------------------------------------------------------
-_SIDE_STREAMS = {}
-
-
-def _side_enabled():
-    """independent work on extra HIP streams?  ISEG_SIDE_STREAM = 1 always, `capture` only while a HIP graph is being captured, 0 / unset never.
-    Eager (flagship step, interleaved A/B): 9.08 ms with one queue, 9.39 ms with two -- every fork / join is a pair of host-side event calls.
-    Inside a captured graph the forks are edges of the graph; measured replayed (one box, interleaved): flagship 9.12 / 9.16 ms with one queue,
-    9.17 / 9.17 ms with two (an earlier box: 9.11 vs 8.98); ResNet-50 + ASPP 8.18 vs 11.6 ms, InternImage-B 36.6 vs 45.9 ms, Swin-T equal -- the
-    runtime pays for every fork / join of a replayed graph, and the small-kernel models have hundreds.  Off by default."""
-    import os
-
-    mode = os.environ.get("ISEG_SIDE_STREAM", "0")
-    if mode == "1":
-        return True
-    if mode != "capture" or not torch.cuda.is_available():
-        return False
-    return torch.cuda.is_current_stream_capturing()
-
-
-_BRANCH_STREAMS = {}
-
-
-def parallel_branches(fns, device=None):
-    """[fn() for fn in fns], each on its own HIP stream when side streams are enabled (_side_enabled): the branches of ASPP are five
-    independent conv -> BatchNorm -> ReLU chains of 64..256-workgroup kernels that leave most of the chip idle one at a time.  The autograd
-    engine replays each branch's backward on the stream its forward ran on, so the backward pass forks the same way."""
-    if len(fns) < 2 or not _side_enabled():
-        return [fn() for fn in fns]
-    main = torch.cuda.current_stream()
-    key = main.device.index
-    pool = _BRANCH_STREAMS.setdefault(key, [])
-    while len(pool) < len(fns):
-        pool.append(torch.cuda.Stream(device=main.device))
-    outs = []
-    for fn, st in zip(fns, pool):
-        st.wait_stream(main)
-        with torch.cuda.stream(st):
-            outs.append(fn())
-    capturing = torch.cuda.is_current_stream_capturing()
-    for o, st in zip(outs, pool):
-        main.wait_stream(st)
-        if not capturing:      # eager: tell the caching allocator that the main stream reads what a side stream allocated
-            for t in (o if isinstance(o, (list, tuple)) else [o]):
-                if torch.is_tensor(t):
-                    t.record_stream(main)
-    return outs
-
-
-class _SideQueue:
-    """run(fn, *tensors): enqueue fn on this device's side stream behind everything the current stream has enqueued so far; `tensors`
-    are the buffers fn reads that the caller may release before the side stream gets to them (the caching allocator is told).
-    join(): the current stream waits for the side stream.  Without ISEG_SIDE_STREAM=1 (or on the CPU) run() just calls fn."""
-
-    def __init__(self, device):
-        self.stream = None
-        if device.type == "cuda" and _side_enabled():
-            key = device.index if device.index is not None else torch.cuda.current_device()
-            st = _SIDE_STREAMS.get(key)
-            if st is None:
-                st = _SIDE_STREAMS[key] = torch.cuda.Stream(device=device)
-            self.stream = st
-        self.used = False
-
-    def run(self, fn, *tensors):
-        if self.stream is None:
-            return fn()
-        main = torch.cuda.current_stream()
-        self.stream.wait_stream(main)
-        with torch.cuda.stream(self.stream):
-            fn()
-        for t in tensors:
-            if t is not None:
-                t.record_stream(self.stream)
-        self.used = True
-
-    def join(self):
-        if self.stream is not None and self.used:
-            torch.cuda.current_stream().wait_stream(self.stream)
-            self.used = False
 
 
 def convnext_block(x, params, dilation, eps, dp_mask):
