@@ -121,11 +121,10 @@ int iseg_gemm_splits(const iseg_gemm_args* args_h);
 int iseg_gemm_slabs(const iseg_gemm_args* args_h);
 /* which main loop iseg_gemm runs for this problem (profiling labels): 0 = register-staged gemm_bf16_kernel / fp32 kernel,
    1..4 = LDS-DMA pipeline gemm_bf16_dma_kernel with tile 128x64 / 256x128 / 128x128 (2 stages) / 128x128 (3 stages),
-   5 = 256x128 persistent (one workgroup per CU walks several tiles), 6 = 256x192 (2 stages),
+   6 = 256x192 (2 stages),
    7 / 8 = the weight-gradient orientation (a_kcontig = b_kcontig = 0, split over K: Dense / 1x1-conv kernel gradients,
    layers' `kernel` of backbones/convnext.py:51-55, backbones/swin.py:17-43) on the LDS-DMA pipeline gemm_bf16_dma_tn_kernel with
-   256x128 / 128x256 tiles (M, N multiples of 8 and >= 128 -- or one of them 64..127 when the other is >= 320 --, any K >= 2048, aligned operands; ISEG_GEMM_DMA_TN=0 pins the
-   register-staged kernel) */
+   256x128 / 128x256 tiles (M, N multiples of 8 and >= 128 -- or one of them 64..127 when the other is >= 320 --, any K >= 2048, aligned operands) */
 int iseg_gemm_variant(const iseg_gemm_args* args_h);
 size_t iseg_gemm_workspace_bytes(const iseg_gemm_args* args_h);
 int iseg_gemm(const iseg_gemm_args* args_h, void* ws, size_t ws_bytes, iseg_stream_t stream);
@@ -181,8 +180,8 @@ int iseg_layernorm_gather_bwd(const void* dy, const int32_t* dy_index, const voi
 int iseg_dwconv2d_fwd(const void* x, const float* w, const float* bias, const void* add, void* y, int N, int H, int W, int C,
                       int K, int dil, int pad_t, int pad_l, int flip, int dtype, iseg_stream_t stream);
 /* The 7 x 7 / bf16 / C % 32 == 0 case of iseg_dwconv2d_fwd on the matrix cores (csrc/dwconv_mfma.hip: banded products with
- * v_mfma_f32_4x4x4_16b_bf16, block = channel) -- the route iseg_dwconv2d_fwd takes by itself for large planes (ISEG_DW_MFMA), exported so that
- * tests and benchmarks can name it.  Same arguments and semantics (backbones/convnext.py:23-27,47-50); weights are rounded to bf16 as the
+ * v_mfma_f32_4x4x4_16b_bf16, block = channel) -- the route iseg_dwconv2d_fwd takes by itself for large planes, exported so that
+ * tests and benchmarks can take it whenever the shape is eligible.  Same arguments and semantics (backbones/convnext.py:23-27,47-50); weights are rounded to bf16 as the
  * reference's mixed_bfloat16 policy does.  ISEG_ERR_UNSUPPORTED when the shape is not eligible. */
 int iseg_dwconv2d7_mfma(const void* x, const float* w, const float* bias, const void* add, void* y, int N, int H, int W, int C, int pad_t,
                         int pad_l, int flip, iseg_stream_t stream);

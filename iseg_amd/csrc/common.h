@@ -200,9 +200,8 @@ static inline void launch_reduce_rows(const float* partials, int P, int64_t pstr
                                       hipStream_t stream) {
     const bool aligned = (((uintptr_t)partials | (uintptr_t)out0 | (uintptr_t)out1) & 15) == 0;
     // (up to 128 partial rows: the chunk records of the fused-stage weight gradients are 40 / 80 rows of 0.3 M floats -- the 16 x 16 kernel below
-    // reads them in 64-byte segments at 2.8 TB/s; flagship 8.91 -> 8.87 ms.  ISEG_REDUCE_WIDE_MAXP overrides.)
-    static const int wide_max_p = [] { const char* e = getenv("ISEG_REDUCE_WIDE_MAXP"); return e ? atoi(e) : 128; }();
-    if (batch == 1 && P <= wide_max_p && n >= 32768 && n % 4 == 0 && n0 % 4 == 0 && pstride % 4 == 0 && aligned) {
+    // reads them in 64-byte segments at 2.8 TB/s; flagship 8.91 -> 8.87 ms)
+    if (batch == 1 && P <= 128 && n >= 32768 && n % 4 == 0 && n0 % 4 == 0 && pstride % 4 == 0 && aligned) {
         hipLaunchKernelGGL((reduce_rows_wide_kernel<0>), dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, stream, partials, P,
                            pstride, n, out0, out1, n0, scale, accumulate);
         return;
@@ -244,26 +243,20 @@ __device__ __forceinline__ void gelu_fast_both(float x, float& y, float& dy) {
 }
 
 // Cheapest GELU that is still far below bf16 rounding (used by the fused ConvNeXt MLP kernels, whose hidden tile never leaves the
-// CU and is rounded to bf16 as the next MFMA operand): Phi(x) ~ sigmoid(x * (a0 + a1 x^2 + a2 x^4)), coefficients from a minimax
-// fit of x * Phi(x) on [-8, 8] (tools/fit_gelu_sigmoid.py): |gelu error| <= 2.6e-5, |gelu' error| <= 1.1e-4 (bf16 half-ulp at 1 is
-// 2e-3).  One v_exp_f32 + one v_rcp_f32 + 7 plain VALU per element instead of the ~27 issue slots of the erfc form above.
-// The polynomial's x^4 coefficient is negative, so x^2 is clamped at 64 (|x| > 8: sigmoid is saturated either way).
-#define ISEG_GELU_SIG_A0 1.5950157270240881f
-#define ISEG_GELU_SIG_A1 0.07401132728640801f
-#define ISEG_GELU_SIG_A2 (-0.0007030389408329068f)
-// gelu(x) AND gelu'(x) of the bf16 kernels that need both (weight-gradient recompute, the forward GEMM epilogue that saves the derivative): the
-// two-coefficient sigmoid fit -- no clamp (its polynomial is monotone), 9 full-rate VALU + v_exp_f32 + v_rcp_f32 for the pair;
+// CU and is rounded to bf16 as the next MFMA operand): Phi(x) ~ sigmoid(x * (a0 + a1 x^2)), coefficients from a minimax fit of x * Phi(x)
+// (tools/fit_gelu_sigmoid.py) -- no clamp (the polynomial is monotone), one v_exp_f32 + one v_rcp_f32 + a few plain VALU per element instead
+// of the ~27 issue slots of the erfc form above.  gelu_sig_both returns gelu(x) AND gelu'(x) for the bf16 kernels that need both (weight-gradient
+// recompute, the forward GEMM epilogue that saves the derivative): 9 full-rate VALU + v_exp_f32 + v_rcp_f32 for the pair;
 // |gelu error| <= 2.7e-4, |gelu' error| <= 8.7e-4 (bf16 half-ulp at 1: 2e-3; the reference evaluates GELU in bf16 arithmetic under
 // mixed_bfloat16, utils/common.py:32-64 + backbones/convnext.py:53, i.e. with ~4e-3 per operation).  Round 5: measured 39 issue cycles per
-// pair against 48 for the three-coefficient fit and 45 for two polynomials (tools/micro/valu_rates.hip, profiles/r05_micro.txt).
-// ISEG_GELU_SIG3 (A/B build define) restores the three-coefficient fit (2.6e-5 / 1.1e-4).
-#ifndef ISEG_GELU_SIG3
+// pair against 48 for a three-coefficient fit (2.6e-5 / 1.1e-4) and 45 for two polynomials (tools/micro/valu_rates.hip, profiles/r05_micro.txt).
 __device__ __forceinline__ float gelu_sig(float x) {
-    constexpr float L = -1.4426950408889634f;
+    constexpr float L = -1.4426950408889634f;      // -log2(e): sigmoid(u) = 1 / (1 + exp2(-u * log2 e))
     const float p = fmaf(0.06940208738399849f * L, x * x, 1.600313485784997f * L);
     const float s = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * p));
     return x * s;
 }
+// gelu(x) and d/dx of the SAME approximation: s + x s (1 - s) (a0 + 3 a1 x^2)
 __device__ __forceinline__ void gelu_sig_both(float x, float& y, float& dy) {
     constexpr float L = -1.4426950408889634f;
     const float x2 = x * x;
@@ -273,25 +266,6 @@ __device__ __forceinline__ void gelu_sig_both(float x, float& y, float& dy) {
     y = x * s;
     dy = fmaf(y * dp, 1.0f - s, s);
 }
-#else
-__device__ __forceinline__ float gelu_sig(float x) {
-    const float x2 = fminf(x * x, 64.f);
-    constexpr float L = -1.4426950408889634f;      // -log2(e): sigmoid(u) = 1 / (1 + exp2(-u * log2 e))
-    const float p = fmaf(fmaf(ISEG_GELU_SIG_A2 * L, x2, ISEG_GELU_SIG_A1 * L), x2, ISEG_GELU_SIG_A0 * L);
-    const float s = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * p));
-    return x * s;
-}
-// gelu(x) and d/dx of the SAME approximation: s + x s (1 - s) (a0 + 3 a1 x^2 + 5 a2 x^4)
-__device__ __forceinline__ void gelu_sig_both(float x, float& y, float& dy) {
-    const float x2 = fminf(x * x, 64.f);
-    constexpr float L = -1.4426950408889634f;
-    const float p = fmaf(fmaf(ISEG_GELU_SIG_A2 * L, x2, ISEG_GELU_SIG_A1 * L), x2, ISEG_GELU_SIG_A0 * L);
-    const float s = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * p));
-    const float dp = fmaf(fmaf(5.f * ISEG_GELU_SIG_A2, x2, 3.f * ISEG_GELU_SIG_A1), x2, ISEG_GELU_SIG_A0);
-    y = x * s;
-    dy = fmaf(y * dp, 1.0f - s, s);
-}
-#endif
 
 // Transcendental-free GELU / GELU' for the bf16 kernels that need ONE of the two (round 5; fits: tools/fit_gelu_poly.py).  Every instruction is
 // on the vector pipe's full-rate path (v_fma_f32 / v_mul_f32 / v_add_f32: 2.3-2.7 cycles per wave-instruction at two wavefronts per SIMD; v_exp /
@@ -314,7 +288,6 @@ __device__ __forceinline__ float iseg_opaque_scalar(float v) {
 __device__ __forceinline__ float iseg_fma_half_clamp01(float a, float b) {
     return __builtin_amdgcn_fmed3f(fmaf(a, iseg_opaque_scalar(b), 0.5f), 0.f, 1.f);
 }
-#ifndef ISEG_GELU_NOPOLY
 __device__ __forceinline__ float gelu_poly(float x) {
     const float w = iseg_fma_half_clamp01(x, 1.f / 7.5f) - 0.5f;
     const float t = w * w;
@@ -338,14 +311,6 @@ __device__ __forceinline__ float gelu_poly_grad(float x) {
     r = fmaf(r, t, 6.365922927856445f);
     return fmaf(w, r, 0.5f);
 }
-#else      // A/B build define: the sigmoid forms everywhere (round 4's arithmetic)
-__device__ __forceinline__ float gelu_poly(float x) { return gelu_sig(x); }
-__device__ __forceinline__ float gelu_poly_grad(float x) {
-    float y, d;
-    gelu_sig_both(x, y, d);
-    return d;
-}
-#endif
 
 // exact-erf GELU, as keras.activations.gelu(approximate=False)
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }

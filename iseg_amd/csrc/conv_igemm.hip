@@ -410,13 +410,8 @@ int run_phases(const Problem& q, const iseg_conv_geom* g, hipStream_t stream, co
 }
 
 // ---- LDS-DMA form (conv_igemm_dma.h): forward on the K-contiguous kernel copy, stride-1 data gradient on the Keras kernel ----
-static int igemm_dma_mode() {      // ISEG_IGEMM_DMA: 0 = never, 1 = whenever eligible (default)
-    static const int v = [] { const char* e = getenv("ISEG_IGEMM_DMA"); return e ? atoi(e) : 1; }();
-    return v;
-}
-
 bool dma_conv_eligible(const Problem& q, const iseg_conv_geom* g, int pass) {
-    if (!igemm_dma_mode() || g->groups != 1 || q.p.Cg % 64 != 0 || q.N % 8 != 0 || q.N < 64 || q.M < 64 || q.K < 128) return false;
+    if (g->groups != 1 || q.p.Cg % 64 != 0 || q.N % 8 != 0 || q.N < 64 || q.M < 64 || q.K < 128) return false;
     if (pass == 1 && (g->sh != 1 || g->sw != 1)) return false;      // strided data gradients run by stride phase (pass 3)
     if (((uintptr_t)q.p.src | (uintptr_t)q.B | (uintptr_t)q.D) % 16 || q.ldd % 8 || q.ldb % 8 || q.p.Cs % 8) return false;
     if (q.bias && (uintptr_t)q.bias % 16) return false;
@@ -424,10 +419,7 @@ bool dma_conv_eligible(const Problem& q, const iseg_conv_geom* g, int pass) {
 }
 
 template <int PASS> int run_dma(const Problem& q, void* ws, size_t ws_bytes, hipStream_t stream, const char* what) {
-    static const int force_split = [] { const char* e = getenv("ISEG_IGEMM_DMA_SPLIT"); return e ? atoi(e) : 0; }();      // experiment knobs
-    static const int force_tile = [] { const char* e = getenv("ISEG_IGEMM_DMA_TILE"); return e ? atoi(e) : 0; }();
-    int nsplit = conv_splits(q.M, q.N, q.K, 1);
-    if (force_split > 0 && force_split <= nsplit) nsplit = force_split;
+    const int nsplit = conv_splits(q.M, q.N, q.K, 1);
     int64_t kps = q.K;
     float* slabs = nullptr;
     if (nsplit > 1) {
@@ -460,7 +452,7 @@ template <int PASS> int run_dma(const Problem& q, void* ws, size_t ws_bytes, hip
     };
     struct T256 { enum { WM = 4, WN = 2, NS = 3 }; };
     struct T128 { enum { WM = 2, WN = 2, NS = 2 }; };
-    if (force_tile == 1 || (force_tile == 0 && ceil_div64(q.M, 256) * ceil_div64(q.N, 128) * eff >= 192)) launch(T256{});
+    if (ceil_div64(q.M, 256) * ceil_div64(q.N, 128) * eff >= 192) launch(T256{});
     else launch(T128{});
     if (!slabs) return iseg_check_launch(what);
     iseg_gemm_args ga{};
@@ -560,7 +552,7 @@ extern "C" int iseg_conv2d_igemm_fwd_kt(const void* x, const void* wt, const flo
 }
 
 extern "C" int iseg_conv2d_igemm_fwd_kt_supported(const iseg_conv_geom* g, int dtype) {
-    if (!geom_ok(g) || dtype != ISEG_BF16 || !igemm_dma_mode()) return 0;
+    if (!geom_ok(g) || dtype != ISEG_BF16) return 0;
     return g->groups == 1 && g->Cin % 64 == 0 && g->Cout % 8 == 0 && g->Cout >= 64 && (int64_t)g->N * g->Ho * g->Wo >= 64 &&
            (int64_t)g->KH * g->KW * g->Cin >= 128;
 }

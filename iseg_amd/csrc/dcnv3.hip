@@ -880,8 +880,7 @@ extern "C" int iseg_dcnv3_fwd_ld(const void* x, const void* offset, const void* 
 #define DCN_FWD_PIPE(T, CG)                                                                                                         \
     hipLaunchKernelGGL((dcnv3_fwd_pipe_kernel<T, CG>), dim3(lane_blocks(lanes)), dim3(256), 0, stream, (const T*)x, (const T*)offset, \
                        (const T*)mask, (T*)y, g)
-    static const bool allow_pipe = [] { const char* e = getenv("ISEG_DCN_FWD_PIPE"); return !e || atoi(e) != 0; }();
-    const bool pipe = allow_pipe && v8 && (Cg == 8 || Cg == 16) && kh * kw <= DCN_PMAX;
+    const bool pipe = v8 && (Cg == 8 || Cg == 16) && kh * kw <= DCN_PMAX;
     if (dtype == ISEG_BF16) {
         if (pipe && Cg == 16) DCN_FWD_PIPE(bf16_t, 16);
         else if (pipe) DCN_FWD_PIPE(bf16_t, 8);
@@ -910,7 +909,7 @@ extern "C" size_t iseg_dcnv3_bwd_workspace_bytes(int N, int H, int W, int G, int
     if (!dcn_window(g, &wn)) return fallback;
     size_t so, fo;
     const size_t win = dcn_win_bytes(g, wn, &so, &fo);
-    return win > fallback ? win : fallback;      // (ISEG_DCN_BWD_WIN=0 sends window geometries down the general route too)
+    return win > fallback ? win : fallback;      // (the larger of the two, so a workspace sized by it serves either route)
 }
 
 extern "C" int iseg_dcnv3_bwd(const void* x, const void* offset, const void* mask, const void* dy, float* dx_f32, void* doffset,
@@ -945,8 +944,7 @@ extern "C" int iseg_dcnv3_bwd_ld(const void* x, const void* offset, const void* 
     if (rc != ISEG_OK) return rc;
     ISEG_REQUIRE(dtype != ISEG_BF16 || (uintptr_t)doffset % 4 == 0, "iseg_dcnv3_bwd_ld: doffset must be 4-byte aligned");
     DcnWin wn;
-    static const bool allow_win = [] { const char* e = getenv("ISEG_DCN_BWD_WIN"); return !e || atoi(e) != 0; }();
-    if (allow_win && dcn_window(g, &wn)) {
+    if (dcn_window(g, &wn)) {
         size_t side_off, flag_off;
         const size_t need = dcn_win_bytes(g, wn, &side_off, &flag_off);
         if (!ws || ws_bytes < need) {

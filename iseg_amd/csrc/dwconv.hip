@@ -2,8 +2,8 @@
 // dilation d) -- the 7x7 depthwise of backbones/convnext.py:25,50 (dilated by build_dilated_convnext :245-266)
 // and the 3x3 depthwise of layers/dcn_v3/dcn_v3.py.  49 FMA per element but only 4 B of HBM traffic: the kernels
 // are limited by how many L1/L2 loads they keep in flight, so:
-//   * a lane owns CV (4 or 8) consecutive channels (one 8/16-B load per pixel) and TW output pixels along W, and slides a
-//     register window over the input row so each loaded pixel feeds up to KW taps;
+//   * a lane owns CV consecutive channels (8 in the forward, 4 in the weight gradient: one 8/16-B load per pixel) and TW output
+//     pixels along W, and slides a register window over the input row so each loaded pixel feeds up to KW taps;
 //   * every load is issued unconditionally from a clamped address and zeroed by a select afterwards (no divergent
 //     branch between loads, so a whole kernel row's loads are in flight together); interior tiles skip the selects;
 //   * weights of the block's channel slab sit in LDS as fp32 (the fp32 master kernel is read directly);
@@ -14,7 +14,6 @@
 //     grid (fixed-order partial sums, deterministic).
 #include "common.h"
 #include "iseg_hip.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -33,13 +32,6 @@ template <> __device__ __forceinline__ void loadv<bf16_t, 4>(const bf16_t* p, fl
 template <class T, int CV> __device__ __forceinline__ void storev(T* p, const float* in);
 template <> __device__ __forceinline__ void storev<float, 8>(float* p, const float* in) { store8<float>(p, in); }
 template <> __device__ __forceinline__ void storev<bf16_t, 8>(bf16_t* p, const float* in) { store8<bf16_t>(p, in); }
-template <> __device__ __forceinline__ void storev<float, 4>(float* p, const float* in) { Vec16<float>::store(p, in); }
-template <> __device__ __forceinline__ void storev<bf16_t, 4>(bf16_t* p, const float* in) {
-    bf16x4 v;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = (bf16_t)in[i];
-    *reinterpret_cast<bf16x4*>(p) = v;
-}
 
 // channel groups (of CV channels) per block slab: the largest divisor of C/CV that is <= maxg
 static inline int groups_per_slab(int C, int CV, int maxg) {
@@ -96,8 +88,7 @@ __device__ __forceinline__ void dw_accumulate_row(const T* __restrict__ xr, cons
     }
 }
 
-// ROLLED: keep the kernel-row loop rolled so only one row's loads are live (fewer VGPRs, more waves per SIMD)
-template <class T, int K, int CV, bool DIL1, bool ROLLED>
+template <class T, int K, int CV, bool DIL1>
 __global__ __launch_bounds__(256) void dwconv_fwd_kernel(const T* __restrict__ x, const float* __restrict__ w,
                                                          const float* __restrict__ bias, const T* __restrict__ add,
                                                          T* __restrict__ y, int N, int H, int W, int C, int dil, int pad_t,
@@ -143,13 +134,9 @@ __global__ __launch_bounds__(256) void dwconv_fwd_kernel(const T* __restrict__ x
                 else dw_accumulate_row<T, K, CV, DIL1, true>(xr, wrow, w0, pad_l, W, C, dil, sc, acc);
             }
         };
-        if (ROLLED) {
+        // the kernel-row loop stays rolled so only one row's loads are live (fewer VGPRs, more waves per SIMD)
 #pragma unroll 1
-            for (int kh = 0; kh < K; ++kh) row(kh);
-        } else {
-#pragma unroll
-            for (int kh = 0; kh < K; ++kh) row(kh);
-        }
+        for (int kh = 0; kh < K; ++kh) row(kh);
 #pragma unroll
         for (int t = 0; t < TW; ++t) {
             const int ow = w0 + t;
@@ -578,15 +565,6 @@ __global__ __launch_bounds__(256) void dwconv_bwd_weight_lds_kernel(const T* __r
     }
 }
 
-// experiment knobs (read once): ISEG_DW_FWD_CV / ISEG_DW_BW_CV in {4,8}, ISEG_DW_FWD_ROLLED in {0,1}
-static int env_int(const char* name, int dflt) {
-    const char* v = getenv(name);
-    return v ? atoi(v) : dflt;
-}
-static int fwd_cv() { static int v = env_int("ISEG_DW_FWD_CV", 8); return v == 4 ? 4 : 8; }
-static int fwd_rolled() { static int v = env_int("ISEG_DW_FWD_ROLLED", 1); return v != 0; }
-static int bw_cv() { static int v = env_int("ISEG_DW_BW_CV", 4); return v == 8 ? 8 : 4; }
-
 // DMA-tiled bf16 weight gradient (K x K, dil == 1, C % 32 == 0): the variant the ConvNeXt stages take.
 //   * a workgroup owns a 32-channel slab and walks (image, row band, column band) tiles; the x tile (with halo) and the dy tile
 //     go HBM -> LDS by global_load_lds_dwordx4 (one instruction = 16 pixels x 64 B; halo and padding pixels read a zero page), so
@@ -766,12 +744,10 @@ struct BwDmaGeom {
     size_t lds_bytes;
 };
 
-static int use_bw_dma() { static int v = env_int("ISEG_DW_BW_DMA", 1); return v != 0; }
-
 static BwDmaGeom bw_dma_geom(int N, int H, int W, int C, int K, int dil, size_t elem) {
     BwDmaGeom g;
     g.ok = 0;
-    if (!use_bw_dma() || elem != 2 || K != 7 || dil != 1 || C % 32 != 0) return g;
+    if (elem != 2 || K != 7 || dil != 1 || C % 32 != 0) return g;
     g.twd = W <= 16 ? 16 : 32;
     const int t8 = (H + 7) / 8, t9 = (H + 8) / 9;
     g.th = t9 < t8 ? 9 : 8;
@@ -782,8 +758,7 @@ static BwDmaGeom bw_dma_geom(int N, int H, int W, int C, int K, int dil, size_t 
     const int64_t ntiles = (int64_t)N * g.tiles_h * g.tiles_w;
     if (ntiles >= (1ll << 30)) return g;
     // two resident workgroups per CU: ~512 in flight; every workgroup of a slab gets the same number of tiles (+-1)
-    static const int slots = env_int("ISEG_DW_BW_DMA_SLOTS", 512);
-    int64_t cap = slots / g.slabs;
+    int64_t cap = 512 / g.slabs;
     if (cap < 8) cap = 8;
     const int64_t rounds = ceil_div64(ntiles, cap);
     int64_t bx = ceil_div64(ntiles, rounds);
@@ -960,11 +935,9 @@ __global__ __launch_bounds__(256, 2) void dwconv_fwd_dma_kernel(const bf16_t* __
     }
 }
 
-static int use_fwd_dma() { static int v = env_int("ISEG_DW_FWD_DMA", 1); return v != 0; }
-
 static bool launch_fwd_dma(const void* x, const float* w, const float* bias, const void* add, void* y, int N, int H, int W, int C, int K,
                            int dil, int pad_t, int pad_l, int flip, hipStream_t s) {
-    if (!use_fwd_dma() || K != 7 || dil != 1 || C % 32 != 0) return false;
+    if (K != 7 || dil != 1 || C % 32 != 0) return false;
     // tile shapes (rows x columns, output pixels per lane): 16 x 32 (8) for the wide planes, 8 x 32 (4) when that leaves fewer than two tiles per
     // resident workgroup (32 x 32 planes: three smaller workgroups per CU overlap each other's fills), 16 x 16 (4) for 16-pixel planes.
     // Measured (16 images, us, LDS kernel -> this one): 128x128x96 70.4 -> 53.8, 64x64x192 37.2 -> 33.9, 16x16x768 14.5 -> 12.1; 32x32x384 with
@@ -975,11 +948,6 @@ static bool launch_fwd_dma(const void* x, const float* w, const float* bias, con
     const int slabs = C / 32;
     int two = W <= 16 ? 4 : 8, th = 16;
     if (two == 8 && (int64_t)N * ((H + 15) / 16) * ((W + 31) / 32) * slabs < 1536) {      // (64x64x192: 33.6 -> 32.3 us; 128x128x96 would lose: 53.0 -> 58.5)
-        two = 4;
-        th = 8;
-    }
-    static const int force_small = env_int("ISEG_DW_FWD_SMALL", 0);      // experiment: the 8 x 32 (4) tile everywhere
-    if (force_small && W > 16) {
         two = 4;
         th = 8;
     }
@@ -1005,33 +973,20 @@ static bool launch_fwd_dma(const void* x, const float* w, const float* bias, con
 }
 
 struct BwGeom {
-    int cv, gs, rt, slabs, wseg, ipl, bx;
+    int gs, rt, slabs, wseg, ipl, bx;
     int lds, tiles_h, tiles_w;   // LDS-tiled variant
     size_t lds_bytes;
 };
-
-static int use_bw_lds() { static int v = env_int("ISEG_DW_BW_LDS", 1); return v != 0; }
-static int bw_lds_min_w() { static int v = env_int("ISEG_DW_BW_LDS_MINW", 48); return v; }
 
 static BwGeom bw_geom(int N, int H, int W, int C, int K, int dil, size_t elem) {
     BwGeom g;
     g.lds = 0;
     // bf16 takes the register-batched kernel below at every plane size (measured at 64x64x192: 69 us vs 88 us for the LDS tiles, equal
     // at 128x128x96); the LDS-tiled variant serves fp32 storage
-    static const int lds_bf16 = env_int("ISEG_DW_BW_LDS_BF16", 0);
-    if (use_bw_lds() && dil == 1 && C % 8 == 0 && W >= bw_lds_min_w() && (elem != 2 || lds_bf16)) {
-        // channel slab of <= 6 groups (48 channels): 6 x K x rt lanes.  Small planes (W <= 32: one tile spans the row) take
-        // the widest slab whose lane rows still cover the whole image height, so one tile = one image plane.
-        static const int max_groups = env_int("ISEG_DW_BW_LDS_GROUPS", 3);   // measured 1..6 at 128x128x96 / 64x64x192: 163/107, 155/101, 137/88, 141/99, 144/92 us
-        int gs = groups_per_slab(C, 8, max_groups);
-        if (W <= BWW) {
-            gs = 1;
-            for (int cand = 6; cand >= 1; --cand)
-                if ((C / 8) % cand == 0 && 256 / (cand * K) >= H) {
-                    gs = cand;
-                    break;
-                }
-        }
+    if (elem != 2 && dil == 1 && C % 8 == 0 && W >= 48) {      // (narrower planes: the register-batched kernel)
+        // channel slab of <= 3 groups (24 channels): 3 x K x rt lanes.  Measured 1..6 groups at 128x128x96 / 64x64x192:
+        // 163/107, 155/101, 137/88, 141/99, 144/92 us
+        const int gs = groups_per_slab(C, 8, 3);
         int rt = 256 / (gs * K);
         if (rt > H) rt = H;
         const size_t tile_bytes = ((size_t)(rt + K - 1) * (BWW + K - 1) + (size_t)rt * BWW) * gs * 8 * elem;
@@ -1039,7 +994,6 @@ static BwGeom bw_geom(int N, int H, int W, int C, int K, int dil, size_t elem) {
         const size_t bytes = tile_bytes > slab_bytes ? tile_bytes : slab_bytes;
         if (rt >= 1 && bytes <= 80 * 1024) {
             g.lds = 1;
-            g.cv = 8;
             g.gs = gs;
             g.rt = rt;
             g.slabs = (C / 8) / gs;
@@ -1055,18 +1009,18 @@ static BwGeom bw_geom(int N, int H, int W, int C, int K, int dil, size_t elem) {
             return g;
         }
     }
-    g.cv = (C % 8 == 0 && bw_cv() == 8) ? 8 : 4;
-    g.gs = groups_per_slab(C, g.cv, g.cv == 8 ? 16 : 12);
+    // register-batched kernel: 4 channels per lane
+    g.gs = groups_per_slab(C, 4, 12);
     g.rt = 256 / (g.gs * K);
     if (g.rt < 1) g.rt = 1;
-    g.slabs = (C / g.cv) / g.gs;
+    g.slabs = (C / 4) / g.gs;
     g.wseg = W <= 32 ? W : 32;
     const int nseg = (W + g.wseg - 1) / g.wseg;
     const int64_t items = (int64_t)N * H * nseg;
     // aim at ~1024 blocks in total: enough waves to hide L2 latency, small enough partial buffers.  The register-batched bf16 path
     // (W <= 32) keeps ~70 loads in flight per lane by itself and runs 2 waves per SIMD: ~512 blocks = one resident round
-    const bool batched = elem == 2 && g.cv == 4 && dil == 1 && g.wseg <= BWSEG;
-    int64_t target = (batched ? env_int("ISEG_DW_BW_BLOCKS", 512) : 1024) / g.slabs;
+    const bool batched = elem == 2 && dil == 1 && g.wseg <= BWSEG;
+    int64_t target = (batched ? 512 : 1024) / g.slabs;
     if (target < (batched ? 8 : 64)) target = batched ? 8 : 64;
     int64_t ipl = ceil_div64(items, (int64_t)g.rt * target);
     if (ipl < 1) ipl = 1;
@@ -1076,9 +1030,10 @@ static BwGeom bw_geom(int N, int H, int W, int C, int K, int dil, size_t elem) {
     return g;
 }
 
-template <class T, int K, int CV>
+template <class T, int K>
 int launch_fwd(const void* x, const float* w, const float* bias, const void* add, void* y, int N, int H, int W, int C, int dil,
                int pad_t, int pad_l, int flip, hipStream_t s) {
+    constexpr int CV = 8;
     const int gs = groups_per_slab(C, CV, 16);
     const int pt = 256 / gs;
     const int slabs = (C / CV) / gs;
@@ -1087,21 +1042,16 @@ int launch_fwd(const void* x, const float* w, const float* bias, const void* add
     const int64_t cap = 256 * 8 / slabs > 1 ? 256 * 8 / slabs : 1;
     if (bx > cap) bx = cap;
     const size_t lds = (size_t)K * K * gs * CV * sizeof(float);
-#define DW_LAUNCH(D1, RL)                                                                                                         \
-    hipLaunchKernelGGL((dwconv_fwd_kernel<T, K, CV, D1, RL>), dim3((unsigned)bx, slabs), dim3(256), lds, s, (const T*)x, w, bias, \
-                       (const T*)add, (T*)y, N, H, W, C, dil, pad_t, pad_l, flip, gs, pt)
-    if (dil == 1) {
-        if (fwd_rolled()) DW_LAUNCH(true, true);
-        else DW_LAUNCH(true, false);
-    } else {
-        DW_LAUNCH(false, true);
-    }
-#undef DW_LAUNCH
+    if (dil == 1)
+        hipLaunchKernelGGL((dwconv_fwd_kernel<T, K, CV, true>), dim3((unsigned)bx, slabs), dim3(256), lds, s, (const T*)x, w, bias,
+                           (const T*)add, (T*)y, N, H, W, C, dil, pad_t, pad_l, flip, gs, pt);
+    else
+        hipLaunchKernelGGL((dwconv_fwd_kernel<T, K, CV, false>), dim3((unsigned)bx, slabs), dim3(256), lds, s, (const T*)x, w, bias,
+                           (const T*)add, (T*)y, N, H, W, C, dil, pad_t, pad_l, flip, gs, pt);
     return iseg_check_launch("iseg_dwconv2d");
 }
 
-static int use_lds() { static int v = env_int("ISEG_DW_LDS", 1); return v != 0; }
-// channel groups (of 8) per workgroup slab; 0 = automatic.  Measured at the four ConvNeXt-T stages (16 images, us per launch):
+// channel groups (of 8) per workgroup slab.  Measured at the four ConvNeXt-T stages (16 images, us per launch):
 //   groups      2      3      4      6      8
 //   128x128x96  79.8   89.8   69.8   79.8   79.9
 //   64x64x192   36.1   53.6   39.4   49.8   49.2
@@ -1109,12 +1059,11 @@ static int use_lds() { static int v = env_int("ISEG_DW_LDS", 1); return v != 0; 
 //   16x16x768   14.3   14.4   14.9   15.9   15.8
 // Power-of-two slabs give square-ish pixel tiles (32x16 / 16x16: halo amplification 1.6 / 1.9 instead of 2.2 at 10x16) and keep
 // all 256 lanes busy; the widest planes prefer 64-byte pixel pieces (4 groups) for their L2 -> L1 line use.
-static int fwd_lds_groups() { static int v = env_int("ISEG_DW_LDS_GROUPS", 0); return v < 0 ? 0 : (v > 16 ? 16 : v); }
 
 template <class T, int K>
 bool launch_fwd_lds(const void* x, const float* w, const float* bias, const void* add, void* y, int N, int H, int W, int C, int dil,
                     int pad_t, int pad_l, int flip, hipStream_t s) {
-    const int want = fwd_lds_groups() ? fwd_lds_groups() : ((int64_t)H * W >= 128 * 128 ? 4 : 2);
+    const int want = (int64_t)H * W >= 128 * 128 ? 4 : 2;
     const int gs = groups_per_slab(C, 8, want);
     const int TH = (256 / gs) / (TWB / TW);
     if (TH < 1) return false;
@@ -1137,15 +1086,14 @@ bool launch_fwd_lds(const void* x, const float* w, const float* bias, const void
 template <class T, int K>
 int launch_fwd_cv(const void* x, const float* w, const float* bias, const void* add, void* y, int N, int H, int W, int C, int dil,
                   int pad_t, int pad_l, int flip, hipStream_t s) {
-    if (use_lds() && C % 8 == 0 && launch_fwd_lds<T, K>(x, w, bias, add, y, N, H, W, C, dil, pad_t, pad_l, flip, s))
-        return iseg_check_launch("iseg_dwconv2d");
-    if (C % 8 == 0 && fwd_cv() == 8) return launch_fwd<T, K, 8>(x, w, bias, add, y, N, H, W, C, dil, pad_t, pad_l, flip, s);
-    return launch_fwd<T, K, 4>(x, w, bias, add, y, N, H, W, C, dil, pad_t, pad_l, flip, s);
+    if (launch_fwd_lds<T, K>(x, w, bias, add, y, N, H, W, C, dil, pad_t, pad_l, flip, s)) return iseg_check_launch("iseg_dwconv2d");
+    return launch_fwd<T, K>(x, w, bias, add, y, N, H, W, C, dil, pad_t, pad_l, flip, s);
 }
 
-template <class T, int K, int CV>
+template <class T, int K>
 void launch_bw(const void* x, const void* dy, float* ws, int N, int H, int W, int C, int dil, int pad_t, int pad_l, const BwGeom& g,
                hipStream_t s) {
+    constexpr int CV = 4;
     const size_t lds = (size_t)g.rt * (K * K + 1) * g.gs * CV * sizeof(float);
     if (dil == 1)
         hipLaunchKernelGGL((dwconv_bwd_weight_kernel<T, K, CV, true>), dim3(g.bx, g.slabs), dim3(256), lds, s, (const T*)x,
@@ -1153,13 +1101,6 @@ void launch_bw(const void* x, const void* dy, float* ws, int N, int H, int W, in
     else
         hipLaunchKernelGGL((dwconv_bwd_weight_kernel<T, K, CV, false>), dim3(g.bx, g.slabs), dim3(256), lds, s, (const T*)x,
                            (const T*)dy, ws, N, H, W, C, dil, pad_t, pad_l, g.gs, g.rt, g.wseg, g.ipl);
-}
-
-template <class T, int K>
-void launch_bw_cv(const void* x, const void* dy, float* ws, int N, int H, int W, int C, int dil, int pad_t, int pad_l, const BwGeom& g,
-                  hipStream_t s) {
-    if (g.cv == 8) launch_bw<T, K, 8>(x, dy, ws, N, H, W, C, dil, pad_t, pad_l, g, s);
-    else launch_bw<T, K, 4>(x, dy, ws, N, H, W, C, dil, pad_t, pad_l, g, s);
 }
 
 }  // namespace
@@ -1178,7 +1119,7 @@ extern "C" int iseg_dwconv2d_fwd(const void* x, const float* w, const float* bia
     (K == 7   ? launch_fwd_cv<T, 7>(x, w, bias, add, y, N, H, W, C, dil, pad_t, pad_l, flip, stream)          \
      : K == 5 ? launch_fwd_cv<T, 5>(x, w, bias, add, y, N, H, W, C, dil, pad_t, pad_l, flip, stream)          \
               : launch_fwd_cv<T, 3>(x, w, bias, add, y, N, H, W, C, dil, pad_t, pad_l, flip, stream))
-    // 7 x 7, bf16, C % 32 == 0: the banded products on the matrix cores (dwconv_mfma.hip, round 5; ISEG_DW_MFMA=0 keeps the VALU kernels)
+    // 7 x 7, bf16, C % 32 == 0: the banded products on the matrix cores where dwconv_mfma.hip finds them faster (round 5)
     if (dtype == ISEG_BF16 && iseg_dwconv7_mfma_launch(x, w, bias, add, y, N, H, W, C, K, dil, pad_t, pad_l, flip, stream))
         return iseg_check_launch("iseg_dwconv2d (mfma)");
     if (dtype == ISEG_BF16 && launch_fwd_dma(x, w, bias, add, y, N, H, W, C, K, dil, pad_t, pad_l, flip, stream))
@@ -1220,27 +1161,21 @@ extern "C" int iseg_dwconv2d_bwd_weight(const void* x, const void* dy, float* dw
     if (gd.ok) {
         launch_bw_dma(x, dy, (float*)ws, N, H, W, C, pad_t, pad_l, gd, stream);
     } else if (g.lds) {
-#define DW_BWL(T, KK)                                                                                                               \
-    hipLaunchKernelGGL((dwconv_bwd_weight_lds_kernel<T, KK>), dim3(g.bx, g.slabs), dim3(256), g.lds_bytes, stream, (const T*)x,         \
-                       (const T*)dy, (float*)ws, N, H, W, C, pad_t, pad_l, g.gs, g.rt, g.tiles_h, g.tiles_w)
-        if (dtype == ISEG_BF16) {
-            if (K == 7) DW_BWL(bf16_t, 7);
-            else if (K == 5) DW_BWL(bf16_t, 5);
-            else DW_BWL(bf16_t, 3);
-        } else {
-            if (K == 7) DW_BWL(float, 7);
-            else if (K == 5) DW_BWL(float, 5);
-            else DW_BWL(float, 3);
-        }
+#define DW_BWL(KK)                                                                                                                   \
+    hipLaunchKernelGGL((dwconv_bwd_weight_lds_kernel<float, KK>), dim3(g.bx, g.slabs), dim3(256), g.lds_bytes, stream, (const float*)x, \
+                       (const float*)dy, (float*)ws, N, H, W, C, pad_t, pad_l, g.gs, g.rt, g.tiles_h, g.tiles_w)
+        if (K == 7) DW_BWL(7);      // (fp32 storage only: see bw_geom)
+        else if (K == 5) DW_BWL(5);
+        else DW_BWL(3);
 #undef DW_BWL
     } else if (dtype == ISEG_BF16) {
-        if (K == 7) launch_bw_cv<bf16_t, 7>(x, dy, (float*)ws, N, H, W, C, dil, pad_t, pad_l, g, stream);
-        else if (K == 5) launch_bw_cv<bf16_t, 5>(x, dy, (float*)ws, N, H, W, C, dil, pad_t, pad_l, g, stream);
-        else launch_bw_cv<bf16_t, 3>(x, dy, (float*)ws, N, H, W, C, dil, pad_t, pad_l, g, stream);
+        if (K == 7) launch_bw<bf16_t, 7>(x, dy, (float*)ws, N, H, W, C, dil, pad_t, pad_l, g, stream);
+        else if (K == 5) launch_bw<bf16_t, 5>(x, dy, (float*)ws, N, H, W, C, dil, pad_t, pad_l, g, stream);
+        else launch_bw<bf16_t, 3>(x, dy, (float*)ws, N, H, W, C, dil, pad_t, pad_l, g, stream);
     } else {
-        if (K == 7) launch_bw_cv<float, 7>(x, dy, (float*)ws, N, H, W, C, dil, pad_t, pad_l, g, stream);
-        else if (K == 5) launch_bw_cv<float, 5>(x, dy, (float*)ws, N, H, W, C, dil, pad_t, pad_l, g, stream);
-        else launch_bw_cv<float, 3>(x, dy, (float*)ws, N, H, W, C, dil, pad_t, pad_l, g, stream);
+        if (K == 7) launch_bw<float, 7>(x, dy, (float*)ws, N, H, W, C, dil, pad_t, pad_l, g, stream);
+        else if (K == 5) launch_bw<float, 5>(x, dy, (float*)ws, N, H, W, C, dil, pad_t, pad_l, g, stream);
+        else launch_bw<float, 3>(x, dy, (float*)ws, N, H, W, C, dil, pad_t, pad_l, g, stream);
     }
     const int n = (K * K + 1) * C;
     if (arena) iseg_deferred_push((const float*)ws, g.bx, n, n, dw, db, K * K * C, 1.f, stream);

@@ -29,7 +29,6 @@
 // 672 MFMAs, 128 accumulator writes, 32 tile reads.
 #include "common.h"
 #include "iseg_hip.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -328,14 +327,6 @@ __global__ __launch_bounds__(64 * WAVES) void dwconv7_mfma_kernel(const bf16_t* 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the dummy DMA of the last iteration must not outlive the workgroup's LDS
 }
 
-int dw_mfma_mode() {
-    static const int v = [] {
-        const char* e = getenv("ISEG_DW_MFMA");
-        return e ? atoi(e) : 1;
-    }();
-    return v;
-}
-
 }  // namespace
 
 static bool dwm_eligible(const void* x, const void* add, const void* y, int C, int K, int dil) {
@@ -365,14 +356,13 @@ static bool dwm_launch(const void* x, const float* w, const float* bias, const v
 // kernel -> this one (tools/kbench_dw_mfma.py, profiles/r05_dw_mfma.txt): 128 x 128 x 96 forward 54.0 -> 48.9, data gradient 61.6 -> 53.4;
 // 64 x 64 x 192 31.2 -> 32.5; 32 x 32 x 384 17.3 -> 21.3; 16 x 16 x 768 11.2 -> 13.5.  v_mfma_f32_4x4x4_16b_bf16 issues every 16 cycles (64 MAC per
 // clock and SIMD, 37 of them taps): 1.4x the packed-FMA kernels' arithmetic rate, and the kernel's phases (fill, transposition, products, write-out)
-// do not overlap inside its one workgroup per CU -- it wins where a workgroup walks >= 8 tiles.  ISEG_DW_MFMA: 0 = never, 1 = automatic (default),
-// 2 = whenever eligible.
+// do not overlap inside its one workgroup per CU -- it wins where a workgroup walks >= 8 tiles.  iseg_dwconv2d7_mfma below launches it whenever
+// eligible.
 bool iseg_dwconv7_mfma_launch(const void* x, const float* w, const float* bias, const void* add, void* y, int N, int H, int W, int C, int K, int dil,
                               int pad_t, int pad_l, int flip, hipStream_t s) {
-    const int mode = dw_mfma_mode();
-    if (!mode || !dwm_eligible(x, add, y, C, K, dil)) return false;
+    if (!dwm_eligible(x, add, y, C, K, dil)) return false;
     const int64_t units = (int64_t)N * ((H + TR - 1) / TR) * ((W + TC - 1) / TC) * (C / CH);
-    if (mode == 1 && units < 2048) return false;
+    if (units < 2048) return false;
     return dwm_launch(x, w, bias, add, y, N, H, W, C, pad_t, pad_l, flip, s);
 }
 

@@ -50,47 +50,10 @@ void gemm_log(const iseg_gemm_args* g, int nsplit) {
 }
 }  // namespace
 namespace iseg_mm {
-int long_k_tile() {
-    static const int v = [] {
-        const char* e = getenv("ISEG_GEMM_BK");
-        return (e && atoi(e) == 64) ? 64 : 128;
-    }();
-    return v;
-}
-int dma_mode() {
-    static const int v = [] {
-        const char* e = getenv("ISEG_GEMM_DMA");
-        return e ? atoi(e) : 1;
-    }();
-    return v;
-}
 int dma_bk32() {
     static const int v = [] {
         const char* e = getenv("ISEG_GEMM_DMA_BK32");
         return e ? atoi(e) : 1;
-    }();
-    return v;
-}
-int dma_min_k() {
-    static const int v = [] {
-        const char* e = getenv("ISEG_GEMM_DMA_MIN_K");
-        const int k = e ? atoi(e) : 32;
-        return k < 16 ? 16 : k;
-    }();
-    return v;
-}
-int dma_tn_mode() {
-    static const int v = [] {
-        const char* e = getenv("ISEG_GEMM_DMA_TN");
-        return e ? atoi(e) : 1;
-    }();
-    return v;
-}
-int tile_waves() {
-    static const int v = [] {
-        const char* e = getenv("ISEG_GEMM_WAVES");
-        const int w = e ? atoi(e) : 8;
-        return (w == 4 || w == 16) ? w : 8;
     }();
     return v;
 }
@@ -186,7 +149,7 @@ int choose_split(const iseg_gemm_args* g, int tile) {
     const int64_t tiles = ceil_div64(g->M + (g->colsum_out ? 1 : 0), tile) * ceil_div64(g->N, tile);
     if (tiles >= 256 || g->K < 2048 || g->batch > 1 || g->b_group_rows > 0) return 1;
     // the LDS-DMA pipeline keeps several K-tiles in flight per workgroup: half-filled grids are better left unsplit
-    if (g->in_dtype == ISEG_BF16 && tiles >= 96 && iseg_mm::dma_mode() && iseg_mm::dma_eligible(g, 128)) return 1;
+    if (g->in_dtype == ISEG_BF16 && tiles >= 96 && iseg_mm::dma_eligible(g, 128)) return 1;
     // two 128x128 workgroups fit a CU: the grid must stay within ONE resident round of 512 (measured: 42 splits of a 12-tile
     // weight gradient = 504 workgroups 61.5 us, 43 splits = 516 workgroups 74.7 us)
     int64_t want = 512 / tiles;
@@ -219,7 +182,7 @@ extern "C" int iseg_gemm_variant(const iseg_gemm_args* g) {
     const int nsplit = iseg_gemm_splits(g);
     const int64_t kps = nsplit > 1 ? ceil_div64(ceil_div64(g->K, nsplit), 128) * 128 : g->K;
     if (nsplit > 1 && iseg_mm::dma_tn_form(g)) return iseg_mm::dma_tn_form(g);      // 7 / 8: the weight-gradient LDS-DMA kernel
-    if (!iseg_mm::dma_mode() || !iseg_mm::dma_eligible(g, kps)) return 0;
+    if (!iseg_mm::dma_eligible(g, kps)) return 0;
     return iseg_mm::dma_form(g, (int)ceil_div64(g->K, kps));
 }
 
@@ -254,7 +217,7 @@ extern "C" int iseg_gemm(const iseg_gemm_args* g, void* ws, size_t ws_bytes, hip
     }
     if (g->b_group_rows > 0) {
         if (!(g->in_dtype == ISEG_BF16 && g->a_kcontig && g->b_kcontig && batch == 1 && g->split_k <= 1 && g->b_group_rows % 256 == 0 &&
-              g->b_group_stride % 8 == 0 && iseg_mm::dma_mode() && iseg_mm::dma_eligible(g, g->K))) {
+              g->b_group_stride % 8 == 0 && iseg_mm::dma_eligible(g, g->K))) {
             iseg_set_error("iseg_gemm: B per row group needs the LDS-DMA path (bf16, K-contiguous operands, K %% 64 == 0, aligned) with "
                            "b_group_rows %% 256 == 0, no split and no batch");
             return ISEG_ERR_UNSUPPORTED;
@@ -330,8 +293,7 @@ extern "C" int iseg_gemm_tn_pair_splits(const iseg_gemm_args* g0, const iseg_gem
     if (!g0 || !g1) return 0;
     iseg_gemm_args a = *g0, b = *g1;
     a.split_k = b.split_k = 0;
-    static const int off = [] { const char* e = getenv("ISEG_GEMM_TN_PAIR"); return e && atoi(e) == 0; }();
-    return off ? 0 : iseg_mm::gemm_bf16_tn_pair_split(&a, &b);
+    return iseg_mm::gemm_bf16_tn_pair_split(&a, &b);
 }
 
 extern "C" int iseg_gemm_tn_pair(const iseg_gemm_args* g0, void* ws0, size_t ws0_bytes, const iseg_gemm_args* g1, void* ws1, size_t ws1_bytes,

@@ -81,15 +81,15 @@ template <int EK> __device__ __forceinline__ Epi epi_known(Epi e) {
 // sixteen zero bytes in device memory: what a lane past the K tail asks the DMA for
 static __device__ __attribute__((aligned(16))) unsigned int dma_zero_chunk[4] = {0u, 0u, 0u, 0u};
 
-int dma_min_k();      // ISEG_GEMM_DMA_MIN_K (default 32): shortest reduction the pipeline takes (262144 x 96 x 48: 22.4 -> 19.4 us)
+// shortest reduction the pipeline takes (262144 x 96 x 48: 22.4 -> 19.4 us against a floor of 16).  functional._DMA_MIN_K repeats it.
+constexpr int dma_min_k = 32;
 
 inline int epi_kind(const Epi& e, const float* slabs) {
     if (slabs || e.alpha != 1.f || e.accumulate) return EK_ANY;
     if (e.act == ISEG_ACT_GELU && e.pre_out && e.pre_deriv && e.bias && !e.residual && !e.aux && !e.colscale) return EK_GELU_DERIV;
     if (e.act == ISEG_ACT_MUL_AUX && e.aux && !e.bias && !e.pre_out && !e.residual && !e.colscale) return EK_MUL_AUX;
     if (e.act == ISEG_ACT_NONE && e.bias && e.residual && !e.aux && !e.pre_out) return EK_BIAS_RESIDUAL;
-    static const bool bias_kind = [] { const char* v = getenv("ISEG_GEMM_EK_BIAS"); return !v || atoi(v) != 0; }();      // 0: A/B against the run-time epilogue
-    if (bias_kind && e.act == ISEG_ACT_NONE && e.bias && !e.residual && !e.aux && !e.pre_out && !e.colscale && !e.rowscale) return EK_BIAS;
+    if (e.act == ISEG_ACT_NONE && e.bias && !e.residual && !e.aux && !e.pre_out && !e.colscale && !e.rowscale) return EK_BIAS;
     if (e.act == ISEG_ACT_NONE && !e.bias && !e.residual && !e.aux && !e.pre_out && !e.colscale && !e.rowscale) return EK_PLAIN;
     return EK_ANY;
 }
@@ -104,7 +104,7 @@ inline int epi_kind(const Epi& e, const float* slabs) {
 __device__ __forceinline__ int key32(int quad) { return (0x6C >> (2 * (quad & 3))) & 3; }      // {0, 3, 2, 1}
 
 // FM: 16-row blocks per wavefront (4; 2 for the 128 x 192 tile of round 6: eight wavefronts of 32 x 96)
-template <int WM, int WN, int NS, class TO, bool PERSIST = false, int FN = 4, int EK = EK_ANY, bool KT = false, int BKS = 64, int FM = 4>
+template <int WM, int WN, int NS, class TO, int FN = 4, int EK = EK_ANY, bool KT = false, int BKS = 64, int FM = 4>
 __global__ __launch_bounds__(WM* WN * 64) __attribute__((amdgpu_waves_per_eu(BKS == 32 ? 4 : 1, BKS == 32 ? 4 : 8))) void gemm_bf16_dma_kernel(const bf16_t* __restrict__ A, int64_t lda, const bf16_t* __restrict__ B,
                                                                      int64_t ldb, TO* __restrict__ D, int64_t ldd, int64_t M, int64_t N,
                                                                      int64_t K, int tiles_n, int ntiles, int64_t k_per_split,
@@ -112,7 +112,7 @@ __global__ __launch_bounds__(WM* WN * 64) __attribute__((amdgpu_waves_per_eu(BKS
     constexpr int NW = WM * WN;
     constexpr int BM = WM * FM * 16, BN = WN * FN * 16;      // a wavefront owns FM*16 rows x FN*16 columns (FN = 4, or 6 for the 256 x 192 tile)
     static_assert(FN % 2 == 0, "column fragments come in pairs (eight consecutive columns per lane)");
-    static_assert(BKS == 64 || (BKS == 32 && !KT && !PERSIST), "ring stages hold 64 or 32 K elements; the 32 form has no K tail and no persistent walk");
+    static_assert(BKS == 64 || (BKS == 32 && !KT), "ring stages hold 64 or 32 K elements; the 32 form has no K tail");
     constexpr int RB = BKS * 2;                // bytes per stage row
     constexpr int CPR = BKS / 8;               // 16-byte chunks per stage row
     constexpr int RPP = 1024 / RB;             // stage rows per 1-KiB DMA piece
@@ -129,19 +129,9 @@ __global__ __launch_bounds__(WM* WN * 64) __attribute__((amdgpu_waves_per_eu(BKS
         B += epi.off_b(blockIdx.z);
         D += epi.off_d(blockIdx.z);
     }
-    // PERSIST (one K split, no batch, NS >= 3): gridDim.x <= the number of CUs and a workgroup walks the virtual workgroup ids
-    // blockIdx.x, blockIdx.x + gridDim.x, ... (gridDim.x % 8 == 0, so every id of a workgroup maps to the same XCD and xcd_remap hands
-    // it tiles of that XCD's contiguous run).  The first NS-1 stages of tile i+1 are requested BEFORE tile i's epilogue: the ring is
-    // idle there (the epilogue runs from registers), so the HBM -> LDS latency of the next tile and the epilogue's own operand reads,
-    // GELU evaluations and stores overlap instead of queueing.
     int t, ksplit;
-    if (PERSIST) {
-        t = xcd_remap(blockIdx.x, ntiles);
-        ksplit = 0;
-    } else {
-        tile_and_split(ntiles, t, ksplit);
-    }
-    int64_t m0 = (int64_t)(t / tiles_n) * BM, n0 = (int64_t)(t % tiles_n) * BN;
+    tile_and_split(ntiles, t, ksplit);
+    const int64_t m0 = (int64_t)(t / tiles_n) * BM, n0 = (int64_t)(t % tiles_n) * BN;
     const int64_t kbeg = (int64_t)ksplit * k_per_split;
     const int64_t kend = (kbeg + k_per_split < K) ? kbeg + k_per_split : K;
     // K tail: a last K-step of fewer than eight 16-B chunks.  The lanes whose source chunk lies beyond it request a 16-B run of zeros instead
@@ -228,12 +218,6 @@ __global__ __launch_bounds__(WM* WN * 64) __attribute__((amdgpu_waves_per_eu(BKS
                 for (int j = 0; j < FN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);
         }
     };
-    if (PERSIST) {      // (NS >= 3) prologue of the first tile; every later tile's prologue is issued in front of the previous epilogue
-#pragma unroll
-        for (int p = 0; p < NS - 1; ++p)
-            if (p < nk) issue(p, p);
-    }
-    for (int vt = blockIdx.x;;) {
 #pragma unroll
     for (int i = 0; i < FM; ++i)
 #pragma unroll
@@ -258,11 +242,9 @@ __global__ __launch_bounds__(WM* WN * 64) __attribute__((amdgpu_waves_per_eu(BKS
     } else {
         // ring of NS stages, NS-1 tiles in flight, ONE barrier per K-step: the barrier of step kt proves both that tile kt has
         // landed for everyone and that everyone is past the fragment reads of tile kt-1, whose stage tile kt+NS-1 then takes
-        if (!PERSIST) {
 #pragma unroll
-            for (int p = 0; p < NS - 1; ++p)
-                if (p < nk) issue(p, p);
-        }
+        for (int p = 0; p < NS - 1; ++p)
+            if (p < nk) issue(p, p);
         int stage = 0, fill = (NS - 1) % NS;
         for (int kt = 0; kt < nk; ++kt) {
             const int ahead = nk - 1 - kt;      // tiles issued after tile kt that may stay in flight (capped at NS-2)
@@ -281,30 +263,16 @@ __global__ __launch_bounds__(WM* WN * 64) __attribute__((amdgpu_waves_per_eu(BKS
         __builtin_amdgcn_s_barrier();      // the epilogue slab overwrites the ring
         asm volatile("" ::: "memory");
     }
-    // (the barrier above: every wavefront is past its last fragment read, the whole ring is free)
-    const int64_t em0 = m0, en0 = n0;
-    if (PERSIST) {
-        vt += gridDim.x;
-        if (vt < ntiles) {
-            t = xcd_remap(vt, ntiles);
-            m0 = (int64_t)(t / tiles_n) * BM;
-            n0 = (int64_t)(t % tiles_n) * BN;
-            point(m0, n0);
-#pragma unroll
-            for (int p = 0; p < NS - 1; ++p)
-                if (p < nk) issue(p, p);
-        }
-    }
     // ---- epilogue from registers: per 16-row block, two 8-column vectors per lane (N % 8 == 0 and aligned operands are
     // eligibility conditions, so there is no scalar path) ----
     const bool split = slabs != nullptr;
     float* const slab = split ? slabs + (int64_t)ksplit * M * N : nullptr;
 #pragma unroll
     for (int i = 0; i < FM; ++i) {
-        const int64_t m = em0 + wm * (FM * 16) + i * 16 + c15;
+        const int64_t m = m0 + wm * (FM * 16) + i * 16 + c15;
 #pragma unroll
         for (int h = 0; h < FN / 2; ++h) {
-            const int64_t n = en0 + wn * (FN * 16) + 32 * h + 8 * g;
+            const int64_t n = n0 + wn * (FN * 16) + 32 * h + 8 * g;
             if (m < M && n < N) {
                 float v[8];
 #pragma unroll
@@ -322,15 +290,13 @@ __global__ __launch_bounds__(WM* WN * 64) __attribute__((amdgpu_waves_per_eu(BKS
             }
         }
     }
-    if (!PERSIST || vt >= ntiles) break;
-    }      // tiles of this workgroup
 }
 
 // eligibility of a problem for the DMA pipeline (checked on the host)
 inline bool dma_eligible(const iseg_gemm_args* g, int64_t kps) {
     if (!g->a_kcontig || !g->b_kcontig || g->a_act != ISEG_ACT_NONE || g->colsum_out) return false;
     // K: whole 16-B chunks per row (a last K-step of fewer than eight is zero-filled, see the kernel); a split cuts at multiples of 64
-    if (g->K % 8 != 0 || (kps != g->K && kps % 64 != 0) || g->K < dma_min_k() || g->N % 8 != 0 || g->N < 64 || g->M < 64) return false;
+    if (g->K % 8 != 0 || (kps != g->K && kps % 64 != 0) || g->K < dma_min_k || g->N % 8 != 0 || g->N < 64 || g->M < 64) return false;
     if (((uintptr_t)g->A % 16) || ((uintptr_t)g->B % 16) || g->lda % 8 || g->ldb % 8) return false;
     if (((uintptr_t)g->D % 16) || g->ldd % 8) return false;
     if (g->residual && (((uintptr_t)g->residual % 16) || g->ldr % 8)) return false;
@@ -354,73 +320,49 @@ void launch_dma(const iseg_gemm_args* g, const Epi& epi, int nsplit, int64_t k_p
     static_assert(FM == 4 || BKS == 64, "the 32-deep stages exist for the 256 x 128 tile");
     if constexpr (BKS == 32) {      // (dispatch_dma sends only whole-K problems here: K % 32 == 0, splits cut at multiples of 64)
         static const bool raised32 = [] {
-            return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_dma_kernel<WM, WN, NS, TO, false, FN, EK, false, 32>),
+            return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_dma_kernel<WM, WN, NS, TO, FN, EK, false, 32>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess;
         }();
         (void)raised32;
-        hipLaunchKernelGGL((gemm_bf16_dma_kernel<WM, WN, NS, TO, false, FN, EK, false, 32>), grid, dim3(WM * WN * 64), lds, s, (const bf16_t*)g->A, g->lda,
+        hipLaunchKernelGGL((gemm_bf16_dma_kernel<WM, WN, NS, TO, FN, EK, false, 32>), grid, dim3(WM * WN * 64), lds, s, (const bf16_t*)g->A, g->lda,
                            (const bf16_t*)g->B, g->ldb, (TO*)g->D, g->ldd, g->M, g->N, g->K, tiles_n, ntiles, k_per_split, slabs, epi, vecD);
         return;
     }
     if (g->K % 64 != 0) {
         static const bool raised_kt = [] {      // > 64 KiB of dynamic LDS needs the attribute once per instantiation
-            return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_dma_kernel<WM, WN, NS, TO, false, FN, EK, true, 64, FM>),
+            return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_dma_kernel<WM, WN, NS, TO, FN, EK, true, 64, FM>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess;
         }();
         (void)raised_kt;
-        hipLaunchKernelGGL((gemm_bf16_dma_kernel<WM, WN, NS, TO, false, FN, EK, true, 64, FM>), grid, dim3(WM * WN * 64), lds, s, (const bf16_t*)g->A, g->lda,
+        hipLaunchKernelGGL((gemm_bf16_dma_kernel<WM, WN, NS, TO, FN, EK, true, 64, FM>), grid, dim3(WM * WN * 64), lds, s, (const bf16_t*)g->A, g->lda,
                            (const bf16_t*)g->B, g->ldb, (TO*)g->D, g->ldd, g->M, g->N, g->K, tiles_n, ntiles, k_per_split, slabs, epi, vecD);
         return;
     }
     static const bool raised = [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_dma_kernel<WM, WN, NS, TO, false, FN, EK, false, 64, FM>),
+        return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_dma_kernel<WM, WN, NS, TO, FN, EK, false, 64, FM>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess;
     }();
     (void)raised;
-    hipLaunchKernelGGL((gemm_bf16_dma_kernel<WM, WN, NS, TO, false, FN, EK, false, 64, FM>), grid, dim3(WM * WN * 64), lds, s, (const bf16_t*)g->A, g->lda,
+    hipLaunchKernelGGL((gemm_bf16_dma_kernel<WM, WN, NS, TO, FN, EK, false, 64, FM>), grid, dim3(WM * WN * 64), lds, s, (const bf16_t*)g->A, g->lda,
                        (const bf16_t*)g->B, g->ldb, (TO*)g->D, g->ldd, g->M, g->N, g->K, tiles_n, ntiles, k_per_split, slabs, epi, vecD);
 }
 
-// persistent form of the 256 x 128 kernel: one workgroup per CU (its 144-KiB ring allows no more), each walking ntiles / gridDim.x tiles
-template <class TO>
-void launch_dma_persistent(const iseg_gemm_args* g, const Epi& epi, int64_t k_per_split, int cus, hipStream_t s) {
-    constexpr int WM = 4, WN = 2, NS = 3, BM = WM * 64, BN = WN * 64;
-    const int tiles_m = (int)ceil_div64(g->M, BM), tiles_n = (int)ceil_div64(g->N, BN);
-    const int ntiles = tiles_m * tiles_n;
-    constexpr int lds = NS * (BM + BN) * 128;
-    static const bool raised = [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_dma_kernel<WM, WN, NS, TO, true>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess;
-    }();
-    (void)raised;
-    const int grid = (ntiles < cus ? ntiles : cus) & ~7;      // a multiple of 8: every virtual id of a workgroup sits on its XCD
-    hipLaunchKernelGGL((gemm_bf16_dma_kernel<WM, WN, NS, TO, true>), dim3(grid), dim3(WM * WN * 64), lds, s, (const bf16_t*)g->A, g->lda,
-                       (const bf16_t*)g->B, g->ldb, (TO*)g->D, g->ldd, g->M, g->N, g->K, tiles_n, ntiles, k_per_split, (float*)nullptr, epi, 1);
-}
-
-int dma_mode();      // ISEG_GEMM_DMA: 0 = never, 1 = whenever eligible (default)
-
 // 1: 128 x 64 (4-deep ring)   2: 256 x 128 (8 wavefronts, 3-deep ring)   3: 128 x 128, two workgroups per CU (2 stages)
-// 4: 128 x 128, one workgroup per CU with the 3-deep ring.  (dispatch_dma adds two forms of 2: persistent, and 256 x 192.)  Measured on MI355X (tools/kbench_gemm_ref.py): 256 x 128 once it fills
+// 4: 128 x 128, one workgroup per CU with the 3-deep ring.  (dma_form adds the 256 x 192, 128 x 192 and 64 x 192 forms.)  Measured on MI355X (tools/kbench_gemm_ref.py): 256 x 128 once it fills
 // most CUs -- it reads each B panel half as often; otherwise 128 x 128, two per CU when there are enough tiles, the deeper ring when
 // the grid is thin.
 inline int dma_variant(const iseg_gemm_args* g, int nsplit) {
-    // experiment knobs.  Measured on the flagship step: 128 x 128 tiles, two workgroups per CU (3) for the GEMMs with fused gelu / aux / residual
+    // Measured on the flagship step: forcing 128 x 128 tiles, two workgroups per CU (3) for the GEMMs with fused gelu / aux / residual
     // epilogues 10.66 vs 10.69 ms (equal), the deep-ring 128 x 128 (4) 11.28 ms; requesting the fused operands of four row blocks together
     // in the epilogue: equal, +44 registers.  The 13-17 us these epilogues add are VALU (gelu) and un-overlapped operand reads either way.
-    static const int forced = [] { const char* e = getenv("ISEG_GEMM_DMA_VARIANT"); return e ? atoi(e) : 0; }();
-    static const int forced_epi = [] { const char* e = getenv("ISEG_GEMM_DMA_VARIANT_EPI"); return e ? atoi(e) : 0; }();
-    if (forced >= 1 && forced <= 4 && g->N > 64) return forced;
-    if (forced_epi >= 1 && forced_epi <= 4 && g->N > 64 && (g->act != 0 || g->aux || g->residual)) return forced_epi;
     const int64_t tiles256 = ceil_div64(g->M, 256) * ceil_div64(g->N, 128), tiles128 = ceil_div64(g->M, 128) * ceil_div64(g->N, 128);
     if (g->N <= 64) return 1;
-    static const int t256 = [] { const char* e = getenv("ISEG_GEMM_DMA_T256"); return e ? atoi(e) : 192; }();
-    if (tiles256 * nsplit >= t256) return 2;
+    if (tiles256 * nsplit >= 192) return 2;
     if (tiles128 * nsplit >= 384) return 3;
     return 4;
 }
 
-// number of CUs of the current device (persistent grids)
+// number of CUs of the current device (the 192-column forms fill whole rounds of them)
 inline int dma_cus() {
     static const int n = [] {
         int dev = 0, v = 0;
@@ -430,14 +372,13 @@ inline int dma_cus() {
     return n;
 }
 
-// dma_variant plus the two further forms of the 256-row tile:
+// dma_variant plus the further forms of the 192-column tile:
 //   6: 256 x 192 tiles (a wavefront owns 64 x 96, two ring stages = 112 KiB): a third fewer re-reads of the A panel than 256 x 128 when N is a
 //      multiple of 192 (the 4C = 768 / 1536 / 3072 outputs of the ConvNeXt stages); taken when its tiles fill whole rounds of the CUs better
 //      (with equal rounds the flagship step measured the same and the in-situ launches of the x aux data gradient 51.7 vs 50.5 us).
 //      Measured (tools/kbench_gemm_dma_ab.py): M=4096 N=3072 K=768 34.5 -> 27.5 us (384 tiles = 1.5 rounds -> 256 = one round),
 //      M=16384 N=1536 K=384 34.4 -> 33.1 us, with the x aux epilogue 42.2 -> 41.4 us, M=65536 N=768 K=192 45.7 -> 43.0 us.
-//   5: several 256 x 128 tiles per CU, one K split, no batch: the persistent form overlaps a tile's epilogue with the next tile's first DMAs
-//      (ISEG_GEMM_DMA_PERSIST=1; see below why it is not the default).
+//   (5 was a persistent 256 x 128 form, slower inside the training step: EXPERIMENTS.md.  The number stays unused.)
 inline int dma_form(const iseg_gemm_args* g, int nsplit) {
     const int variant = dma_variant(g, nsplit);
     // 9 (round 6): 64 x 192 tiles (eight wavefronts of 16 x 96) where the thin-grid 128 x 128 form leaves a quarter of the CUs idle --
@@ -448,11 +389,6 @@ inline int dma_form(const iseg_gemm_args* g, int nsplit) {
         if (t4 * 8 <= (int64_t)dma_cus() * 7 && t9 <= dma_cus() && t9 * 6 >= t4 * 7) return 9;
     }
     if (variant != 2 || nsplit != 1 || g->batch > 1) return variant;
-    static const int wide = [] { const char* e = getenv("ISEG_GEMM_DMA_WIDE"); return e ? atoi(e) : 1; }();
-    // off by default: 1 us per launch faster back to back (tools/kbench_gemm_ref.py) but slower inside the training step -- 59.8 vs 53.9 us for the
-    // x aux data gradient under bench.py's event timer, 9.82 vs 9.70 ms per step: three tiles per workgroup is a static partition, and the
-    // hardware dispatcher's dynamic one (768 workgroups, a new one wherever a CU frees up) absorbs CUs that run behind on cold operands
-    static const int persist = [] { const char* e = getenv("ISEG_GEMM_DMA_PERSIST"); return e ? atoi(e) : 0; }();
     const int cus = dma_cus();
     const int64_t t128 = ceil_div64(g->M, 256) * ceil_div64(g->N, 128);
     // 8 (round 6): 128 x 192 tiles where the 256 x 128 ones leave more than an eighth of the CUs idle in their single round and these fit one
@@ -462,12 +398,11 @@ inline int dma_form(const iseg_gemm_args* g, int nsplit) {
         const int64_t t8 = ceil_div64(g->M, 128) * (g->N / 192);
         if (t8 <= cus && t8 * 6 >= t128 * 7) return 8;
     }
-    if (wide && g->N % 192 == 0) {
+    if (g->N % 192 == 0) {
         const int64_t t192 = ceil_div64(g->M, 256) * (g->N / 192);
         const double e128 = (double)t128 / (double)(ceil_div64(t128, cus) * cus), e192 = (double)t192 / (double)(ceil_div64(t192, cus) * cus);
         if (t192 >= cus && e192 >= e128 + 0.1) return 6;      // only where it fills the rounds better: equal rounds measured equal in situ
     }
-    if (persist && t128 > cus && g->K % 64 == 0) return 5;      // (the persistent instantiation has no K-tail form)
     return variant;
 }
 
@@ -506,7 +441,6 @@ void dispatch_dma(const iseg_gemm_args* g, const Epi& epi, int nsplit, int64_t k
             else launch_dma_kinds<4, 2, 3, TO, 4>(g, epi, nsplit, kps, slabs, s);
             break;
         case 3: launch_dma<2, 2, 2, TO>(g, epi, nsplit, kps, slabs, s); break;
-        case 5: launch_dma_persistent<TO>(g, epi, kps, dma_cus(), s); break;
         case 6: launch_dma_kinds<4, 2, 2, TO, 6>(g, epi, nsplit, kps, slabs, s); break;      // 256 x 192: stage 3
         case 9: launch_dma_kinds<4, 2, 3, TO, 6, 64, 1>(g, epi, nsplit, kps, slabs, s); break;      // 64 x 192, eight wavefronts of 16 x 96
         case 8: launch_dma_kinds<4, 2, 3, TO, 6, 64, 2>(g, epi, nsplit, kps, slabs, s); break;      // 128 x 192, eight wavefronts of 32 x 96

@@ -115,12 +115,7 @@ __device__ __forceinline__ void tn_tile(const bf16_t* __restrict__ A, int64_t ld
         for (int i = 0; i < FM; ++i) aa[i] = sbase + a_off[i];
 #pragma unroll
         for (int j = 0; j < FN; ++j) ab[j] = sbase + b_off[j];
-        // (ISEG_TN_ABL_*: ablation builds of tools/micro/tn_bench.hip -- results are wrong, timings tell what the loop is made of)
-#ifdef ISEG_TN_ABL_NOREAD
-#define ISEG_TR_READ(dst, addr, OFF) asm volatile("" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory")
-#else
 #define ISEG_TR_READ(dst, addr, OFF) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory")
-#endif
 #pragma unroll
         for (int i = 0; i < FM; ++i) {
             ISEG_TR_READ(ra[0][i][0], aa[i], 0);
@@ -158,14 +153,10 @@ __device__ __forceinline__ void tn_tile(const bf16_t* __restrict__ A, int64_t ld
             for (int i = 0; i < FM; ++i) af[i] = join(ra[ks][i][0], ra[ks][i][1]);
 #pragma unroll
             for (int j = 0; j < FN; ++j) bfr[j] = join(rb[ks][j][0], rb[ks][j][1]);
-#ifdef ISEG_TN_ABL_NOMFMA
-            acc[0][0][0] += __builtin_bit_cast(float, ra[ks][0][0].x ^ rb[ks][0][0].x);
-#else
 #pragma unroll
             for (int i = 0; i < FM; ++i)
 #pragma unroll
                 for (int j = 0; j < FN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);
-#endif
             if (ones) {
 #pragma unroll
                 for (int j = 0; j < FN; ++j) acc1[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], one8, acc1[j], 0, 0, 0);
@@ -189,17 +180,13 @@ __device__ __forceinline__ void tn_tile(const bf16_t* __restrict__ A, int64_t ld
     int stage = 0, fill = (NS - 1) % NS;
     for (int kt = 0; kt < nk; ++kt) {
         const int ahead = nk - 1 - kt;
-#ifndef ISEG_TN_ABL_NOWAIT
         if (ahead >= NS - 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NS - 2) * PPW) : "memory");
         else if (NS > 3 && ahead == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPW) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-#ifndef ISEG_TN_ABL_NODMA
         if (kt + NS - 1 < nk) issue(fill);
-#endif
         compute(stage);
         stage = stage + 1 == NS ? 0 : stage + 1;
         fill = fill + 1 == NS ? 0 : fill + 1;
@@ -260,20 +247,15 @@ __global__ __launch_bounds__(512) void gemm_bf16_dma_tn_pair_kernel(TnProblem p0
     else tn_tile<2, 4, NS>(p.A, p.lda, p.B, p.ldb, p.M, p.N, K, p.tiles_n, t, ksplit, k_per_split, p.slabs, p.ones_row);
 }
 
-int dma_tn_mode();      // ISEG_GEMM_DMA_TN: 0 = never, 1 = whenever eligible (default)
 bool dma_tn_lds_ok();   // gemm_tn.hip: the 144-KiB dynamic-LDS limit of both tile forms was raised (once per process); false -> the register kernel keeps these problems
 
 // 0 = not eligible; 7 = 256 x 128 tiles, 8 = 128 x 256 tiles (the codes iseg_gemm_variant reports)
 inline int dma_tn_form(const iseg_gemm_args* g) {
-    if (!dma_tn_mode() || g->in_dtype != ISEG_BF16 || g->a_kcontig || g->b_kcontig || g->a_act != ISEG_ACT_NONE) return 0;
+    if (g->in_dtype != ISEG_BF16 || g->a_kcontig || g->b_kcontig || g->a_act != ISEG_ACT_NONE) return 0;
     if (!dma_tn_lds_ok()) return 0;
     if (g->batch > 1 || g->b_group_rows > 0 || g->split_k == 1) return 0;
-    static const int min_mn = [] {      // ISEG_GEMM_DMA_TN_MIN: narrowest M / N the kernel takes (columns past M / N are clamped duplicates)
-        const char* e = getenv("ISEG_GEMM_DMA_TN_MIN");
-        const int v = e ? atoi(e) : 64;
-        return v < 64 ? 64 : v;      // (the ones-row lives in the first 64 rows' wavefronts)
-    }();
-    if (g->M < min_mn || g->N < min_mn || g->M % 8 || g->N % 8 || g->K < 2048) return 0;      // (any K: a ragged last stage reads zeros)
+    // narrowest M / N: 64 (columns past M / N are clamped duplicates; the ones-row lives in the first 64 rows' wavefronts)
+    if (g->M < 64 || g->N < 64 || g->M % 8 || g->N % 8 || g->K < 2048) return 0;      // (any K: a ragged last stage reads zeros)
     // a side below 128 pays for clamped duplicate columns: measured (tools/kbench_wgrad_tn.py, KBENCH_NARROW=1, register kernel -> this one, us)
     // 96 x 384 55.0 -> 47.4, 384 x 96 58.0 -> 45.9, 112 x 336 29.9 -> 26.0, 112 x 448 32.9 -> 27.9, but 96 x 288 46.4 -> 51.7 and 96 x 96 23.7 -> 24.4
     if ((g->M < 128 || g->N < 128) && (g->M > g->N ? g->M : g->N) < 320) return 0;

@@ -534,10 +534,6 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_bf16_kernel(const bf16_t* __
     tile_epilogue<WM, WN, FM, FN, TO>(acc, smem, D, ldd, M, N, m0, n0, wm, wn, wid, lane, slabs, epi, ones_row, vecD, ksplit);
 }
 
-// experiment knob (read once)
-int long_k_tile();  // ISEG_GEMM_BK in {64,128}: K-tile depth for reductions >= 256 (default 128)
-int tile_waves();   // ISEG_GEMM_WAVES in {4,8,16}: workgroup size of the 128x128 tile (default 8)
-
 template <int WM, int WN, int FM, int FN, bool AKC, bool BKC, int BK, class TO>
 void launch_bf16(const iseg_gemm_args* g, const Epi& epi, int nsplit, int64_t k_per_split, float* slabs, hipStream_t s) {
     constexpr int BM = WM * FM * 16, BN = WN * FN * 16;
@@ -573,18 +569,17 @@ void dispatch_tile(const iseg_gemm_args* g, const Epi& epi, int nsplit, int64_t 
     if (N <= 32) launch_bf16<8, 1, 1, 2, AKC, BKC, BK, TO>(g, epi, nsplit, kps, slabs, s);                               // 128x32
     else if (N <= 64) launch_bf16<4, 2, 2, 2, AKC, BKC, BK, TO>(g, epi, nsplit, kps, slabs, s);                          // 128x64
     else if (N % 128 != 0 && N % 96 == 0) launch_bf16<4, 2, 2, 3, AKC, BKC, BK, TO>(g, epi, nsplit, kps, slabs, s);      // 128x96
-    else if (tile_waves() == 4) launch_bf16<2, 2, 4, 4, AKC, BKC, BK, TO>(g, epi, nsplit, kps, slabs, s);                // 128x128
-    else if (tile_waves() == 16) launch_bf16<4, 4, 2, 2, AKC, BKC, BK, TO>(g, epi, nsplit, kps, slabs, s);
-    else launch_bf16<2, 4, 4, 2, AKC, BKC, BK, TO>(g, epi, nsplit, kps, slabs, s);
+    else launch_bf16<2, 4, 4, 2, AKC, BKC, BK, TO>(g, epi, nsplit, kps, slabs, s);                                       // 128x128
 }
 
-// one K-tile for short reductions (no loop, all loads issued up front), BK = 64 otherwise
+// one K-tile for short reductions (no loop, all loads issued up front), BK = 128 for long reductions (twice the bytes in flight per
+// barrier pair), BK = 64 otherwise
 template <bool AKC, bool BKC, class TO>
 void dispatch_bk(const iseg_gemm_args* g, const Epi& epi, int nsplit, int64_t kps, float* slabs, hipStream_t s) {
     const int64_t kspan = kps < g->K ? kps : g->K;
     if (AKC && kspan > 64 && kspan <= 96) dispatch_tile<AKC, BKC, 96, TO>(g, epi, nsplit, kps, slabs, s);
-    else if (kspan >= 256 && long_k_tile() == 128) dispatch_tile<AKC, BKC, 128, TO>(g, epi, nsplit, kps, slabs, s);  // long reductions:
-    else dispatch_tile<AKC, BKC, 64, TO>(g, epi, nsplit, kps, slabs, s);   // twice the bytes in flight per barrier pair
+    else if (kspan >= 256) dispatch_tile<AKC, BKC, 128, TO>(g, epi, nsplit, kps, slabs, s);
+    else dispatch_tile<AKC, BKC, 64, TO>(g, epi, nsplit, kps, slabs, s);
 }
 
 // implemented in gemm_nn.hip (A K-contig, B N-contig), gemm_nt.hip (both K-contig), gemm_tn.hip (both MN-contig)

@@ -4,7 +4,7 @@
 
 namespace iseg_mm {
 void gemm_bf16_nt(const iseg_gemm_args* g, const Epi& epi, int nsplit, int64_t kps, float* slabs, hipStream_t s) {
-    if (dma_mode() && dma_eligible(g, kps)) {
+    if (dma_eligible(g, kps)) {
         if (g->out_dtype == ISEG_BF16) dispatch_dma<bf16_t>(g, epi, nsplit, kps, slabs, s);
         else dispatch_dma<float>(g, epi, nsplit, kps, slabs, s);
         return;

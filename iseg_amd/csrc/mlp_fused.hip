@@ -108,16 +108,8 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(C ==
         int64_t row = m0 + r;
         row = row < M ? row : M - 1;
         const bf16_t* yp = Y + row * C + 8 * h;
-#ifdef ISEG_ABL_MLP_NOIO      // ablation (tools/kbench_mlp.py under ISEG_BUILD_DEFINES): no row loads, no residual loads, no stores
-#pragma unroll
-        for (int kk = 0; kk < KK; ++kk)
-#pragma unroll
-            for (int u = 0; u < 8; ++u) yf[kk][u] = (bf16_t)(0.01f * (float)((lane + kk + u) & 15));
-        (void)yp;
-#else
 #pragma unroll
         for (int kk = 0; kk < KK; ++kk) yf[kk] = *reinterpret_cast<const bf16x8*>(yp + 16 * kk);
-#endif
         // Y is the LayerNorm INPUT (ln.gamma != NULL): a row lives in the two lanes r and r + 32, so the statistics are an in-lane sum and one
         // lane-half exchange; y2 never exists in HBM (round 3).  The row's mean / rstd are saved for the backward kernels.
         if (ln.gamma) mlp_layernorm_rows<KK>(yf, ln, m0 + r < M ? m0 + r : -1, h, C);
@@ -232,13 +224,8 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(C ==
         if (m < M) {
             const int c0 = 32 * cb + 16 * eh;
             float res[16], bb[16], gg[16];
-#ifdef ISEG_ABL_MLP_NOIO
-#pragma unroll
-            for (int u = 0; u < 16; ++u) res[u] = 0.f;
-#else
             load8<bf16_t>(R + m * C + c0, res);
             load8<bf16_t>(R + m * C + c0 + 8, res + 8);
-#endif
             load8<float>(b2 + c0, bb);      // (16-byte vector loads: one dword load per element was 96 extra loads per lane at C = 96)
             load8<float>(b2 + c0 + 8, bb + 8);
             if (gamma) {
@@ -251,13 +238,8 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(C ==
                 if (gamma) t *= gg[u];
                 v[u] = fmaf(t, rs, res[u]);
             }
-#ifdef ISEG_ABL_MLP_NOIO
-            if (v[0] == 12345.678f)
-#endif
-            {
-                store8<bf16_t>(O + m * C + c0, v);
-                store8<bf16_t>(O + m * C + c0 + 8, v + 8);
-            }
+            store8<bf16_t>(O + m * C + c0, v);
+            store8<bf16_t>(O + m * C + c0 + 8, v + 8);
         }
     }
 }
@@ -362,7 +344,7 @@ __global__ __launch_bounds__(64 * WAVES) void convnext_mlp_bwd_kernel(const bf16
     const int64_t row_o = (row_ok ? m0 + r : 0) * HID + 8 * h;
 
     // fragment pieces of a stage in address order: A1 (KK), A3 (KK), A4 (2 CB) of each slab -- rolling window as in the forward kernel
-    constexpr int NF = SUB * (2 * KK + 2 * CB), FD = C >= 384 ? 2 : 4;      // (C = 384 runs at 490 of 512 registers)
+    constexpr int NF = SUB * (2 * KK + 2 * CB), FD = 4;
     auto compute = [&](int stage, int kt) {
         const char* fb = smem + stage * STAGE + fo;
         bf16x8 win[FD];
@@ -610,11 +592,8 @@ __device__ __forceinline__ void mlp_prep_elements(const float* __restrict__ W1, 
         const int i = bw ? e - nfw : e, nimg = bw ? 3 : 2;
         const int slab = i / (nimg * per_img), rem = i % (nimg * per_img);
         const int img = rem / per_img, x = rem % per_img;
-#ifdef ISEG_MLP_PIECE_ROWMAJOR      // (the piece layout of rounds 2-5, kept for A/B builds: [32 rows][16 k], 2-way bank conflicts on every fragment read)
-        const int piece = x / 512, y = x % 512, rr = y / 16, kq = y % 16, hh = kq / 8, j = kq % 8;
-#else                               // [k-half][32 rows][8 k]: lane l = 32 (k-half) + row reads the piece's bytes 16 l .. 16 l + 15
+        // [k-half][32 rows][8 k]: lane l = 32 (k-half) + row reads the piece's bytes 16 l .. 16 l + 15
         const int piece = x / 512, y = x % 512, hh = y / 256, rr = (y % 256) / 8, j = y % 8, kq = 8 * hh + j;
-#endif
         // image kinds: 0 = A1, 1 = A2 (forward) ; 0 = A1, 1 = A3, 2 = A4 (backward)
         const int kind = bw ? (img == 0 ? 1 : img + 2) : img + 1;      // 1 = A1, 2 = A2, 3 = A3, 4 = A4
         float v;
@@ -708,11 +687,9 @@ int launch_mlp_bwd(const void* y2, const void* dbr, const float* rowscale, int64
 }  // namespace
 
 extern "C" int iseg_convnext_mlp_supported(int C, int dtype) {
-    // C = 384 is instantiated (one wavefront per SIMD, 128-row workgroups, a two-stage ring in the backward kernel) but measured SLOWER than the
-    // GEMM pair at the flagship's 16384 rows: 115 vs 103 us forward, 199 vs 69 + 36 us backward -- only 128 workgroups, and with one wavefront
-    // per SIMD nothing overlaps the gelu VALU section with MFMAs.  Opt-in for experiments: ISEG_MLP_FUSED_384=1.
-    static const bool wide = [] { const char* e = getenv("ISEG_MLP_FUSED_384"); return e && atoi(e) != 0; }();
-    return dtype == ISEG_BF16 && (C == 96 || C == 192 || (C == 384 && wide)) ? 1 : 0;
+    // (C = 384, one wavefront per SIMD with 128-row workgroups, measured SLOWER than the GEMM pair at the flagship's 16384 rows: 115 vs 103 us
+    // forward, 199 vs 69 + 36 us backward -- only 128 workgroups, and with one wavefront per SIMD nothing overlaps the gelu VALU section with MFMAs)
+    return dtype == ISEG_BF16 && (C == 96 || C == 192) ? 1 : 0;
 }
 
 extern "C" size_t iseg_convnext_mlp_tiled_bytes(int C, int backward) { return (size_t)(backward ? 3 : 2) * 4 * C * C * 2; }
@@ -737,16 +714,14 @@ extern "C" int iseg_convnext_weight_prep_batched(const int64_t* table, int entri
 extern "C" int iseg_convnext_mlp_fwd(const void* y2, const void* fw_tiled, const float* b1, const float* b2, const float* gamma,
                                      const float* rowscale, int64_t rows_per_group, const void* residual, void* out, int64_t M, int C, int dtype,
                                      hipStream_t stream) {
-    ISEG_REQUIRE(iseg_convnext_mlp_supported(C, dtype), "iseg_convnext_mlp_fwd: bf16 storage with C = 96, 192 or 384 only (C = %d, dtype = %d)", C, dtype);
+    ISEG_REQUIRE(iseg_convnext_mlp_supported(C, dtype), "iseg_convnext_mlp_fwd: bf16 storage with C = 96 or 192 only (C = %d, dtype = %d)", C, dtype);
     ISEG_REQUIRE(y2 && fw_tiled && b1 && b2 && residual && out && M > 0, "iseg_convnext_mlp_fwd: null operand or empty problem");
     ISEG_REQUIRE(!rowscale || rows_per_group > 0, "iseg_convnext_mlp_fwd: rowscale needs rows_per_group > 0");
     ISEG_REQUIRE((((uintptr_t)y2 | (uintptr_t)fw_tiled | (uintptr_t)residual | (uintptr_t)out | (uintptr_t)b1 | (uintptr_t)b2 | (uintptr_t)gamma) & 15) == 0,
                  "iseg_convnext_mlp_fwd: operands must be 16-byte aligned");
     const MlpLayerNorm none{};
     if (C == 96) return launch_mlp_fwd<96, 2, 8, 3>(y2, fw_tiled, b1, b2, gamma, rowscale, rows_per_group, residual, out, M, none, stream);
-    if (C == 192) return launch_mlp_fwd<192, 1, 8, 3>(y2, fw_tiled, b1, b2, gamma, rowscale, rows_per_group, residual, out, M, none, stream);
-    // C = 384: 96 fragment + 192 accumulator registers per lane -> one wavefront per SIMD, 128-row workgroups
-    return launch_mlp_fwd<384, 1, 4, 3>(y2, fw_tiled, b1, b2, gamma, rowscale, rows_per_group, residual, out, M, none, stream);
+    return launch_mlp_fwd<192, 1, 8, 3>(y2, fw_tiled, b1, b2, gamma, rowscale, rows_per_group, residual, out, M, none, stream);
 }
 
 extern "C" int iseg_convnext_mlp_fwd_ln(const void* y1, const float* ln_gamma, const float* ln_beta, float eps, float* mean, float* rstd,
@@ -765,14 +740,13 @@ extern "C" int iseg_convnext_mlp_fwd_ln(const void* y1, const float* ln_gamma, c
 
 extern "C" int iseg_convnext_mlp_bwd(const void* y2, const void* dbr, const void* bw_tiled, const float* b1, void* g, void* dh, void* dy2,
                                      int64_t M, int C, int dtype, hipStream_t stream) {
-    ISEG_REQUIRE(iseg_convnext_mlp_supported(C, dtype), "iseg_convnext_mlp_bwd: bf16 storage with C = 96, 192 or 384 only (C = %d, dtype = %d)", C, dtype);
+    ISEG_REQUIRE(iseg_convnext_mlp_supported(C, dtype), "iseg_convnext_mlp_bwd: bf16 storage with C = 96 or 192 only (C = %d, dtype = %d)", C, dtype);
     ISEG_REQUIRE(y2 && dbr && bw_tiled && b1 && g && dh && dy2 && M > 0, "iseg_convnext_mlp_bwd: null operand or empty problem");
     ISEG_REQUIRE((((uintptr_t)y2 | (uintptr_t)dbr | (uintptr_t)bw_tiled | (uintptr_t)b1 | (uintptr_t)g | (uintptr_t)dh | (uintptr_t)dy2) & 15) == 0,
                  "iseg_convnext_mlp_bwd: operands must be 16-byte aligned");
     const MlpLayerNorm none{};
     if (C == 96) return launch_mlp_bwd<96, 2, 8, 3, true>(y2, dbr, nullptr, 0, bw_tiled, b1, g, dh, dy2, M, none, stream);
-    if (C == 192) return launch_mlp_bwd<192, 1, 4, 3, true>(y2, dbr, nullptr, 0, bw_tiled, b1, g, dh, dy2, M, none, stream);
-    return launch_mlp_bwd<384, 1, 4, 2, true>(y2, dbr, nullptr, 0, bw_tiled, b1, g, dh, dy2, M, none, stream);      // 72-KiB slabs: a two-stage ring is what fits
+    return launch_mlp_bwd<192, 1, 4, 3, true>(y2, dbr, nullptr, 0, bw_tiled, b1, g, dh, dy2, M, none, stream);
 }
 
 extern "C" int iseg_convnext_mlp_bwd_data(const void* y2, const float* mean, const float* rstd, const float* ln_gamma, const float* ln_beta,

@@ -29,11 +29,7 @@ struct LnPost {
 // LOSES with it at every width (39 -> 59, 26 -> 32, 19.5 -> 22.9, 16.5 -> 19.3 us: 144 more registers of rows in flight) and keeps the old split.
 static inline int ln_lanes_per_row(int C, bool thirds = false) {
     const int chunks = (C + 7) / 8;
-    static const int cpl3 = [] {
-        const char* e = getenv("ISEG_LN_CPL3");
-        return e ? atoi(e) : 1;
-    }();
-    if (thirds && cpl3 && chunks % 3 == 0 && chunks <= 24) {
+    if (thirds && chunks % 3 == 0 && chunks <= 24) {
         const int t = chunks / 3;
         if (t >= 1 && (t & (t - 1)) == 0) return t;
     }
@@ -863,34 +859,16 @@ static int layernorm_fwd_launch(const void* x, const int32_t* src_index, const f
     return iseg_check_launch("iseg_layernorm_fwd");
 }
 
-static int ln_bwd_u8() {      // experiment (round 5): eight rows in flight per wavefront instead of four where a wavefront holds one or two rows per iteration
-    static const int v = [] {
-        const char* e = getenv("ISEG_LN_BWD_U8");
-        return e ? atoi(e) : 0;
-    }();
-    return v;
-}
-
 static int ln_bwd_blocks(int64_t rows, int C) {
     const int lpr = ln_lanes_per_row(C);
     const int rpw = 64 / lpr;
     // every workgroup pays a fixed price (LDS combine, 2C partial sums written and read again by the reduce), so a workgroup takes ~24 K elements
     // (48 KB of bf16 per operand), between 256 and 1024 workgroups.  Measured best (us incl. the reduce): 262144 x 96 -> 1024 workgroups (37),
-    // 65536 x 192 -> 512 (25), 16384 x 384 -> 256 (20.7; 2048 workgroups: 31), 4096 x 768 -> 256..512 (19).  ISEG_LN_BWD_ITERS pins the row
-    // groups per wavefront instead.
-    static const int iters_env = [] {
-        const char* e = getenv("ISEG_LN_BWD_ITERS");
-        return e ? atoi(e) : 0;
-    }();
-    int64_t blocks;
-    if (iters_env > 0) {
-        blocks = ceil_div64(rows, (int64_t)rpw * 4 * iters_env);
-    } else {
-        int64_t rows_per_block = 24576 / C;
-        if (rows_per_block < rpw * 4) rows_per_block = rpw * 4;
-        blocks = ceil_div64(rows, rows_per_block);
-        if (blocks < 256) blocks = ceil_div64(rows, (int64_t)rpw * 4) < 256 ? ceil_div64(rows, (int64_t)rpw * 4) : 256;
-    }
+    // 65536 x 192 -> 512 (25), 16384 x 384 -> 256 (20.7; 2048 workgroups: 31), 4096 x 768 -> 256..512 (19).
+    int64_t rows_per_block = 24576 / C;
+    if (rows_per_block < rpw * 4) rows_per_block = rpw * 4;
+    int64_t blocks = ceil_div64(rows, rows_per_block);
+    if (blocks < 256) blocks = ceil_div64(rows, (int64_t)rpw * 4) < 256 ? ceil_div64(rows, (int64_t)rpw * 4) : 256;
     if (blocks > 1024) blocks = 1024;
     if (blocks < 1) blocks = 1;
     return (int)blocks;
@@ -985,8 +963,7 @@ static int layernorm_bwd_launch(const void* dy, const int32_t* dy_index, const v
 #define LN_BWD_T(T)                                     \
     do {                                                \
         if (cpl <= 1) {                                 \
-            if (lpr >= 32 && ln_bwd_u8()) LN_BWD(T, 1, 8); \
-            else if (lpr >= 32) LN_BWD(T, 1, 4);        \
+            if (lpr >= 32) LN_BWD(T, 1, 4);             \
             else if (lpr >= 16) LN_BWD(T, 1, 2);        \
             else LN_BWD(T, 1, 1);                       \
         } else if (cpl <= 2) LN_BWD(T, 2, 4);           \

@@ -580,8 +580,7 @@ extern "C" int iseg_resize_bilinear_bwd(const void* dy, int dy_dtype, void* dx, 
     float* tmp = (float*)ws;
     const float sy = (float)Hi / (float)Ho, sx = (float)Wi / (float)Wo;
     // exact x2 up-sampling with 16-byte channel chunks: one pass, no intermediate
-    static const bool x2_off = [] { const char* e = getenv("ISEG_RESIZE_BWD_X2"); return e && atoi(e) == 0; }();
-    if (!x2_off && Ho == 2 * Hi && Wo == 2 * Wi && C % 8 == 0 && dy_dtype == dx_dtype && (int64_t)N * Hi * Wi * (C / 8) < (1ll << 31) &&
+    if (Ho == 2 * Hi && Wo == 2 * Wi && C % 8 == 0 && dy_dtype == dx_dtype && (int64_t)N * Hi * Wi * (C / 8) < (1ll << 31) &&
         (((uintptr_t)dy | (uintptr_t)dx | (uintptr_t)dx_add) & 15) == 0) {
         const unsigned vb = cap_blocks((int64_t)N * Hi * Wi * (C / 8));
         if (dy_dtype == ISEG_BF16)

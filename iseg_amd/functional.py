@@ -80,7 +80,7 @@ class _CastFn(Function):
 # ---------------------------------------------------------------------------------------------------------
 # Dense / 1x1 conv:  y = act(x @ W + b)         keras.layers.Dense, Conv2D(1x1)
 # ---------------------------------------------------------------------------------------------------------
-_DMA_MIN_K = max(16, int(os.environ.get("ISEG_GEMM_DMA_MIN_K", "32")))      # the same knob csrc/gemm.hip reads (dma_min_k)
+_DMA_MIN_K = 32      # the other half: dma_min_k in csrc/gemm_dma.h
 
 
 def _kcontig_kernel(W, x2, Kd, N):

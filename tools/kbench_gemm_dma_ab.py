@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""One LDS-DMA GEMM shape, timed with the environment's tile knobs (run once per setting: the knobs are read at first use).
+"""One LDS-DMA GEMM shape, timed on the tile form the dispatcher picks (ISEG_GEMM_DMA_BK32 / _128X192 / _64X192 still select among forms;
+they are read at first use, so run once per setting).
   python tools/kbench_gemm_dma_ab.py M N K [aux]      # aux: the x aux epilogue (dgrad x gelu')"""
 import os
 import sys
@@ -38,5 +39,4 @@ for _ in range(50):
 e1.record()
 torch.cuda.synchronize()
 us = e0.elapsed_time(e1) * 1e3 / 50
-print(f"M={M} N={N} K={Kd} aux={aux_on}  {us:7.1f} us  {2.0 * M * N * Kd / us * 1e-6:7.1f} TFLOP/s  rel err {err:.2e}  "
-      f"WIDE={os.environ.get('ISEG_GEMM_DMA_WIDE', '0')} PERSIST={os.environ.get('ISEG_GEMM_DMA_PERSIST', '1')}")
+print(f"M={M} N={N} K={Kd} aux={aux_on}  {us:7.1f} us  {2.0 * M * N * Kd / us * 1e-6:7.1f} TFLOP/s  rel err {err:.2e}")

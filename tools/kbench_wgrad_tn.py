@@ -1,11 +1,8 @@
 #!/usr/bin/env python3
 """Weight-gradient GEMM shapes of the flagship (dW = X^T dY, split over the pixels, bias gradient on the ones-row), timed with the reduction of the
-slabs and without, on the register-staged kernel (ISEG_GEMM_DMA_TN=0) and on the LDS-DMA kernel of csrc/gemm_dma_tn.h (default).  The knob is read
-at first use, so each setting runs in its own process:
-  python tools/kbench_wgrad_tn.py            # both settings, all shapes
-  python tools/kbench_wgrad_tn.py one        # this process's setting only"""
+slabs and without, on the kernel the dispatcher picks (the LDS-DMA kernel of csrc/gemm_dma_tn.h where eligible):
+  python tools/kbench_wgrad_tn.py"""
 import os
-import subprocess
 import sys
 
 SHAPES = [(16384, 1536, 384), (16384, 384, 1536), (4096, 3072, 768), (4096, 768, 3072), (65536, 768, 192), (65536, 192, 768)]
@@ -56,15 +53,10 @@ def one():
             torch.cuda.synchronize()
             res.append(e0.elapsed_time(e1) * 1e3 / 50)
         tf = 2.0 * rows * Cc * N / (res[1] * 1e-6) / 1e12
-        print(f"DMA_TN={os.environ.get('ISEG_GEMM_DMA_TN', '1')} rows {rows:6d} M {Cc:5d} N {N:5d}: variant {int(L.iseg_gemm_variant(C.byref(g)))} "
+        print(f"rows {rows:6d} M {Cc:5d} N {N:5d}: variant {int(L.iseg_gemm_variant(C.byref(g)))} "
               f"slabs {int(L.iseg_gemm_slabs(C.byref(g))):3d}  with reduce {res[0]:7.1f} us  product alone {res[1]:7.1f} us ({tf:6.1f} TFLOP/s)  "
               f"rel err dW {err:.1e} db {errb:.1e}", flush=True)
 
 
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "one":
-        one()
-    else:
-        for v in ("0", "1"):
-            env = dict(os.environ, ISEG_GEMM_DMA_TN=v)
-            subprocess.run([sys.executable, os.path.abspath(__file__), "one"], env=env, check=False)
+    one()

@@ -1,6 +1,6 @@
-// Timing harness for gemm_bf16_dma_tn_kernel and its ablation builds:
-//   hipcc --offload-arch=gfx950 -O3 -w -Iinclude -Iiseg_amd/csrc [-DISEG_TN_ABL_NOWAIT] [-DISEG_TN_ABL_NODMA] [-DISEG_TN_ABL_NOMFMA] tools/micro/tn_bench.hip -o tools/micro/tnb_<name>
-//   ./tools/micro/tnb_<name> [M N K splits]        (defaults: the stage-2 pwconv2 weight gradient 1536 384 16384 13)
+// Timing harness for gemm_bf16_dma_tn_kernel:
+//   hipcc --offload-arch=gfx950 -O3 -w -Iinclude -Iiseg_amd/csrc tools/micro/tn_bench.hip -o tools/micro/tnb_bench
+//   ./tools/micro/tnb_bench [M N K splits]        (defaults: the stage-2 pwconv2 weight gradient 1536 384 16384 13)
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -8,12 +8,6 @@
 extern "C" void iseg_set_error(const char* fmt, ...) { va_list a; va_start(a, fmt); vfprintf(stderr, fmt, a); va_end(a); fputc('\n', stderr); }
 int iseg_check_launch(const char* what) { hipError_t e = hipGetLastError(); if (e != hipSuccess) { fprintf(stderr, "%s: %s\n", what, hipGetErrorString(e)); return -2; } return 0; }
 #include "../../iseg_amd/csrc/gemm_dma_tn.h"
-namespace iseg_mm {
-int dma_mode() { return 1; }
-int dma_tn_mode() { return 1; }
-int long_k_tile() { return 128; }
-int tile_waves() { return 8; }
-}
 
 int main(int argc, char** argv) {
     const int64_t M = argc > 4 ? atoll(argv[1]) : 1536, N = argc > 4 ? atoll(argv[2]) : 384, K = argc > 4 ? atoll(argv[3]) : 16384;
