@@ -316,6 +316,38 @@ int iseg_bnfold_dwconv3_relu_bwd(const void* D, const void* z, const void* x, co
                                  int stride, int dil, int dtype, void* ws, size_t ws_bytes, iseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * ResNet-9 / 10 / 18 basic-block tail (backbones/resnet_blocks_small.py, BlockType2Small.call :84-119: shortcut_bn :89-90, avg_pool2d of the
+ * shortcut :92-98, conv2_bn :105, add + relu :107-108):
+ *   out = relu(bn2(z2) + pool_s(sc)),  sc = bn0(z0) (shortcut conv) or x (identity),  bn(v) = (v - mean) * rstd * gamma + beta
+ *   pool_s = avg_pool2d(window = strides = s, "SAME"), s in {1, 2}, padded cells excluded from the divisor.
+ * The shortcut input z0 / x is [N, H, W, C]; z2, out, dout, dz2 are [N, ceil(H/s), ceil(W/s), C]; NHWC fp32 or bf16 (dtype), statistics fp32.
+ * Training statistics: mean / rstd from iseg_bn_stats + (all-reduce) + iseg_bn_finalize; moving statistics: moving_mean and
+ * iseg_rsqrt_eps(moving_variance).  mean0 / z0 == NULL selects the identity shortcut.
+ *   iseg_resblock_tail_fwd         reads z2 and the shortcut input once, writes only out (no BN output, no pooled shortcut)
+ *   iseg_resblock_tail_bwd_reduce  g = dout * [out > 0]; sums [2C] = (sum g, sum g*xhat2) over the output rows, and with a BN0 shortcut
+ *                                  [4C]: + (sum u, sum u*xhat0) over the full-resolution rows, u = unpool(g) / count -- each half in
+ *                                  iseg_bn_bwd_reduce's layout, so the SyncBN all-reduce carries the message unchanged.  Per-workgroup
+ *                                  partials go to ws (iseg_resblock_tail_workspace_bytes) and are summed in a fixed order.
+ *   iseg_resblock_tail_bwd_apply   dz2 = gamma2*rstd2*(g - sums0*inv_n2 - xhat2*sums1*inv_n2), and dsc [N, H, W, C] = dz0 (the same with BN0's
+ *                                  sums and inv_n0 on u) or u (identity shortcut: the caller's fork sums it with the main path's gradient).
+ *                                  train == 0 (moving statistics): dz = gamma*rstd*g.  dgamma / dbeta (either BN, any may be NULL) += the
+ *                                  sums by the same launch -- only while the sums are this replica's own.
+ * C % 8 == 0, stride 1 or 2, 16-byte aligned tensors and vectors; anything else returns ISEG_ERR_UNSUPPORTED.  No float atomics.
+ * --------------------------------------------------------------------------------------------------------- */
+int iseg_resblock_tail_supported(int C, int stride, int dtype);
+size_t iseg_resblock_tail_workspace_bytes(int N, int H, int W, int C, int stride, int bn0);
+int iseg_resblock_tail_fwd(const void* z2, const float* mean2, const float* rstd2, const float* gamma2, const float* beta2, const void* sc,
+                           const float* mean0, const float* rstd0, const float* gamma0, const float* beta0, void* out, int N, int H, int W, int C,
+                           int stride, int dtype, iseg_stream_t stream);
+int iseg_resblock_tail_bwd_reduce(const void* dout, const void* out, const void* z2, const float* mean2, const float* rstd2, const void* z0,
+                                  const float* mean0, const float* rstd0, float* sums, int N, int H, int W, int C, int stride, int dtype, void* ws,
+                                  size_t ws_bytes, iseg_stream_t stream);
+int iseg_resblock_tail_bwd_apply(const void* dout, const void* out, const void* z2, const float* mean2, const float* rstd2, const float* gamma2,
+                                 const void* z0, const float* mean0, const float* rstd0, const float* gamma0, const float* sums, float inv_n2,
+                                 float inv_n0, int train, void* dz2, void* dsc, float* dgamma2, float* dbeta2, float* dgamma0, float* dbeta0,
+                                 int N, int H, int W, int C, int stride, int dtype, iseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Exchange step of the data-parallel path: distribution/distribution_utils.py:158-169 all_reduce_values -> ReplicaContext.all_reduce(SUM)
  * (SyncBN statistics layers/keras3/bn.py:60-117, gradient sums), over RCCL on xGMI.  One process per GPU: rank 0 creates the 128-byte id
  * and hands it to the other ranks through the host program; every rank then calls iseg_comm_init.  iseg_allreduce_sum works in place and is

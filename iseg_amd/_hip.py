@@ -113,6 +113,11 @@ SIGNATURES = {
     "iseg_sepconv_fold_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _p]),
     "iseg_bnfold_dwconv3_relu_bwd_workspace_bytes": (_z, [_i, _i, _i, _i, _i, _i]),
     "iseg_bnfold_dwconv3_relu_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _f, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _z, _p]),
+    "iseg_resblock_tail_supported": (_i, [_i, _i, _i]),
+    "iseg_resblock_tail_workspace_bytes": (_z, [_i, _i, _i, _i, _i, _i]),
+    "iseg_resblock_tail_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "iseg_resblock_tail_bwd_reduce": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _z, _p]),
+    "iseg_resblock_tail_bwd_apply": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _f, _f, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "iseg_cast": (_i, [_p, _i, _p, _i, _l, _p]),
     "iseg_deferred_begin": (_i, [_p, _z, _p, _z, _p]),
     "iseg_deferred_flush": (_i, [_p]),

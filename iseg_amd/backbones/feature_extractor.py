@@ -11,7 +11,7 @@ from .efficientnet import (EfficientNetB0, EfficientNetB1, EfficientNetB2, Effic
                            EfficientNetB7, EfficientNetL2, build_dilated_efficientnet)
 from .hrnet import HRNetW32, HRNetW48
 from .mobilenetv2_common import MobileNetV2, build_atrous_mobilenetv2
-from .resnet_common import apply_multi_grid, build_atrous_resnet, resnet50, resnet101, resnet152
+from .resnet_common import apply_multi_grid, build_atrous_resnet, resnet9, resnet10, resnet18, resnet50, resnet101, resnet152
 from .xception import build_atrous_xception, xception65
 
 
@@ -38,6 +38,9 @@ def _builtin_backbones():
         ss.MOBILENETV2: MobileNetV2,
         ss.HRNET_W48: HRNetW48,
         ss.HRNET_W32: HRNetW32,
+        ss.RESNET9: resnet9,      # (feature_extractor.py:79-81)
+        ss.RESNET10: resnet10,
+        ss.RESNET18: resnet18,
         ss.RESNET50: resnet50,
         ss.RESNET52: resnet50,
         ss.RESNET101: resnet101,

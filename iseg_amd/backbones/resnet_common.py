@@ -1,5 +1,5 @@
 """backbones/resnet_common.py of the reference: Stack (:24-91), Stack2 (:94-184, stride in the LAST block), ResNet (:187-345,
-3x3 deep stem when replace_7x7_conv), constructors (:348-520), build_stacks (:523-560), build_atrous_resnet (:561-588),
+3x3 deep stem when replace_7x7_conv), constructors (:348-520; resnet9 / 10 / 18 on BlockType2Small of resnet_blocks_small.py), build_stacks (:523-560), build_atrous_resnet (:561-588),
 apply_multi_grid (:591-598)."""
 import torch
 
@@ -9,6 +9,7 @@ from ..layers.base_layers import Conv2D
 from ..layers.normalizations import normalization
 from ..nn import Layer
 from .resnet_blocks import BN_EPSILON, BlockType1, BlockType2, _bn_relu
+from .resnet_blocks_small import BlockType2Small
 from .utils.layerwise_decay import decay_layers_lr
 
 DEFAULT_CONV_FUNC = Conv2D
@@ -180,17 +181,25 @@ def get_resnet(resnet_name=ss.RESNET50, num_of_blocks=[3, 4, 6, 3], use_bias=Tru
                   name=resnet_name)
 
 
-def _ctor(name, blocks):
+def _ctor(name, blocks, conv1_depth_multiplier=1, default_block=None, fn_name=None):
+    """conv1_depth_multiplier: a value, or a function of replace_7x7_conv; default_block: the block when custom_block is None"""
     def fn(use_bias=True, norm_method=None, replace_7x7_conv=False, slim_behaviour=False, custom_block=None, return_endpoints=False,
            conv_func=DEFAULT_CONV_FUNC):
+        mult = conv1_depth_multiplier(replace_7x7_conv) if callable(conv1_depth_multiplier) else conv1_depth_multiplier
         return get_resnet(resnet_name=name, num_of_blocks=blocks, use_bias=use_bias, norm_method=norm_method,
-                          replace_7x7_conv=replace_7x7_conv, slim_behaviour=slim_behaviour, custom_block=custom_block,
-                          return_endpoints=return_endpoints, conv_func=conv_func)
+                          replace_7x7_conv=replace_7x7_conv, slim_behaviour=slim_behaviour, conv1_depth_multiplier=mult,
+                          custom_block=default_block if custom_block is None else custom_block, return_endpoints=return_endpoints,
+                          conv_func=conv_func)
 
-    fn.__name__ = name
+    fn.__name__ = fn_name or name
     return fn
 
 
+resnet9 = _ctor(ss.RESNET9, [1, 1, 1, 1], 0.5, BlockType2Small)
+# the reference's resnet10 (:372-393) names its model RESNET9 as well
+resnet10 = _ctor(ss.RESNET9, [1, 1, 1, 1], lambda replace_7x7_conv: (0.375, 0.5, 0.5) if replace_7x7_conv else 0.5, BlockType2Small,
+                 fn_name=ss.RESNET10)
+resnet18 = _ctor(ss.RESNET18, [2, 2, 2, 2], 0.5, BlockType2Small)
 resnet50 = _ctor(ss.RESNET50, [3, 4, 6, 3])
 resnet101 = _ctor(ss.RESNET101, [3, 4, 23, 3])
 resnet152 = _ctor(ss.RESNET152, [3, 8, 36, 3])

@@ -1076,6 +1076,150 @@ def sepconv_unit(x, dw_kernel, bn, pw_kernel, training, strides=1, dilation=1):
 
 
 # ---------------------------------------------------------------------------------------------------------
+# ResNet-9 / 10 / 18 basic-block tail (backbones/resnet_blocks_small.py:84-119): relu(bn2(z2) + avg_pool_s(bn0(z0) or x)) as one tape node
+# (csrc/resblock.hip).  Neither BN output nor the pooled shortcut is written; the statistics and gradient-sum messages are
+# _BatchNormTrainFn's (both layers' in one message), so the SyncBN all-reduces carry them unchanged.
+# ---------------------------------------------------------------------------------------------------------
+def _bn_vecs(gamma, beta):
+    return gamma.data, beta.data
+
+
+def _resblock_backward(ctx, dout, train, inv_n2, inv_n0):
+    """reduce -> (all-reduce of both layers' [2C] sums in one message) -> apply; returns (dz2, dsc)"""
+    out, z2, z0, mean2, rstd2, mean0, rstd0 = ctx.saved_tensors
+    gamma2, beta2, gamma0, beta0 = ctx.params
+    C = z2.shape[-1]
+    bn0 = z0 is not None
+    dO = _c(dout)
+    sums = K.resblock_tail_bwd_reduce(dO, out, z2, mean2, rstd2, ctx.sc_shape, ctx.stride, z0, mean0, rstd0)
+    pg = [_grad(p) if p is not None and p.requires_grad else None for p in (gamma2, beta2, gamma0, beta0)]
+    own = dict(dgamma2=pg[0], dbeta2=pg[1], dgamma0=pg[2], dbeta0=pg[3])
+    if train and ctx.sync and dist.active():
+        # local parameter gradients first (the gradient all-reduce sums them over ranks later), then the sums of all replicas
+        K.accumulate_pair(sums[:2 * C], C, pg[1], pg[0])
+        if bn0:
+            K.accumulate_pair(sums[2 * C:], C, pg[3], pg[2])
+        dist.grads_ready(gamma2, beta2, gamma0, beta0)
+        sums = sums.clone()
+        dist.all_reduce_sum(sums)           # [2C] per layer: the sums message of _BatchNormTrainFn's backward
+        w = dist.world_size()
+        inv_n2, inv_n0 = inv_n2 / w, inv_n0 / w
+        own = {}
+    g0 = gamma0.data if bn0 else None
+    dz2, dsc = K.resblock_tail_bwd_apply(dO, out, z2, mean2, rstd2, gamma2.data, sums, inv_n2, inv_n0, train, ctx.sc_shape, ctx.stride, z0, mean0,
+                                         rstd0, g0, **own)
+    if own:
+        dist.grads_ready(gamma2, beta2, gamma0, beta0)
+    return dz2, (dsc if ctx.needs_input_grad[1] else None)
+
+
+class _ResBlockTailTrainFn(Function):
+    @staticmethod
+    def forward(ctx, z2, sc, gamma2, beta2, gamma0, beta0, moving2, moving0, eps, momentum, stride, sync):
+        C = z2.shape[-1]
+        z2c, scc = _c(z2), _c(sc)
+        bn0 = gamma0 is not None
+        r2, r0 = z2c.numel() // C, scc.numel() // C
+        if bn0:
+            # one message for both layers: [sum | sumsq | count] of z2, 3 floats of padding (16-byte aligned slots), then z0's
+            msg = torch.empty(4 * C + 5, dtype=torch.float32, device=z2.device)
+            K.bn_stats(z2c.reshape(r2, C), C, r2, C, out=msg[:2 * C + 1])
+            K.bn_stats(scc.reshape(r0, C), C, r0, C, out=msg[2 * C + 4:])
+        else:
+            msg = K.bn_stats(z2c.reshape(r2, C), C, r2, C)
+        if sync:
+            dist.all_reduce_sum(msg)          # the packed statistics message of _BatchNormTrainFn
+        mean2, rstd2 = K.bn_finalize(msg[:2 * C + 1], C, eps[0], momentum[0], moving2[0], moving2[1])
+        mean0 = rstd0 = None
+        if bn0:
+            mean0, rstd0 = K.bn_finalize(msg[2 * C + 4:], C, eps[1], momentum[1], moving0[0], moving0[1])
+        out = K.resblock_tail_fwd(z2c, mean2, rstd2, *_bn_vecs(gamma2, beta2), scc, stride,
+                                  (mean0, rstd0) + _bn_vecs(gamma0, beta0) if bn0 else None)
+        ctx.params, ctx.sync, ctx.stride, ctx.sc_shape, ctx.rows = (gamma2, beta2, gamma0, beta0), sync, stride, tuple(sc.shape), (r2, r0)
+        ctx.save_for_backward(out, z2c, scc if bn0 else None, mean2, rstd2, mean0, rstd0)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        r2, r0 = ctx.rows
+        return _resblock_backward(ctx, dout, True, 1.0 / r2, 1.0 / r0) + (None,) * 10
+
+
+class _ResBlockTailInferFn(Function):
+    @staticmethod
+    def forward(ctx, z2, sc, gamma2, beta2, gamma0, beta0, moving2, moving0, eps, stride):
+        z2c, scc = _c(z2), _c(sc)
+        bn0 = gamma0 is not None
+        # the backward reads the statistics of THIS call: a later training-mode call updates the buffers in place
+        mean2, rstd2 = moving2[0].clone(), K.rsqrt_eps(moving2[1], eps[0])
+        mean0 = rstd0 = None
+        if bn0:
+            mean0, rstd0 = moving0[0].clone(), K.rsqrt_eps(moving0[1], eps[1])
+        out = K.resblock_tail_fwd(z2c, mean2, rstd2, *_bn_vecs(gamma2, beta2), scc, stride,
+                                  (mean0, rstd0) + _bn_vecs(gamma0, beta0) if bn0 else None)
+        ctx.params, ctx.sync, ctx.stride, ctx.sc_shape = (gamma2, beta2, gamma0, beta0), False, stride, tuple(sc.shape)
+        ctx.save_for_backward(out, z2c, scc if bn0 else None, mean2, rstd2, mean0, rstd0)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        return _resblock_backward(ctx, dout, False, 0.0, 0.0) + (None,) * 8
+
+
+def resblock_fused_enabled():
+    """ISEG_RESBLOCK_FUSED=0 routes the ResNet-9 / 10 / 18 block tail through the composed operators (the A/B baseline)"""
+    return os.environ.get("ISEG_RESBLOCK_FUSED", "1") != "0"
+
+
+def resblock_tail_supported(z2, sc, bn2, bn0=None, strides=1):
+    """the shape rules of csrc/resblock.hip, and the 16-byte alignment its vector accesses need: of z2 / sc when they are passed as is (a
+    non-contiguous tensor is copied into a fresh, aligned buffer first) and of the per-channel vectors it reads directly"""
+    sh, sw = (strides, strides) if isinstance(strides, int) else tuple(strides)
+    if sh != sw or sh not in (1, 2) or z2.dim() != 4 or sc.dim() != 4 or z2.dtype != sc.dtype:
+        return False
+    N, H, W, C = sc.shape
+    if tuple(z2.shape) != (N, -(-H // sh), -(-W // sh), C):
+        return False
+    if any(t.is_contiguous() and t.data_ptr() % 16 for t in (z2, sc)):
+        return False
+    layers = (bn2,) if bn0 is None else (bn2, bn0)
+    vectors = [v for b in layers for v in (b.gamma, b.beta, b.moving_mean, b.moving_variance)]
+    if any(v.data_ptr() % 16 or not v.is_contiguous() for v in vectors):
+        return False
+    return K.resblock_tail_supported(C, sh, z2.dtype)
+
+
+def resblock_tail(z2, bn2, sc, bn0, strides, training):
+    """relu(bn2(z2) + avg_pool2d(sc', strides, strides, "same")), sc' = bn0(sc) (bn0 a BatchNormalization layer) or sc (bn0 None): the tail
+    of BlockType2Small.  Fused unless ISEG_RESBLOCK_FUSED=0, the two layers differ in mode or synchronisation, or resblock_tail_supported
+    refuses the shapes or tensors; then the composed operators run."""
+    _check_act_dtype(z2)
+    st = (strides, strides) if isinstance(strides, int) else tuple(strides)
+    layers = (bn2,) if bn0 is None else (bn2, bn0)
+    for b in layers:
+        if not b.built:
+            b.build(tuple((z2 if b is bn2 else sc).shape))
+    modes = {bool(training) and b.trainable for b in layers}
+    syncs = {bool(b.synchronized) for b in layers}
+    if (nn.dry_run() or not resblock_fused_enabled() or len(modes) > 1 or len(syncs) > 1
+            or not resblock_tail_supported(z2, sc, bn2, bn0, st)):
+        if bn0 is not None:
+            sc = bn0(sc, training=training)
+        if st[0] > 1 or st[1] > 1:
+            sc = avg_pool2d(sc, st, st, "same")
+        return add_relu(sc, bn2(z2, training=training))
+    s = st[0]
+    eps = (float(bn2.epsilon), float(bn0.epsilon) if bn0 is not None else 0.0)
+    moving2 = (bn2.moving_mean, bn2.moving_variance)
+    moving0 = (bn0.moving_mean, bn0.moving_variance) if bn0 is not None else (None, None)
+    g0, b0 = (bn0.gamma, bn0.beta) if bn0 is not None else (None, None)
+    if modes.pop():
+        momentum = (float(bn2.momentum), float(bn0.momentum) if bn0 is not None else 0.0)
+        return _ResBlockTailTrainFn.apply(z2, sc, bn2.gamma, bn2.beta, g0, b0, moving2, moving0, eps, momentum, s, syncs.pop())
+    return _ResBlockTailInferFn.apply(z2, sc, bn2.gamma, bn2.beta, g0, b0, moving2, moving0, eps, s)
+
+
+# ---------------------------------------------------------------------------------------------------------
 # activations, add, dropout, drop-path
 # ---------------------------------------------------------------------------------------------------------
 class _ActFn(Function):

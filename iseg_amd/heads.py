@@ -112,6 +112,12 @@ def resnet50_aspp(num_class=21, output_stride=32, build_input_size=(256, 256), d
                     build_input_size)
 
 
+def resnet18_aspp(num_class=21, output_stride=32, build_input_size=(256, 256), dropout_rate=0.1):
+    """ResNet-18 (slim, BlockType2Small) + ASPP: the light counterpart of resnet50_aspp"""
+    return _managed("resnet18", ASPPHead(256, output_stride=output_stride, dropout_rate=dropout_rate), num_class, output_stride,
+                    build_input_size)
+
+
 def efficientnet_b0_aspp(num_class=21, output_stride=32, build_input_size=(512, 512), dropout_rate=0.1):
     """EfficientNet-B0 (backbones/efficientnet.py, with top_conv) + ASPP"""
     return _managed("efficientnetb0", ASPPHead(256, output_stride=output_stride, dropout_rate=dropout_rate), num_class, output_stride,

@@ -684,6 +684,50 @@ def bnfold_dwconv3_relu_bwd(D, z, x, w, mean, rstd, gamma, sums, inv_n, train, d
 
 
 # ---------------------------------------------------------------------------------------------------------
+# ResNet-9 / 10 / 18 basic-block tail: relu(bn2(z2) + avg_pool_s(bn0(z0) or x)) (csrc/resblock.hip)
+# ---------------------------------------------------------------------------------------------------------
+def resblock_tail_supported(Cc, stride, dtype):
+    return bool(_hip.lib().iseg_resblock_tail_supported(int(Cc), int(stride), dt(dtype)))
+
+
+def resblock_tail_fwd(z2, mean2, rstd2, gamma2, beta2, sc, stride, bn0=None):
+    """out = relu(bn2(z2) + pool_s(sc')), sc' = bn0(sc) when bn0 = (mean0, rstd0, gamma0, beta0) is given, else sc; sc [N, H, W, C],
+    z2 [N, ceil(H/s), ceil(W/s), C]"""
+    _require_cuda(z2, sc)
+    N, H, W, Cc = sc.shape
+    m0, r0, g0, b0 = bn0 if bn0 is not None else (None,) * 4
+    out = torch.empty_like(z2)
+    _hip.call("iseg_resblock_tail_fwd", ptr(z2), ptr(mean2), ptr(rstd2), ptr(gamma2), ptr(beta2), ptr(sc), ptr(m0), ptr(r0), ptr(g0), ptr(b0),
+              ptr(out), N, H, W, Cc, int(stride), dt(z2), stream())
+    return out
+
+
+def resblock_tail_bwd_reduce(dout, out, z2, mean2, rstd2, sc_shape, stride, z0=None, mean0=None, rstd0=None):
+    """sums [2C] = (sum g, sum g*xhat2), g = dout*[out > 0]; with z0 [4C]: + (sum u, sum u*xhat0) over the full-resolution rows"""
+    _require_cuda(dout, out, z2)
+    N, H, W, Cc = sc_shape
+    sums = torch.empty((4 if z0 is not None else 2) * Cc, dtype=torch.float32, device=z2.device)
+    ws, wsb = workspace(_hip.lib().iseg_resblock_tail_workspace_bytes(N, H, W, Cc, int(stride), int(z0 is not None)), z2.device)
+    _hip.call("iseg_resblock_tail_bwd_reduce", ptr(dout), ptr(out), ptr(z2), ptr(mean2), ptr(rstd2), ptr(z0), ptr(mean0), ptr(rstd0), ptr(sums),
+              N, H, W, Cc, int(stride), dt(z2), ptr(ws), wsb, stream())
+    return sums
+
+
+def resblock_tail_bwd_apply(dout, out, z2, mean2, rstd2, gamma2, sums, inv_n2, inv_n0, train, sc_shape, stride, z0=None, mean0=None, rstd0=None,
+                            gamma0=None, dgamma2=None, dbeta2=None, dgamma0=None, dbeta0=None):
+    """(dz2, dsc): dsc [N, H, W, C] = dz0 (BN0 shortcut) or unpool(g) / count (identity); dgamma / dbeta (+)= the sums by the same launch --
+    only while `sums` are this replica's own"""
+    _require_cuda(dout, out, z2)
+    N, H, W, Cc = sc_shape
+    dz2 = torch.empty_like(z2)
+    dsc = torch.empty(tuple(sc_shape), dtype=z2.dtype, device=z2.device)
+    _hip.call("iseg_resblock_tail_bwd_apply", ptr(dout), ptr(out), ptr(z2), ptr(mean2), ptr(rstd2), ptr(gamma2), ptr(z0), ptr(mean0), ptr(rstd0),
+              ptr(gamma0), ptr(sums), float(inv_n2), float(inv_n0), int(train), ptr(dz2), ptr(dsc), ptr(dgamma2), ptr(dbeta2), ptr(dgamma0),
+              ptr(dbeta0), N, H, W, Cc, int(stride), dt(z2), stream())
+    return dz2, dsc
+
+
+# ---------------------------------------------------------------------------------------------------------
 # depthwise conv
 # ---------------------------------------------------------------------------------------------------------
 def dwconv2d(x, w, bias, K, dil, pad_t, pad_l, *, flip=False, add=None):
