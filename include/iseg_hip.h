@@ -498,6 +498,26 @@ int iseg_argmax_confusion(const float* logits, const int32_t* labels, int64_t P,
                           unsigned long long* cm, iseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * losses/mask_loss.py:10-201 MaskLoss (+ dice(), :159-200) on losses/seg_loss_base.py:12-95 SegLossBase: per-class sigmoid (focal) loss,
+ * per-image dice loss and softmax cross-entropy, the ignore label carried as a Keras loss mask (a mean over VALID pixels).
+ * logits [B, HW, C] fp32, labels [B, HW] int32 (already at the logits' size), C <= 256.  flags = ISEG_MASKLOSS_* ; at least one term.
+ *   loss_px [B*HW]  (optional) the masked per-pixel loss, dice value of the image included      (reduction = none)
+ *   loss_mean[0]    (optional) loss_scale * sum(valid * loss) / (sum(valid) + 1e-7)             (sum_over_batch_size under the mask)
+ *   dlogits         (optional) grad_scale * d(mean)/d(logits); with grad_px [B*HW] instead grad_scale * sum_p grad_px[p] d(loss_px[p])/d(logits)
+ * Two streaming passes over the logits and one fixed-order finalize launch in between; no floating-point atomics, no host read.
+ * --------------------------------------------------------------------------------------------------------- */
+#define ISEG_MASKLOSS_SIGMOID 1
+#define ISEG_MASKLOSS_DICE 2
+#define ISEG_MASKLOSS_CE 4
+#define ISEG_MASKLOSS_FOCAL_SIGMOID 8
+#define ISEG_MASKLOSS_FOCAL_CE 16
+#define ISEG_MASKLOSS_CLASS_BALANCING 32
+size_t iseg_mask_loss_workspace_bytes(int B, int64_t HW, int C);
+int iseg_mask_loss(const float* logits, const int32_t* labels, int B, int64_t HW, int C, int ignore_label, int flags, float sigmoid_coef,
+                   float dice_coef, float ce_coef, float* loss_px, float* loss_mean, float loss_scale, float* dlogits, float grad_scale,
+                   const float* grad_px, void* ws, size_t ws_bytes, iseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * optimizers/modern/adamw.py:13-74, optimizers/modern/sgd.py:12-51 over the flat parameter buffer.
  * Every tensor is padded to a multiple of 256 elements; seg_of_block[b] = tensor index of 256-element block b
  * (-1 = padding).  hp (device): [lr, sqrt(1-b2^t)/(1-b1^t), grad_scale, clipvalue(<=0 off)].

@@ -1899,6 +1899,76 @@ def softmax_ce_per_pixel(logits, labels, num_class, ignore_label, class_w=None, 
 
 
 # ---------------------------------------------------------------------------------------------------------
+# MaskLoss: sigmoid (focal) + dice + cross-entropy under the ignore-label mask          losses/mask_loss.py:10-201
+# ---------------------------------------------------------------------------------------------------------
+def _mask_loss_inputs(logits, labels):
+    B, H, W, Cc = logits.shape
+    z = _c(logits).reshape(B, H * W, Cc)
+    if z.dtype != torch.float32:
+        z = K.cast(z, torch.float32)
+    y = _c(labels).reshape(B, H * W)
+    if y.dtype != torch.int32:
+        y = y.to(torch.int32)
+    return z, y
+
+
+class _MaskLossPerPixelFn(Function):
+    """the masked per-pixel loss [B, H*W] (Keras reduction none); the backward takes the per-pixel upstream gradient through both passes"""
+
+    @staticmethod
+    def forward(ctx, logits, labels, ignore_label, flags, coefs):
+        z, y = _mask_loss_inputs(logits, labels)
+        px, _, _ = K.mask_loss(z, y, ignore_label, flags, coefs, want_px=True)
+        ctx.args = (ignore_label, flags, coefs)
+        ctx.in_dtype, ctx.in_shape = logits.dtype, logits.shape
+        ctx.save_for_backward(z, y)
+        return px.reshape(z.shape[0], z.shape[1])
+
+    @staticmethod
+    def backward(ctx, dpx):
+        z, y = ctx.saved_tensors
+        ignore_label, flags, coefs = ctx.args
+        gp = _c(dpx).reshape(-1)
+        if gp.dtype != torch.float32:
+            gp = K.cast(gp, torch.float32)
+        _, _, dz = K.mask_loss(z, y, ignore_label, flags, coefs, want_grad=True, grad_scale=1.0, grad_px=gp)
+        if dz.dtype != ctx.in_dtype:
+            dz = K.cast(dz, ctx.in_dtype)
+        return dz.reshape(ctx.in_shape), None, None, None, None
+
+
+class _MaskLossMeanFn(Function):
+    """weight * masked mean over the VALID pixels, and its gradient, from one call (two passes over the logits)"""
+
+    @staticmethod
+    def forward(ctx, logits, labels, ignore_label, flags, coefs, weight):
+        z, y = _mask_loss_inputs(logits, labels)
+        _, s, dz = K.mask_loss(z, y, ignore_label, flags, coefs, want_mean=True, mean_scale=weight, want_grad=ctx.needs_input_grad[0],
+                               grad_scale=weight)
+        ctx.shape, ctx.in_dtype = logits.shape, logits.dtype
+        ctx.save_for_backward(dz)
+        return s.reshape(())
+
+    @staticmethod
+    def backward(ctx, dloss):
+        (dz,) = ctx.saved_tensors
+        if not _UNIT_LOSS_GRAD[0]:      # as _SoftmaxCEMeanFn: the scalar chain factor is applied on the device
+            dz = K.scale_dev(dz, _c(dloss).reshape(1).to(torch.float32))
+        if dz.dtype != ctx.in_dtype:
+            dz = K.cast(dz, ctx.in_dtype)
+        return dz.reshape(ctx.shape), None, None, None, None, None
+
+
+def mask_loss_per_pixel(logits, labels, ignore_label, flags, coefs):
+    """logits [B,H,W,C], labels [B,H,W] (already at the logits' size); flags = kernels.MASKLOSS_*, coefs = (sigmoid, dice, ce)"""
+    return _MaskLossPerPixelFn.apply(logits, labels, int(ignore_label), int(flags), tuple(coefs))
+
+
+def mask_loss_mean(logits, labels, ignore_label, flags, coefs, weight=1.0):
+    return _MaskLossMeanFn.apply(logits, labels, int(ignore_label), int(flags), tuple(coefs), float(weight))
+
+
+# ---------------------------------------------------------------------------------------------------------
 # Deferred logits upsample: inside CoreTrain's step the model hands the low-resolution logits to the loss, and one kernel does
 # bilinear upsample + cross-entropy + its gradient through the resize + the confusion matrix  (layers/core_model_ext.py:199-256,
 # losses/catecrossentropy_ignore_label.py:44-88, metrics/seg_metric_wrapper.py:89-102)

@@ -1169,6 +1169,26 @@ def softmax_ce_ignore(logits2d, labels1d, ignore_label, *, class_w=None, want_px
     return loss_px, loss_sum, dlogits
 
 
+MASKLOSS_SIGMOID, MASKLOSS_DICE, MASKLOSS_CE, MASKLOSS_FOCAL_SIGMOID, MASKLOSS_FOCAL_CE, MASKLOSS_CLASS_BALANCING = 1, 2, 4, 8, 16, 32
+
+
+def mask_loss(logits3d, labels2d, ignore_label, flags, coefs, *, want_px=False, want_mean=False, mean_scale=1.0, want_grad=False,
+              grad_scale=1.0, grad_px=None):
+    """MaskLoss of losses/mask_loss.py (csrc/mask_loss.hip): logits [B,HW,C] fp32, labels [B,HW] int32, coefs = (sigmoid, dice, ce).
+    returns (loss_px [B*HW] | None, loss_mean [1] | None, dlogits | None); with grad_px the gradient is that of sum(grad_px * loss_px)"""
+    _require_cuda(logits3d, labels2d, grad_px)
+    B, HW, Cc = logits3d.shape
+    dev = logits3d.device
+    loss_px = torch.empty(B * HW, dtype=torch.float32, device=dev) if want_px else None
+    loss_mean = torch.empty(1, dtype=torch.float32, device=dev) if want_mean else None
+    dlogits = torch.empty_like(logits3d) if want_grad else None
+    ws, wsb = workspace(_hip.lib().iseg_mask_loss_workspace_bytes(B, HW, Cc), dev)
+    _hip.call("iseg_mask_loss", ptr(logits3d), ptr(labels2d), B, HW, Cc, int(ignore_label), int(flags), float(coefs[0]), float(coefs[1]),
+              float(coefs[2]), ptr(loss_px), ptr(loss_mean), float(mean_scale), ptr(dlogits), float(grad_scale), ptr(grad_px), ptr(ws), wsb,
+              stream())
+    return loss_px, loss_mean, dlogits
+
+
 def upsample_ce_supported(Hi, Wi, Ho, Wo, Cc):
     return bool(_hip.lib().iseg_upsample_ce_supported(int(Hi), int(Wi), int(Ho), int(Wo), int(Cc)))
 
