@@ -518,6 +518,31 @@ int iseg_mask_loss(const float* logits, const int32_t* labels, int B, int64_t HW
                    const float* grad_px, void* ws, size_t ws_bytes, iseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * metrics/sod/sod_metrics.py on metrics/sod/sod_metric_utils.py:17-109: TFMAEMetric (:114-190), TFSmeasureMetric (:193-438),
+ * TFEmeasureMetric (:441-743), TFFmeasureMetric (:746-938) and, with ISEG_SOD_WFM, TFWeightedFmeasureMetric (:941-1076, the SciPy
+ * distance transform and convolution of :35-111 included).  B images per call, each scored on its own.
+ *   pred [B,H,W]   fp32 in [0,1] (pred_is_u8 = normalize = 0), or uint8 with normalize = 1 (prepare_data, sod_metric_utils.py:67-95)
+ *   gt   [B,H,W]   one byte per pixel: non-zero is foreground, > 128 under normalize
+ *   state [ISEG_SOD_STATE_DOUBLES] += the per-image record summed in image order, count[0] += B   (both optional, together):
+ *       0 MAE, 1 S-measure, 2 adaptive E, 3 adaptive F, 4 weighted F, 5.. E curve [256], 261.. F curve [257], 518.. precision [257],
+ *       775.. recall [257]; curve index i is threshold 255 - i (E) or 256 - i (precision / recall / F), as the reference orders them
+ *   per_image_out [B, ISEG_SOD_STATE_DOUBLES]  (optional) the same record of every image
+ *   ints_out [B, ISEG_SOD_INTS] (optional): 0.. foreground histogram [256] of int(p * 255.0f), 256.. background histogram [256],
+ *       512 foreground count, 513 count of p >= thr, 514 of p >= thr && g, 515 cy, 516 cx (centroid + 1), 517 bits of the fp32 adaptive threshold
+ *   dist2_out / nearest_out [B,H,W] int32 (optional, ISEG_SOD_WFM): exact squared Euclidean distance to the nearest foreground pixel and its
+ *       row-major index (the smallest index among equidistant ones); unwritten for an image without foreground
+ * Two streaming passes over pred and gt with a mid step between them, the weighted F-measure's own kernels, a per-image finalize and one
+ * launch that adds to the state.  Float sums are fixed-order fp64 partials, integers use integer atomics; no host read.
+ * --------------------------------------------------------------------------------------------------------- */
+#define ISEG_SOD_WFM 1
+#define ISEG_SOD_STATE_DOUBLES 1032
+#define ISEG_SOD_INTS 544
+size_t iseg_sod_metrics_workspace_bytes(int B, int H, int W, int flags);
+int iseg_sod_metrics(const void* pred, int pred_is_u8, const uint8_t* gt, int normalize, int B, int H, int W, int flags, double alpha,
+                     double beta_fm, double beta_wfm, double* state, long long* count, int32_t* ints_out, double* per_image_out,
+                     int32_t* dist2_out, int32_t* nearest_out, void* ws, size_t ws_bytes, iseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * optimizers/modern/adamw.py:13-74, optimizers/modern/sgd.py:12-51 over the flat parameter buffer.
  * Every tensor is padded to a multiple of 256 elements; seg_of_block[b] = tensor index of 256-element block b
  * (-1 = padding).  hp (device): [lr, sqrt(1-b2^t)/(1-b1^t), grad_scale, clipvalue(<=0 off)].

@@ -1189,6 +1189,39 @@ def mask_loss(logits3d, labels2d, ignore_label, flags, coefs, *, want_px=False, 
     return loss_px, loss_mean, dlogits
 
 
+SOD_WFM = 1
+SOD_STATE_DOUBLES, SOD_INTS = 1032, 544
+SOD_CALLS = [0]      # launches of the shared passes (tests count them: a metric set updates all of its metrics from ONE call)
+
+
+def sod_metrics(pred, gt, *, normalize=False, wfm=True, alpha=0.5, beta_fm=0.3, beta_wfm=1.0, state=None, count=None, want_ints=False,
+                want_per_image=False, want_dist=False):
+    """SOD metrics of metrics/sod/sod_metrics.py (csrc/sod_metrics.hip): pred [B,H,W] fp32 in [0,1] (uint8 under normalize), gt [B,H,W] bool / uint8.
+    Adds every image's scores to state [1032] fp64 and B to count [1] int64 (see include/iseg_hip.h for the layout); nothing is read back.
+    returns (ints [B,544] int32 | None, per_image [B,1032] fp64 | None, dist2 [B,H,W] int32 | None, nearest [B,H,W] int32 | None)"""
+    _require_cuda(pred, gt, state, count)
+    B, H, W = pred.shape
+    if tuple(gt.shape) != (B, H, W):
+        raise ValueError("Shape mismatch between prediction and ground truth")
+    if normalize and pred.dtype != torch.uint8 or not normalize and pred.dtype != torch.float32:
+        raise TypeError("sod_metrics: pred is float32 in [0, 1], or uint8 with normalize=True")
+    if gt.dtype not in (torch.bool, torch.uint8):
+        raise TypeError("sod_metrics: gt is bool or uint8")
+    if not (pred.is_contiguous() and gt.is_contiguous()):
+        raise ValueError("sod_metrics: contiguous tensors only")
+    dev = pred.device
+    flags = SOD_WFM if wfm else 0
+    ints = torch.empty(B, SOD_INTS, dtype=torch.int32, device=dev) if want_ints else None
+    per = torch.empty(B, SOD_STATE_DOUBLES, dtype=torch.float64, device=dev) if want_per_image else None
+    d2 = torch.empty(B, H, W, dtype=torch.int32, device=dev) if want_dist and wfm else None
+    nn_ = torch.empty(B, H, W, dtype=torch.int32, device=dev) if want_dist and wfm else None
+    ws, wsb = workspace(_hip.lib().iseg_sod_metrics_workspace_bytes(B, H, W, flags), dev)
+    SOD_CALLS[0] += 1
+    _hip.call("iseg_sod_metrics", ptr(pred), int(normalize), ptr(gt), int(normalize), B, H, W, flags, float(alpha), float(beta_fm), float(beta_wfm),
+              ptr(state), ptr(count), ptr(ints), ptr(per), ptr(d2), ptr(nn_), ptr(ws), wsb, stream())
+    return ints, per, d2, nn_
+
+
 def upsample_ce_supported(Hi, Wi, Ho, Wo, Cc):
     return bool(_hip.lib().iseg_upsample_ce_supported(int(Hi), int(Wi), int(Ho), int(Wo), int(Cc)))
 
