@@ -543,6 +543,54 @@ int iseg_sod_metrics(const void* pred, int pred_is_u8, const uint8_t* gt, int no
                      int32_t* dist2_out, int32_t* nearest_out, void* ws, size_t ws_bytes, iseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * metrics/sod/fmeasurev2.py: TFBaseHandler.update_state (:117-237: _get_statistics :156-177, _adaptively_binarizing :179-195,
+ * _dynamically_binarizing :197-237) and the compute_metric of its ten handlers: TFIOUHandler (:336-340), TFSpecificityHandler (:378-382),
+ * TFDICEHandler (:424-428), TFOverallAccuracyHandler (:466-470), TFKappaHandler (:509-523), TFPrecisionHandler (:561-565),
+ * TFRecallHandler (:603-607), TFFPRHandler (:650-654), TFBERHandler (:692-700), TFFmeasureHandler (:741-749).  B images per call, each
+ * scored on its own, n_handlers handlers (1..ISEG_SODV2_MAX_HANDLERS) from ONE pass over the pixels.
+ *   pred [B,H,W]   fp32 in [0,1] (pred_is_u8 = normalize = 0), or uint8 with normalize = 1 (prepare_data, sod_metric_utils.py:67-95)
+ *   gt   [B,H,W]   one byte per pixel: non-zero is foreground, > 128 under normalize
+ *   kinds_h / modes_h / betas_h [n_handlers]  HOST arrays, read during the call and passed on by value: ISEG_SODV2_<kind>, an OR of
+ *       ISEG_SODV2_DYNAMIC / ADAPTIVE / BINARY (0 is allowed: the handler records nothing), and beta of the F-measure (read for that kind only)
+ *   state [n_handlers, ISEG_SODV2_HANDLER_DOUBLES] += the per-image records summed in image order, count[0] += B  (both optional, together).
+ *       A handler's record: 0..255 the dynamic curve, index i is threshold 255 - i (TP = pixels of the foreground in bins >= 255 - i of
+ *       int(p * 255.0f), the fp32 product); 256 the score at the adaptive threshold p >= float(min(2 mean p, 1)); 257 the score at p > 0.5;
+ *       258..261 tp, fp, tn, fn at p > 0.5 (the dataset-based binary mode sums them); 262..263 zero.  Slots of a mode the handler did not
+ *       ask for are 0.
+ *   per_image_out [B, n_handlers, ISEG_SODV2_HANDLER_DOUBLES]  (optional) the same record of every image
+ *   ints_out [B, ISEG_SODV2_INTS] (optional): 0.. foreground histogram [256] of int(p * 255.0f), 256.. background histogram [256],
+ *       512 foreground count, 513 count of p >= thr, 514 of p >= thr && g, 515 count of p > 0.5, 516 of p > 0.5 && g, 517 bits of the fp32
+ *       adaptive threshold, 518..519 zero.  For an fp32 prediction 513, 514 and 517 are 0 unless some handler has ISEG_SODV2_ADAPTIVE.
+ * FN = FG - TP and TN = BG - FP with FG = count_nonzero(gt) (:129-130, :175-176).  Scores are fp64 on the exact counts; safe_divide tests the
+ * integer denominator, and Kappa's 1 - p_e == 0 is (tp+fp)(tp+fn) + (tn+fn)(tn+tp) == total^2 in int64.  That second product is the
+ * reference's own formula (:519), kept as it writes it.
+ * uint8: one streaming pass (the 2 x 256 histogram of raw grey levels by gt) and one wavefront per image that derives every other quantity from
+ * those 512 integers.  fp32: one streaming pass; a threshold step and a second pass only if some handler has ISEG_SODV2_ADAPTIVE.  Then a
+ * per-image finalize and one launch that adds to the state.  Integer atomics and fixed-order fp64 partials only; no host read, no
+ * host-to-device copy: the call captures into a graph.  Errors: n_handlers outside 1..32, an unknown kind or mode bit, H or W > 16384.
+ * --------------------------------------------------------------------------------------------------------- */
+#define ISEG_SODV2_IOU 0
+#define ISEG_SODV2_SPECIFICITY 1
+#define ISEG_SODV2_DICE 2
+#define ISEG_SODV2_OA 3
+#define ISEG_SODV2_KAPPA 4
+#define ISEG_SODV2_PRECISION 5
+#define ISEG_SODV2_RECALL 6
+#define ISEG_SODV2_FPR 7
+#define ISEG_SODV2_BER 8
+#define ISEG_SODV2_FMEASURE 9
+#define ISEG_SODV2_DYNAMIC 1
+#define ISEG_SODV2_ADAPTIVE 2
+#define ISEG_SODV2_BINARY 4
+#define ISEG_SODV2_MAX_HANDLERS 32
+#define ISEG_SODV2_HANDLER_DOUBLES 264
+#define ISEG_SODV2_INTS 520
+size_t iseg_sod_fmv2_workspace_bytes(int B, int H, int W, int n_handlers);
+int iseg_sod_fmv2(const void* pred, int pred_is_u8, const uint8_t* gt, int normalize, int B, int H, int W, int n_handlers,
+                  const int32_t* kinds_h, const int32_t* modes_h, const double* betas_h, double* state, long long* count, int32_t* ints_out,
+                  double* per_image_out, void* ws, size_t ws_bytes, iseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * optimizers/modern/adamw.py:13-74, optimizers/modern/sgd.py:12-51 over the flat parameter buffer.
  * Every tensor is padded to a multiple of 256 elements; seg_of_block[b] = tensor index of 256-element block b
  * (-1 = padding).  hp (device): [lr, sqrt(1-b2^t)/(1-b1^t), grad_scale, clipvalue(<=0 off)].

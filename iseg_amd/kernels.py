@@ -1222,6 +1222,45 @@ def sod_metrics(pred, gt, *, normalize=False, wfm=True, alpha=0.5, beta_fm=0.3, 
     return ints, per, d2, nn_
 
 
+(SODV2_IOU, SODV2_SPECIFICITY, SODV2_DICE, SODV2_OA, SODV2_KAPPA, SODV2_PRECISION, SODV2_RECALL, SODV2_FPR, SODV2_BER,
+ SODV2_FMEASURE) = range(10)
+SODV2_DYNAMIC, SODV2_ADAPTIVE, SODV2_BINARY = 1, 2, 4
+SODV2_MAX_HANDLERS, SODV2_HANDLER_DOUBLES, SODV2_INTS = 32, 264, 520
+SODV2_CALLS = [0]      # calls of iseg_sod_fmv2 (tests count them: an evaluator updates all of its handlers from ONE call)
+
+
+def sod_fmv2(pred, gt, handlers, *, normalize=False, state=None, count=None, want_ints=False, want_per_image=False):
+    """FmeasureV2 handlers of metrics/sod/fmeasurev2.py (csrc/sod_fmv2.hip): pred [B,H,W] fp32 in [0,1] (uint8 under normalize), gt [B,H,W]
+    bool / uint8, handlers a sequence of (kind, modes, beta): SODV2_<kind>, an OR of SODV2_DYNAMIC / ADAPTIVE / BINARY, the F-measure's beta.
+    Adds every image's records to state [n,264] fp64 and B to count [1] int64 (see include/iseg_hip.h for the layout); nothing is read back.
+    returns (ints [B,520] int32 | None, per_image [B,n,264] fp64 | None)"""
+    _require_cuda(pred, gt, state, count)
+    B, H, W = pred.shape
+    if tuple(gt.shape) != (B, H, W):
+        raise ValueError("Shape mismatch between prediction and ground truth")
+    if normalize and pred.dtype != torch.uint8 or not normalize and pred.dtype != torch.float32:
+        raise TypeError("sod_fmv2: pred is float32 in [0, 1], or uint8 with normalize=True")
+    if gt.dtype not in (torch.bool, torch.uint8):
+        raise TypeError("sod_fmv2: gt is bool or uint8")
+    if not (pred.is_contiguous() and gt.is_contiguous()):
+        raise ValueError("sod_fmv2: contiguous tensors only")
+    handlers = list(handlers)
+    n = len(handlers)
+    if state is not None and (state.dtype != torch.float64 or state.numel() != n * SODV2_HANDLER_DOUBLES or not state.is_contiguous()):
+        raise ValueError(f"sod_fmv2: state is a contiguous float64 [{n}, {SODV2_HANDLER_DOUBLES}]")
+    kinds = (C.c_int32 * n)(*[int(h[0]) for h in handlers])
+    modes = (C.c_int32 * n)(*[int(h[1]) for h in handlers])
+    betas = (C.c_double * n)(*[float(h[2]) for h in handlers])
+    dev = pred.device
+    ints = torch.empty(B, SODV2_INTS, dtype=torch.int32, device=dev) if want_ints else None
+    per = torch.empty(B, n, SODV2_HANDLER_DOUBLES, dtype=torch.float64, device=dev) if want_per_image else None
+    ws, wsb = workspace(_hip.lib().iseg_sod_fmv2_workspace_bytes(B, H, W, n), dev)
+    SODV2_CALLS[0] += 1
+    _hip.call("iseg_sod_fmv2", ptr(pred), int(normalize), ptr(gt), int(normalize), B, H, W, n, kinds, modes, betas, ptr(state), ptr(count),
+              ptr(ints), ptr(per), ptr(ws), wsb, stream())
+    return ints, per
+
+
 def upsample_ce_supported(Hi, Wi, Ho, Wo, Cc):
     return bool(_hip.lib().iseg_upsample_ce_supported(int(Hi), int(Wi), int(Ho), int(Wo), int(Cc)))
 
