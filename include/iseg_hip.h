@@ -186,6 +186,10 @@ int iseg_dwconv2d_fwd(const void* x, const float* w, const float* bias, const vo
 int iseg_dwconv2d7_mfma(const void* x, const float* w, const float* bias, const void* add, void* y, int N, int H, int W, int C, int pad_t,
                         int pad_l, int flip, iseg_stream_t stream);
 size_t iseg_dwconv2d_bwd_weight_workspace_bytes(int N, int H, int W, int C, int K);
+/* The 7 x 7 weight gradient on the matrix cores (csrc/dwconv_wgrad_mfma.hip), named explicitly: bf16 storage, C % 32 == 0, stride 1, dilation 1.
+ * iseg_dwconv2d_bwd_weight takes this route by itself where it measured faster; the workspace size is the same query (K = 7). */
+int iseg_dwconv2d7_bwd_weight_mfma(const void* x, const void* dy, float* dw, float* db, int accumulate, int N, int H, int W, int C, int pad_t,
+                                   int pad_l, void* ws, size_t ws_bytes, iseg_stream_t stream);
 int iseg_dwconv2d_bwd_weight(const void* x, const void* dy, float* dw, float* db, int accumulate, int N, int H, int W, int C,
                              int K, int dil, int pad_t, int pad_l, int dtype, void* ws, size_t ws_bytes, iseg_stream_t stream);
 

@@ -79,6 +79,7 @@ SIGNATURES = {
     "iseg_dwconv2d7_mfma": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "iseg_dwconv2d_bwd_weight_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
     "iseg_dwconv2d_bwd_weight": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _z, _p]),
+    "iseg_dwconv2d7_bwd_weight_mfma": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _z, _p]),
     "iseg_dwconv2d_strided_fwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "iseg_dwconv2d_strided_bwd_data": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "iseg_dwconv2d_strided_bwd_weight_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),

@@ -1128,6 +1128,20 @@ extern "C" int iseg_dwconv2d_fwd(const void* x, const float* w, const float* bia
 #undef DW_FWD
 }
 
+int iseg_dwconv7_wgrad_mfma_blocks(int N, int H, int W, int C, int K, int dil);      // dwconv_wgrad_mfma.hip
+bool iseg_dwconv7_wgrad_mfma_launch(const void* x, const void* dy, float* partials, int N, int H, int W, int C, int pad_t, int pad_l, int blocks,
+                                    hipStream_t s);
+
+// Automatic route of iseg_dwconv2d_bwd_weight to the matrix-core kernel (dwconv_wgrad_mfma.hip), taken where it was measured against
+// dwconv_bwd_weight_dma_kernel: 16 images, us per call incl. the partial reduce (tools/kbench_dwbww_one.py, EXPERIMENTS.md): 128 x 128 x 96
+// 68.1 -> 44.5, 64 x 64 x 192 44.7 -> 27.4, 32 x 32 x 384 25.3 -> 18.2, 16 x 16 x 768 17.4 -> 12.2.  The smallest of them is 768 units
+// (16 x 16 tiles x 16-channel slabs); nothing below that was timed, so smaller problems keep the VALU kernel.
+static bool bw_mfma_auto(const void* x, const void* dy, int N, int H, int W, int C) {
+    if ((((uintptr_t)x | (uintptr_t)dy) & 15) != 0 || C % 32 != 0) return false;
+    const int64_t units = (int64_t)N * ((H + 15) / 16) * ((W + 15) / 16) * (C / 16);
+    return units >= 768;
+}
+
 extern "C" size_t iseg_dwconv2d_bwd_weight_workspace_bytes(int N, int H, int W, int C, int K) {
     // upper bound over storage dtypes and over the LDS / non-LDS variants
     const BwGeom g = bw_geom(N, H, W, C, K, 1, 4);
@@ -1137,6 +1151,8 @@ extern "C" size_t iseg_dwconv2d_bwd_weight_workspace_bytes(int N, int H, int W, 
     if (g3.bx > bx) bx = g3.bx;
     const BwDmaGeom gd = bw_dma_geom(N, H, W, C, K, 1, 2);
     if (gd.ok && gd.bx > bx) bx = gd.bx;
+    const int bm = iseg_dwconv7_wgrad_mfma_blocks(N, H, W, C, K, 1);
+    if (bm > bx) bx = bm;
     return (size_t)bx * (K * K + 1) * C * sizeof(float);
 }
 
@@ -1151,6 +1167,8 @@ extern "C" int iseg_dwconv2d_bwd_weight(const void* x, const void* dy, float* dw
     BwGeom g = bw_geom(N, H, W, C, K, dil, dtype == ISEG_BF16 ? 2 : 4);
     ISEG_REQUIRE(g.gs * K * g.rt <= 256, "iseg_dwconv2d_bwd_weight: slab does not fit a block");
     if (gd.ok) g.bx = gd.bx;
+    const int bm = dtype == ISEG_BF16 && bw_mfma_auto(x, dy, N, H, W, C) ? iseg_dwconv7_wgrad_mfma_blocks(N, H, W, C, K, dil) : 0;
+    if (bm) g.bx = bm;
     const size_t need = (size_t)g.bx * (K * K + 1) * C * sizeof(float);
     if (!ws || ws_bytes < need) {
         iseg_set_error("iseg_dwconv2d_bwd_weight: needs %zu workspace bytes, got %zu", need, ws_bytes);
@@ -1158,7 +1176,12 @@ extern "C" int iseg_dwconv2d_bwd_weight(const void* x, const void* dy, float* dw
     }
     float* const arena = iseg_deferred_partials(need, dw, db, accumulate, stream);      // (see common.h: deferred reductions)
     if (arena) ws = arena;
-    if (gd.ok) {
+    if (bm) {
+        if (!iseg_dwconv7_wgrad_mfma_launch(x, dy, (float*)ws, N, H, W, C, pad_t, pad_l, bm, stream)) {
+            iseg_set_error("iseg_dwconv2d_bwd_weight: the matrix-core kernel could not be launched");
+            return ISEG_ERR_UNSUPPORTED;
+        }
+    } else if (gd.ok) {
         launch_bw_dma(x, dy, (float*)ws, N, H, W, C, pad_t, pad_l, gd, stream);
     } else if (g.lds) {
 #define DW_BWL(KK)                                                                                                                   \

@@ -28,14 +28,17 @@
 // LDS: two workgroups per CU overlap each other's phases.  Per unit: 35 KiB of DMA, 66 + 66 transposing reads / writes, 336 fragment reads,
 // 672 MFMAs, 128 accumulator writes, 32 tile reads.
 #include "common.h"
+#include "dwconv_mfma_common.h"
 #include "iseg_hip.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
-typedef __attribute__((address_space(3))) void* dwm_lds_ptr;
-typedef const __attribute__((address_space(1))) void* dwm_glb_ptr;
+using dwm::s16x4;
+using dwm::f32x4_t;
+using dwm::u32x2_t;
+using dwm::u32x4_t;
+typedef dwm::lds_ptr dwm_lds_ptr;
+typedef dwm::glb_ptr dwm_glb_ptr;
 
 __device__ uint4 dwm_zero_page[4];      // 64 zero bytes (device globals are zero-initialised)
 
@@ -51,24 +54,13 @@ constexpr int O_BYTES = TR * O_PITCH;
 constexpr int P_OFF = 2 * RAW_BUF, O_OFF = P_OFF + P_BYTES, LDS_BYTES = O_OFF + O_BYTES;
 static_assert(RAW_COLS * COLP <= PLANE && LDS_BYTES <= 160 * 1024, "one workgroup of 8 wavefronts per CU");
 
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2_t;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
-
-#define DWM_BARRIER()                                       \
-    do {                                                    \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
-        __builtin_amdgcn_s_barrier();                       \
-        asm volatile("" ::: "memory");                      \
-    } while (0)
 // wait until at most N LDS operations are outstanding; the registers named are the ones the wait makes valid (keeps their consumers behind it)
 #define DWM_GUARD7(N, A)                                                                                                                        \
     asm volatile("s_waitcnt lgkmcnt(%7)" : "+v"((A)[0]), "+v"((A)[1]), "+v"((A)[2]), "+v"((A)[3]), "+v"((A)[4]), "+v"((A)[5]), "+v"((A)[6]) \
                  : "n"(N) : "memory")
 
-// Every LDS access inside the unit loop is inline assembly: hipcc has no alias information between an LDS access it can see and the LDS-DMA
-// (global_load_lds) in flight for the NEXT tile, and would put s_waitcnt vmcnt(0) in front of it -- the prefetch would never overlap anything
-// (the same reason as in gemm_dma_tn.h / mlp_fused.hip).  The waits are written out; barriers are raw s_barrier (__syncthreads() carries a fence that
-// drains vmcnt as well).
+// Every LDS access inside the unit loop is inline assembly (see dwconv_mfma_common.h: the LDS-DMA for the NEXT tile is in flight; the same reason
+// as in gemm_dma_tn.h / mlp_fused.hip).
 __global__ __launch_bounds__(64 * WAVES) void dwconv7_mfma_kernel(const bf16_t* __restrict__ x, const float* __restrict__ w,
                                                                 const float* __restrict__ bias, const bf16_t* __restrict__ add,
                                                                 bf16_t* __restrict__ y, int N, int H, int W, int C, int pad_t, int pad_l, int flip,

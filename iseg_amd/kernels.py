@@ -762,6 +762,16 @@ def dwconv2d_bwd_weight(x, dy, dw, db, K, dil, pad_t, pad_l, accumulate=True):
               dt(x), ptr(ws), wsb, stream())
 
 
+def dwconv2d7_bwd_weight_mfma(x, dy, dw, db, pad_t=3, pad_l=3, accumulate=True):
+    """the 7 x 7 depthwise weight gradient on the matrix cores (csrc/dwconv_wgrad_mfma.hip), named explicitly; dwconv2d_bwd_weight takes this route by
+    itself where it measured faster"""
+    _require_cuda(x, dy, dw)
+    N, H, W, Cc = x.shape
+    need = _hip.lib().iseg_dwconv2d_bwd_weight_workspace_bytes(N, H, W, Cc, 7)
+    ws, wsb = workspace(need, x.device)
+    _hip.call("iseg_dwconv2d7_bwd_weight_mfma", ptr(x), ptr(dy), ptr(dw), ptr(db), int(accumulate), N, H, W, Cc, pad_t, pad_l, ptr(ws), wsb, stream())
+
+
 def dwconv2d_strided(x, w, bias, K, stride, dil):
     """DepthwiseConv2D(strides=stride, padding='same') at the strided positions only; x [N,H,W,C], w [K*K, C] fp32"""
     _require_cuda(x, w)
