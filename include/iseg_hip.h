@@ -766,6 +766,24 @@ int iseg_dcn_center_blend_fwd(const void* x, const void* x_proj, const void* sca
 int iseg_dcn_center_blend_bwd(const void* dout, const void* x, const void* x_proj, const void* scale, void* dx, void* dx_proj, void* dscale,
                               int64_t pixels, int G, int Cg, int dtype, iseg_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * layers/deformable_multihead_self_attention.py:89-244 (compute_attention_internal behind the projections): tanh-bounded offsets (:203-207),
+ * softmax over each head's P points (:210-214), clipped sampling positions (:225-230), the four gather_nd of _bilinear_sample with weights from
+ * the unclipped floor (:124-169) and the weighted sum over the points (:236-240) as ONE launch, no intermediate tensor.
+ * value [N,H,W,heads*Ch], offset_logits [N,H,W,heads*P*2] (raw, read as [heads, P, (y, x)]), attn_logits [N,H,W,heads*P] (raw), out [N,H,W,heads*Ch];
+ * 1 <= P <= 16 (otherwise ISEG_ERR_UNSUPPORTED), any heads and Ch (Ch % 8 == 0 with 16-byte aligned value / out takes the 16-byte-load route).
+ * tanh, softmax, coordinates and weights in fp32 whatever the storage dtype.
+ * Backward (the gradient of the same lines): from the three operands and dout, dvalue / doffset_logits / dattn_logits in the storage dtype; tanh and
+ * softmax are recomputed.  dvalue is accumulated by int64 2^-40 fixed-point atomics (order-free: bit-identical from run to run) in `ws`, at least
+ * iseg_defattn_bwd_workspace_bytes(...) bytes, 16-byte aligned, zeroed by the call; a non-finite contribution makes the whole dvalue NaN.
+ * --------------------------------------------------------------------------------------------------------- */
+int iseg_defattn_fwd(const void* value, const void* offset_logits, const void* attn_logits, void* out, int N, int H, int W, int heads, int P, int Ch,
+                     float offset_range_factor, int dtype, iseg_stream_t stream);
+size_t iseg_defattn_bwd_workspace_bytes(int N, int H, int W, int heads, int Ch);
+int iseg_defattn_bwd(const void* value, const void* offset_logits, const void* attn_logits, const void* dout, void* dvalue, void* doffset_logits,
+                     void* dattn_logits, int N, int H, int W, int heads, int P, int Ch, float offset_range_factor, int dtype, void* ws,
+                     size_t ws_bytes, iseg_stream_t stream);
+
 /* out[c] (+)= sum_r a[r][c]*b[r][c]: gradient of the per-channel layer scale x * gamma (backbones/intern_image/
  * intern_image_layer.py:128,136,160,168) */
 int iseg_scale_cols(const void* x, const float* colscale, void* y, int64_t rows, int C, int dtype, iseg_stream_t stream);

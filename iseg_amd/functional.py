@@ -2930,6 +2930,40 @@ def dcnv3_core(x, offset, mask, groups, group_channels, kernel_size=(3, 3), stri
                                              float(offset_scale)))
 
 
+class _DeformableAttentionFn(Function):
+    """layers/deformable_multihead_self_attention.py:195-240 behind the projections: tanh-bounded offsets, softmax over the points, clipped
+    bilinear sampling and the weighted sum as one kernel each way (csrc/defattn.hip); only the three operands are kept for the backward"""
+
+    @staticmethod
+    def forward(ctx, value, offset_logits, attn_logits, cfg):
+        heads, points, orf = cfg
+        vc, oc, ac = _c(value), _c(offset_logits), _c(attn_logits)
+        ctx.cfg = cfg
+        ctx.save_for_backward(vc, oc, ac)
+        return K.defattn_fwd(vc, oc, ac, heads, points, orf)
+
+    @staticmethod
+    def backward(ctx, dout):
+        vc, oc, ac = ctx.saved_tensors
+        heads, points, orf = ctx.cfg
+        dvalue, doff, dattn = K.defattn_bwd(vc, oc, ac, _c(dout), heads, points, orf)
+        return dvalue, doff, dattn, None
+
+
+def deformable_attention_core(value, offset_logits, attn_logits, num_heads, num_points, offset_range_factor=8.0):
+    """value [N,H,W,Cv], raw offset logits [N,H,W,heads*P*2], raw attention logits [N,H,W,heads*P] -> [N,H,W,Cv]"""
+    _check_act_dtype(value)
+    heads, points = int(num_heads), int(num_points)
+    if heads < 1 or value.shape[-1] % heads != 0:
+        raise ValueError(f"deformable_attention_core: {value.shape[-1]} value channels are not divisible by num_heads ({heads})")
+    if tuple(offset_logits.shape) != (*value.shape[:3], heads * points * 2) or tuple(attn_logits.shape) != (*value.shape[:3], heads * points):
+        raise ValueError(f"deformable_attention_core: offset logits {tuple(offset_logits.shape)} / attention logits {tuple(attn_logits.shape)} do not "
+                         f"match value {tuple(value.shape)} with {heads} heads x {points} points")
+    if nn.dry_run():
+        return _dry(value.shape, value)
+    return _DeformableAttentionFn.apply(value, offset_logits, attn_logits, (heads, points, float(offset_range_factor)))
+
+
 class _GroupSoftmaxFn(Function):
     @staticmethod
     def forward(ctx, x, P):

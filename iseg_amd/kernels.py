@@ -1572,6 +1572,43 @@ def dcnv3_bwd(x, offset, mask, dy, G, Cg, kh, kw, stride, dil, pad, offset_scale
     return dx, doff, dmask
 
 
+# ---------------------------------------------------------------------------------------------------------
+# Deformable multi-head self-attention core (csrc/defattn.hip; layers/deformable_multihead_self_attention.py:89-244)
+# ---------------------------------------------------------------------------------------------------------
+def _defattn_geom(value, offset_logits, attn_logits, heads, points, who):
+    N, H, W, Cv = value.shape
+    if heads < 1 or points < 1 or Cv % heads != 0 or tuple(offset_logits.shape) != (N, H, W, heads * points * 2) or \
+            tuple(attn_logits.shape) != (N, H, W, heads * points):
+        raise ValueError(f"{who}: shapes value {tuple(value.shape)} offset logits {tuple(offset_logits.shape)} attention logits "
+                         f"{tuple(attn_logits.shape)} do not match heads={heads} points={points}")
+    if not (value.dtype == offset_logits.dtype == attn_logits.dtype):
+        raise TypeError(f"{who}: value, offset logits and attention logits must share one storage dtype")
+    return N, H, W, Cv // heads
+
+
+def defattn_fwd(value, offset_logits, attn_logits, heads, points, offset_range_factor):
+    """value [N,H,W,heads*Ch], raw offset logits [N,H,W,heads*P*2], raw attention logits [N,H,W,heads*P] -> out [N,H,W,heads*Ch]"""
+    _require_cuda(value, offset_logits, attn_logits)
+    N, H, W, Ch = _defattn_geom(value, offset_logits, attn_logits, heads, points, "defattn_fwd")
+    out = torch.empty_like(value)
+    _hip.call("iseg_defattn_fwd", ptr(value), ptr(offset_logits), ptr(attn_logits), ptr(out), N, H, W, heads, points, Ch,
+              float(offset_range_factor), dt(value), stream())
+    return out
+
+
+def defattn_bwd(value, offset_logits, attn_logits, dout, heads, points, offset_range_factor):
+    """-> dvalue, doffset_logits, dattn_logits in the storage dtype (dvalue through int64 fixed-point atomics: bit-identical from run to run)"""
+    _require_cuda(value, offset_logits, attn_logits, dout)
+    N, H, W, Ch = _defattn_geom(value, offset_logits, attn_logits, heads, points, "defattn_bwd")
+    if tuple(dout.shape) != tuple(value.shape) or dout.dtype != value.dtype:
+        raise ValueError("defattn_bwd: dout does not match value")
+    dvalue, doff, dattn = torch.empty_like(value), torch.empty_like(offset_logits), torch.empty_like(attn_logits)
+    ws, wsb = workspace(_hip.lib().iseg_defattn_bwd_workspace_bytes(N, H, W, heads, Ch), value.device)
+    _hip.call("iseg_defattn_bwd", ptr(value), ptr(offset_logits), ptr(attn_logits), ptr(dout), ptr(dvalue), ptr(doff), ptr(dattn), N, H, W, heads,
+              points, Ch, float(offset_range_factor), dt(value), ptr(ws), wsb, stream())
+    return dvalue, doff, dattn
+
+
 def dcnv3_fwd_joint(x, om, G, Cg, kh, kw, stride, dil, pad, offset_scale):
     """dcnv3_fwd with the offsets and the (soft-maxed) mask as column ranges [0, 2GP) and [2GP, 3GP) of ONE matrix om [pixels, ld]"""
     _require_cuda(x, om)

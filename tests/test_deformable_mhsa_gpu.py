@@ -1,0 +1,198 @@
+"""Deformable multi-head self-attention (csrc/defattn.hip, iseg_amd/layers/deformable_multihead_self_attention.py) against the fp64 restatement of
+layers/deformable_multihead_self_attention.py:89-244 in tests/deformable_mhsa_ref.py: the fused core forward and backward, run-to-run identity and
+resolution of the fixed-point value gradient, the non-finite flag, and the layer with every parameter gradient."""
+import functools
+
+import pytest
+import torch
+
+from tests import deformable_mhsa_ref as R
+from tests.test_kernels_gpu import DTYPES, close, q, rnd
+from tests.util_models import randomize_parameters
+
+pytestmark = pytest.mark.gpu
+
+# (shape, heads, P, offset_range_factor)
+CASES = [((2, 9, 7, 32), 2, 4, 2.0),        # Ch 16: 16-byte-load forward, batch indexing
+         ((1, 12, 12, 64), 4, 4, 8.0),      # the default factor
+         ((2, 5, 8, 9), 3, 3, 2.0),         # Ch 3, odd everything: the one-channel-per-lane forward
+         ((1, 6, 6, 12), 4, 1, 4.0),        # a single point: softmax identically 1, its gradient 0
+         ((1, 33, 30, 32), 2, 4, 1.0)]      # ~2 000 (pixel, head) items over several workgroups, samples flung across the whole map
+BIG, ODD = CASES[4], CASES[2]
+
+
+@functools.lru_cache(maxsize=None)
+def _case(case, dtype, dout_scale=1.0):
+    """inputs rounded to the storage dtype (host copies; the tests upload them) and the restatement's fp64 output and gradients, computed once"""
+    shape, heads, P, orf = case
+    N, H, W, C = shape
+    host = [rnd(shape, 1).to(dtype), (rnd((N, H, W, heads * P * 2), 2) * 1.5).to(dtype), (rnd((N, H, W, heads * P), 3) * 1.5).to(dtype),
+            (rnd(shape, 4) * dout_scale).to(dtype)]
+    v, o, a = (t.double().requires_grad_(True) for t in host[:3])
+    out = R.core(v, o, a, heads, P, orf, scrub=False)
+    out.backward(host[3].double())
+    yu, xu, _, _ = R.sampling_coordinates(o.detach(), H, W, heads, P, orf)
+    clipped = ((yu < 0) | (yu > H - 1) | (xu < 0) | (xu > W - 1)).double().mean().item()
+    return host, out.detach(), (v.grad, o.grad, a.grad), clipped
+
+
+def _dev(host):
+    return [t.cuda() for t in host]
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("case", CASES, ids=lambda c: "x".join(map(str, c[0])) + f"-h{c[1]}p{c[2]}")
+def test_deformable_attention_core_forward_backward(cuda, dtype, case):
+    from iseg_amd import functional as F
+    from iseg_amd import nn
+
+    shape, heads, P, orf = case
+    host, want, (dv, do, da), clipped = _case(case, dtype)
+    assert clipped >= 0.2 and 1.0 - clipped >= 0.1, clipped      # both sides of the clip take part
+    nn.set_compute_dtype(dtype)
+    try:
+        v, o, a, dout = _dev(host)
+        for t in (v, o, a):
+            t.requires_grad_(True)
+        out = F.deformable_attention_core(v, o, a, heads, P, orf)
+        assert tuple(out.shape) == shape and out.dtype == dtype
+        print(f"fwd max err {(out.detach().cpu().double() - want).abs().max().item():.3e} scale {want.abs().max().item():.3e}")
+        close(out, want, dtype, "defattn fwd", f32_tol=1e-5, bf16_tol=1.5e-2)
+        out.backward(dout)
+        for name, got, ref in (("dvalue", v.grad, dv), ("dattn", a.grad, da), ("doffset", o.grad, do)):
+            d = got.cpu().double() - ref
+            print(f"{name} max err {d.abs().max().item():.3e} scale {ref.abs().max().item():.3e} rel l2 {d.norm().item() / max(ref.norm().item(), 1e-300):.3e}")
+        close(v.grad, dv, dtype, "defattn dvalue", f32_tol=2e-5, bf16_tol=2e-2)
+        close(a.grad, da, dtype, "defattn dattn", f32_tol=2e-5, bf16_tol=2e-2)
+        if dtype == torch.float32:
+            close(o.grad, do, dtype, "defattn doffset", f32_tol=5e-5)
+        else:
+            # bf16 logits put a few per mille of the coordinates within 1e-4 of a cell border, where floor() in fp32 (kernel) and fp64
+            # (restatement) may pick different cells and the offset gradient is discontinuous: relative L2 instead of the max-norm
+            assert (o.grad.cpu().double() - do).norm().item() / do.norm().item() < 5e-2
+    finally:
+        nn.set_compute_dtype(torch.float32)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("case", [BIG, ODD], ids=["33x30x32", "5x8x9"])
+def test_deformable_attention_backward_is_bit_identical(cuda, dtype, case):
+    from iseg_amd import kernels as K
+
+    _, heads, P, orf = case
+    v, o, a, dout = _dev(_case(case, dtype)[0])
+    outs = [K.defattn_bwd(v, o, a, dout, heads, P, orf) for _ in range(3)]
+    for other in outs[1:]:
+        assert all(torch.equal(x, y) for x, y in zip(outs[0], other))
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_deformable_attention_value_gradient_keeps_its_precision_for_tiny_gradients(cuda, dtype):
+    """output gradients of 1e-8: single contributions are ~1e-9 and below, and the 2^-40 = 9.1e-13 accumulators must resolve them"""
+    from iseg_amd import kernels as K
+
+    _, heads, P, orf = BIG
+    host, _, (dv, _, _), _ = _case(BIG, dtype, 1e-8)
+    dvalue, _, _ = K.defattn_bwd(*_dev(host), heads, P, orf)
+    err = (dvalue.cpu().double() - dv).norm().item() / dv.norm().item()
+    print(f"tiny-gradient dvalue rel l2 {err:.3e}")
+    assert err < (5e-3 if dtype == torch.float32 else 1.5e-2), err
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_deformable_attention_non_finite_gradient_poisons_dvalue_once(cuda, dtype):
+    """the fixed-point conversion would saturate an inf / NaN contribution to finite garbage: the flag turns the whole dvalue into NaN instead, and is
+    cleared by the next call"""
+    from iseg_amd import kernels as K
+
+    _, heads, P, orf = ODD
+    v, o, a, dout = _dev(_case(ODD, dtype)[0])
+    clean = K.defattn_bwd(v, o, a, dout, heads, P, orf)
+    assert all(torch.isfinite(t).all().item() for t in clean)
+    for bad in (float("inf"), float("nan")):
+        d2 = dout.clone()
+        d2[1, 2, 3, 4] = bad
+        dvalue, _, _ = K.defattn_bwd(v, o, a, d2, heads, P, orf)
+        assert torch.isnan(dvalue).all().item()
+        again = K.defattn_bwd(v, o, a, dout, heads, P, orf)
+        assert all(torch.equal(x, y) for x, y in zip(clean, again))
+
+
+def test_deformable_attention_refuses_more_points_than_the_kernels_hold(cuda):
+    from iseg_amd import _hip
+    from iseg_amd import kernels as K
+
+    v = torch.zeros(1, 4, 4, 8, device="cuda")
+    with pytest.raises(_hip.HipCallError):
+        K.defattn_fwd(v, torch.zeros(1, 4, 4, 17 * 2, device="cuda"), torch.zeros(1, 4, 4, 17, device="cuda"), 1, 17, 8.0)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("apply_linear", [True, False])
+@pytest.mark.parametrize("dense", [False, True], ids=["conv", "dense"])
+def test_deformable_mhsa_layer_forward_and_gradients(cuda, dtype, apply_linear, dense):
+    """output, the gradients of the input and of a separate value= input, and every parameter gradient; offset_proj is scaled up so that the samples
+    leave their cell.  bf16: the relative L2 band of the DCNv2 layer test, for its reason -- the offset gradient is discontinuous at cell borders.
+    Conditioning of the inputs: under bf16 the kernel side computes the offset logits from bf16 weights and rounds them to bf16, the restatement
+    from the fp32 masters in fp64, so a logit of size 2 differs by about 2 * 2^-8 = 0.008 and a coordinate by that times (1 - t^2) * H / factor.  A
+    sample whose coordinate moves across a cell border has an offset gradient that is wrong by its own size, so the relative L2 error of every
+    gradient behind the offsets is about sqrt(share of such samples).  Measured on the host with the restatement alone (fp64 against the same
+    restatement with bf16-rounded weights, logits, value and output; apply_linear=False, the worse case): input gradient 0.25 and offset_proj
+    gradients 0.17-0.26 at a factor of 2 (offsets up to 4.5 pixels), 0.06 and 0.06-0.09 at the layer's default factor 8 (1.1 pixels: samples still
+    leave their cell).  At a factor of 2 the test would measure its own inputs against the 0.25 band; it therefore runs at the default."""
+    from iseg_amd import nn
+    from iseg_amd.layers.deformable_multihead_self_attention import DeformableMultiHeadSelfAttentionLayer
+    from iseg_amd.param_store import ParamStore
+    from oracle import models as OM
+
+    nn.set_compute_dtype(dtype)
+    nn.set_device("cuda:0")
+    try:
+        shape, heads, P, orf = (2, 9, 7, 16), 2, 4, 8.0
+        layer = DeformableMultiHeadSelfAttentionLayer(num_heads=heads, num_points=P, apply_linear=apply_linear, use_dense_for_linear=dense,
+                                                      offset_range_factor=orf, name="dmhsa")
+        with nn.dry_run_scope():
+            layer(torch.empty(shape, dtype=dtype, device="cuda"))
+        layer._iseg_store = ParamStore(list(layer.parameters()))
+        randomize_parameters(layer, 5)
+        with torch.no_grad():       # tanh arguments of order 2: offsets up to (H / 8, W / 8) = (1.1, 0.9) pixels -- every negative one leaves its cell
+            for p in layer.parameters():
+                if "offset_proj" in p.iseg_name:
+                    p.mul_(2.0)
+        layer._iseg_store.sync_shadow()
+        w = {k: v.requires_grad_(True) for k, v in OM.export_weights(layer).items()}
+        f32 = dtype == torch.float32
+
+        def rel(a, b):
+            return (a.detach().cpu().double() - b).norm().item() / max(b.norm().item(), 1e-12)
+
+        for separate_value in (False, True):
+            x, xv = rnd(shape, 1).to(dtype), rnd(shape, 2).to(dtype)
+            xg, vg = x.cuda().requires_grad_(True), xv.cuda().requires_grad_(True)
+            xr, vr = x.double().requires_grad_(True), xv.double().requires_grad_(True)
+            for p in layer.parameters():      # (views into the store's gradient buffer: cleared in place)
+                if p.grad is not None:
+                    p.grad.zero_()
+            for t in w.values():
+                t.grad = None
+            y = layer(xg, value=vg) if separate_value else layer(xg)
+            yr = R.layer(w, "dmhsa", xr, vr if separate_value else None, heads, P, orf, apply_linear=apply_linear)
+            assert tuple(y.shape) == tuple(yr.shape)
+            scale = yr.abs().max().item()
+            err = (y.detach().cpu().double() - yr.detach()).abs().max().item()
+            print(f"layer out max err {err:.3e} scale {scale:.3e}")
+            assert err < (2e-5 if f32 else 4e-2) * scale
+            dy = rnd(shape, 3).to(dtype)
+            y.backward(dy.cuda())
+            yr.backward(dy.double())
+            tol = 2e-4 if f32 else 0.25
+            print(f"dx rel l2 {rel(xg.grad, xr.grad):.3e}")
+            assert rel(xg.grad, xr.grad) < tol
+            if separate_value:
+                print(f"dvalue-input rel l2 {rel(vg.grad, vr.grad):.3e}")
+                assert rel(vg.grad, vr.grad) < tol
+            for p in layer.parameters():
+                print(f"{p.iseg_name} rel l2 {rel(p.grad, w[p.iseg_name].grad):.3e}")
+                assert rel(p.grad, w[p.iseg_name].grad) < tol, p.iseg_name
+    finally:
+        nn.set_compute_dtype(torch.float32)
