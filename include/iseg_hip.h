@@ -855,6 +855,25 @@ int iseg_augment_crop_batch(const void* images, int image_dtype, const int32_t* 
 int iseg_normalize_image(const float* x, float* y, int64_t pixels, const float* norm_scale, const float* norm_shift, iseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * augments/random_rotate_augment.py:20-115 (transform = tf.raw_ops.ImageProjectiveTransformV3) and :221-296 (random_rotated_inputs) for a
+ * padded batch in one launch, CONSTANT fill mode only.  images [B][Hs][Ws][C] fp32, C in 1..4; labels [B][Hs][Ws] int32 or NULL (with
+ * out_labels); transforms [B][8] = a0 a1 a2 b0 b1 b2 c0 c1 on the device, mapping the OUTPUT (x, y) to the INPUT point
+ * x' = ((a0 x + a1 y) + a2) / k, y' = ((b0 x + b1 y) + b2) / k, k = c0 x + c1 y + 1 (k == 0 -> fill), fp32 without FMA contraction (bit-equal
+ * to a float32 restatement in this order); sizes [B][2] int32 on the device = (H, W) of each sample in the top-left corner of its Hs x Ws slot,
+ * NULL = (Hs, Ws).  image_interp 0: nearest at (lround(y'), lround(x')), half away from zero; 1: bilinear over floor / floor + 1 with weights
+ * (xc - x'), (x' - xf), every tap outside the sample's own H x W reading image_fill.  Labels are always nearest with label_fill.  Bounds are
+ * tested on the float coordinate (huge / NaN = outside).  replace [C] (host) or NULL: out < -1e-6 ? replace[c] : out, the reference's tf.where
+ * after a fill of -1 (border pixels blend with -1 first: a 0 that blends to -1e-5 IS replaced).  Output positions outside a sample's (H, W)
+ * get replace (image_fill when NULL) and label_fill.  ISEG_ERR_UNSUPPORTED for C outside 1..4 or another image_interp.
+ * One departure from TensorFlow's arithmetic: a bilinear pixel none of whose four taps lies inside the sample is image_fill itself.  TF evaluates
+ * the weighted sum there too, which is image_fill up to rounding for ordinary coordinates but 0 for |x'| or |y'| >= 2^24, where its fp32
+ * weights xc - x' and x' - xf both round to 0.
+ * --------------------------------------------------------------------------------------------------------- */
+int iseg_projective_transform_batch(const float* images, const int32_t* labels, const float* transforms, const int32_t* sizes,
+                                    float* out_images, int32_t* out_labels, int B, int Hs, int Ws, int C, int image_interp, float image_fill,
+                                    const float* replace, int label_fill, iseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Fused logits tail of the training step: tf.image.resize(bilinear) of the low-resolution logits z [N,Hi,Wi,C] to the label size
  * (layers/core_model_ext.py:199-256) + the ignore-label cross-entropy mean and its gradient w.r.t. z
  * (losses/catecrossentropy_ignore_label.py:44-88) + the argmax confusion matrix (metrics/seg_metric_wrapper.py:89-102), in one pass that

@@ -234,6 +234,7 @@ SIGNATURES = {
     "iseg_augment_crop_batch": (_i, [_p, _i, _p, _p, _p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), _i, _p, _p, _i, _i, _i,
                                      _i, _i, _u64, _p]),
     "iseg_normalize_image": (_i, [_p, _p, _l, C.POINTER(C.c_float), C.POINTER(C.c_float), _p]),
+    "iseg_projective_transform_batch": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, C.POINTER(C.c_float), _i, _p]),
     "iseg_upsample_ce_supported": (_i, [_i, _i, _i, _i, _i]),
     "iseg_upsample_ce_workspace_bytes": (_z, [_i, _i, _i, _i, _i, _i]),
     "iseg_upsample_ce": (_i, [_p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _f, _p, _f, _p, _p, _z, _p]),

@@ -10,6 +10,52 @@ from .. import kernels as K
 from .. import nn
 from .input_norm import norm_affine
 from .input_norm_types import InputNormTypes
+from .augments import *  # noqa: F401,F403  (the reference's recipes reach the augment classes through this module)
+
+
+class AugmentationsPipeLine:
+    """Counterpart of the reference's generic pipeline (pipeline.py:10-82): any list of augments (data_process/augments/), applied in order
+    to one sample (image [H, W, 3], label [H, W, 1] / [H, W] / None, on the device), then post_process."""
+
+    def __init__(self, target_height=None, target_width=None, augments=[], perform_post_process=True, name=None):
+        self.name = name or type(self).__name__
+        self.augments = augments
+        # a size of None or <= 0 means "not fixed"
+        self.target_height, self.target_width = (v if v is not None and v > 0 else None for v in (target_height, target_width))
+        self.perform_post_process = perform_post_process
+        self._names_printed = False
+
+    def _check_size(self, what, tensor):
+        want = (self.target_height, self.target_width)
+        if None not in want and tuple(tensor.shape[:2]) != want:
+            raise ValueError(f"{self.name}: {what} is {tuple(tensor.shape[:2])}, expected {want}")
+
+    def post_process(self, image, label):
+        """float32 image, int32 label without its channel axis; with a target size set, a result of another size is an error (where the
+        reference pins the static shape)"""
+        self._check_size("image", image)
+        if label is not None:
+            self._check_size("label", label)
+            label = label.to(torch.int32).squeeze()
+        return image.to(torch.float32), label
+
+    def process(self, *inputs):
+        for augment in self.augments:
+            inputs = augment(*inputs)
+        if not self._names_printed:      # once per pipeline, in the reference's wording
+            print(f"Processed augments = {[augment.name for augment in self.augments]}")
+            self._names_printed = True
+        return self.post_process(*inputs) if self.perform_post_process else inputs
+
+    def __call__(self, ds):
+        """dataset -> dataset of augmented samples, for code written against the tf.data form"""
+        if ds is None:
+            return ds
+
+        def one(image, label=None):
+            return self.process(image.to(nn.device()), None if label is None else label.to(nn.device()).to(torch.int32))
+
+        return ds.map(one)
 
 
 class StandardAugmentationsPipeline:

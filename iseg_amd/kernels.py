@@ -1110,6 +1110,44 @@ def augment_crop_batch(images, labels, params, mean_pixel, norm_scale, norm_shif
     return out, out_lab
 
 
+def projective_transform_batch(images, labels, transforms, sizes=None, interpolation="bilinear", image_fill=0.0, replace=None, label_fill=255):
+    """tf.raw_ops.ImageProjectiveTransformV3, CONSTANT fill mode, for a padded batch in one launch (csrc/projective.hip;
+    augments/random_rotate_augment.py:20-115, :221-296).  images [B, Hs, Ws, C] (C in 1..4), labels [B, Hs, Ws] int32 or None, transforms
+    [B, 8] float32 (output (x, y) -> input point), sizes [B, 2] int32 (H, W) of each sample in its slot or None; replace [C] or None:
+    out < -1e-6 -> replace[c].  Labels are sampled nearest with label_fill.  uint8 images are converted to float32 here and the output is
+    always float32: TF keeps the input's type, but the reference's fill of -1 and where(out < -1e-6) presuppose a float image anyway.
+    -> (float32 [B, Hs, Ws, C], int32 [B, Hs, Ws] or None)"""
+    _require_cuda(images, labels, transforms, sizes)
+    if interpolation not in ("nearest", "bilinear"):
+        raise ValueError(f"interpolation must be 'nearest' or 'bilinear', got {interpolation!r}")
+    if images.dim() != 4 or 0 in images.shape:
+        raise ValueError(f"images must be a non-empty [B, Hs, Ws, C] batch, got {tuple(images.shape)}")
+    B, Hs, Ws, Cc = images.shape
+    images = images.to(torch.float32).contiguous()
+    transforms = transforms.to(torch.float32).contiguous()
+    if tuple(transforms.shape) != (B, 8):
+        raise ValueError(f"transforms must be [{B}, 8], got {tuple(transforms.shape)}")
+    if sizes is not None:
+        sizes = sizes.to(torch.int32).contiguous()
+        if tuple(sizes.shape) != (B, 2):
+            raise ValueError(f"sizes must be [{B}, 2], got {tuple(sizes.shape)}")
+    out = torch.empty((B, Hs, Ws, Cc), dtype=torch.float32, device=images.device)
+    lab = out_lab = None
+    if labels is not None:
+        if tuple(labels.shape) != (B, Hs, Ws):
+            raise ValueError(f"labels must be [{B}, {Hs}, {Ws}], got {tuple(labels.shape)}")
+        lab = labels.to(torch.int32).contiguous()
+        out_lab = torch.empty((B, Hs, Ws), dtype=torch.int32, device=images.device)
+    rep = None
+    if replace is not None:
+        if len(replace) != Cc:
+            raise ValueError(f"replace needs one value per channel ({Cc}), got {len(replace)}")
+        rep = (C.c_float * Cc)(*[float(v) for v in replace])
+    _hip.call("iseg_projective_transform_batch", ptr(images), ptr(lab), ptr(transforms), ptr(sizes), ptr(out), ptr(out_lab), B, Hs, Ws, Cc,
+              1 if interpolation == "bilinear" else 0, float(image_fill), rep, int(label_fill), stream())
+    return out, out_lab
+
+
 def normalize_image(x, norm_scale, norm_shift):
     _require_cuda(x)
     y = torch.empty_like(x)
