@@ -351,9 +351,10 @@ template <bool FAST> __device__ __forceinline__ float act_value(float v, int act
 template <bool FAST> __device__ __forceinline__ float act_deriv(float a, int act) {
     switch (act) {
         case ISEG_ACT_RELU: return a > 0.f ? 1.f : 0.f;
-        case ISEG_ACT_SIGMOID: {
-            const float s = 1.f / (1.f + expf(-a));
-            return s * (1.f - s);
+        case ISEG_ACT_SIGMOID: {      // s (1 - s) = e / (1 + e)^2 with e = exp(-|a|): 1 - s cancels to zero from a = 17 on, this form keeps the tail
+            const float e = expf(-fabsf(a));
+            const float r = 1.f / (1.f + e);
+            return e * r * r;
         }
         case ISEG_ACT_SWISH: {
             const float s = 1.f / (1.f + expf(-a));

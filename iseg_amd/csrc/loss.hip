@@ -78,10 +78,10 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict
                 z[c] = e;
                 se += e;
             }
-            const float lse = mx + __logf(se);
             if (!focal) {
-                // -sum_c onehot_c * log_softmax_c : zero row when y is out of range
-                my_loss = in_range ? w * (lse - zy) : 0.f;
+                // -sum_c onehot_c * log_softmax_c : zero row when y is out of range.  log(se) - (zy - mx), not (mx + log(se)) - zy: with logits
+                // of ~1e4 the sum mx + log(se) is rounded to 1e-3 and the loss with it (zy - mx is exact for neighbouring magnitudes)
+                my_loss = in_range ? w * (__logf(se) - (zy - mx)) : 0.f;
                 if (loss_px) loss_px[p0 + threadIdx.x] = my_loss;
                 if (dlogits) {
                     const float g = w * grad_scale * (grad_px ? grad_px[p0 + threadIdx.x] : 1.f);
@@ -93,19 +93,25 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict
                 // loss = alpha * (1 - p)^gamma * (-log p); the clip passes no gradient outside its range
                 const float py = in_range ? z[y] / se : 1.f;
                 const float pc = fminf(fmaxf(py, 1e-7f), 1.f - 1e-7f);
-                const float om = 1.f - pc;
+                const bool inside = py > 1e-7f && py < 1.f - 1e-7f;
+                // 1 - p_y as (sum of the other terms) / se: for a confident pixel 1 - z[y] / se cancels, and the running sum se = 1 + many
+                // terms of ~1e-6 carries ~5e-7 of rounding, which is 10 % of that pixel's loss.  log p_y = log1p(-(1 - p_y)) on that side.
+                float others = 0.f;
+                for (int c = 0; c < C; ++c) others += (c == y) ? 0.f : z[c];
+                const float inv = 1.f / se;
+                const float q = others * inv;
+                const float om = inside ? q : 1.f - pc;
                 const float mod = __powf(om, f_gamma);
-                const float lg = __logf(pc);
+                const float lg = (inside && q < 0.5f) ? log1pf(-q) : logf(pc);
                 my_loss = in_range ? w * f_alpha * mod * (-lg) : 0.f;
                 if (loss_px) loss_px[p0 + threadIdx.x] = my_loss;
                 if (dlogits) {
                     const float g = w * grad_scale * (grad_px ? grad_px[p0 + threadIdx.x] : 1.f);
-                    const bool live = in_range && py > 1e-7f && py < 1.f - 1e-7f;
+                    const bool live = in_range && inside;
                     // dL/dp = alpha * (gamma (1-p)^(gamma-1) log p - (1-p)^gamma / p);   dp/dz_c = p (delta_cy - p_c)
                     const float dldp = live ? f_alpha * (f_gamma * (mod / om) * lg - mod / pc) : 0.f;
                     const float k = g * dldp * py;
-                    const float inv = 1.f / se;
-                    for (int c = 0; c < C; ++c) z[c] = k * (((c == y) ? 1.f : 0.f) - z[c] * inv);
+                    for (int c = 0; c < C; ++c) z[c] = k * ((c == y) ? q : -z[c] * inv);
                 }
             }
         }
