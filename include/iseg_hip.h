@@ -10,8 +10,11 @@
  *   - dtype: ISEG_F32 (0) or ISEG_BF16 (1) storage; arithmetic is fp32 (MFMA accumulates in fp32).
  *   - Returns ISEG_OK (0) or a negative iseg status; iseg_last_error() holds a per-thread message.
  *   - Nothing allocates or frees device memory: the caller owns inputs, outputs and workspace
- *     (query iseg_*_workspace_bytes first).  All work is enqueued on `stream`; entry points never
- *     synchronise, so they can be captured into a hipGraph.
+ *     (query iseg_*_workspace_bytes first).  An entry point that is handed fewer workspace bytes than
+ *     its query answers returns ISEG_STATUS_WORKSPACE and launches nothing (a NULL workspace where one
+ *     is needed: ISEG_STATUS_WORKSPACE or ISEG_STATUS_ARG); the answer may be an upper bound over the
+ *     routes an entry point can take, and it is the answer that is checked.  All work is
+ *     enqueued on `stream`; entry points never synchronise, so they can be captured into a hipGraph.
  *   - Keras weight layouts are consumed as they are: Dense [in,out], Conv2D [kh,kw,Cin,Cout],
  *     DepthwiseConv2D [kh,kw,C,1].
  */
@@ -153,7 +156,7 @@ int iseg_layernorm_bwd(const void* dy, const void* x, const float* gamma, const 
 /* Tail of a post-norm residual branch in one pass each way (backbones/intern_image/intern_image.py:226-236: x = residual + drop_path(gamma *
  * norm(f(x))), utils/drops.py:8-22): y = residual + rowscale[row / rows_per_group] * colscale[c] * LN(x); colscale [C], rowscale, residual
  * optional.  Backward: dx = LN^T(rowscale colscale dy); dgamma, dbeta and dcolscale (NULL: not wanted) are ACCUMULATED -- the three come from
- * the same two column sums.  Workspace of the backward: iseg_layernorm_bwd_workspace_bytes(rows, C) + 2 C floats. */
+ * the same two column sums.  Workspace of the backward: iseg_layernorm_bwd_workspace_bytes(rows, C) + 2 C floats, with or without a scale. */
 int iseg_layernorm_post_fwd(const void* x, const float* gamma, const float* beta, const float* colscale, const float* rowscale,
                             int64_t rows_per_group, const void* residual, void* y, float* mean, float* rstd, int64_t rows, int C, float eps,
                             int dtype, iseg_stream_t stream);

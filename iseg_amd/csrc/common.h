@@ -27,6 +27,15 @@ int iseg_check_launch(const char* what);
         }                                       \
     } while (0)
 
+// a workspace smaller than the entry point's iseg_*_workspace_bytes function answers: ISEG_STATUS_WORKSPACE, nothing launched
+#define ISEG_REQUIRE_WORKSPACE(cond, ...)       \
+    do {                                        \
+        if (!(cond)) {                          \
+            iseg_set_error(__VA_ARGS__);        \
+            return ISEG_ERR_WORKSPACE;          \
+        }                                       \
+    } while (0)
+
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline size_t dtype_size(int dtype) { return dtype == ISEG_BF16 ? 2 : 4; }
 

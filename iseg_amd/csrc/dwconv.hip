@@ -1170,8 +1170,11 @@ extern "C" int iseg_dwconv2d_bwd_weight(const void* x, const void* dy, float* dw
     const int bm = dtype == ISEG_BF16 && bw_mfma_auto(x, dy, N, H, W, C) ? iseg_dwconv7_wgrad_mfma_blocks(N, H, W, C, K, dil) : 0;
     if (bm) g.bx = bm;
     const size_t need = (size_t)g.bx * (K * K + 1) * C * sizeof(float);
-    if (!ws || ws_bytes < need) {
-        iseg_set_error("iseg_dwconv2d_bwd_weight: needs %zu workspace bytes, got %zu", need, ws_bytes);
+    // the caller is held to iseg_dwconv2d_bwd_weight_workspace_bytes (the bound over every route), not to the chosen route's smaller count:
+    // what the header tells a caller to ask for is then also what is checked, whichever route a later change picks
+    const size_t promised = iseg_dwconv2d_bwd_weight_workspace_bytes(N, H, W, C, K);
+    if (!ws || ws_bytes < need || ws_bytes < promised) {
+        iseg_set_error("iseg_dwconv2d_bwd_weight: needs %zu workspace bytes, got %zu", need > promised ? need : promised, ws_bytes);
         return ISEG_ERR_WORKSPACE;
     }
     float* const arena = iseg_deferred_partials(need, dw, db, accumulate, stream);      // (see common.h: deferred reductions)

@@ -295,7 +295,9 @@ extern "C" int iseg_dwconv2d7_bwd_weight_mfma(const void* x, const void* dy, flo
     ISEG_REQUIRE(x && dy && dw && N > 0 && H > 0 && W > 0, "iseg_dwconv2d7_bwd_weight_mfma: bad arguments");
     ISEG_REQUIRE((int64_t)N * H * W * C < (1ll << 31), "iseg_dwconv2d7_bwd_weight_mfma: more than 2^31 elements");
     const int blocks = iseg_dwconv7_wgrad_mfma_blocks(N, H, W, C, KS, 1);
-    const size_t need = (size_t)blocks * NT * C * sizeof(float);
+    size_t need = (size_t)blocks * NT * C * sizeof(float);
+    const size_t promised = iseg_dwconv2d_bwd_weight_workspace_bytes(N, H, W, C, KS);      // (what the header tells the caller to ask for)
+    if (promised > need) need = promised;
     if (blocks > 0 && (!ws || ws_bytes < need)) {
         iseg_set_error("iseg_dwconv2d7_bwd_weight_mfma: needs %zu workspace bytes, got %zu", need, ws_bytes);
         return ISEG_ERR_WORKSPACE;

@@ -896,8 +896,10 @@ extern "C" int iseg_layerscale_grads(const float* Z, const float* W2, const floa
     ISEG_REQUIRE(Z && W2 && b2 && gamma && S && dW2 && dgamma && db2, "iseg_layerscale_grads: null pointer");
     const int P = layerscale_ksplits(K);
     const size_t need = (size_t)P * N * sizeof(float);
-    if (!ws || ws_bytes < need) {
-        iseg_set_error("iseg_layerscale_grads: needs %zu workspace bytes, got %zu", need, ws_bytes);
+    // (the caller is held to the query, which also covers the slab form's finer strips: one rule for both forms)
+    const size_t promised = iseg_layerscale_grads_workspace_bytes(K, N);
+    if (!ws || ws_bytes < need || ws_bytes < promised) {
+        iseg_set_error("iseg_layerscale_grads: needs %zu workspace bytes, got %zu", need > promised ? need : promised, ws_bytes);
         return ISEG_ERR_WORKSPACE;
     }
     float* const arena = iseg_deferred_partials(need, dgamma, nullptr, accumulate, stream);      // (see common.h: deferred reductions)
@@ -944,10 +946,11 @@ static int layerscale_grads_slabs_impl(const float* slabs, int nslabs, const flo
     int P = K / 16;
     if (P > 128) P = 128;
     if (P < 1) P = 1;
-    if ((size_t)P * N * sizeof(float) > ws_bytes) P = layerscale_ksplits(K);
     const size_t need = (size_t)P * N * sizeof(float);
-    if (!ws || ws_bytes < need) {
-        iseg_set_error("iseg_layerscale_grads_slabs: needs %zu workspace bytes, got %zu", need, ws_bytes);
+    // (a buffer smaller than the query answers is refused, not served with coarser strips)
+    const size_t promised = iseg_layerscale_grads_workspace_bytes(K, N);
+    if (!ws || ws_bytes < need || ws_bytes < promised) {
+        iseg_set_error("iseg_layerscale_grads_slabs: needs %zu workspace bytes, got %zu", need > promised ? need : promised, ws_bytes);
         return ISEG_ERR_WORKSPACE;
     }
     float* const arena = iseg_deferred_partials(need, dgamma, nullptr, accumulate, stream);

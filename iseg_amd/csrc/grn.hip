@@ -308,7 +308,7 @@ extern "C" int iseg_grn_fwd(const void* x, const float* gamma, const float* beta
     ISEG_REQUIRE(x && nx && gx && N > 0 && HW > 0 && C > 0 && (!y || (gamma && beta)), "iseg_grn_fwd: bad arguments");
     ISEG_REQUIRE((dtype == ISEG_BF16 || dtype == ISEG_F32) && C % 8 == 0, "iseg_grn_fwd: C %% 8 == 0 required (got dtype %d, C %d)", dtype, C);
     ISEG_REQUIRE(N <= 65535, "iseg_grn_fwd: at most 65535 samples");
-    ISEG_REQUIRE(ws && ws_bytes >= iseg_grn_workspace_bytes(N, HW, C), "iseg_grn_fwd: workspace too small");
+    ISEG_REQUIRE_WORKSPACE(ws && ws_bytes >= iseg_grn_workspace_bytes(N, HW, C), "iseg_grn_fwd: workspace too small");
     const int P = grn_parts(N, HW, C);
     float* parts = (float*)ws;
     float* sumsq = (float*)((char*)ws + align256((size_t)N * P * 2 * C * sizeof(float)));
@@ -338,7 +338,7 @@ extern "C" int iseg_grn_bwd(const void* dy, const void* x, const float* gamma, c
     ISEG_REQUIRE(dy && x && gamma && nx && gx && dx && dgamma && dbeta && N > 0 && HW > 0 && C > 0, "iseg_grn_bwd: bad arguments");
     ISEG_REQUIRE((dtype == ISEG_BF16 || dtype == ISEG_F32) && C % 8 == 0, "iseg_grn_bwd: C %% 8 == 0 required (got dtype %d, C %d)", dtype, C);
     ISEG_REQUIRE(N <= 65535, "iseg_grn_bwd: at most 65535 samples");
-    ISEG_REQUIRE(ws && ws_bytes >= iseg_grn_workspace_bytes(N, HW, C), "iseg_grn_bwd: workspace too small");
+    ISEG_REQUIRE_WORKSPACE(ws && ws_bytes >= iseg_grn_workspace_bytes(N, HW, C), "iseg_grn_bwd: workspace too small");
     const int P = grn_parts(N, HW, C);
     const size_t side = align256((size_t)N * 2 * C * sizeof(float));
     float* parts = (float*)ws;
@@ -407,7 +407,7 @@ extern "C" int iseg_grn_bwd_folded(const void* dy, const void* x, const float* g
     ISEG_REQUIRE(dy && x && gamma && nx && gx && dstats && dx && dgamma && dbeta && N > 0 && HW > 0 && C > 0, "iseg_grn_bwd_folded: bad arguments");
     ISEG_REQUIRE((dtype == ISEG_BF16 || dtype == ISEG_F32) && C % 8 == 0, "iseg_grn_bwd_folded: C %% 8 == 0 required (got dtype %d, C %d)", dtype, C);
     ISEG_REQUIRE(N <= 65535, "iseg_grn_bwd_folded: at most 65535 samples");
-    ISEG_REQUIRE(ws && ws_bytes >= iseg_grn_workspace_bytes(N, HW, C), "iseg_grn_bwd_folded: workspace too small");
+    ISEG_REQUIRE_WORKSPACE(ws && ws_bytes >= iseg_grn_workspace_bytes(N, HW, C), "iseg_grn_bwd_folded: workspace too small");
     float* t = (float*)ws;
     hipLaunchKernelGGL(grn_bwd_stats_kernel, dim3((unsigned)N), dim3(256), 0, stream, dstats, 2 * (int64_t)C, gamma, nx, gx, t, C, eps);
     launch_reduce_rows(dstats, (int)N, 2 * (int64_t)C, 0, 1, 2 * (int64_t)C, dgamma, dbeta, C, 0, 1.f, accumulate, stream);

@@ -567,7 +567,7 @@ extern "C" int iseg_se_excite_bwd(const float* partials, int N, int HW, int C, i
                                   float* sums, void* ws, size_t ws_bytes, hipStream_t stream) {
     ISEG_REQUIRE(partials && W1 && W2 && m && hpre && g && dmh && sums && ws, "iseg_se_excite_bwd: null pointer");
     if (!mb_shape_ok(N, HW, C, Cse)) MB_UNSUPPORTED("iseg_se_excite_bwd", N, HW, C, Cse);
-    ISEG_REQUIRE(ws_bytes >= iseg_se_excite_bwd_workspace_bytes(N, C, Cse), "iseg_se_excite_bwd: workspace too small");
+    ISEG_REQUIRE_WORKSPACE(ws_bytes >= iseg_se_excite_bwd_workspace_bytes(N, C, Cse), "iseg_se_excite_bwd: workspace too small");
     const MbTile t = mb_tile(HW, C);
     float* S = (float*)ws;
     float* de = S + (int64_t)N * 5 * C;

@@ -892,6 +892,12 @@ extern "C" int iseg_layernorm_post_bwd(const void* dy, const void* x, const floa
                                        hipStream_t stream) {
     ISEG_REQUIRE(beta && (!rowscale || rows_per_group > 0) && (!dcolscale || colscale), "iseg_layernorm_post_bwd: bad arguments");
     ISEG_REQUIRE(((uintptr_t)colscale & 15) == 0, "iseg_layernorm_post_bwd: colscale must be 16-byte aligned");
+    // the documented size whether or not this call has a scale (without one the two finish rows are not used): one rule for the caller
+    const size_t promised = iseg_layernorm_bwd_workspace_bytes(rows, C) + (size_t)2 * C * sizeof(float);
+    if (rows > 0 && C > 0 && (!ws || ws_bytes < promised)) {
+        iseg_set_error("iseg_layernorm_post_bwd: needs %zu workspace bytes, got %zu", promised, ws_bytes);
+        return ISEG_ERR_WORKSPACE;
+    }
     return layernorm_bwd_launch(dy, nullptr, x, gamma, mean, rstd, dx, nullptr, dgamma, dbeta, 1, rows, C, dtype, ws, ws_bytes, stream,
                                 LnPost{colscale, rowscale, rows_per_group, nullptr}, beta, dcolscale);
 }
@@ -1024,7 +1030,8 @@ extern "C" int iseg_bn_stats(const void* x, int64_t ldx, float* packed, int64_t 
     ISEG_REQUIRE(rows > 0 && C > 0 && C % 8 == 0 && ldx % 8 == 0, "iseg_bn_stats: C=%d ldx=%lld must be multiples of 8", C,
                  (long long)ldx);
     const int blocks = bn_blocks(rows, C);
-    const size_t need = (size_t)blocks * 2 * C * sizeof(float);
+    // (the statistics pass runs at most 256 workgroups, the backward sums 1024: the caller is held to the one query that serves both)
+    const size_t need = iseg_bn_workspace_bytes(rows, C);
     if (!ws || ws_bytes < need) {
         iseg_set_error("iseg_bn_stats: needs %zu workspace bytes, got %zu", need, ws_bytes);
         return ISEG_ERR_WORKSPACE;

@@ -442,7 +442,7 @@ extern "C" int iseg_resblock_tail_bwd_reduce(const void* dout, const void* out, 
     if (!rb_shape_ok(N, H, W, C, stride) || !iseg_resblock_tail_supported(C, stride, dtype) || !rb_aligned(dout) || !rb_aligned(out) ||
         !rb_aligned(z2) || !rb_aligned(mean2) || !rb_aligned(rstd2) || (bn0 && (!rb_aligned(z0) || !rb_aligned(mean0) || !rb_aligned(rstd0))))
         RB_UNSUPPORTED("iseg_resblock_tail_bwd_reduce", N, H, W, C, stride);
-    ISEG_REQUIRE(ws_bytes >= iseg_resblock_tail_workspace_bytes(N, H, W, C, stride, bn0), "iseg_resblock_tail_bwd_reduce: workspace too small");
+    ISEG_REQUIRE_WORKSPACE(ws_bytes >= iseg_resblock_tail_workspace_bytes(N, H, W, C, stride, bn0), "iseg_resblock_tail_bwd_reduce: workspace too small");
     const RbGeom g = rb_geom(N, H, W, C, stride);
     const RbTile t = rb_tile(g.P, C);
     float* partials = (float*)ws;

@@ -421,8 +421,8 @@ extern "C" int iseg_relu_dwconv3_stats(const void* x, const float* w, void* z, f
     const size_t lds = sc_lds_bytes(t);
     float* part = (float*)ws;
     if (packed) {
-        ISEG_REQUIRE(ws && ws_bytes >= iseg_relu_dwconv3_stats_workspace_bytes(N, H, W, C, stride, dil),
-                     "iseg_relu_dwconv3_stats: workspace too small");
+        ISEG_REQUIRE_WORKSPACE(ws && ws_bytes >= iseg_relu_dwconv3_stats_workspace_bytes(N, H, W, C, stride, dil),
+                               "iseg_relu_dwconv3_stats: workspace too small");
         if (dtype == ISEG_BF16)
             hipLaunchKernelGGL((sc_fwd_kernel<bf16_t, true>), grid, dim3(SC_THREADS), lds, stream, (const bf16_t*)x, w, (bf16_t*)z, part,
                                packed + 2 * C, g, t);
@@ -478,7 +478,7 @@ extern "C" int iseg_bnfold_dwconv3_relu_bwd(const void* D, const void* z, const 
     if (!iseg_sepconv_supported(N, H, W, C, stride, dil, dtype) || !sc_aligned(D) || !sc_aligned(z) || !sc_aligned(x) || !sc_aligned(w) ||
         !sc_aligned(dx))
         SC_UNSUPPORTED("iseg_bnfold_dwconv3_relu_bwd", N, H, W, C, stride, dil);
-    ISEG_REQUIRE(ws_bytes >= iseg_bnfold_dwconv3_relu_bwd_workspace_bytes(N, H, W, C, stride, dil), "iseg_bnfold_dwconv3_relu_bwd: workspace too small");
+    ISEG_REQUIRE_WORKSPACE(ws_bytes >= iseg_bnfold_dwconv3_relu_bwd_workspace_bytes(N, H, W, C, stride, dil), "iseg_bnfold_dwconv3_relu_bwd: workspace too small");
     const ScGeom g = sc_geom(N, H, W, C, stride, dil);
     const ScTile t = sc_tile(g, true);
     const dim3 grid(t.tiles_w * t.hsteps, N, t.groups);

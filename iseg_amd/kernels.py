@@ -612,8 +612,7 @@ def bn_swish_se_bwd_sums(dO, x, mean, rstd, gamma, beta, W1, W2, m, hpre, g, dW1
     part, pbytes = _mb_partials(N, HW, Cc, True, x.device)
     _hip.call("iseg_bn_swish_gate_bwd_reduce", ptr(dO), ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(part), pbytes, N, HW, Cc, dt(x),
               stream())
-    wsb = _hip.lib().iseg_se_excite_bwd_workspace_bytes(N, Cc, Cse)
-    ws = torch.empty(wsb // 4, dtype=torch.float32, device=x.device)
+    ws, wsb = workspace(_hip.lib().iseg_se_excite_bwd_workspace_bytes(N, Cc, Cse), x.device)
     dmh = torch.empty((N, Cc), dtype=torch.float32, device=x.device)
     sums = torch.empty(2 * Cc, dtype=torch.float32, device=x.device)
     _hip.call("iseg_se_excite_bwd", ptr(part), N, HW, Cc, Cse, ptr(W1), ptr(W2), ptr(m), ptr(hpre), ptr(g), ptr(dW1), ptr(db1), ptr(dW2), ptr(db2),

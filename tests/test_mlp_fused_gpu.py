@@ -271,10 +271,10 @@ def test_convnext_mlp_chain_through_the_layernorm_backward(cuda, C, M):
     ln = (mean, rstd, lng, lnb)
     dout = torch.randn(M, C, generator=torch.Generator().manual_seed(4)).to(bf).cuda()
     dy2 = K.convnext_mlp_bwd_data(y1b, dout, bw, b1.cuda(), rs, rpg, ln=ln)
+    dg, db = torch.full((C,), 0.25, device="cuda"), torch.full((C,), -0.5, device="cuda")      # (accumulated into: the gradient buffers are live)
+    got = K.convnext_mlp_bwd_data_ln(y1b, dout, bw, b1.cuda(), ln, dg, db, rs, rpg)      # (first: the body's first user of scratch)
     dg_want, db_want = torch.full((C,), 0.25, device="cuda"), torch.full((C,), -0.5, device="cuda")
     want = K.layernorm_bwd(dy2, y1b, lng, mean, rstd, dg_want, db_want)
-    dg, db = torch.full((C,), 0.25, device="cuda"), torch.full((C,), -0.5, device="cuda")      # (accumulated into: the gradient buffers are live)
-    got = K.convnext_mlp_bwd_data_ln(y1b, dout, bw, b1.cuda(), ln, dg, db, rs, rpg)
     # fp64 formula on the bf16-rounded dy2 the separate route hands over (the fused route keeps fp32 rows: differences are bf16 roundings of dy2)
     d, x = dy2.double().cpu(), y1b.double().cpu()
     xh = (x - mean.double().cpu()[:, None]) * rstd.double().cpu()[:, None]
