@@ -923,6 +923,40 @@ int iseg_conv2d_igemm_bwd_data(const void* dy, const void* w, void* dx, const is
 int iseg_conv2d_igemm_bwd_weight(const void* x, const void* dy, float* dw, int accumulate, const iseg_conv_geom* geom_h, int dtype, void* ws,
                                  size_t ws_bytes, iseg_stream_t stream);
 
+/* Several convolutions of ONE input [N,H,W,Cin] -- layers/aspp.py:33-52, the pixel-level 1x1 and the dilated 3x3 branches: stride 1, "same"
+ * padding, one group, Cout filters each, their own kernel size / dilation -- as one launch per pass (csrc/conv_igemm_dma.h):
+ *   fwd         blockIdx.z = branch: y_b = conv(x, w_b) (+ bias_b), written at column y_col of rows of ldy elements
+ *   bwd_data    dx = sum_b conv^T(dy_b, w_b) (+ residual) as ONE product whose reduction runs over (branch, tap, channel): the branch
+ *               gradients meet in the fp32 accumulators and are rounded once
+ *   bwd_weight  blockIdx.z = branch: gw_b (+)= x^T * dy_b per tap, one pass over the pixels, no slabs
+ * A branch lists the operands of all three passes; a pass reads only its own.  bf16 storage, Cin % 64 == 0, Cout % 64 == 0, N*H*W >= 64
+ * (iseg_conv2d_branches_supported), 16-byte aligned operands, leading dimensions multiples of 8; anything else returns ISEG_ERR_UNSUPPORTED.
+ * Workspace: fwd and bwd_weight need none (their branches fill the chip; ws may be NULL).  bwd_data is one stride-1 data gradient whose taps
+ * are the taps of every branch in a row, and may split that reduction: iseg_conv2d_igemm_workspace_bytes(g, 1) with g = {N, H, W, Cin, Cout,
+ * KH = 1, KW = sum of KH_b * KW_b, strides and dilations 1, pt = pl = 0, Ho = H, Wo = W, groups = 1}. */
+#define ISEG_CONV_MAX_BRANCHES 4
+typedef struct iseg_conv_branch {
+    int KH, KW, dh, dw, pt, pl;
+    const void* wt;          /* fwd: K-contiguous kernel copy [Cout][KH*KW*Cin] */
+    const void* w;           /* bwd_data: Keras kernel [KH,KW,Cin,Cout] */
+    const float* bias;       /* fwd, may be NULL */
+    void* y;                 /* fwd: output rows */
+    int64_t ldy, y_col;
+    const void* dy;          /* bwd_data, bwd_weight: gradient rows of lddy elements */
+    int64_t lddy;
+    float* gw;               /* bwd_weight: fp32 [KH,KW,Cin,Cout] */
+} iseg_conv_branch;
+typedef struct iseg_conv_branches {
+    int N, H, W, Cin, Cout, count;
+    iseg_conv_branch b[ISEG_CONV_MAX_BRANCHES];
+} iseg_conv_branches;
+int iseg_conv2d_branches_supported(const iseg_conv_branches* t, int dtype);
+int iseg_conv2d_branches_fwd(const void* x, const iseg_conv_branches* t, int dtype, void* ws, size_t ws_bytes, iseg_stream_t stream);
+int iseg_conv2d_branches_bwd_data(const iseg_conv_branches* t, void* dx, const void* residual, int64_t ldr, int dtype, void* ws, size_t ws_bytes,
+                                  iseg_stream_t stream);
+int iseg_conv2d_branches_bwd_weight(const void* x, const iseg_conv_branches* t, int accumulate, int dtype, void* ws, size_t ws_bytes,
+                                    iseg_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------------------
  * Fused ConvNeXt MLP (backbones/convnext.py:51-63 Block.call: pwconv1 -> act (exact GELU) -> pwconv2 -> gamma -> drop_path ->
  * + input) for the wide stages, bf16 storage, C = 96 / 192 (iseg_convnext_mlp_supported):

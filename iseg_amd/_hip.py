@@ -48,6 +48,19 @@ class ConvGeom(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("N", "H", "W", "Cin", "Cout", "KH", "KW", "sh", "sw", "dh", "dw", "pt", "pl", "Ho", "Wo", "groups")]
 
 
+CONV_MAX_BRANCHES = 4
+
+
+class ConvBranch(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("KH", "KW", "dh", "dw", "pt", "pl")] + [
+        ("wt", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("y", C.c_void_p), ("ldy", C.c_int64), ("y_col", C.c_int64),
+        ("dy", C.c_void_p), ("lddy", C.c_int64), ("gw", C.c_void_p)]
+
+
+class ConvBranches(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("N", "H", "W", "Cin", "Cout", "count")] + [("b", ConvBranch * CONV_MAX_BRANCHES)]
+
+
 _p, _i, _l, _f, _z, _u64 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t, C.c_uint64
 
 # name -> (restype, argtypes); must list every symbol include/iseg_hip.h declares (tests/test_abi.py checks it)
@@ -245,6 +258,10 @@ SIGNATURES = {
     "iseg_conv2d_igemm_fwd_kt_supported": (_i, [C.POINTER(ConvGeom), _i]),
     "iseg_conv2d_igemm_bwd_data": (_i, [_p, _p, _p, C.POINTER(ConvGeom), _i, _p, _z, _p]),
     "iseg_conv2d_igemm_bwd_weight": (_i, [_p, _p, _p, _i, C.POINTER(ConvGeom), _i, _p, _z, _p]),
+    "iseg_conv2d_branches_supported": (_i, [C.POINTER(ConvBranches), _i]),
+    "iseg_conv2d_branches_fwd": (_i, [_p, C.POINTER(ConvBranches), _i, _p, _z, _p]),
+    "iseg_conv2d_branches_bwd_data": (_i, [C.POINTER(ConvBranches), _p, _p, _l, _i, _p, _z, _p]),
+    "iseg_conv2d_branches_bwd_weight": (_i, [_p, C.POINTER(ConvBranches), _i, _i, _p, _z, _p]),
     "iseg_convnext_mlp_supported": (_i, [_i, _i]),
     "iseg_convnext_mlp_tiled_bytes": (_z, [_i, _i]),
     "iseg_convnext_mlp_prep": (_i, [_p, _p, _p, _p, _p, _i, _p]),

@@ -70,6 +70,24 @@ struct PhaseRows {
 
 constexpr int INVALID = -(1 << 28);
 
+// Several convolutions of ONE input (stride 1, "same" padding, one group, the same channel counts): what differs from branch to branch.
+struct BranchP {
+    const bf16_t* src;      // gathered tensor and its row stride in channels: x (pass 0, 2; the same for every branch) or this branch's dy (pass 1)
+    const bf16_t* B;        // pass 0: K-contiguous kernel copy [Cout][kh*kw*Cin]; pass 1: Keras kernel; pass 2: this branch's dy
+    void* D;                // pass 0: y at its column offset; pass 2: dW (fp32)
+    const float* bias;      // pass 0
+    int64_t ldb, ldd;
+    int Cs;
+    int kw, dh, dw, pt, pl;
+    int K;                  // pass 0: reduction length kh*kw*Cin; pass 1: END of the branch's range in the joined reduction; pass 2: rows of dW
+};
+constexpr int MAX_BRANCHES = ISEG_CONV_MAX_BRANCHES;
+struct BranchTable {
+    BranchP b[MAX_BRANCHES];
+    int count;
+};
+struct NoBranches {};
+
 }  // namespace
 
 #include "conv_igemm_dma.h"
@@ -177,13 +195,12 @@ template <int ROWS, int NT, int BK> struct TapWeightStager : Stager<ROWS, true, 
     }
 };
 
-template <int WM, int WN, int FM, int FN, int PASS, int BK, class TO>
-__global__ __launch_bounds__(WM* WN * 64) void conv_igemm_kernel(ConvP p, const bf16_t* __restrict__ Bop, int64_t ldb, int64_t b_group_stride,
-                                                                  int64_t tap_stride, TO* __restrict__ D, int64_t ldd, int64_t d_group_stride,
-                                                                  int64_t M, int64_t N, int64_t K, int tiles_n, int ntiles,
-                                                                  int64_t k_per_split, float* __restrict__ slabs, int64_t slab_group_stride,
-                                                                  Epi epi, int vecD,
-                                                                  typename std::conditional<PASS == 3, PhaseTable, NoPhases>::type phases) {
+// one output tile of a pass; grp = channel group.  RAGGED: the grid is sized for the largest of several problems, a tile past this one's rows leaves
+template <int WM, int WN, int FM, int FN, int PASS, int BK, class TO, bool RAGGED = false>
+__device__ __forceinline__ void conv_igemm_tile(ConvP p, const bf16_t* __restrict__ Bop, int64_t ldb, int64_t b_group_stride, int64_t tap_stride,
+                                                TO* __restrict__ D, int64_t ldd, int64_t d_group_stride, int64_t M, int64_t N, int64_t K, int tiles_n,
+                                                int ntiles, int64_t k_per_split, float* __restrict__ slabs, int64_t slab_group_stride, Epi epi,
+                                                int vecD, const typename std::conditional<PASS == 3, PhaseTable, NoPhases>::type& phases, int grp) {
     constexpr bool AKC = PASS != 2, BKC = PASS == 1 || PASS == 3;
     constexpr int GPASS = PASS == 3 ? 1 : PASS;      // a phase is a stride-1 data-gradient gather in quotient coordinates
     constexpr int NT = WM * WN * 64;
@@ -200,7 +217,6 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_kernel(ConvP p, const 
 
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int wm = wid / WN, wn = wid % WN;
-    const int grp = blockIdx.z;
     const int coff = grp * p.Cg;
     Bop += grp * b_group_stride;
     D += grp * d_group_stride;
@@ -227,6 +243,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_kernel(ConvP p, const 
     }
     const int tile_n = t % tiles_n, tile_m = t / tiles_n;
     const int64_t m0 = (int64_t)tile_m * BM, n0 = (int64_t)tile_n * BN;
+    if (RAGGED && m0 >= M) return;      // (workgroup-uniform)
     const int64_t kbeg = (int64_t)ksplit * k_per_split;
     const int64_t kend = (kbeg + k_per_split < K) ? kbeg + k_per_split : K;
     const int nk = (int)((kend - kbeg + BK - 1) / BK);
@@ -280,6 +297,28 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_kernel(ConvP p, const 
     }
     if constexpr (PASS == 3) tile_epilogue<WM, WN, FM, FN, TO, PhaseRows>(acc, smem, D, ldd, M, N, m0, n0, wm, wn, wid, lane, nullptr, epi, false, vecD, 0, rows);
     else tile_epilogue<WM, WN, FM, FN, TO>(acc, smem, D, ldd, M, N, m0, n0, wm, wn, wid, lane, slabs, epi, false, vecD, ksplit);
+}
+
+template <int WM, int WN, int FM, int FN, int PASS, int BK, class TO>
+__global__ __launch_bounds__(WM* WN * 64) void conv_igemm_kernel(ConvP p, const bf16_t* __restrict__ Bop, int64_t ldb, int64_t b_group_stride,
+                                                                  int64_t tap_stride, TO* __restrict__ D, int64_t ldd, int64_t d_group_stride,
+                                                                  int64_t M, int64_t N, int64_t K, int tiles_n, int ntiles,
+                                                                  int64_t k_per_split, float* __restrict__ slabs, int64_t slab_group_stride,
+                                                                  Epi epi, int vecD,
+                                                                  typename std::conditional<PASS == 3, PhaseTable, NoPhases>::type phases) {
+    conv_igemm_tile<WM, WN, FM, FN, PASS, BK, TO>(p, Bop, ldb, b_group_stride, tap_stride, D, ldd, d_group_stride, M, N, K, tiles_n, ntiles,
+                                                  k_per_split, slabs, slab_group_stride, epi, vecD, phases, blockIdx.z);
+}
+
+// The weight gradients of several convolutions of one input: blockIdx.z = branch, each with its own taps (p.kw / dilation / padding), dy and dW.
+// grid.x covers the branch with the most taps; one pass over the pixels, no slabs.
+template <int WM, int WN, int FM, int FN, int BK>
+__global__ __launch_bounds__(WM* WN * 64) void conv_branches_wgrad_kernel(ConvP p, BranchTable tab, int64_t N, int64_t K, int tiles_n, int ntiles,
+                                                                           Epi epi, int vecD) {
+    const BranchP& br = tab.b[blockIdx.z];
+    p.kw = br.kw, p.dh = br.dh, p.dw = br.dw, p.pt = br.pt, p.pl = br.pl;
+    conv_igemm_tile<WM, WN, FM, FN, 2, BK, float, true>(p, br.B, br.ldb, 0, 0, (float*)br.D, br.ldd, 0, br.K, N, K, tiles_n, ntiles, K, nullptr, 0, epi,
+                                                        vecD, NoPhases{}, 0);
 }
 
 struct Problem {
@@ -603,4 +642,210 @@ extern "C" int iseg_conv2d_igemm_bwd_weight(const void* x, const void* dy, float
     q.accumulate = accumulate;
     q.groups = g->groups;
     return run<2, float>(q, ws, ws_bytes, stream, "iseg_conv2d_igemm_bwd_weight");
+}
+
+// ---- several convolutions of one input (ASPP's pixel-level branches): grouped forward / weight gradient, K-joined data gradient ----
+namespace {
+
+bool branches_ok(const iseg_conv_branches* t) {
+    if (!t || t->count < 1 || t->count > MAX_BRANCHES || t->N <= 0 || t->H <= 0 || t->W <= 0 || t->Cin <= 0 || t->Cout <= 0) return false;
+    for (int i = 0; i < t->count; ++i) {
+        const iseg_conv_branch& b = t->b[i];
+        if (b.KH <= 0 || b.KW <= 0 || b.dh <= 0 || b.dw <= 0 || b.pt < 0 || b.pl < 0) return false;
+    }
+    return true;
+}
+
+// what the branches share; `src` / `Cs` are the gathered tensor of passes 0 and 2 (the table brings pass 1's)
+ConvP branches_shared(const iseg_conv_branches* t, const void* src, int Cs, int Cg) {
+    return ConvP{(const bf16_t*)src, t->H, t->W, Cs, t->H, t->W, Cg, 1, 1, 1, 1, 1, 0, 0, 1};
+}
+
+// The K-joined data gradient's tile and split.  Flagship (M = 4096, N = 768, K = 7168), kernel only: 256 x 128 tiles, 2 splits + reducer 126 us;
+// 128 x 128 tiles, 2 splits + reducer 132 us; 128 x 128, no split (192 workgroups for 256 CUs) 138 us; 256 x 128, no split 207 us.
+struct DgradPlan {
+    bool big;         // 256 x 128 tiles (8 wavefronts of 64 x 64, 3 stages) instead of 128 x 128 (8 wavefronts of 64 x 32, 2 stages)
+    int nsplit;
+};
+DgradPlan branches_dgrad_plan(int64_t M, int64_t N, int64_t K) { return DgradPlan{M >= 256, conv_splits(M, N, K, 1)}; }
+
+// The K-joined data gradient IS one stride-1 data gradient whose taps are the taps of every branch in a row: its slabs are sized by
+// iseg_conv2d_igemm_workspace_bytes of this geometry (pass 1), here and by the caller.
+iseg_conv_geom branches_joined_geom(const iseg_conv_branches* t) {
+    int taps = 0;
+    for (int i = 0; i < t->count; ++i) taps += t->b[i].KH * t->b[i].KW;
+    return iseg_conv_geom{t->N, t->H, t->W, t->Cin, t->Cout, 1, taps, 1, 1, 1, 1, 0, 0, t->H, t->W, 1};
+}
+
+template <int PASS, class Tile>
+void launch_branches_dma(Tile, const ConvP& p, const BranchTable& tab, int64_t ldb, int64_t tap_stride, bf16_t* D, int64_t ldd, int64_t M, int64_t N,
+                         int64_t K, int eff, int64_t kps, float* slabs, const Epi& epi, hipStream_t stream) {
+    constexpr int WM = Tile::WM, WN = Tile::WN, FN = Tile::FN, NS = Tile::NS;
+    constexpr int BM = WM * 64, BN = WN * FN * 16;
+    constexpr int lds = NS * (BM + BN) * 128;
+    const int tiles_m = (int)ceil_div64(M, BM), tiles_n = (int)ceil_div64(N, BN);
+    static const bool raised = [] {
+        return hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_branches_dma_kernel<WM, WN, FN, NS, PASS>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess;
+    }();
+    (void)raised;
+    hipLaunchKernelGGL((conv_branches_dma_kernel<WM, WN, FN, NS, PASS>), dim3(tiles_m * tiles_n, eff, PASS == 0 ? tab.count : 1), dim3(WM * WN * 64), lds,
+                       stream, p, tab, ldb, tap_stride, D, ldd, M, N, K, tiles_n, tiles_m * tiles_n, kps, slabs, epi);
+}
+struct BT256 { enum { WM = 4, WN = 2, FN = 4, NS = 3 }; };
+// 128 x 128 as 8 wavefronts of 64 x 32: the grouped forward is ONE workgroup per CU (4 branches x 64 tiles at the flagship), and two wavefronts
+// per SIMD hide each other's LDS reads -- 100 us against 115 us for conv_igemm_dma_kernel's 4 wavefronts of 64 x 64 (3 / 4 stages: 97 / 94 us;
+// 256 x 128 tiles, half the CUs: 131 us; the four per-branch launches with their reducers: 136 us)
+struct BT128 { enum { WM = 2, WN = 4, FN = 2, NS = 2 }; };
+
+}  // namespace
+
+extern "C" int iseg_conv2d_branches_supported(const iseg_conv_branches* t, int dtype) {
+    if (!branches_ok(t) || dtype != ISEG_BF16) return 0;
+    // the LDS-DMA pipeline's K-step is 64 channels of one tap, on the x side (forward) and on the dy side (data gradient)
+    if (t->Cin % 64 != 0 || t->Cout % 64 != 0) return 0;
+    const int64_t M = (int64_t)t->N * t->H * t->W;
+    return M >= 64 && M < (1ll << 31) / 8;
+}
+
+#define BRANCHES_COMMON(name)                                                                                                                  \
+    ISEG_REQUIRE(t, name ": null branch table");                                                                                              \
+    ISEG_REQUIRE(t->count >= 1 && t->count <= MAX_BRANCHES, name ": %d branches, the table holds 1 .. %d", t->count, MAX_BRANCHES);          \
+    ISEG_REQUIRE(branches_ok(t), name ": bad geometry");                                                                                      \
+    if (!iseg_conv2d_branches_supported(t, dtype)) {                                                                                          \
+        iseg_set_error(name ": needs bf16 storage, Cin and Cout multiples of 64 and at least 64 pixels (Cin %d, Cout %d, dtype %d)", t->Cin,  \
+                       t->Cout, dtype);                                                                                                       \
+        return ISEG_ERR_UNSUPPORTED;                                                                                                          \
+    }                                                                                                                                         \
+    const int64_t M = (int64_t)t->N * t->H * t->W
+
+extern "C" int iseg_conv2d_branches_fwd(const void* x, const iseg_conv_branches* t, int dtype, void* ws, size_t ws_bytes, hipStream_t stream) {
+    BRANCHES_COMMON("iseg_conv2d_branches_fwd");
+    (void)ws;
+    (void)ws_bytes;
+    ISEG_REQUIRE(x && ((uintptr_t)x & 15) == 0, "iseg_conv2d_branches_fwd: x must be a 16-byte aligned device pointer");
+    BranchTable tab{};
+    tab.count = t->count;
+    for (int i = 0; i < t->count; ++i) {
+        const iseg_conv_branch& b = t->b[i];
+        ISEG_REQUIRE(b.wt && b.y, "iseg_conv2d_branches_fwd: branch %d: null operand", i);
+        bf16_t* const y = (bf16_t*)b.y + b.y_col;
+        ISEG_REQUIRE((((uintptr_t)b.wt | (uintptr_t)y | (uintptr_t)b.bias) & 15) == 0 && b.ldy % 8 == 0 && b.y_col >= 0 && b.y_col + t->Cout <= b.ldy,
+                     "iseg_conv2d_branches_fwd: branch %d: operands must be 16-byte aligned, the column slice inside a row of ldy %% 8 == 0", i);
+        BranchP& d = tab.b[i];
+        d.B = (const bf16_t*)b.wt;
+        d.K = b.KH * b.KW * t->Cin;
+        d.ldb = d.K;
+        d.D = y;
+        d.ldd = b.ldy;
+        d.bias = b.bias;
+        d.kw = b.KW, d.dh = b.dh, d.dw = b.dw, d.pt = b.pt, d.pl = b.pl;
+    }
+    Epi epi{};
+    epi.alpha = 1.f;
+    epi.batch_inner = 1;
+    const ConvP p = branches_shared(t, x, t->Cin, t->Cin);
+    launch_branches_dma<0>(BT128{}, p, tab, 0, 0, nullptr, 0, M, t->Cout, 0, 1, 0, nullptr, epi, stream);
+    return iseg_check_launch("iseg_conv2d_branches_fwd");
+}
+
+extern "C" int iseg_conv2d_branches_bwd_data(const iseg_conv_branches* t, void* dx, const void* residual, int64_t ldr, int dtype, void* ws,
+                                             size_t ws_bytes, hipStream_t stream) {
+    BRANCHES_COMMON("iseg_conv2d_branches_bwd_data");
+    ISEG_REQUIRE(dx && ((uintptr_t)dx & 15) == 0, "iseg_conv2d_branches_bwd_data: dx must be a 16-byte aligned device pointer");
+    ISEG_REQUIRE(!residual || (((uintptr_t)residual & 15) == 0 && ldr % 8 == 0 && ldr >= t->Cin),
+                 "iseg_conv2d_branches_bwd_data: the residual must be 16-byte aligned with ldr %% 8 == 0");
+    BranchTable tab{};
+    tab.count = t->count;
+    int64_t K = 0;
+    for (int i = 0; i < t->count; ++i) {
+        const iseg_conv_branch& b = t->b[i];
+        ISEG_REQUIRE(b.dy && b.w, "iseg_conv2d_branches_bwd_data: branch %d: null operand", i);
+        ISEG_REQUIRE((((uintptr_t)b.dy | (uintptr_t)b.w) & 15) == 0 && b.lddy % 8 == 0 && b.lddy >= t->Cout && b.lddy < (1ll << 31),
+                     "iseg_conv2d_branches_bwd_data: branch %d: operands must be 16-byte aligned, lddy %% 8 == 0", i);
+        K += (int64_t)b.KH * b.KW * t->Cout;
+        BranchP& d = tab.b[i];
+        d.src = (const bf16_t*)b.dy;
+        d.Cs = (int)b.lddy;
+        d.B = (const bf16_t*)b.w;
+        d.K = (int)K;
+        d.kw = b.KW, d.dh = b.dh, d.dw = b.dw, d.pt = b.pt, d.pl = b.pl;
+    }
+    const int64_t N = t->Cin;
+    const DgradPlan plan = branches_dgrad_plan(M, N, K);
+    int64_t kps = K;
+    float* slabs = nullptr;
+    if (plan.nsplit > 1) {
+        const iseg_conv_geom joined = branches_joined_geom(t);
+        const size_t need = iseg_conv2d_igemm_workspace_bytes(&joined, 1);
+        ISEG_REQUIRE_WORKSPACE(ws && ws_bytes >= need, "iseg_conv2d_branches_bwd_data: split-K needs %zu workspace bytes, got %zu", need, ws_bytes);
+        slabs = (float*)ws;
+        kps = ceil_div64(ceil_div64(K, plan.nsplit), 64) * 64;
+    }
+    const int eff = (int)ceil_div64(K, kps);
+    Epi epi{};
+    epi.alpha = 1.f;
+    epi.batch_inner = 1;
+    epi.residual = residual;
+    epi.ldr = ldr;
+    const ConvP p = branches_shared(t, nullptr, 0, t->Cout);
+    const int64_t tap_stride = (int64_t)t->Cin * t->Cout;
+    if (plan.big) launch_branches_dma<1>(BT256{}, p, tab, t->Cout, tap_stride, (bf16_t*)dx, N, M, N, K, eff, kps, slabs, epi, stream);
+    else launch_branches_dma<1>(BT128{}, p, tab, t->Cout, tap_stride, (bf16_t*)dx, N, M, N, K, eff, kps, slabs, epi, stream);
+    if (!slabs) return iseg_check_launch("iseg_conv2d_branches_bwd_data");
+    iseg_gemm_args ga{};
+    ga.M = M;
+    ga.N = N;
+    ga.K = K;
+    ga.D = dx;
+    ga.ldd = N;
+    ga.in_dtype = ISEG_BF16;
+    ga.out_dtype = ISEG_BF16;
+    ga.alpha = 1.f;
+    ga.residual = residual;
+    ga.ldr = ldr;
+    return gemm_reduce(&ga, epi, slabs, eff, M, stream);
+}
+
+extern "C" int iseg_conv2d_branches_bwd_weight(const void* x, const iseg_conv_branches* t, int accumulate, int dtype, void* ws, size_t ws_bytes,
+                                               hipStream_t stream) {
+    BRANCHES_COMMON("iseg_conv2d_branches_bwd_weight");
+    (void)ws;
+    (void)ws_bytes;
+    ISEG_REQUIRE(x && ((uintptr_t)x & 15) == 0, "iseg_conv2d_branches_bwd_weight: x must be a 16-byte aligned device pointer");
+    BranchTable tab{};
+    tab.count = t->count;
+    int maxK = 0;
+    for (int i = 0; i < t->count; ++i) {
+        const iseg_conv_branch& b = t->b[i];
+        ISEG_REQUIRE(b.dy && b.gw, "iseg_conv2d_branches_bwd_weight: branch %d: null operand", i);
+        ISEG_REQUIRE((((uintptr_t)b.dy | (uintptr_t)b.gw) & 15) == 0 && b.lddy % 8 == 0 && b.lddy >= t->Cout,
+                     "iseg_conv2d_branches_bwd_weight: branch %d: operands must be 16-byte aligned, lddy %% 8 == 0", i);
+        BranchP& d = tab.b[i];
+        d.B = (const bf16_t*)b.dy;
+        d.ldb = b.lddy;
+        d.D = b.gw;
+        d.ldd = t->Cout;
+        d.K = b.KH * b.KW * t->Cin;
+        d.kw = b.KW, d.dh = b.dh, d.dw = b.dw, d.pt = b.pt, d.pl = b.pl;
+        if (d.K > maxK) maxK = d.K;
+    }
+    Epi epi{};
+    epi.alpha = 1.f;
+    epi.accumulate = accumulate;
+    epi.batch_inner = 1;
+    const ConvP p = branches_shared(t, x, t->Cin, t->Cin);
+    const int64_t N = t->Cout;
+    auto launch = [&](auto tile) {
+        constexpr int WM = decltype(tile)::WM, WN = decltype(tile)::WN, FM = decltype(tile)::FM, FN = decltype(tile)::FN;
+        constexpr int BM = WM * FM * 16, BN = WN * FN * 16;
+        const int tiles_m = (int)ceil_div64(maxK, BM), tiles_n = (int)ceil_div64(N, BN);
+        hipLaunchKernelGGL((conv_branches_wgrad_kernel<WM, WN, FM, FN, 64>), dim3(tiles_m * tiles_n, 1, tab.count), dim3(WM * WN * 64), 0, stream, p, tab,
+                           N, M, tiles_n, tiles_m * tiles_n, epi, 1);
+    };
+    struct T128 { enum { WM = 2, WN = 4, FM = 4, FN = 2 }; };
+    struct T64 { enum { WM = 4, WN = 2, FM = 2, FN = 2 }; };
+    if (N <= 64) launch(T64{});
+    else launch(T128{});
+    return iseg_check_launch("iseg_conv2d_branches_bwd_weight");
 }

@@ -10,6 +10,12 @@
 // The register-staged gather of conv_igemm.hip spends its issue slots on address arithmetic, two LDS writes per chunk and the staging
 // registers; here the address of a piece is ~10 VALU per K-step and the data never touches a register.  The ASPP 3x3 convolutions of the
 // flagship (16 x 16 x 16 x 768 -> 256, K = 6912, 8 K-splits) ran 47.5 / 67.3 us (forward / data gradient): see DESIGN 5 for what this form gives.
+//
+// Several convolutions of ONE input (ASPP's pixel-level branches: same map, stride 1, "same" padding, their own kernel size and dilation) run
+// through the same tile body from a BranchTable (conv_branches_dma_kernel):
+//   pass 0  blockIdx.z = branch; a branch brings its own taps, K-contiguous kernel copy, reduction length and output
+//   pass 1  ONE product: the gradient of the shared input is a sum over branches, i.e. a longer reduction over (branch, tap, 64 channels of that
+//           branch's dy).  The branch of a K-step is uniform; its dilation / padding / dy / kernel are switched when the reduction crosses into it.
 #pragma once
 #include "gemm_dma.h"
 
@@ -17,13 +23,16 @@ namespace {
 
 __device__ uint4 conv_zero_page[8];      // 128 zero bytes (device globals are zero-initialised): one swizzled stage row of a halo tap
 
-template <int WM, int WN, int NS, int PASS, class TO>
-__global__ __launch_bounds__(WM* WN * 64) void conv_igemm_dma_kernel(ConvP p, const bf16_t* __restrict__ Bop, int64_t ldb, int64_t tap_stride,
-                                                                      TO* __restrict__ D, int64_t ldd, int64_t M, int64_t N, int64_t K,
-                                                                      int tiles_n, int ntiles, int64_t k_per_split, float* __restrict__ slabs,
-                                                                      Epi epi) {
+// Tab = NoBranches: one convolution, described by the arguments.  Tab = BranchTable (pass 1): the K-joined data gradient; p.pt = p.pl = 0 and
+// Bop is unused, every branch's padding / dilation / taps / dy / kernel come from the table, whose K fields are the END of a branch's K range.
+template <int WM, int WN, int NS, int PASS, class TO, class Tab, int FN = 4>
+__device__ __forceinline__ void conv_igemm_dma_tile(ConvP p, const bf16_t* __restrict__ Bop, int64_t ldb, int64_t tap_stride, TO* __restrict__ D,
+                                                    int64_t ldd, int64_t M, int64_t N, int64_t K, int tiles_n, int ntiles, int64_t k_per_split,
+                                                    float* __restrict__ slabs, const Epi& epi, const Tab& tab) {
     using namespace iseg_mm;
-    constexpr int FN = 4;
+    constexpr bool JOINED = std::is_same<Tab, BranchTable>::value;
+    static_assert(!JOINED || PASS == 1, "only the data gradient joins its branches along K");
+    static_assert(FN == 2 || FN == 4, "a wavefront's tile is 64 rows by 32 or 64 columns");
     constexpr int NW = WM * WN;
     constexpr int BM = WM * 64, BN = WN * FN * 16;
     constexpr int PIECES = (BM + BN) / 8, PPW = PIECES / NW;
@@ -70,8 +79,28 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_dma_kernel(ConvP p, co
             a2[q] = row * ldb;
         }
     }
+    // the branch the reduction is in (uniform; issue() walks K upwards, so a branch is entered at most once per workgroup)
+    int bi = 0;
+    int64_t bk0 = 0, bk1 = K;
+    auto enter = [&](int64_t k0) {
+        if constexpr (JOINED) {
+            while (bi + 1 < tab.count && k0 >= tab.b[bi].K) ++bi;
+            const BranchP& br = tab.b[bi];
+            bk0 = bi ? tab.b[bi - 1].K : 0;
+            bk1 = br.K;
+            p.src = br.src, p.Cs = br.Cs, p.kw = br.kw, p.dh = br.dh, p.dw = br.dw, p.pt = br.pt, p.pl = br.pl;
+            Bop = br.B;
+        }
+    };
+    enter(kbeg);
     auto issue = [&](int stage, int kt) {
-        const int64_t k0 = kbeg + (int64_t)kt * 64;
+        int64_t k0 = kbeg + (int64_t)kt * 64;
+        int pt = 0, pl = 0;      // (pass 1, one convolution: already part of a0 / a1)
+        if constexpr (JOINED) {
+            if (k0 >= bk1) enter(k0);
+            k0 -= bk0;
+            pt = p.pt, pl = p.pl;
+        }
         const int tap = (int)(k0 / p.Cg), c0 = (int)(k0 % p.Cg);      // (uniform)
         const int ti = tap / p.kw, tj = tap % p.kw;
 #pragma unroll
@@ -87,7 +116,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_dma_kernel(ConvP p, co
                     iw = a1[q] + tj * p.dw;
                     ok = (unsigned)ih < (unsigned)p.Hs && (unsigned)iw < (unsigned)p.Ws;
                 } else {
-                    const int th = a0[q] - ti * p.dh, tw = a1[q] - tj * p.dw;
+                    const int th = a0[q] + pt - ti * p.dh, tw = a1[q] + pl - tj * p.dw;
                     ih = th / p.sh;
                     iw = tw / p.sw;
                     ok = th >= 0 && tw >= 0 && ih * p.sh == th && iw * p.sw == tw && ih < p.Hs && iw < p.Ws;
@@ -188,6 +217,32 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_dma_kernel(ConvP p, co
                 }
             }
         }
+    }
+}
+
+template <int WM, int WN, int NS, int PASS, class TO>
+__global__ __launch_bounds__(WM* WN * 64) void conv_igemm_dma_kernel(ConvP p, const bf16_t* __restrict__ Bop, int64_t ldb, int64_t tap_stride,
+                                                                      TO* __restrict__ D, int64_t ldd, int64_t M, int64_t N, int64_t K,
+                                                                      int tiles_n, int ntiles, int64_t k_per_split, float* __restrict__ slabs,
+                                                                      Epi epi) {
+    conv_igemm_dma_tile<WM, WN, NS, PASS, TO>(p, Bop, ldb, tap_stride, D, ldd, M, N, K, tiles_n, ntiles, k_per_split, slabs, epi, NoBranches{});
+}
+
+// Several convolutions of one input.  p holds what the branches share (maps, channel counts, stride 1); D / ldd / K / slabs are pass 1's.
+template <int WM, int WN, int FN, int NS, int PASS>
+__global__ __launch_bounds__(WM* WN * 64) void conv_branches_dma_kernel(ConvP p, BranchTable tab, int64_t ldb, int64_t tap_stride,
+                                                                         bf16_t* __restrict__ D, int64_t ldd, int64_t M, int64_t N, int64_t K,
+                                                                         int tiles_n, int ntiles, int64_t k_per_split, float* __restrict__ slabs,
+                                                                         Epi epi) {
+    if constexpr (PASS == 0) {
+        const BranchP& br = tab.b[blockIdx.z];
+        p.kw = br.kw, p.dh = br.dh, p.dw = br.dw, p.pt = br.pt, p.pl = br.pl;
+        epi.bias = br.bias;
+        conv_igemm_dma_tile<WM, WN, NS, 0, bf16_t, NoBranches, FN>(p, br.B, br.ldb, 0, (bf16_t*)br.D, br.ldd, M, N, br.K, tiles_n, ntiles, br.K,
+                                                                   nullptr, epi, NoBranches{});
+    } else {
+        conv_igemm_dma_tile<WM, WN, NS, 1, bf16_t, BranchTable, FN>(p, nullptr, ldb, tap_stride, D, ldd, M, N, K, tiles_n, ntiles, k_per_split, slabs,
+                                                                    epi, tab);
     }
 }
 

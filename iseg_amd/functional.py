@@ -493,6 +493,72 @@ def conv2d(x, W, b=None, strides=(1, 1), dilation=(1, 1), padding="same", groups
 
 
 # ---------------------------------------------------------------------------------------------------------
+# Several Conv2D of ONE input (ASPP's pixel-level branches): stride 1, "same" padding, one group, no bias, the same filter count
+# ---------------------------------------------------------------------------------------------------------
+def _branch_taps(Ws, dilations):
+    return [(W.shape[0], W.shape[1], d[0], d[1]) for W, d in zip(Ws, dilations)]
+
+
+def conv2d_branches_supported(x, Ws, dilations):
+    """one launch per pass can take these convolutions of x (csrc/conv_igemm.hip iseg_conv2d_branches_*): bf16 storage, kernels
+    [kh,kw,Cin,Cout] of one Cin / Cout, both multiples of 64, at most K.CONV_MAX_BRANCHES of them"""
+    from . import _hip
+
+    cdt = nn.compute_dtype()
+    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.dtype == cdt and 1 <= len(Ws) <= _hip.CONV_MAX_BRANCHES):
+        return False
+    N, H, Wd, Cin = x.shape
+    Cout = Ws[0].shape[3]
+    if any(W is None or W.dim() != 4 or W.shape[2] != Cin or W.shape[3] != Cout for W in Ws):
+        return False
+    if not K.conv2d_branches_supported(K.conv_branches(N, H, Wd, Cin, Cout, _branch_taps(Ws, dilations)), cdt):
+        return False
+    return all(nn.wt(W, (W.shape[0] * W.shape[1] * Cin, Cout)) is not None for W in Ws)
+
+
+class _Conv2dBranchesFn(Function):
+    """y_b = conv(x, W_b) for every branch in one grouped launch; backward: one grouped weight-gradient launch and ONE data-gradient product
+    whose reduction runs over (branch, tap, channel) -- the branch gradients of x are summed in fp32 and rounded once, no axpby"""
+
+    @staticmethod
+    def forward(ctx, x, dilations, *Ws):
+        N, H, Wd, Cin = x.shape
+        Cout = Ws[0].shape[3]
+        xc = _c(x)
+        ctx.taps = _branch_taps(Ws, dilations)
+        table = K.conv_branches(N, H, Wd, Cin, Cout, ctx.taps)
+        ys = K.conv2d_branches_fwd(xc, [nn.wt(W, (W.shape[0] * W.shape[1] * Cin, Cout)) for W in Ws], table)
+        ctx.Ws = Ws
+        ctx.save_for_backward(xc)
+        return tuple(ys)
+
+    @staticmethod
+    def backward(ctx, *dys):
+        (xc,) = ctx.saved_tensors
+        Ws = ctx.Ws
+        N, H, Wd, Cin = xc.shape
+        Cout = Ws[0].shape[3]
+        rows = [_rows2d(dy) for dy in dys]
+        dy2, ld = [r[0] for r in rows], [r[1] for r in rows]
+        live = [i for i, W in enumerate(Ws) if W.requires_grad]
+        if live:
+            table = K.conv_branches(N, H, Wd, Cin, Cout, [ctx.taps[i] for i in live])
+            K.conv2d_branches_bwd_weight(xc, [dy2[i] for i in live], [ld[i] for i in live], [_grad(Ws[i]) for i in live], table, accumulate=True)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = K.conv2d_branches_bwd_data(dy2, ld, [nn.w(W) for W in Ws], K.conv_branches(N, H, Wd, Cin, Cout, ctx.taps))
+        for W in Ws:
+            dist.grads_ready(W, None)
+        return (dx, None) + (None,) * len(Ws)
+
+
+def conv2d_branches(x, Ws, dilations):
+    """[conv2d(x, W, dilation=d, padding="same") for W, d in zip(Ws, dilations)] as ONE tape node (conv2d_branches_supported(...) must hold)"""
+    _check_act_dtype(x)
+    return list(_Conv2dBranchesFn.apply(x, tuple(tuple(d) for d in dilations), *Ws))
+
+
+# ---------------------------------------------------------------------------------------------------------
 # DepthwiseConv2D, stride 1;  kernel [K,K,C,1]
 # ---------------------------------------------------------------------------------------------------------
 class _DWConvFn(Function):

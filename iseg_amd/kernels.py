@@ -896,6 +896,59 @@ def conv2d_igemm_bwd_weight(x, dy, dw, geom, accumulate=True):
     return dw
 
 
+# ---- several convolutions of one input (csrc/conv_igemm.hip: grouped forward / weight gradient, K-joined data gradient) ----
+def conv_branches(N, H, W, Cin, Cout, taps):
+    """branch table for `taps` = [(KH, KW, dh, dw), ...] of a [N,H,W,Cin] -> Cout convolution family (stride 1, "same" padding); the operand
+    pointers are filled in by the three passes below"""
+    t = _hip.ConvBranches(N, H, W, Cin, Cout, len(taps))
+    for b, (kh, kw, dh, dw) in zip(t.b, taps[:_hip.CONV_MAX_BRANCHES]):
+        b.KH, b.KW, b.dh, b.dw = kh, kw, dh, dw
+        b.pt, b.pl = same_pad(H, kh, 1, dh)[1], same_pad(W, kw, 1, dw)[1]
+    return t
+
+
+def conv2d_branches_supported(table, dtype):
+    return dtype in _DT and bool(_hip.lib().iseg_conv2d_branches_supported(C.byref(table), _DT[dtype]))
+
+
+def conv_branches_joined_geom(table):
+    """the K-joined data gradient as ONE stride-1 data gradient whose taps are the taps of every branch in a row: the geometry that sizes its
+    workspace (iseg_conv2d_igemm_workspace_bytes, pass 1)"""
+    taps = sum(b.KH * b.KW for b in table.b[:table.count])
+    return conv_geom(table.N, table.H, table.W, table.Cin, table.Cout, 1, taps, 1, 1, 1, 1, 0, 0, table.H, table.W, 1)
+
+
+def conv2d_branches_fwd(x, wts, table, biases=None):
+    """x [N,H,W,Cin], wts[b] = the K-contiguous kernel copy [Cout, KH*KW*Cin] (nn.wt) -> one [N,H,W,Cout] per branch, ONE launch"""
+    _require_cuda(x, *wts)
+    ys = [torch.empty((table.N, table.H, table.W, table.Cout), dtype=x.dtype, device=x.device) for _ in wts]
+    for i, (b, wt, y) in enumerate(zip(table.b, wts, ys)):
+        b.wt, b.y, b.ldy, b.y_col = ptr(wt), ptr(y), table.Cout, 0
+        b.bias = ptr(biases[i]) if biases is not None else None
+    _hip.call("iseg_conv2d_branches_fwd", ptr(x), C.byref(table), dt(x), None, 0, stream())
+    return ys
+
+
+def conv2d_branches_bwd_data(dys, lddys, ws_, table, residual=None):
+    """dx [N,H,W,Cin] = sum over branches of conv^T(dy_b, w_b) (+ residual) as one product; dys[b] = rows of lddys[b] elements, ws_[b] = Keras kernel"""
+    _require_cuda(*dys, *ws_)
+    dx = torch.empty((table.N, table.H, table.W, table.Cin), dtype=dys[0].dtype, device=dys[0].device)
+    for b, dy, ld, w in zip(table.b, dys, lddys, ws_):
+        b.dy, b.lddy, b.w = ptr(dy), ld, ptr(w)
+    ws, wsb = _conv_ws(conv_branches_joined_geom(table), 1, dx.device)
+    _hip.call("iseg_conv2d_branches_bwd_data", C.byref(table), ptr(dx), ptr(residual), table.Cin, dt(dx), ptr(ws), wsb, stream())
+    return dx
+
+
+def conv2d_branches_bwd_weight(x, dys, lddys, gws, table, accumulate=True):
+    """gws[b] [KH,KW,Cin,Cout] fp32 (+)= per-tap x^T dy_b, every branch in ONE launch"""
+    _require_cuda(x, *dys, *gws)
+    for b, dy, ld, gw in zip(table.b, dys, lddys, gws):
+        b.dy, b.lddy, b.gw = ptr(dy), ld, ptr(gw)
+    _hip.call("iseg_conv2d_branches_bwd_weight", ptr(x), C.byref(table), int(accumulate), dt(x), None, 0, stream())
+    return gws
+
+
 def colsum(x, ldx, batch_stride, batch, rows, Cc, out, scale=1.0, accumulate=False):
     if Cc > 8192 and batch == 1 and scale == 1.0:
         # few rows, very wide (token-axis sums, score gradients): the LDS-staged kernel would need C floats of LDS per workgroup

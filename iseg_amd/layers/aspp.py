@@ -31,11 +31,39 @@ class AtrousSpatialPyramidPooling(Layer):
     def call(self, inputs, training=None):
         if self._can_group(training):
             return self._call_grouped(inputs)
+        pixel = self._pixel_blocks()
+        if self._convs_as_one_node(inputs, pixel):
+            # the fork over the shared input: the image-level branch and ONE node for every pixel-level convolution
+            xs = list(F.fork(inputs, int(self.use_image_level) + 1))
+            outs = [self.image_level_block(xs[0], training=training)] if self.use_image_level else []
+            pre = self._pixel_convs(xs[-1], pixel)
+            return F.concat(outs + [b.norm_act(y, training=training) for b, y in zip(pixel, pre)])
         branches = int(self.use_image_level) + int(self.use_pixel_level) + len(self.asp_convs)
         xs = list(F.fork(inputs, branches))      # one alias per branch: the branch gradients are summed by our own kernel
         blocks = ([self.image_level_block] if self.use_image_level else []) + ([self.pixel_level_block] if self.use_pixel_level else []) + \
             list(self.asp_convs)
         return F.concat([b(x, training=training) for b, x in zip(blocks, xs)])
+
+    # ---- the pixel-level 1x1 and the dilated 3x3 convolutions read the same map: one grouped launch per pass (F.conv2d_branches) ----------
+    def _pixel_blocks(self):
+        return ([self.pixel_level_block] if self.use_pixel_level else []) + list(self.asp_convs)
+
+    def _convs_as_one_node(self, inputs, blocks):
+        from .. import nn
+        from .base_layers import Conv2D
+
+        if nn.dry_run() or len(blocks) < 2:
+            return False
+        for b in blocks:
+            c = b.conv
+            if not (isinstance(c, Conv2D) and c.built and c.bias is None and c.activation is None and c.groups == 1 and
+                    tuple(c.strides) == (1, 1) and c.padding == "same"):
+                return False
+        return F.conv2d_branches_supported(inputs, [b.conv.kernel for b in blocks], [b.conv.dilation_rate for b in blocks])
+
+    @staticmethod
+    def _pixel_convs(x, blocks):
+        return F.conv2d_branches(x, [b.conv.kernel for b in blocks], [b.conv.dilation_rate for b in blocks])
 
     # ---- data-parallel training: the branches' SyncBN statistics share one all-reduce (and one in backward) -----------------------
     def _branch_blocks(self):
@@ -61,14 +89,20 @@ class AtrousSpatialPyramidPooling(Layer):
     def _call_grouped(self, inputs):
         """conv of every branch first, then ONE statistics exchange for the five BatchNormalizations (F.batch_norm_group)"""
         blocks = self._branch_blocks()
-        xs = list(F.fork(inputs, len(blocks)))
         h, w = inputs.shape[1], inputs.shape[2]
-        pre = []
-        for i, b in enumerate(blocks):
-            x = xs[i]
-            if self.use_image_level and i == 0:
-                x = F.global_avg_pool(x)
-            pre.append(b.conv(x))
+        pixel = self._pixel_blocks()
+        if self._convs_as_one_node(inputs, pixel):
+            xs = list(F.fork(inputs, int(self.use_image_level) + 1))
+            pre = [blocks[0].conv(F.global_avg_pool(xs[0]))] if self.use_image_level else []
+            pre += self._pixel_convs(xs[-1], pixel)
+        else:
+            xs = list(F.fork(inputs, len(blocks)))
+            pre = []
+            for i, b in enumerate(blocks):
+                x = xs[i]
+                if self.use_image_level and i == 0:
+                    x = F.global_avg_pool(x)
+                pre.append(b.conv(x))
         outs = list(F.batch_norm_group(pre, [b.bn for b in blocks], relu=True))
         if self.use_image_level:
             outs[0] = F.broadcast_hw(outs[0], h, w)

@@ -33,7 +33,10 @@ class ConvNormAct(Layer):
             self.dropout = Dropout(dropout_rate, name=f"{self.name}/dropout")
 
     def call(self, inputs, training=None):
-        x = self.conv(inputs)
+        return self.norm_act(self.conv(inputs), training=training)
+
+    def norm_act(self, x, training=None):
+        """everything behind the convolution (a caller that ran self.conv's product itself, grouped with others, continues here)"""
         should_dropout = (self.dropout is not None) and self.trainable
         if should_dropout and self.dropout_before_bn:
             x = self.dropout(x, training=training)
