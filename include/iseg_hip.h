@@ -833,6 +833,33 @@ int iseg_attention_bwd(const void* qkv, const void* out, const void* dout, const
                        int heads, int head_dim, float scale, int dtype, void* ws, size_t ws_bytes, iseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Attention core of the single-head non-local block, layers/self_attention.py:65-93 (between the 1x1 projections and the feature
+ * dropout) with get_attention of utils/attention_utils.py:23-40: out[b] = softmax(scale * q[b] k[b]^T) v[b] for a 64-wide query /
+ * key and a wide value.  q, k [batch, T, dk]; v, out, dout [batch, T, dv]; every operand has its own row pitch in elements (ld*),
+ * the sample stride is T * pitch -- column ranges of one packed projection output or separate tensors; q and k may be the same
+ * pointer (shared_querykey).  Online softmax over key tiles of 64, one wavefront per (sample, 64-query tile, 64-column value slab):
+ * no T x T tensor in HBM.  Supported (iseg_self_attention_supported): bf16, dk == 64, dv % 64 == 0, 64 <= dv <= 1024; any T >= 1;
+ * pitches that are multiples of 8 elements and cover their rows, 16-byte aligned bases, scale > 0.  Anything else returns
+ * ISEG_ERR_UNSUPPORTED before any memory is touched.
+ * layers/self_attention.py:65-93, utils/attention_utils.py:23-40 -- forward: lse2 NULL for inference; for training it receives, per
+ * (sample, token) and padded to a multiple of 64 tokens (iseg_self_attention_lse_elems floats, zeros in the padding), log2 of the
+ * softmax denominator in the kernel's exp2 domain. */
+int iseg_self_attention_supported(int dk, int dv, int dtype);
+/* layers/self_attention.py:65-93, utils/attention_utils.py:23-40 -- floats in lse2, and in the dsum vector of the backward call */
+size_t iseg_self_attention_lse_elems(int64_t batch, int T);
+int iseg_self_attention_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* out, int64_t ldo,
+                            float* lse2, int64_t batch, int T, int dk, int dv, float scale, int dtype, iseg_stream_t stream);
+/* layers/self_attention.py:65-93, utils/attention_utils.py:23-40 -- gradient of the same lines: the probabilities are recomputed from
+ * q, k and lse2, tile by tile (dV per (key tile, value slab), dQ per query tile, dK per key tile: no atomics, fixed summation order, a
+ * second run is bit-identical).  dsum is caller-owned scratch of iseg_self_attention_lse_elems floats (overwritten: row dots of
+ * dout and out over all dv columns).  dq, dk, dv are overwritten; dq and dk are always separate buffers -- when q and k alias, the
+ * caller adds the two. */
+int iseg_self_attention_bwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const void* out,
+                            int64_t ldo, const void* dout, int64_t lddo, const float* lse2, float* dsum, void* dq, int64_t lddq, void* dk,
+                            int64_t lddk, void* dv, int64_t lddv, int64_t batch, int T, int dk_dim, int dv_dim, float scale, int dtype,
+                            iseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * On-device input pipeline: data_process/pipeline.py:85-170 (StandardAugmentationsPipeline, training branch) + data_process/input_norm.py:7-80
  * as one gather per output pixel -- random scale (bilinear image / nearest label, utils.py:303-370), bottom / right pad with the mean
  * pixel / ignore label (augments/pad_augment.py), random crop, random flip, random erasing with noise (augments/random_erasing_augment.py)

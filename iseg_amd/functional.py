@@ -2442,6 +2442,67 @@ def attention_packed(qkv, heads, Cq, Cv, scale, *, bias_table=None, bias_index=N
                               rate, next_seed() if rate > 0 else 0, int(bias_window))
 
 
+class _SelfAttentionFn(Function):
+    """single-head attention with a 64-wide query / key and a wide value, bf16, no dropout (layers/self_attention.py:76-85): online-softmax
+    forward per value slab that keeps one log-sum-exp float per row, backward kernels that recompute the probabilities (csrc/selfattn.hip);
+    no T x T tensor.  q and k may be aliases of one tensor (shared_querykey): the kernels then read one buffer and dq, dk still arrive apart."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, scale):
+        out, lse = K.self_attention_fwd(q, k, v, scale, True)
+        ctx.scale = scale
+        ctx.save_for_backward(q, k, v, out, lse)
+        return out
+
+    @staticmethod
+    def backward(ctx, dO):
+        q, k, v, out, lse = ctx.saved_tensors
+        dq, dk, dv = K.self_attention_bwd(q, k, v, out, dO, lse, ctx.scale)
+        return dq, dk, dv, None
+
+
+_SELFATTN_TRAIN_SHARE = 0.25      # of the device's memory: beyond it the composed route's probabilities and their gradient give way
+_DEVICE_BYTES = {}
+
+
+def _self_attention_route(B, T, device, training):
+    """True: the fused kernels.  ISEG_SELFATTN_FUSED=0: composed, =1: fused, unset: fused for inference (not slower, nothing of size T x T);
+    for training the composed route, which is faster while its tensors fit (EXPERIMENTS.md 'SelfAttention core': 3.2 ms against 6.0 ms at
+    16 x 4096, dv 512) -- until its [B, T, T] probabilities and their gradient together pass a quarter of the device's memory"""
+    mode = os.environ.get("ISEG_SELFATTN_FUSED", "")
+    if mode in ("0", "1"):
+        return mode == "1"
+    if not training:
+        return True
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    total = _DEVICE_BYTES.get(idx)
+    if total is None:
+        total = _DEVICE_BYTES[idx] = torch.cuda.get_device_properties(idx).total_memory
+    return 2 * (B * T * T * 2) > _SELFATTN_TRAIN_SHARE * total
+
+
+def self_attention_core(q, k, v, scale, *, dropout_rate=0.0, training=False):
+    """softmax(scale * q k^T) v with dropout on the probabilities: q, k [B, T, dk], v [B, T, dv] -> [B, T, dv]
+    (layers/self_attention.py:76-85, get_attention of utils/attention_utils.py:23-40: a plain softmax, no clip).
+    bf16 with dk 64, dv a multiple of 64 up to 1024 and no dropout in effect can run on the fused kernels of csrc/selfattn.hip, and does
+    where _self_attention_route says so (inference; training past a memory share; ISEG_SELFATTN_FUSED=1: always, =0: composed); everything
+    else is concatenated and takes attention_packed's materialised route."""
+    _check_act_dtype(v)
+    if q.dim() != 3 or q.shape != k.shape or v.dim() != 3 or v.shape[:2] != q.shape[:2]:
+        raise ValueError(f"self_attention_core: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} are not [B,T,dk], [B,T,dk], [B,T,dv]")
+    if nn.dry_run():
+        return _dry(v.shape, v)
+    rate = float(dropout_rate) if training else 0.0
+    dk, dv = int(q.shape[2]), int(v.shape[2])
+    need_grad = torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad)
+    if (rate <= 0 and scale > 0 and q.dtype == k.dtype == v.dtype and K.self_attention_supported(dk, dv, v.dtype)
+            and _self_attention_route(int(q.shape[0]), int(q.shape[1]), v.device, need_grad)):
+        if not need_grad:
+            return K.self_attention_fwd(q, k, v, float(scale), False)[0]
+        return _SelfAttentionFn.apply(q, k, v, float(scale))
+    return attention_packed(concat([q, k, v]), 1, dk, dv, float(scale), dropout_rate=dropout_rate, training=training)
+
+
 class _Dcnv2SampleFn(Function):
     """DCNv2's modulated deformable sampling (layers/dcn_v2.py:114-229): x [N,H,W,C], offset [N,H,W,27] -> [N,H,W,9 C]"""
 

@@ -1882,6 +1882,53 @@ def attention_bwd(qkv, out, dout, lse, heads, scale):
     return dqkv
 
 
+# ---------------------------------------------------------------------------------------------------------
+# single-head attention with a 64-wide key and a wide value (csrc/selfattn.hip)
+# ---------------------------------------------------------------------------------------------------------
+def self_attention_supported(dk, dv, dtype):
+    return dtype == torch.bfloat16 and bool(_hip.lib().iseg_self_attention_supported(int(dk), int(dv), BF16))
+
+
+def _pitched(t):
+    """[B, T, C] as (tensor, row pitch in elements) without a copy when its rows are equally spaced across samples (a column range of a
+    packed projection output), the pitch is a multiple of 8 elements and the base 16-byte aligned; else through a contiguous copy"""
+    B, T, C = t.shape
+    ld = t.stride(1)
+    if t.stride(2) == 1 and ld >= C and ld % 8 == 0 and (B == 1 or t.stride(0) == T * ld) and t.data_ptr() % 16 == 0:
+        return t, ld
+    return t.contiguous(), C
+
+
+def self_attention_fwd(q, k, v, scale, want_lse):
+    """softmax(scale * q k^T) v for q, k [B, T, 64], v [B, T, dv]; want_lse: also the per-row log2-sum-exp vector of the backward kernels"""
+    _require_cuda(q, k, v)
+    B, T, dk = q.shape
+    dv = v.shape[2]
+    L = _hip.lib()
+    (q, ldq), (k, ldk), (v, ldv) = _pitched(q), _pitched(k), _pitched(v)
+    out = torch.empty((B, T, dv), dtype=v.dtype, device=v.device)
+    lse = torch.empty(int(L.iseg_self_attention_lse_elems(B, T)), dtype=torch.float32, device=v.device) if want_lse else None
+    _hip.check(L.iseg_self_attention_fwd(ptr(q), ldq, ptr(k), ldk, ptr(v), ldv, ptr(out), dv, ptr(lse), B, T, dk, dv, float(scale), dt(v),
+                                         stream()), "iseg_self_attention_fwd")
+    return out, lse
+
+
+def self_attention_bwd(q, k, v, out, dout, lse, scale):
+    """(dq, dk, dv) of self_attention_fwd; dq and dk are separate tensors also when q and k alias"""
+    _require_cuda(q, k, v, out, dout, lse)
+    B, T, dk = q.shape
+    dv = v.shape[2]
+    L = _hip.lib()
+    (q, ldq), (k, ldk), (v, ldv), (out, ldo), (dout, lddo) = _pitched(q), _pitched(k), _pitched(v), _pitched(out), _pitched(dout)
+    dq = torch.empty((B, T, dk), dtype=q.dtype, device=q.device)
+    dkk = torch.empty((B, T, dk), dtype=q.dtype, device=q.device)
+    dvv = torch.empty((B, T, dv), dtype=v.dtype, device=v.device)
+    dsum = torch.empty(int(L.iseg_self_attention_lse_elems(B, T)), dtype=torch.float32, device=v.device)
+    _hip.check(L.iseg_self_attention_bwd(ptr(q), ldq, ptr(k), ldk, ptr(v), ldv, ptr(out), ldo, ptr(dout), lddo, ptr(lse), ptr(dsum), ptr(dq), dk,
+                                         ptr(dkk), dk, ptr(dvv), dv, B, T, dk, dv, float(scale), dt(v), stream()), "iseg_self_attention_bwd")
+    return dq, dkk, dvv
+
+
 def window_attention_supported(T, head_dim, dtype):
     return dtype == torch.bfloat16 and bool(_hip.lib().iseg_window_attention_supported(int(T), int(head_dim), BF16))
 
