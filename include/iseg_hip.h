@@ -930,7 +930,8 @@ int iseg_upsample_ce(const void* z, int dtype, const int32_t* labels, const floa
  *   fwd         y = conv(x, w) (+ bias)
  *   bwd_data    dx = conv^T(dy, w)          gather form, deterministic
  *   bwd_weight  dw (+)= x^T * dy per tap    fp32 [KH,KW,Cin/groups,Cout], fixed-order split-K slabs
- * Workspace (split-K slabs): iseg_conv2d_igemm_workspace_bytes(geom, pass) with pass 0 fwd, 1 bwd_data, 2 bwd_weight.
+ * Workspace (split-K slabs): iseg_conv2d_igemm_workspace_bytes(geom, pass) with pass 0 fwd, 1 bwd_data, 2 bwd_weight,
+ * 3 = iseg_conv2d_patch_bwd_weight (below).
  * --------------------------------------------------------------------------------------------------------- */
 typedef struct iseg_conv_geom {
     int N, H, W, Cin, Cout, KH, KW, sh, sw, dh, dw, pt, pl, Ho, Wo, groups;
@@ -949,6 +950,26 @@ int iseg_conv2d_igemm_bwd_data(const void* dy, const void* w, void* dx, const is
                                iseg_stream_t stream);
 int iseg_conv2d_igemm_bwd_weight(const void* x, const void* dy, float* dw, int accumulate, const iseg_conv_geom* geom_h, int dtype, void* ws,
                                  size_t ws_bytes, iseg_stream_t stream);
+
+/* Patchify convolutions (kernel == stride, dilation 1, one group, H % KH == 0, W % KW == 0, pt = pl = 0: backbones/convnext.py:72-75, the 2x2 /
+ * stride-2 downsampling layers) as plain GEMMs over a patch view of the NHWC tensor (csrc/conv_patchify.hip): the [pixels, KH*KW*Cin] patch
+ * matrix is the tensor itself with a grouped row stride and KH contiguous K segments of KW*Cin elements, so nothing is gathered or scattered.
+ *   fwd         y = P wt^T (+ bias)   wt = the K-contiguous kernel copy [Cout][KH*KW*Cin]; LDS-DMA GEMM with a patch-view A
+ *   bwd_data    dx = dy w^T           w = the Keras kernel; the product iseg_gemm runs for the column buffer, stored at the pixels (same bits
+ *                                     as iseg_gemm + iseg_col2im)
+ *   bwd_weight  dw (+)= P^T dy, dbias (+)= column sums of dy (NULL: not wanted)   fp32, the weight-gradient LDS-DMA GEMM with iseg_gemm's
+ *                                     split rule and fixed-order slab sum; needs iseg_conv2d_igemm_workspace_bytes(geom, 3)
+ * iseg_conv2d_patch_supported(geom, dtype, pass): pass 0 / 1 / 2 as above -- bf16, KW*Cin % 8 == 0, Cout % 8 == 0, the LDS-DMA GEMM's own
+ * conditions for the pass's M, N, K without a reduction split (fwd also: KW*Cin a multiple of the K-step, 64 or 32; bwd_weight: the
+ * conditions of iseg_gemm_variant 7 / 8, >= 2048 output pixels).  The passes are independent; fwd and bwd_data need no workspace (ws may be NULL).
+ * 16-byte aligned operands; anything else returns ISEG_ERR_UNSUPPORTED. */
+int iseg_conv2d_patch_supported(const iseg_conv_geom* geom_h, int dtype, int pass);
+int iseg_conv2d_patch_fwd(const void* x, const void* wt, const float* bias, void* y, const iseg_conv_geom* geom_h, int dtype, void* ws,
+                          size_t ws_bytes, iseg_stream_t stream);
+int iseg_conv2d_patch_bwd_data(const void* dy, const void* w, void* dx, const iseg_conv_geom* geom_h, int dtype, void* ws, size_t ws_bytes,
+                               iseg_stream_t stream);
+int iseg_conv2d_patch_bwd_weight(const void* x, const void* dy, float* dw, float* dbias, int accumulate, const iseg_conv_geom* geom_h, int dtype,
+                                 void* ws, size_t ws_bytes, iseg_stream_t stream);
 
 /* Several convolutions of ONE input [N,H,W,Cin] -- layers/aspp.py:33-52, the pixel-level 1x1 and the dilated 3x3 branches: stride 1, "same"
  * padding, one group, Cout filters each, their own kernel size / dilation -- as one launch per pass (csrc/conv_igemm_dma.h):

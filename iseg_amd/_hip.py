@@ -262,6 +262,10 @@ SIGNATURES = {
     "iseg_conv2d_igemm_fwd_kt_supported": (_i, [C.POINTER(ConvGeom), _i]),
     "iseg_conv2d_igemm_bwd_data": (_i, [_p, _p, _p, C.POINTER(ConvGeom), _i, _p, _z, _p]),
     "iseg_conv2d_igemm_bwd_weight": (_i, [_p, _p, _p, _i, C.POINTER(ConvGeom), _i, _p, _z, _p]),
+    "iseg_conv2d_patch_supported": (_i, [C.POINTER(ConvGeom), _i, _i]),
+    "iseg_conv2d_patch_fwd": (_i, [_p, _p, _p, _p, C.POINTER(ConvGeom), _i, _p, _z, _p]),
+    "iseg_conv2d_patch_bwd_data": (_i, [_p, _p, _p, C.POINTER(ConvGeom), _i, _p, _z, _p]),
+    "iseg_conv2d_patch_bwd_weight": (_i, [_p, _p, _p, _p, _i, C.POINTER(ConvGeom), _i, _p, _z, _p]),
     "iseg_conv2d_branches_supported": (_i, [C.POINTER(ConvBranches), _i]),
     "iseg_conv2d_branches_fwd": (_i, [_p, C.POINTER(ConvBranches), _i, _p, _z, _p]),
     "iseg_conv2d_branches_bwd_data": (_i, [C.POINTER(ConvBranches), _p, _p, _l, _i, _p, _z, _p]),

@@ -525,8 +525,13 @@ extern "C" int iseg_conv2d_igemm_supported(const iseg_conv_geom* g, int dtype) {
     return 1;
 }
 
+namespace iseg_mm {
+size_t conv_patch_wgrad_workspace(const iseg_conv_geom* g);      // conv_patchify.hip
+}
+
 extern "C" size_t iseg_conv2d_igemm_workspace_bytes(const iseg_conv_geom* g, int pass) {
     if (!geom_ok(g) || g->groups > 1) return 0;
+    if (pass == 3) return iseg_mm::conv_patch_wgrad_workspace(g);
     const int64_t Mo = (int64_t)g->N * g->Ho * g->Wo, Mi = (int64_t)g->N * g->H * g->W, Kd = (int64_t)g->KH * g->KW * g->Cin;
     int64_t M, N, K;
     if (pass == 0) M = Mo, N = g->Cout, K = Kd;

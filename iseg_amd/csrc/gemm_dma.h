@@ -104,7 +104,12 @@ inline int epi_kind(const Epi& e, const float* slabs) {
 __device__ __forceinline__ int key32(int quad) { return (0x6C >> (2 * (quad & 3))) & 3; }      // {0, 3, 2, 1}
 
 // FM: 16-row blocks per wavefront (4; 2 for the 128 x 192 tile of round 6: eight wavefronts of 32 x 96)
-template <int WM, int WN, int NS, class TO, int FN = 4, int EK = EK_ANY, bool KT = false, int BKS = 64, int FM = 4>
+// PV: an operand seen through the patch view of an NHWC tensor (Epi::pv_*; kernel == stride convolutions, csrc/conv_patchify.hip).
+//   1: A is the patch matrix (forward): only the per-lane DMA source address of the A pieces differs -- the row decode happens once per tile,
+//      the segment is chosen per K-step (pv_seg is a multiple of BKS, so no K-step straddles two segments);
+//   2: D is the patch matrix (data gradient): the epilogue's 16-byte vectors go to the pixel they belong to (pv_seg % 8 == 0 keeps a vector
+//      inside one segment) -- no column buffer, no col2im.  Plain epilogue only.
+template <int WM, int WN, int NS, class TO, int FN = 4, int EK = EK_ANY, bool KT = false, int BKS = 64, int FM = 4, int PV = 0>
 __global__ __launch_bounds__(WM* WN * 64) __attribute__((amdgpu_waves_per_eu(BKS == 32 ? 4 : 1, BKS == 32 ? 4 : 8))) void gemm_bf16_dma_kernel(const bf16_t* __restrict__ A, int64_t lda, const bf16_t* __restrict__ B,
                                                                      int64_t ldb, TO* __restrict__ D, int64_t ldd, int64_t M, int64_t N,
                                                                      int64_t K, int tiles_n, int ntiles, int64_t k_per_split,
@@ -113,6 +118,8 @@ __global__ __launch_bounds__(WM* WN * 64) __attribute__((amdgpu_waves_per_eu(BKS
     constexpr int BM = WM * FM * 16, BN = WN * FN * 16;      // a wavefront owns FM*16 rows x FN*16 columns (FN = 4, or 6 for the 256 x 192 tile)
     static_assert(FN % 2 == 0, "column fragments come in pairs (eight consecutive columns per lane)");
     static_assert(BKS == 64 || (BKS == 32 && !KT), "ring stages hold 64 or 32 K elements; the 32 form has no K tail");
+    static_assert(PV != 1 || !KT, "a patch-view A has whole K-steps (pv_seg % BKS == 0)");
+    static_assert(PV != 2 || EK == EK_PLAIN, "a patch-view D takes the plain epilogue");
     constexpr int RB = BKS * 2;                // bytes per stage row
     constexpr int CPR = BKS / 8;               // 16-byte chunks per stage row
     constexpr int RPP = 1024 / RB;             // stage rows per 1-KiB DMA piece
@@ -152,7 +159,8 @@ __global__ __launch_bounds__(WM* WN * 64) __attribute__((amdgpu_waves_per_eu(BKS
                 int64_t row = pm0 + r;
                 row = row < M ? row : M - 1;
                 const int ch = (lane & (CPR - 1)) ^ (BKS == 64 ? (r & 7) : key32(r >> 2));
-                src[p] = A + row * lda + kbeg + ch * 8;
+                if (PV == 1) src[p] = A + epi.pv_off((int)row, (int)kbeg) + ch * 8;      // (rows past M were clamped on the row index above)
+                else src[p] = A + row * lda + kbeg + ch * 8;
                 beyond[p] = ch >= tail_chunks;
             } else {
                 const int rb = r - BM;
@@ -167,6 +175,7 @@ __global__ __launch_bounds__(WM* WN * 64) __attribute__((amdgpu_waves_per_eu(BKS
         }
     };
     point(m0, n0);
+    int pv_kin = PV == 1 ? (int)(kbeg % epi.pv_seg) : 0;      // patch-view A: where in its segment the next K-step to issue begins
     // kstep: the K-step the stage is filled with (only the last one can be a tail)
     auto issue = [&](int stage, int kstep) {
         if (KT && tail_chunks != 0 && kstep == nk - 1) {
@@ -182,6 +191,15 @@ __global__ __launch_bounds__(WM* WN * 64) __attribute__((amdgpu_waves_per_eu(BKS
         for (int p = 0; p < PPW; ++p) {
             __builtin_amdgcn_global_load_lds((glb_void_ptr)src[p], (lds_void_ptr)(smem + stage * STAGE + (wid + p * NW) * 1024), 16, 0, 0);
             src[p] += BKS;
+        }
+        if (PV == 1) {      // the K-step after a segment's last one begins the next kernel row: the A pieces jump to it (B is a plain matrix)
+            pv_kin += BKS;
+            if (pv_kin == epi.pv_seg) {
+                pv_kin = 0;
+#pragma unroll
+                for (int p = 0; p < PPW; ++p)
+                    if ((wid + p * NW) * RPP < BM) src[p] += epi.pv_segstride - epi.pv_seg;
+            }
         }
     };
 
@@ -284,8 +302,12 @@ __global__ __launch_bounds__(WM* WN * 64) __attribute__((amdgpu_waves_per_eu(BKS
                 } else {
                     const Epi ek = epi_known<EK>(epi);
                     EpiPrefetch<TO> pf;
-                    pf.load(ek, m, n, D, ldd);
-                    epi_finish8<TO>(ek, v, pf, m, n, D, ldd);
+                    if (PV == 2) {
+                        epi_finish8<TO>(ek, v, pf, 0, 0, D + epi.pv_off((int)m, (int)n), ldd);      // (plain epilogue: nothing else is indexed by m, n)
+                    } else {
+                        pf.load(ek, m, n, D, ldd);
+                        epi_finish8<TO>(ek, v, pf, m, n, D, ldd);
+                    }
                 }
             }
         }
@@ -293,10 +315,12 @@ __global__ __launch_bounds__(WM* WN * 64) __attribute__((amdgpu_waves_per_eu(BKS
 }
 
 // eligibility of a problem for the DMA pipeline (checked on the host)
-inline bool dma_eligible(const iseg_gemm_args* g, int64_t kps) {
+// floors = false: without the M / N >= 64 floors (rows past M / N are clamped duplicates whose products are never stored): the patch-view
+// products, whose other route is a column buffer and a permutation pass
+inline bool dma_eligible(const iseg_gemm_args* g, int64_t kps, bool floors = true) {
     if (!g->a_kcontig || !g->b_kcontig || g->a_act != ISEG_ACT_NONE || g->colsum_out) return false;
     // K: whole 16-B chunks per row (a last K-step of fewer than eight is zero-filled, see the kernel); a split cuts at multiples of 64
-    if (g->K % 8 != 0 || (kps != g->K && kps % 64 != 0) || g->K < dma_min_k || g->N % 8 != 0 || g->N < 64 || g->M < 64) return false;
+    if (g->K % 8 != 0 || (kps != g->K && kps % 64 != 0) || g->K < dma_min_k || g->N % 8 != 0 || (floors && (g->N < 64 || g->M < 64))) return false;
     if (((uintptr_t)g->A % 16) || ((uintptr_t)g->B % 16) || g->lda % 8 || g->ldb % 8) return false;
     if (((uintptr_t)g->D % 16) || g->ldd % 8) return false;
     if (g->residual && (((uintptr_t)g->residual % 16) || g->ldr % 8)) return false;
@@ -308,7 +332,7 @@ inline bool dma_eligible(const iseg_gemm_args* g, int64_t kps) {
     return true;
 }
 
-template <int WM, int WN, int NS, class TO, int FN = 4, int EK = EK_ANY, int BKS = 64, int FM = 4>
+template <int WM, int WN, int NS, class TO, int FN = 4, int EK = EK_ANY, int BKS = 64, int FM = 4, int PV = 0>
 void launch_dma(const iseg_gemm_args* g, const Epi& epi, int nsplit, int64_t k_per_split, float* slabs, hipStream_t s) {
     constexpr int BM = WM * FM * 16, BN = WN * FN * 16;
     const int tiles_m = (int)ceil_div64(g->M, BM), tiles_n = (int)ceil_div64(g->N, BN);
@@ -320,30 +344,30 @@ void launch_dma(const iseg_gemm_args* g, const Epi& epi, int nsplit, int64_t k_p
     static_assert(FM == 4 || BKS == 64, "the 32-deep stages exist for the 256 x 128 tile");
     if constexpr (BKS == 32) {      // (dispatch_dma sends only whole-K problems here: K % 32 == 0, splits cut at multiples of 64)
         static const bool raised32 = [] {
-            return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_dma_kernel<WM, WN, NS, TO, FN, EK, false, 32>),
+            return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_dma_kernel<WM, WN, NS, TO, FN, EK, false, 32, 4, PV>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess;
         }();
         (void)raised32;
-        hipLaunchKernelGGL((gemm_bf16_dma_kernel<WM, WN, NS, TO, FN, EK, false, 32>), grid, dim3(WM * WN * 64), lds, s, (const bf16_t*)g->A, g->lda,
+        hipLaunchKernelGGL((gemm_bf16_dma_kernel<WM, WN, NS, TO, FN, EK, false, 32, 4, PV>), grid, dim3(WM * WN * 64), lds, s, (const bf16_t*)g->A, g->lda,
                            (const bf16_t*)g->B, g->ldb, (TO*)g->D, g->ldd, g->M, g->N, g->K, tiles_n, ntiles, k_per_split, slabs, epi, vecD);
         return;
     }
-    if (g->K % 64 != 0) {
+    if constexpr (PV != 1) if (g->K % 64 != 0) {
         static const bool raised_kt = [] {      // > 64 KiB of dynamic LDS needs the attribute once per instantiation
-            return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_dma_kernel<WM, WN, NS, TO, FN, EK, true, 64, FM>),
+            return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_dma_kernel<WM, WN, NS, TO, FN, EK, true, 64, FM, PV>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess;
         }();
         (void)raised_kt;
-        hipLaunchKernelGGL((gemm_bf16_dma_kernel<WM, WN, NS, TO, FN, EK, true, 64, FM>), grid, dim3(WM * WN * 64), lds, s, (const bf16_t*)g->A, g->lda,
+        hipLaunchKernelGGL((gemm_bf16_dma_kernel<WM, WN, NS, TO, FN, EK, true, 64, FM, PV>), grid, dim3(WM * WN * 64), lds, s, (const bf16_t*)g->A, g->lda,
                            (const bf16_t*)g->B, g->ldb, (TO*)g->D, g->ldd, g->M, g->N, g->K, tiles_n, ntiles, k_per_split, slabs, epi, vecD);
         return;
     }
     static const bool raised = [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_dma_kernel<WM, WN, NS, TO, FN, EK, false, 64, FM>),
+        return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_dma_kernel<WM, WN, NS, TO, FN, EK, false, 64, FM, PV>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess;
     }();
     (void)raised;
-    hipLaunchKernelGGL((gemm_bf16_dma_kernel<WM, WN, NS, TO, FN, EK, false, 64, FM>), grid, dim3(WM * WN * 64), lds, s, (const bf16_t*)g->A, g->lda,
+    hipLaunchKernelGGL((gemm_bf16_dma_kernel<WM, WN, NS, TO, FN, EK, false, 64, FM, PV>), grid, dim3(WM * WN * 64), lds, s, (const bf16_t*)g->A, g->lda,
                        (const bf16_t*)g->B, g->ldb, (TO*)g->D, g->ldd, g->M, g->N, g->K, tiles_n, ntiles, k_per_split, slabs, epi, vecD);
 }
 
@@ -445,6 +469,30 @@ void dispatch_dma(const iseg_gemm_args* g, const Epi& epi, int nsplit, int64_t k
         case 9: launch_dma_kinds<4, 2, 3, TO, 6, 64, 1>(g, epi, nsplit, kps, slabs, s); break;      // 64 x 192, eight wavefronts of 16 x 96
         case 8: launch_dma_kinds<4, 2, 3, TO, 6, 64, 2>(g, epi, nsplit, kps, slabs, s); break;      // 128 x 192, eight wavefronts of 32 x 96
         default: launch_dma_kinds<2, 2, 3, TO, 4>(g, epi, nsplit, kps, slabs, s); break;
+    }
+}
+
+// The K-step (elements per ring stage) dispatch_dma runs an unsplit bf16 problem with: a patch-view A needs pv_seg to be a multiple of it
+inline int dma_kstep(const iseg_gemm_args* g) {
+    return dma_form(g, 1) == 2 && dma_bk32() && (dma_bk32() == 2 || g->K <= 512) && g->K % 32 == 0 && g->K >= 96 ? 32 : 64;
+}
+
+// dispatch_dma for an unsplit bf16 product with a patch-view operand: the same tile form for the same problem (so the data gradient sums
+// in the order of the plain GEMM it replaces), the epilogue kind fixed by the caller (EK_PLAIN, or EK_BIAS for a forward pass with bias)
+template <int PV, int EK>
+void dispatch_dma_patch(const iseg_gemm_args* g, const Epi& epi, hipStream_t s) {
+    const int64_t kps = g->K;
+    switch (dma_form(g, 1)) {
+        case 1: launch_dma<2, 1, 4, bf16_t, 4, EK, 64, 4, PV>(g, epi, 1, kps, nullptr, s); break;
+        case 2:
+            if (dma_kstep(g) == 32) launch_dma<4, 2, 3, bf16_t, 4, EK, 32, 4, PV>(g, epi, 1, kps, nullptr, s);
+            else launch_dma<4, 2, 3, bf16_t, 4, EK, 64, 4, PV>(g, epi, 1, kps, nullptr, s);
+            break;
+        case 3: launch_dma<2, 2, 2, bf16_t, 4, EK, 64, 4, PV>(g, epi, 1, kps, nullptr, s); break;
+        case 6: launch_dma<4, 2, 2, bf16_t, 6, EK, 64, 4, PV>(g, epi, 1, kps, nullptr, s); break;
+        case 9: launch_dma<4, 2, 3, bf16_t, 6, EK, 64, 1, PV>(g, epi, 1, kps, nullptr, s); break;
+        case 8: launch_dma<4, 2, 3, bf16_t, 6, EK, 64, 2, PV>(g, epi, 1, kps, nullptr, s); break;
+        default: launch_dma<2, 2, 3, bf16_t, 4, EK, 64, 4, PV>(g, epi, 1, kps, nullptr, s); break;
     }
 }
 

@@ -27,10 +27,21 @@ static __device__ uint4 tn_zero_page;      // sixteen zero bytes (device globals
 
 __device__ __forceinline__ int tn_key(int k) { return ((k & 3) << 1) | (((k >> 3) & 1) << 3); }
 
+// A seen through the patch view of an NHWC tensor (the weight gradient of a kernel == stride convolution, csrc/conv_patchify.hip): reduction
+// row r = output pixel, column m = (kernel row, kw*C elements of it); element (r, m) lies at
+//   (r / wo) * group + (r % wo) * seg + (m / seg) * segstride + m % seg
+// adv: what 64 more reduction rows add to that when wo divides 64 (a whole number of pixel rows: a constant); 0 = recompute the base per stage
+struct TnPatch {
+    int wo, seg;
+    int64_t group, segstride, adv;
+    __device__ __forceinline__ int64_t base(int r) const { return (int64_t)(r / wo) * group + (int64_t)(r % wo) * seg; }
+};
+
 // one (tile t, reduction split ksplit) of a problem; the kernels below only decide which problem and which tile a workgroup takes
-template <int WM, int WN, int NS>
+template <int WM, int WN, int NS, bool PV = false>
 __device__ __forceinline__ void tn_tile(const bf16_t* __restrict__ A, int64_t lda, const bf16_t* __restrict__ B, int64_t ldb, int64_t M, int64_t N,
-                                        int64_t K, int tiles_n, int t, int ksplit, int64_t k_per_split, float* __restrict__ slabs, int ones_row) {
+                                        int64_t K, int tiles_n, int t, int ksplit, int64_t k_per_split, float* __restrict__ slabs, int ones_row,
+                                        const TnPatch pv = TnPatch{}) {
     constexpr int NW = WM * WN, FM = 4, FN = 4;      // (the waits in `compute` name FM = FN = 4 fragment pairs)
     constexpr int BM = WM * 64, BN = WN * 64;
     constexpr int ROWA = BM * 2, ROWB = BN * 2;                 // bytes of one k-row of the A / B image
@@ -51,6 +62,8 @@ __device__ __forceinline__ void tn_tile(const bf16_t* __restrict__ A, int64_t ld
     // per-lane DMA sources: piece P = wid + p * NW of a stage; 16-byte slot S = 64 P + lane of the A image (P < PA) or of the B image
     const bf16_t* src[PPW];
     int left[PPW];      // reduction rows from this lane's row of the piece to the end of the split's range (<= 0: a row past K)
+    int pv_row[PV ? PA / NW : 1];          // patch view, any wo: this lane's reduction row of the A piece and its offset inside a patch row
+    int64_t pv_col[PV ? PA / NW : 1];
 #pragma unroll
     for (int p = 0; p < PPW; ++p) {
         const int P = wid + p * NW;
@@ -58,7 +71,13 @@ __device__ __forceinline__ void tn_tile(const bf16_t* __restrict__ A, int64_t ld
             const int S = P * 64 + lane, k = S / CPA, chunk = (S % CPA) ^ tn_key(k);
             int64_t col = m0 + chunk * 8;
             col = col + 8 <= M ? col : M - 8;      // columns past M: any valid chunk (their products are never stored)
-            src[p] = A + (kbeg + k) * lda + col;
+            if (PV) {      // the chunk index gives the segment and the offset inside it (seg % 8 == 0: a chunk lies in one segment), the pixel row the base
+                pv_row[p] = (int)kbeg + k;
+                pv_col[p] = (int64_t)((int)col / pv.seg) * pv.segstride + (int)col % pv.seg;
+                src[p] = A + pv.base(pv_row[p]) + pv_col[p];
+            } else {
+                src[p] = A + (kbeg + k) * lda + col;
+            }
             left[p] = (int)(kend - kbeg) - k;
         } else {
             const int S = (P - PA) * 64 + lane, k = S / CPB, chunk = (S % CPB) ^ tn_key(k);
@@ -75,7 +94,16 @@ __device__ __forceinline__ void tn_tile(const bf16_t* __restrict__ A, int64_t ld
             // (a select, not a branch: rows past the end of a ragged reduction -- K = 17424 pixel rows of a 513 x 513 crop at stride 16 -- contribute zeros)
             const bf16_t* const from = left[p] > 0 ? src[p] : zero;
             __builtin_amdgcn_global_load_lds((glb_void_ptr)from, (lds_void_ptr)(smem + stage * STAGE + (wid + p * NW) * 1024), 16, 0, 0);
-            src[p] += p < PA / NW ? 64 * lda : 64 * ldb;
+            if (PV && p < PA / NW) {
+                if (pv.adv) {
+                    src[p] += pv.adv;
+                } else {      // (a row past K gets an address nobody reads: `left` selects the zero page)
+                    pv_row[p] += 64;
+                    src[p] = A + pv.base(pv_row[p]) + pv_col[p];
+                }
+            } else {
+                src[p] += p < PA / NW ? 64 * lda : 64 * ldb;
+            }
             left[p] -= 64;
         }
     };
@@ -222,6 +250,15 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_bf16_dma_tn_kernel(const bf1
     tn_tile<WM, WN, NS>(A, lda, B, ldb, M, N, K, tiles_n, t, ksplit, k_per_split, slabs, ones_row);
 }
 
+template <int WM, int WN, int NS>
+__global__ __launch_bounds__(WM* WN * 64) void gemm_bf16_dma_tn_patch_kernel(const bf16_t* __restrict__ A, TnPatch pv, const bf16_t* __restrict__ B,
+                                                                              int64_t ldb, int64_t M, int64_t N, int64_t K, int tiles_n, int ntiles,
+                                                                              int64_t k_per_split, float* __restrict__ slabs, int ones_row) {
+    int t, ksplit;
+    tile_and_split(ntiles, t, ksplit);
+    tn_tile<WM, WN, NS, true>(A, 0, B, ldb, M, N, K, tiles_n, t, ksplit, k_per_split, slabs, ones_row, pv);
+}
+
 // TWO weight-gradient problems over the SAME reduction rows in one launch (round 5): the pair of an un-fused ConvNeXt block, Z = g^T dout
 // [4C, C] and dW1 = y2^T dH [C, 4C] (backbones/convnext.py:51-54 backward).  Launched one after the other each fills the chip with
 // 18 tiles x 13 splits; together 36 tiles x 7 splits do -- half the slab bytes written and summed again, one ring fill and one slab-store
@@ -281,6 +318,21 @@ void launch_dma_tn(const iseg_gemm_args* g, int nsplit, int64_t k_per_split, flo
     const int ntiles = tiles_m * tiles_n;
     constexpr int lds = NS * 64 * (BM + BN) * 2;      // (the limit was raised by dma_tn_lds_ok(), which dma_tn_form() requires)
     hipLaunchKernelGGL((gemm_bf16_dma_tn_kernel<WM, WN, NS>), dim3(ntiles, nsplit, 1), dim3(WM * WN * 64), lds, s, (const bf16_t*)g->A, g->lda,
+                       (const bf16_t*)g->B, g->ldb, g->M, g->N, g->K, tiles_n, ntiles, k_per_split, slabs, g->colsum_out ? 1 : 0);
+}
+
+template <int WM, int WN>
+void launch_dma_tn_patch(const iseg_gemm_args* g, const TnPatch& pv, int nsplit, int64_t k_per_split, float* slabs, hipStream_t s) {
+    constexpr int NS = 3, BM = WM * 64, BN = WN * 64;
+    const int tiles_m = (int)ceil_div64(g->M, BM), tiles_n = (int)ceil_div64(g->N, BN);
+    const int ntiles = tiles_m * tiles_n;
+    constexpr int lds = NS * 64 * (BM + BN) * 2;
+    static const bool raised = [] {
+        return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_dma_tn_patch_kernel<WM, WN, NS>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   lds) == hipSuccess;
+    }();
+    (void)raised;
+    hipLaunchKernelGGL((gemm_bf16_dma_tn_patch_kernel<WM, WN, NS>), dim3(ntiles, nsplit, 1), dim3(WM * WN * 64), lds, s, (const bf16_t*)g->A, pv,
                        (const bf16_t*)g->B, g->ldb, g->M, g->N, g->K, tiles_n, ntiles, k_per_split, slabs, g->colsum_out ? 1 : 0);
 }
 

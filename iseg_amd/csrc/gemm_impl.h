@@ -37,6 +37,15 @@ struct Epi {
     int64_t sa_outer, sa_inner, sb_outer, sb_inner, sd_outer, sd_inner;
     int pre_deriv;          // pre_out receives gelu'(pre) instead of pre (act == GELU)
     int64_t b_group_rows, b_group_stride;      // B per row group (LDS-DMA kernel only): rows [i*b_group_rows, ...) use B + i*b_group_stride
+    // patch view of an NHWC tensor (LDS-DMA kernel's PV instantiations only, csrc/conv_patchify.hip): element (row r, column k) of the
+    // [pixels, kh*kw*C] patch matrix of a kernel == stride convolution lies at
+    //   (r / pv_wo) * pv_group + (r % pv_wo) * pv_seg + (k / pv_seg) * pv_segstride + k % pv_seg
+    // with pv_seg = kw*C (one contiguous segment per kernel row), pv_segstride = W*C, pv_group = kh*W*C
+    int pv_wo, pv_seg;
+    int64_t pv_group, pv_segstride;
+    __device__ __forceinline__ int64_t pv_off(int r, int k) const {
+        return (int64_t)(r / pv_wo) * pv_group + (int64_t)(r % pv_wo) * pv_seg + (int64_t)(k / pv_seg) * pv_segstride + k % pv_seg;
+    }
     __device__ __forceinline__ int64_t off_a(int z) const { return (z / batch_inner) * sa_outer + (z % batch_inner) * sa_inner; }
     __device__ __forceinline__ int64_t off_b(int z) const { return (z / batch_inner) * sb_outer + (z % batch_inner) * sb_inner; }
     __device__ __forceinline__ int64_t off_d(int z) const { return (z / batch_inner) * sd_outer + (z % batch_inner) * sd_inner; }

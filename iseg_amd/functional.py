@@ -349,7 +349,9 @@ class _Conv2dFn(Function):
     """Three routes: (1) 1x1 / stride 1 / one group on the activation as it lies = a plain GEMM; (2) bf16 storage with channels per
     group that are multiples of 8 = implicit GEMM on the matrix cores (csrc/conv_igemm.hip: the patch matrix is gathered while the
     operand tile is staged, the data gradient is a gather over dy -- no column buffer, no col2im); (3) everything else (the fp32 parity
-    mode, Cin = 3 stems) = im2col + GEMM + col2im, group by group."""
+    mode, Cin = 3 stems) = im2col + GEMM + col2im, group by group.  Inside (2), a kernel == stride convolution whose map the kernel divides
+    (ConvNeXt's downsampling layers) runs each pass that K.conv2d_patch_supported takes as a plain LDS-DMA GEMM over the patch view of the
+    tensor (csrc/conv_patchify.hip)."""
 
     @staticmethod
     def forward(ctx, x, W, b, strides, dilation, padding, groups):
@@ -364,7 +366,15 @@ class _Conv2dFn(Function):
         direct = kh == 1 and kw == 1 and strides == (1, 1) and groups == 1 and xc.dtype == cdt and Cin % 8 == 0
         igemm = (not direct) and xc.dtype == cdt and K.conv2d_igemm_supported(geom, cdt)
         M = N * Ho * Wo
-        if direct:
+        # kernel == stride (ConvNeXt's 2x2 / s2 downsamples): each pass a plain GEMM over the patch view of the tensor, where the native query
+        # takes it (csrc/conv_patchify.hip); the three passes route independently
+        patch = (False, False, False)
+        if igemm and (kh, kw) == strides and dilation == (1, 1) and groups == 1:
+            patch = tuple(K.conv2d_patch_supported(geom, cdt, p) for p in (K.PATCH_FWD, K.PATCH_BWD_DATA, K.PATCH_BWD_WEIGHT))
+        Wt = nn.wt(W, (kh * kw * Cin, Cout)) if patch[0] else None
+        if Wt is not None:
+            y = K.conv2d_patch_fwd(xc, Wt, b.data if b is not None else None, geom)
+        elif direct:
             Wt = _kcontig_kernel(W, xc.reshape(-1, Cin), Cin, Cout)
             if Wt is not None:
                 y = K.dense_fwd_t(xc.reshape(-1, Cin), Wt, b.data if b is not None else None)
@@ -394,7 +404,7 @@ class _Conv2dFn(Function):
             ctx.col = keep_col if (groups == 1 and W.requires_grad and not ctx.needs_input_grad[0] and Kd * keep_col.element_size() <=
                                    Cin * xc.element_size() * strides[0] * strides[1]) else None
         ctx.W, ctx.b = W, b
-        ctx.geom, ctx.route = geom, (direct, igemm)
+        ctx.geom, ctx.route, ctx.patch = geom, (direct, igemm), patch
         ctx.x_dtype = x.dtype
         ctx.save_for_backward(xc)
         return y.reshape(N, Ho, Wo, Cout)
@@ -412,7 +422,9 @@ class _Conv2dFn(Function):
         cdt = nn.compute_dtype()
         M = N * Ho * Wo
         dy2 = _c(dy).reshape(M, Cout)
-        if b is not None and b.requires_grad:
+        want_b = b is not None and b.requires_grad
+        patch_w = ctx.patch[2] and W.requires_grad      # the bias gradient rides the weight gradient's ones-row
+        if want_b and not patch_w:
             K.colsum(dy2, Cout, 0, 1, M, Cout, _grad(b), accumulate=True)
         need_dx = ctx.needs_input_grad[0]
         dx = None
@@ -424,10 +436,14 @@ class _Conv2dFn(Function):
                 dx = K.dense_dgrad(dy2, nn.w(W).reshape(Cin, Cout)).reshape(N, H, Wd, Cin)
         elif igemm:
             dy4 = dy2.reshape(N, Ho, Wo, Cout)
-            if W.requires_grad:
+            if patch_w:
+                K.conv2d_patch_bwd_weight(xc, dy4, _grad(W), g_, accumulate=True, bias_grad=_grad(b) if want_b else None)
+            elif W.requires_grad:
                 K.conv2d_igemm_bwd_weight(xc, dy4, _grad(W), g_, accumulate=True)
             patchify = (kh, kw) == st      # kernel == stride: the column buffer IS dx up to a permutation, one plain GEMM fills it
-            if need_dx and (st == (1, 1) or (di == (1, 1) and st[0] * st[1] <= 16 and not patchify)):
+            if need_dx and ctx.patch[1]:
+                dx = K.conv2d_patch_bwd_data(dy4, nn.w(W), g_)      # that GEMM, stored straight to the pixels: no column buffer, no col2im
+            elif need_dx and (st == (1, 1) or (di == (1, 1) and st[0] * st[1] <= 16 and not patchify)):
                 # stride 1: one gather over dy; strided and undilated: one stride-1 gather per stride phase, all phases in one launch, rows
                 # scattered to their pixels by the epilogue (csrc/conv_igemm.hip pass 3) -- no zero products, no column buffer, no col2im
                 # (ResNet's 3x3 / s2 at 64x64x128: 23 us against 40 us for GEMM + col2im)

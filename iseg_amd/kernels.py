@@ -896,6 +896,39 @@ def conv2d_igemm_bwd_weight(x, dy, dw, geom, accumulate=True):
     return dw
 
 
+# ---- patchify convolutions (kernel == stride) as GEMMs over a patch view of the tensor (csrc/conv_patchify.hip) ----
+PATCH_FWD, PATCH_BWD_DATA, PATCH_BWD_WEIGHT = 0, 1, 2
+
+
+def conv2d_patch_supported(geom, dtype, which):
+    """pass `which` of this convolution runs as a plain LDS-DMA GEMM over the patch view (the three passes are independent)"""
+    return dtype in _DT and bool(_hip.lib().iseg_conv2d_patch_supported(C.byref(geom), _DT[dtype], int(which)))
+
+
+def conv2d_patch_fwd(x, wt, bias, geom):
+    """y [N,Ho,Wo,Cout] = patches(x) @ wt^T (+ bias); wt = the K-contiguous kernel copy [Cout, KH*KW*Cin] (nn.wt)"""
+    _require_cuda(x, wt)
+    y = torch.empty((geom.N, geom.Ho, geom.Wo, geom.Cout), dtype=x.dtype, device=x.device)
+    _hip.call("iseg_conv2d_patch_fwd", ptr(x), ptr(wt), ptr(bias), ptr(y), C.byref(geom), dt(x), None, 0, stream())
+    return y
+
+
+def conv2d_patch_bwd_data(dy, w, geom):
+    """dx [N,H,W,Cin] = dy @ w^T written through the patch view: the bits of gemm + col2im without the column buffer"""
+    _require_cuda(dy, w)
+    dx = torch.empty((geom.N, geom.H, geom.W, geom.Cin), dtype=dy.dtype, device=dy.device)
+    _hip.call("iseg_conv2d_patch_bwd_data", ptr(dy), ptr(w), ptr(dx), C.byref(geom), dt(dy), None, 0, stream())
+    return dx
+
+
+def conv2d_patch_bwd_weight(x, dy, dw, geom, accumulate=True, bias_grad=None):
+    """dw [KH,KW,Cin,Cout] fp32 (+)= patches(x)^T @ dy; bias_grad [Cout] fp32 (+)= column sums of dy from the kernel's ones-row"""
+    _require_cuda(x, dy, dw)
+    ws, wsb = _conv_ws(geom, 3, x.device)
+    _hip.call("iseg_conv2d_patch_bwd_weight", ptr(x), ptr(dy), ptr(dw), ptr(bias_grad), int(accumulate), C.byref(geom), dt(x), ptr(ws), wsb, stream())
+    return dw
+
+
 # ---- several convolutions of one input (csrc/conv_igemm.hip: grouped forward / weight gradient, K-joined data gradient) ----
 def conv_branches(N, H, W, Cin, Cout, taps):
     """branch table for `taps` = [(KH, KW, dh, dw), ...] of a [N,H,W,Cin] -> Cout convolution family (stride 1, "same" padding); the operand
