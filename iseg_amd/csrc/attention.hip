@@ -314,18 +314,8 @@ static inline int wide_chunks(int64_t rows) {
     return (int)c;
 }
 
-static inline unsigned row_blocks(int64_t rows) {
-    int64_t b = ceil_div64(rows, 4);
-    if (b > 256 * 32) b = 256 * 32;
-    if (b < 1) b = 1;
-    return (unsigned)b;
-}
-static inline unsigned ew_blocks(int64_t n) {
-    int64_t b = ceil_div64(n, 256);
-    if (b > 256 * 16) b = 256 * 16;
-    if (b < 1) b = 1;
-    return (unsigned)b;
-}
+static inline unsigned row_blocks(int64_t rows) { return grid_cap(rows, 4, 256 * 32); }
+static inline unsigned ew_blocks(int64_t n) { return grid_cap(n, 256, 256 * 16); }
 
 }  // namespace
 
@@ -337,71 +327,55 @@ extern "C" int iseg_softmax_rows_fwd(const void* scores, void* probs, int64_t pr
     ISEG_REQUIRE(!mask || windows > 0, "iseg_softmax_rows_fwd: mask needs the window count");
     const int64_t rows = problems * Tq;
     const int hd = heads > 0 ? heads : 1, nw = windows > 0 ? windows : 1;
-#define SM_FWD(T, LPR, EPL)                                                                                                          \
-    hipLaunchKernelGGL((softmax_fwd_reg_kernel<T, LPR, EPL>), dim3(row_blocks(ceil_div64(rows, 64 / LPR))), dim3(256), 0, stream,    \
-                       (const T*)scores, (T*)probs, rows, Tq, cols, ld, bias, hd, mask, nw, clip_lo, clip_hi)
-    bool done;
-    if (dtype == ISEG_BF16)
-        done = softmax_dispatch(ld, [&] { SM_FWD(bf16_t, 16, 1); }, [&] { SM_FWD(bf16_t, 64, 2); }, [&] { SM_FWD(bf16_t, 64, 8); },
-                                [&] { SM_FWD(bf16_t, 64, 32); });
-    else
-        done = softmax_dispatch(ld, [&] { SM_FWD(float, 16, 1); }, [&] { SM_FWD(float, 64, 2); }, [&] { SM_FWD(float, 64, 8); },
-                                [&] { SM_FWD(float, 64, 32); });
-#undef SM_FWD
-    if (done) return iseg_check_launch("iseg_softmax_rows_fwd");
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL((softmax_fwd_kernel<bf16_t>), dim3(row_blocks(rows)), dim3(256), 0, stream, (const bf16_t*)scores,
-                           (bf16_t*)probs, rows, Tq, cols, ld, bias, heads > 0 ? heads : 1, mask, windows > 0 ? windows : 1, clip_lo,
-                           clip_hi);
-    else
-        hipLaunchKernelGGL((softmax_fwd_kernel<float>), dim3(row_blocks(rows)), dim3(256), 0, stream, (const float*)scores,
-                           (float*)probs, rows, Tq, cols, ld, bias, heads > 0 ? heads : 1, mask, windows > 0 ? windows : 1, clip_lo,
-                           clip_hi);
-    return iseg_check_launch("iseg_softmax_rows_fwd");
+    return by_dtype(dtype, "iseg_softmax_rows_fwd", [&](auto t) {
+        using T = decltype(t);
+        auto reg = [&](auto lpr, auto epl) {
+            constexpr int LPR = decltype(lpr)::value, EPL = decltype(epl)::value;
+            hipLaunchKernelGGL((softmax_fwd_reg_kernel<T, LPR, EPL>), dim3(row_blocks(ceil_div64(rows, 64 / LPR))), dim3(256), 0, stream,
+                               (const T*)scores, (T*)probs, rows, Tq, cols, ld, bias, hd, mask, nw, clip_lo, clip_hi);
+        };
+        if (!softmax_dispatch(ld, [&] { reg(IntC<16>{}, IntC<1>{}); }, [&] { reg(IntC<64>{}, IntC<2>{}); }, [&] { reg(IntC<64>{}, IntC<8>{}); },
+                              [&] { reg(IntC<64>{}, IntC<32>{}); }))
+            hipLaunchKernelGGL((softmax_fwd_kernel<T>), dim3(row_blocks(rows)), dim3(256), 0, stream, (const T*)scores, (T*)probs, rows, Tq, cols, ld,
+                               bias, hd, mask, nw, clip_lo, clip_hi);
+        return iseg_check_launch("iseg_softmax_rows_fwd");
+    });
 }
 
 extern "C" int iseg_softmax_rows_bwd(const void* probs, const void* dprobs, void* dscores, int64_t rows, int cols, int ld, float clip_lo,
                                      float clip_hi, int dtype, hipStream_t stream) {
     ISEG_REQUIRE(probs && dprobs && dscores && rows > 0 && cols > 0 && ld >= cols, "iseg_softmax_rows_bwd: bad arguments");
-#define SM_BWD(T, LPR, EPL)                                                                                                          \
-    hipLaunchKernelGGL((softmax_bwd_reg_kernel<T, LPR, EPL>), dim3(row_blocks(ceil_div64(rows, 64 / LPR))), dim3(256), 0, stream,    \
-                       (const T*)probs, (const T*)dprobs, (T*)dscores, rows, cols, ld, clip_lo, clip_hi)
-    bool done;
-    if (dtype == ISEG_BF16)
-        done = softmax_dispatch(ld, [&] { SM_BWD(bf16_t, 16, 1); }, [&] { SM_BWD(bf16_t, 64, 2); }, [&] { SM_BWD(bf16_t, 64, 8); },
-                                [&] { SM_BWD(bf16_t, 64, 32); });
-    else
-        done = softmax_dispatch(ld, [&] { SM_BWD(float, 16, 1); }, [&] { SM_BWD(float, 64, 2); }, [&] { SM_BWD(float, 64, 8); },
-                                [&] { SM_BWD(float, 64, 32); });
-#undef SM_BWD
-    if (done) return iseg_check_launch("iseg_softmax_rows_bwd");
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL((softmax_bwd_kernel<bf16_t>), dim3(row_blocks(rows)), dim3(256), 0, stream, (const bf16_t*)probs,
-                           (const bf16_t*)dprobs, (bf16_t*)dscores, rows, cols, ld, clip_lo, clip_hi);
-    else
-        hipLaunchKernelGGL((softmax_bwd_kernel<float>), dim3(row_blocks(rows)), dim3(256), 0, stream, (const float*)probs,
-                           (const float*)dprobs, (float*)dscores, rows, cols, ld, clip_lo, clip_hi);
-    return iseg_check_launch("iseg_softmax_rows_bwd");
+    return by_dtype(dtype, "iseg_softmax_rows_bwd", [&](auto t) {
+        using T = decltype(t);
+        auto reg = [&](auto lpr, auto epl) {
+            constexpr int LPR = decltype(lpr)::value, EPL = decltype(epl)::value;
+            hipLaunchKernelGGL((softmax_bwd_reg_kernel<T, LPR, EPL>), dim3(row_blocks(ceil_div64(rows, 64 / LPR))), dim3(256), 0, stream,
+                               (const T*)probs, (const T*)dprobs, (T*)dscores, rows, cols, ld, clip_lo, clip_hi);
+        };
+        if (!softmax_dispatch(ld, [&] { reg(IntC<16>{}, IntC<1>{}); }, [&] { reg(IntC<64>{}, IntC<2>{}); }, [&] { reg(IntC<64>{}, IntC<8>{}); },
+                              [&] { reg(IntC<64>{}, IntC<32>{}); }))
+            hipLaunchKernelGGL((softmax_bwd_kernel<T>), dim3(row_blocks(rows)), dim3(256), 0, stream, (const T*)probs, (const T*)dprobs, (T*)dscores,
+                               rows, cols, ld, clip_lo, clip_hi);
+        return iseg_check_launch("iseg_softmax_rows_bwd");
+    });
 }
 
 extern "C" int iseg_clip_fwd(const void* x, void* y, int64_t n, float lo, float hi, int dtype, hipStream_t stream) {
     ISEG_REQUIRE(x && y && n > 0 && hi >= lo, "iseg_clip_fwd: bad arguments");
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL((clip_fwd_kernel<bf16_t>), dim3(ew_blocks(n)), dim3(256), 0, stream, (const bf16_t*)x, (bf16_t*)y, n, lo, hi);
-    else
-        hipLaunchKernelGGL((clip_fwd_kernel<float>), dim3(ew_blocks(n)), dim3(256), 0, stream, (const float*)x, (float*)y, n, lo, hi);
-    return iseg_check_launch("iseg_clip_fwd");
+    return by_dtype(dtype, "iseg_clip_fwd", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((clip_fwd_kernel<T>), dim3(ew_blocks(n)), dim3(256), 0, stream, (const T*)x, (T*)y, n, lo, hi);
+        return iseg_check_launch("iseg_clip_fwd");
+    });
 }
 
 extern "C" int iseg_clip_bwd(const void* x, const void* dy, void* dx, int64_t n, float lo, float hi, int dtype, hipStream_t stream) {
     ISEG_REQUIRE(x && dy && dx && n > 0 && hi >= lo, "iseg_clip_bwd: bad arguments");
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL((clip_bwd_kernel<bf16_t>), dim3(ew_blocks(n)), dim3(256), 0, stream, (const bf16_t*)x, (const bf16_t*)dy,
-                           (bf16_t*)dx, n, lo, hi);
-    else
-        hipLaunchKernelGGL((clip_bwd_kernel<float>), dim3(ew_blocks(n)), dim3(256), 0, stream, (const float*)x, (const float*)dy,
-                           (float*)dx, n, lo, hi);
-    return iseg_check_launch("iseg_clip_bwd");
+    return by_dtype(dtype, "iseg_clip_bwd", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((clip_bwd_kernel<T>), dim3(ew_blocks(n)), dim3(256), 0, stream, (const T*)x, (const T*)dy, (T*)dx, n, lo, hi);
+        return iseg_check_launch("iseg_clip_bwd");
+    });
 }
 
 extern "C" int iseg_gather_rows(const void* x, const int32_t* idx, void* y, int64_t rows_in, int64_t rows_out, int C, int dtype,
@@ -410,22 +384,13 @@ extern "C" int iseg_gather_rows(const void* x, const int32_t* idx, void* y, int6
     (void)rows_in;   // the caller guarantees idx[r] < rows_in (index tables are built on the host from static geometry)
     const size_t es = dtype_size(dtype);
     const bool vec = ((size_t)C * es) % 16 == 0 && (uintptr_t)x % 16 == 0 && (uintptr_t)y % 16 == 0;
-    if (dtype == ISEG_BF16) {
-        if (vec)
-            hipLaunchKernelGGL((gather_rows_kernel<bf16_t, 8>), dim3(ew_blocks(rows_out * (C / 8))), dim3(256), 0, stream,
-                               (const bf16_t*)x, idx, (bf16_t*)y, rows_out, C);
-        else
-            hipLaunchKernelGGL((gather_rows_kernel<bf16_t, 1>), dim3(ew_blocks(rows_out * C)), dim3(256), 0, stream, (const bf16_t*)x,
-                               idx, (bf16_t*)y, rows_out, C);
-    } else {
-        if (vec)
-            hipLaunchKernelGGL((gather_rows_kernel<float, 4>), dim3(ew_blocks(rows_out * (C / 4))), dim3(256), 0, stream, (const float*)x,
-                               idx, (float*)y, rows_out, C);
-        else
-            hipLaunchKernelGGL((gather_rows_kernel<float, 1>), dim3(ew_blocks(rows_out * C)), dim3(256), 0, stream, (const float*)x, idx,
-                               (float*)y, rows_out, C);
-    }
-    return iseg_check_launch("iseg_gather_rows");
+    return by_dtype(dtype, "iseg_gather_rows", [&](auto t) {
+        using T = decltype(t);
+        constexpr int V = 16 / sizeof(T);      // elements of a 16-byte lane
+        hipLaunchKernelGGL((vec ? gather_rows_kernel<T, V> : gather_rows_kernel<T, 1>), dim3(ew_blocks(rows_out * (vec ? C / V : C))), dim3(256), 0,
+                           stream, (const T*)x, idx, (T*)y, rows_out, C);
+        return iseg_check_launch("iseg_gather_rows");
+    });
 }
 
 extern "C" int iseg_gather_rows_fma(const void* x, const int32_t* idx, const float* scale, int64_t rows_per_group, int scale_by_source_row,
@@ -433,13 +398,12 @@ extern "C" int iseg_gather_rows_fma(const void* x, const int32_t* idx, const flo
     ISEG_REQUIRE(x && idx && y && rows_out > 0 && C > 0 && C % 8 == 0, "iseg_gather_rows_fma: bad arguments (C = %d must be a multiple of 8)", C);
     ISEG_REQUIRE(!scale || rows_per_group > 0, "iseg_gather_rows_fma: scale needs rows_per_group > 0");
     ISEG_REQUIRE((((uintptr_t)x | (uintptr_t)y | (uintptr_t)residual) & 15) == 0, "iseg_gather_rows_fma: operands must be 16-byte aligned");
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL((gather_rows_fma_kernel<bf16_t>), dim3(ew_blocks(rows_out * (C / 8))), dim3(256), 0, stream, (const bf16_t*)x, idx, scale,
-                           rows_per_group, scale_by_source_row, (const bf16_t*)residual, (bf16_t*)y, rows_out, C);
-    else
-        hipLaunchKernelGGL((gather_rows_fma_kernel<float>), dim3(ew_blocks(rows_out * (C / 8))), dim3(256), 0, stream, (const float*)x, idx, scale,
-                           rows_per_group, scale_by_source_row, (const float*)residual, (float*)y, rows_out, C);
-    return iseg_check_launch("iseg_gather_rows_fma");
+    return by_dtype(dtype, "iseg_gather_rows_fma", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((gather_rows_fma_kernel<T>), dim3(ew_blocks(rows_out * (C / 8))), dim3(256), 0, stream, (const T*)x, idx, scale,
+                           rows_per_group, scale_by_source_row, (const T*)residual, (T*)y, rows_out, C);
+        return iseg_check_launch("iseg_gather_rows_fma");
+    });
 }
 
 extern "C" int iseg_relpos_bias_scatter_grad_window(const float* dbias, int ld, float* dtable, int ws, int heads, int accumulate,
@@ -459,15 +423,13 @@ extern "C" int iseg_colsum_wide(const void* x, int64_t ldx, int64_t rows, int64_
     ISEG_REQUIRE(x && out && rows > 0 && cols > 0 && ldx >= cols, "iseg_colsum_wide: bad arguments");
     const int chunks = wide_chunks(rows);
     const size_t need = (size_t)chunks * (size_t)cols * sizeof(float);
-    if (!ws || ws_bytes < need) {
-        iseg_set_error("iseg_colsum_wide: needs %zu workspace bytes, got %zu", need, ws_bytes);
-        return ISEG_ERR_WORKSPACE;
-    }
+    ISEG_NEED_WORKSPACE("iseg_colsum_wide", ws, ws_bytes, need);
     const dim3 grid((unsigned)ceil_div64(cols, 256), chunks);
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL((colsum_wide_partial_kernel<bf16_t>), grid, dim3(256), 0, stream, (const bf16_t*)x, ldx, rows, cols, (float*)ws);
-    else
-        hipLaunchKernelGGL((colsum_wide_partial_kernel<float>), grid, dim3(256), 0, stream, (const float*)x, ldx, rows, cols, (float*)ws);
+    const int rc = by_dtype(dtype, "iseg_colsum_wide", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((colsum_wide_partial_kernel<T>), grid, dim3(256), 0, stream, (const T*)x, ldx, rows, cols, (float*)ws);
+    });
+    if (rc != ISEG_OK) return rc;
     launch_reduce_rows((const float*)ws, chunks, cols, 0, 1, cols, out, nullptr, cols, 0, 1.f, accumulate, stream);
     return iseg_check_launch("iseg_colsum_wide");
 }

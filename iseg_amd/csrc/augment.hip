@@ -210,10 +210,7 @@ extern "C" int iseg_augment_channel_means(const void* images, int image_dtype, c
                                           void* ws, size_t ws_bytes, hipStream_t stream) {
     ISEG_REQUIRE(images && params && fparams && B > 0 && Hs > 0 && Ws > 0, "iseg_augment_channel_means: bad arguments");
     ISEG_REQUIRE(image_dtype == ISEG_F32 || image_dtype == 2, "iseg_augment_channel_means: images must be float32 (0) or uint8 (2)");
-    if (!ws || ws_bytes < iseg_augment_means_workspace_bytes(B)) {
-        iseg_set_error("iseg_augment_channel_means: needs %zu workspace bytes, got %zu", iseg_augment_means_workspace_bytes(B), ws_bytes);
-        return ISEG_ERR_WORKSPACE;
-    }
+    ISEG_NEED_WORKSPACE("iseg_augment_channel_means", ws, ws_bytes, iseg_augment_means_workspace_bytes(B));
     if (image_dtype == ISEG_F32)
         hipLaunchKernelGGL((augment_means_kernel<float>), dim3(AUG_MEAN_BLOCKS, B), dim3(256), 0, stream, (const float*)images, params, fparams,
                            (float*)ws, Hs, Ws);
@@ -235,7 +232,7 @@ extern "C" int iseg_augment_crop_batch(const void* images, int image_dtype, cons
     AugConst k;
     for (int c = 0; c < 3; ++c) k.mean[c] = mean_pixel[c], k.a[c] = norm_scale[c], k.b[c] = norm_shift[c];
     const int64_t total = (int64_t)B * crop_h * crop_w;
-    const unsigned blocks = (unsigned)(ceil_div64(total, 256) < 8192 ? ceil_div64(total, 256) : 8192);
+    const unsigned blocks = grid_cap(total, 256, 8192);
     if (image_dtype == ISEG_F32)
         hipLaunchKernelGGL((augment_crop_kernel<float>), dim3(blocks), dim3(256), 0, stream, (const float*)images, labels, params, fparams, k,
                            ignore_label, out_images, out_labels, B, Hs, Ws, crop_h, crop_w, seed);
@@ -250,7 +247,7 @@ extern "C" int iseg_normalize_image(const float* x, float* y, int64_t pixels, co
     AugConst k{};
     for (int c = 0; c < 3; ++c) k.a[c] = norm_scale[c], k.b[c] = norm_shift[c];
     const int64_t n = pixels * 3;
-    const unsigned blocks = (unsigned)(ceil_div64(n, 256) < 8192 ? ceil_div64(n, 256) : 8192);
+    const unsigned blocks = grid_cap(n, 256, 8192);
     hipLaunchKernelGGL(normalize3_kernel, dim3(blocks), dim3(256), 0, stream, x, y, n, k);
     return iseg_check_launch("iseg_normalize_image");
 }

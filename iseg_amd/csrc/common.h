@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <type_traits>
 
 #define ISEG_OK 0
 #define ISEG_ERR_ARG (-1)
@@ -36,8 +37,41 @@ int iseg_check_launch(const char* what);
         }                                       \
     } while (0)
 
+// the workspace check of every launcher: a null or short workspace is refused with both numbers
+#define ISEG_NEED_WORKSPACE(who, ws, ws_bytes, need)                                                                                      \
+    do {                                                                                                                                  \
+        const size_t need_ = (need);                                                                                                      \
+        ISEG_REQUIRE_WORKSPACE((ws) && (size_t)(ws_bytes) >= need_, "%s: needs %zu workspace bytes, got %zu", who, need_, (size_t)(ws_bytes)); \
+    } while (0)
+
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline size_t dtype_size(int dtype) { return dtype == ISEG_BF16 ? 2 : 4; }
+
+// blocks of a grid-stride launch: one block per `per_block` items, at least 1, at most `cap`
+static inline unsigned grid_cap(int64_t items, int64_t per_block, int64_t cap) {
+    const int64_t b = ceil_div64(items, per_block);
+    return (unsigned)(b < 1 ? 1 : b > cap ? cap : b);
+}
+
+// a compile-time int as a launcher argument: generic lambdas pick kernel<..., V> from decltype(v)::value
+template <int V> using IntC = std::integral_constant<int, V>;
+
+// Storage-type dispatch: f(bf16_t{}) or f(float{}); any other dtype is an argument error and nothing runs.  A functor returning void
+// gives ISEG_OK (the launcher goes on to its follow-up launches and one iseg_check_launch), one returning int is passed through.
+template <class F> static inline int by_dtype(int dtype, const char* who, F&& f) {
+    auto call = [&](auto t) -> int {
+        if constexpr (std::is_void_v<decltype(f(t))>) {
+            f(t);
+            return ISEG_OK;
+        } else {
+            return f(t);
+        }
+    };
+    if (dtype == ISEG_BF16) return call(bf16_t{});
+    if (dtype == ISEG_F32) return call(float{});
+    iseg_set_error("%s: dtype %d", who, dtype);
+    return ISEG_ERR_ARG;
+}
 
 // ---- device helpers ---------------------------------------------------------------------
 typedef __attribute__((ext_vector_type(4))) float f32x4;

@@ -349,10 +349,7 @@ template <int PASS, class TO> int run(const Problem& q, void* ws, size_t ws_byte
     float* slabs = nullptr;
     if (nsplit > 1) {
         const size_t need = (size_t)nsplit * q.groups * q.M * q.N * sizeof(float);
-        if (!ws || ws_bytes < need) {
-            iseg_set_error("%s: split-K needs %zu workspace bytes, got %zu", what, need, ws_bytes);
-            return ISEG_ERR_WORKSPACE;
-        }
+        ISEG_NEED_WORKSPACE(what, ws, ws_bytes, need);
         slabs = (float*)ws;
         kps = ceil_div64(ceil_div64(q.K, nsplit), 64) * 64;
     }
@@ -463,10 +460,7 @@ template <int PASS> int run_dma(const Problem& q, void* ws, size_t ws_bytes, hip
     float* slabs = nullptr;
     if (nsplit > 1) {
         const size_t need = (size_t)nsplit * q.M * q.N * sizeof(float);
-        if (!ws || ws_bytes < need) {
-            iseg_set_error("%s: split-K needs %zu workspace bytes, got %zu", what, need, ws_bytes);
-            return ISEG_ERR_WORKSPACE;
-        }
+        ISEG_NEED_WORKSPACE(what, ws, ws_bytes, need);
         slabs = (float*)ws;
         kps = ceil_div64(ceil_div64(q.K, nsplit), 64) * 64;
     }
@@ -783,7 +777,7 @@ extern "C" int iseg_conv2d_branches_bwd_data(const iseg_conv_branches* t, void* 
     if (plan.nsplit > 1) {
         const iseg_conv_geom joined = branches_joined_geom(t);
         const size_t need = iseg_conv2d_igemm_workspace_bytes(&joined, 1);
-        ISEG_REQUIRE_WORKSPACE(ws && ws_bytes >= need, "iseg_conv2d_branches_bwd_data: split-K needs %zu workspace bytes, got %zu", need, ws_bytes);
+        ISEG_NEED_WORKSPACE("iseg_conv2d_branches_bwd_data", ws, ws_bytes, need);
         slabs = (float*)ws;
         kps = ceil_div64(ceil_div64(K, plan.nsplit), 64) * 64;
     }

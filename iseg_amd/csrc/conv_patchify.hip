@@ -169,10 +169,7 @@ extern "C" int iseg_conv2d_patch_bwd_weight(const void* x, const void* dy, float
     const int nsplit = iseg_gemm_splits(&a);
     const int64_t slab_rows = a.M + (a.colsum_out ? 1 : 0);
     const size_t need = (size_t)nsplit * slab_rows * a.N * sizeof(float);
-    if (!ws || ws_bytes < need) {
-        iseg_set_error("iseg_conv2d_patch_bwd_weight: needs %zu workspace bytes, got %zu", need, ws_bytes);
-        return ISEG_ERR_WORKSPACE;
-    }
+    ISEG_NEED_WORKSPACE("iseg_conv2d_patch_bwd_weight", ws, ws_bytes, need);
     const int64_t kps = ceil_div64(ceil_div64(a.K, nsplit), 128) * 128;
     const int eff = (int)ceil_div64(a.K, kps);
     TnPatch pv{g->Wo, g->KW * g->Cin, (int64_t)g->KH * g->W * g->Cin, (int64_t)g->W * g->Cin, 0};

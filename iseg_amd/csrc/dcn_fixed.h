@@ -57,11 +57,6 @@ __global__ __launch_bounds__(256) void dcn_zero_kernel(uint4* __restrict__ p, in
     for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n16; i += (int64_t)gridDim.x * 256) p[i] = make_uint4(0u, 0u, 0u, 0u);
 }
 
-static inline unsigned lane_blocks(int64_t n) {
-    int64_t b = ceil_div64(n, 256);
-    if (b > 256 * 64) b = 256 * 64;
-    if (b < 1) b = 1;
-    return (unsigned)b;
-}
+static inline unsigned lane_blocks(int64_t n) { return grid_cap(n, 256, 256 * 64); }
 
 }  // namespace

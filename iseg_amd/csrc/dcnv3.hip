@@ -725,12 +725,7 @@ __global__ __launch_bounds__(256) void scale_cols_vec_kernel(const T* __restrict
     }
 }
 
-static inline int mc_blocks(int64_t rows) {
-    int64_t b = ceil_div64(rows, 64);
-    if (b > 1024) b = 1024;
-    if (b < 1) b = 1;
-    return (int)b;
-}
+static inline int mc_blocks(int64_t rows) { return (int)grid_cap(rows, 64, 1024); }
 
 static int make_geom(DcnGeom* g, int N, int H, int W, int G, int Cg, int kh, int kw, int stride, int dil, int pad, float s,
                      const char* who) {
@@ -820,27 +815,14 @@ extern "C" int iseg_dcnv3_fwd_ld(const void* x, const void* offset, const void* 
     if (rc != ISEG_OK) return rc;
     const int64_t lanes = (int64_t)N * g.Ho * g.Wo * G;
     const bool v8 = Cg % 8 == 0 && (uintptr_t)x % 16 == 0 && (uintptr_t)y % 16 == 0;
-#define DCN_FWD(T, CV)                                                                                                              \
-    hipLaunchKernelGGL((dcnv3_fwd_kernel<T, CV>), dim3(lane_blocks(lanes)), dim3(256), 0, stream, (const T*)x, (const T*)offset,   \
-                       (const T*)mask, (T*)y, g)
-#define DCN_FWD_PIPE(T, CG)                                                                                                         \
-    hipLaunchKernelGGL((dcnv3_fwd_pipe_kernel<T, CG>), dim3(lane_blocks(lanes)), dim3(256), 0, stream, (const T*)x, (const T*)offset, \
-                       (const T*)mask, (T*)y, g)
     const bool pipe = v8 && (Cg == 8 || Cg == 16) && kh * kw <= DCN_PMAX;
-    if (dtype == ISEG_BF16) {
-        if (pipe && Cg == 16) DCN_FWD_PIPE(bf16_t, 16);
-        else if (pipe) DCN_FWD_PIPE(bf16_t, 8);
-        else if (v8) DCN_FWD(bf16_t, 8);
-        else DCN_FWD(bf16_t, 1);
-    } else {
-        if (pipe && Cg == 16) DCN_FWD_PIPE(float, 16);
-        else if (pipe) DCN_FWD_PIPE(float, 8);
-        else if (v8) DCN_FWD(float, 8);
-        else DCN_FWD(float, 1);
-    }
-#undef DCN_FWD_PIPE
-#undef DCN_FWD
-    return iseg_check_launch("iseg_dcnv3_fwd");
+    return by_dtype(dtype, "iseg_dcnv3_fwd", [&](auto t) {
+        using T = decltype(t);
+        const auto kernel = pipe ? (Cg == 16 ? dcnv3_fwd_pipe_kernel<T, 16> : dcnv3_fwd_pipe_kernel<T, 8>)
+                                 : (v8 ? dcnv3_fwd_kernel<T, 8> : dcnv3_fwd_kernel<T, 1>);
+        hipLaunchKernelGGL(kernel, dim3(lane_blocks(lanes)), dim3(256), 0, stream, (const T*)x, (const T*)offset, (const T*)mask, (T*)y, g);
+        return iseg_check_launch("iseg_dcnv3_fwd");
+    });
 }
 
 // general route: nel int64 accumulators (rounded up to 16 bytes) + a 16-byte slot whose first word is the non-finite flag
@@ -883,6 +865,7 @@ extern "C" int iseg_dcnv3_bwd_ld(const void* x, const void* offset, const void* 
     void* const dx_f32 = dx;
     ISEG_REQUIRE(x && offset && mask && dy && dx_f32 && doffset && dmask, "iseg_dcnv3_bwd: null pointer");
     ISEG_REQUIRE(dx_dtype == ISEG_F32 || dx_dtype == ISEG_BF16, "iseg_dcnv3_bwd_ld: dx_dtype %d", dx_dtype);
+    ISEG_REQUIRE(dtype == ISEG_BF16 || dtype == ISEG_F32, "iseg_dcnv3_bwd: dtype %d", dtype);      // (before the first launch)
     DcnGeom g;
     int rc = make_geom(&g, N, H, W, G, Cg, kh, kw, stride, dil, pad, offset_scale, "iseg_dcnv3_bwd");
     if (rc != ISEG_OK) return rc;
@@ -893,10 +876,7 @@ extern "C" int iseg_dcnv3_bwd_ld(const void* x, const void* offset, const void* 
     if (dcn_window(g, &wn)) {
         size_t side_off, flag_off;
         const size_t need = dcn_win_bytes(g, wn, &side_off, &flag_off);
-        if (!ws || ws_bytes < need) {
-            iseg_set_error("iseg_dcnv3_bwd: needs %zu workspace bytes, got %zu", need, ws_bytes);
-            return ISEG_ERR_WORKSPACE;
-        }
+        ISEG_NEED_WORKSPACE("iseg_dcnv3_bwd", ws, ws_bytes, need);
         float* windows = (float*)ws;
         unsigned long long* side = (unsigned long long*)((char*)ws + side_off);
         int* flag = (int*)((char*)ws + flag_off);
@@ -914,35 +894,29 @@ extern "C" int iseg_dcnv3_bwd_ld(const void* x, const void* offset, const void* 
         const size_t cells = Cg == 16 ? DcnWinLds<16>::CELLS : DcnWinLds<8>::CELLS;
         const size_t stage_bytes = (size_t)256 * 3 * DCN_PMAX * (dtype == ISEG_BF16 ? 2 : 4);      // staged mask / offset gradients
         const size_t lds = cells * (dtype == ISEG_BF16 ? sizeof(int) : sizeof(unsigned long long)) + stage_bytes;
-#define DCN_WIN(T, CG)                                                                                                                      \
-    do {                                                                                                                                    \
-        static const bool raised = [] {                                                                                                     \
-            return hipFuncSetAttribute(reinterpret_cast<const void*>(&dcnv3_bwd_win_kernel<T, CG>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                       DcnWinLds<CG>::CELLS * 8 + 256 * 3 * DCN_PMAX * 4) == hipSuccess;                                    \
-        }();                                                                                                                                \
-        (void)raised;                                                                                                                       \
-        hipLaunchKernelGGL((dcnv3_bwd_win_kernel<T, CG>), dim3(blocks), dim3(256), lds, stream, (const T*)x, (const T*)offset, (const T*)mask, \
-                           (const T*)dy, (T*)doffset, (T*)dmask, windows, side, flag, g, wn);                                               \
-    } while (0)
-        if (dtype == ISEG_BF16) {
-            if (Cg == 16) DCN_WIN(bf16_t, 16);
-            else DCN_WIN(bf16_t, 8);
-        } else {
-            if (Cg == 16) DCN_WIN(float, 16);
-            else DCN_WIN(float, 8);
-        }
-#undef DCN_WIN
+        rc = by_dtype(dtype, "iseg_dcnv3_bwd", [&](auto t) {
+            using T = decltype(t);
+            auto win = [&](auto cg) {
+                constexpr int CG = decltype(cg)::value;
+                static const bool raised =
+                    hipFuncSetAttribute(reinterpret_cast<const void*>(&dcnv3_bwd_win_kernel<T, CG>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        DcnWinLds<CG>::CELLS * 8 + 256 * 3 * DCN_PMAX * 4) == hipSuccess;
+                (void)raised;
+                hipLaunchKernelGGL((dcnv3_bwd_win_kernel<T, CG>), dim3(blocks), dim3(256), lds, stream, (const T*)x, (const T*)offset, (const T*)mask,
+                                   (const T*)dy, (T*)doffset, (T*)dmask, windows, side, flag, g, wn);
+            };
+            if (Cg == 16) win(IntC<16>{});
+            else win(IntC<8>{});
+        });
+        if (rc != ISEG_OK) return rc;
         const int64_t threads = (int64_t)N * H * W * G * (Cg / 4);
-#define DCN_GATHER(CG, TO, RESET)                                                                                                          \
-    hipLaunchKernelGGL((dcnv3_bwd_gather_kernel<CG, TO, RESET>), dim3(lane_blocks(threads)), dim3(256), 0, stream, windows, side, flag, (TO*)dx, g, wn)
-        if (dx_dtype == ISEG_BF16) {
-            if (Cg == 16) { if (keep) DCN_GATHER(16, bf16_t, true); else DCN_GATHER(16, bf16_t, false); }
-            else { if (keep) DCN_GATHER(8, bf16_t, true); else DCN_GATHER(8, bf16_t, false); }
-        } else {
-            if (Cg == 16) { if (keep) DCN_GATHER(16, float, true); else DCN_GATHER(16, float, false); }
-            else { if (keep) DCN_GATHER(8, float, true); else DCN_GATHER(8, float, false); }
-        }
-#undef DCN_GATHER
+        rc = by_dtype(dx_dtype, "iseg_dcnv3_bwd", [&](auto t) {
+            using TO = decltype(t);
+            const auto kernel = Cg == 16 ? (keep ? dcnv3_bwd_gather_kernel<16, TO, true> : dcnv3_bwd_gather_kernel<16, TO, false>)
+                                         : (keep ? dcnv3_bwd_gather_kernel<8, TO, true> : dcnv3_bwd_gather_kernel<8, TO, false>);
+            hipLaunchKernelGGL(kernel, dim3(lane_blocks(threads)), dim3(256), 0, stream, windows, side, flag, (TO*)dx, g, wn);
+        });
+        if (rc != ISEG_OK) return rc;
         if (keep) hipLaunchKernelGGL(dcn_flag_reset_kernel, dim3(1), dim3(1), 0, stream, flag);
         return iseg_check_launch("iseg_dcnv3_bwd");
     }
@@ -951,10 +925,7 @@ extern "C" int iseg_dcnv3_bwd_ld(const void* x, const void* offset, const void* 
     const int64_t nel = (int64_t)N * H * W * G * Cg;
     const size_t need = dcn_general_bytes(nel);
     {
-        if (!ws || ws_bytes < need) {
-            iseg_set_error("iseg_dcnv3_bwd: needs %zu workspace bytes, got %zu", need, ws_bytes);
-            return ISEG_ERR_WORKSPACE;
-        }
+        ISEG_NEED_WORKSPACE("iseg_dcnv3_bwd", ws, ws_bytes, need);
         const int64_t n16 = (int64_t)need / 16;      // (a multiple of 16: accumulators and the flag slot are zeroed by one launch)
         hipLaunchKernelGGL(dcn_zero_kernel, dim3(lane_blocks(n16)), dim3(256), 0, stream, (uint4*)ws, n16);
     }
@@ -962,36 +933,25 @@ extern "C" int iseg_dcnv3_bwd_ld(const void* x, const void* offset, const void* 
     int* const gflag = (int*)((char*)ws + need - 16);
     const int64_t lanes = (int64_t)N * g.Ho * g.Wo * G;
     const bool v8 = Cg % 8 == 0 && (uintptr_t)x % 16 == 0 && (uintptr_t)dy % 16 == 0;
-#define DCN_BWD(T, CV)                                                                                                              \
-    hipLaunchKernelGGL((dcnv3_bwd_kernel<T, CV>), dim3(lane_blocks(lanes)), dim3(256), 0, stream, (const T*)x, (const T*)offset,   \
-                       (const T*)mask, (const T*)dy, acc, (T*)doffset, (T*)dmask, gflag, g)
-#define DCN_BWD_CL(T, LC)                                                                                                            \
-    hipLaunchKernelGGL((dcnv3_bwd_cl_kernel<T, LC>), dim3(lane_blocks(lanes * LC)), dim3(256), 0, stream, (const T*)x,              \
-                       (const T*)offset, (const T*)mask, (const T*)dy, acc, (T*)doffset, (T*)dmask, gflag, g)
-#define DCN_BWD_CL_ANY(T)                    \
-    do {                                     \
-        if (Cg == 4) DCN_BWD_CL(T, 4);       \
-        else if (Cg == 8) DCN_BWD_CL(T, 8);  \
-        else if (Cg == 16) DCN_BWD_CL(T, 16); \
-        else if (Cg == 32) DCN_BWD_CL(T, 32); \
-        else DCN_BWD_CL(T, 64);              \
-    } while (0)
-    const bool pow2 = Cg == 4 || Cg == 8 || Cg == 16 || Cg == 32 || Cg == 64;
-    if (dtype == ISEG_BF16) {
-        if (pow2) DCN_BWD_CL_ANY(bf16_t);
-        else if (v8) DCN_BWD(bf16_t, 8);
-        else DCN_BWD(bf16_t, 1);
-    } else {
-        if (pow2) DCN_BWD_CL_ANY(float);
-        else if (v8) DCN_BWD(float, 8);
-        else DCN_BWD(float, 1);
-    }
-#undef DCN_BWD_CL_ANY
-#undef DCN_BWD_CL
-#undef DCN_BWD
-    if (dx_dtype == ISEG_BF16)
-        hipLaunchKernelGGL(dcn_unfix_kernel<bf16_t>, dim3(lane_blocks(nel)), dim3(256), 0, stream, acc, (bf16_t*)dx, nel, (const int*)gflag);
-    else hipLaunchKernelGGL(dcn_unfix_kernel<float>, dim3(lane_blocks(nel)), dim3(256), 0, stream, acc, (float*)dx, nel, (const int*)gflag);
+    rc = by_dtype(dtype, "iseg_dcnv3_bwd", [&](auto t) {
+        using T = decltype(t);
+        auto launch = [&](auto kernel, int64_t work) {
+            hipLaunchKernelGGL(kernel, dim3(lane_blocks(work)), dim3(256), 0, stream, (const T*)x, (const T*)offset, (const T*)mask, (const T*)dy, acc,
+                               (T*)doffset, (T*)dmask, gflag, g);
+        };
+        if (Cg == 4) launch(dcnv3_bwd_cl_kernel<T, 4>, lanes * 4);
+        else if (Cg == 8) launch(dcnv3_bwd_cl_kernel<T, 8>, lanes * 8);
+        else if (Cg == 16) launch(dcnv3_bwd_cl_kernel<T, 16>, lanes * 16);
+        else if (Cg == 32) launch(dcnv3_bwd_cl_kernel<T, 32>, lanes * 32);
+        else if (Cg == 64) launch(dcnv3_bwd_cl_kernel<T, 64>, lanes * 64);
+        else launch(v8 ? dcnv3_bwd_kernel<T, 8> : dcnv3_bwd_kernel<T, 1>, lanes);
+    });
+    if (rc != ISEG_OK) return rc;
+    rc = by_dtype(dx_dtype, "iseg_dcnv3_bwd", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(dcn_unfix_kernel<T>, dim3(lane_blocks(nel)), dim3(256), 0, stream, acc, (T*)dx, nel, (const int*)gflag);
+    });
+    if (rc != ISEG_OK) return rc;
     return iseg_check_launch("iseg_dcnv3_bwd");
 }
 
@@ -1050,18 +1010,12 @@ extern "C" int iseg_dcn_center_blend_fwd(const void* x, const void* x_proj, cons
     ISEG_REQUIRE(x && x_proj && scale && out && pixels > 0 && G > 0, "iseg_dcn_center_blend_fwd: bad arguments");
     ISEG_REQUIRE(Cg == 8 || Cg == 16, "iseg_dcn_center_blend_fwd: group width %d (8 or 16)", Cg);
     const int64_t groups_total = pixels * G;
-#define DCN_BLEND(T, CG)                                                                                                                    \
-    hipLaunchKernelGGL((dcn_center_blend_fwd_kernel<T, CG>), dim3(lane_blocks(groups_total * (CG / 8))), dim3(256), 0, stream, (const T*)x, \
-                       (const T*)x_proj, (const T*)scale, (T*)out, groups_total)
-    if (dtype == ISEG_BF16) {
-        if (Cg == 16) DCN_BLEND(bf16_t, 16);
-        else DCN_BLEND(bf16_t, 8);
-    } else {
-        if (Cg == 16) DCN_BLEND(float, 16);
-        else DCN_BLEND(float, 8);
-    }
-#undef DCN_BLEND
-    return iseg_check_launch("iseg_dcn_center_blend_fwd");
+    return by_dtype(dtype, "iseg_dcn_center_blend_fwd", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((Cg == 16 ? dcn_center_blend_fwd_kernel<T, 16> : dcn_center_blend_fwd_kernel<T, 8>), dim3(lane_blocks(groups_total * (Cg / 8))),
+                           dim3(256), 0, stream, (const T*)x, (const T*)x_proj, (const T*)scale, (T*)out, groups_total);
+        return iseg_check_launch("iseg_dcn_center_blend_fwd");
+    });
 }
 
 extern "C" int iseg_dcn_center_blend_bwd(const void* dout, const void* x, const void* x_proj, const void* scale, void* dx, void* dx_proj,
@@ -1069,18 +1023,13 @@ extern "C" int iseg_dcn_center_blend_bwd(const void* dout, const void* x, const 
     ISEG_REQUIRE(dout && x && x_proj && scale && dx && dx_proj && dscale && pixels > 0 && G > 0, "iseg_dcn_center_blend_bwd: bad arguments");
     ISEG_REQUIRE(Cg == 8 || Cg == 16, "iseg_dcn_center_blend_bwd: group width %d (8 or 16)", Cg);
     const int64_t groups_total = pixels * G;
-#define DCN_BLEND(T, CG)                                                                                                                     \
-    hipLaunchKernelGGL((dcn_center_blend_bwd_kernel<T, CG>), dim3(lane_blocks(groups_total * (CG / 8))), dim3(256), 0, stream, (const T*)dout, \
-                       (const T*)x, (const T*)x_proj, (const T*)scale, (T*)dx, (T*)dx_proj, (T*)dscale, groups_total)
-    if (dtype == ISEG_BF16) {
-        if (Cg == 16) DCN_BLEND(bf16_t, 16);
-        else DCN_BLEND(bf16_t, 8);
-    } else {
-        if (Cg == 16) DCN_BLEND(float, 16);
-        else DCN_BLEND(float, 8);
-    }
-#undef DCN_BLEND
-    return iseg_check_launch("iseg_dcn_center_blend_bwd");
+    return by_dtype(dtype, "iseg_dcn_center_blend_bwd", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((Cg == 16 ? dcn_center_blend_bwd_kernel<T, 16> : dcn_center_blend_bwd_kernel<T, 8>), dim3(lane_blocks(groups_total * (Cg / 8))),
+                           dim3(256), 0, stream, (const T*)dout, (const T*)x, (const T*)x_proj, (const T*)scale, (T*)dx, (T*)dx_proj, (T*)dscale,
+                           groups_total);
+        return iseg_check_launch("iseg_dcn_center_blend_bwd");
+    });
 }
 
 extern "C" size_t iseg_mul_colsum_workspace_bytes(int64_t rows, int C) { return (size_t)mc_blocks(rows) * C * sizeof(float); }
@@ -1091,23 +1040,14 @@ extern "C" int iseg_mul_colsum(const void* a, const void* b, int64_t rows, int C
     int blocks = mc_blocks(rows);
     if (C % 8 == 0 && ((uintptr_t)a | (uintptr_t)b) % 16 == 0 && blocks > 256) blocks = 256;      // vector kernel: one round of blocks
     const size_t need = (size_t)blocks * C * sizeof(float);
-    if (!ws || ws_bytes < need) {
-        iseg_set_error("iseg_mul_colsum: needs %zu workspace bytes, got %zu", need, ws_bytes);
-        return ISEG_ERR_WORKSPACE;
-    }
+    ISEG_NEED_WORKSPACE("iseg_mul_colsum", ws, ws_bytes, need);
     const bool vec = C % 8 == 0 && ((uintptr_t)a | (uintptr_t)b) % 16 == 0;
-    if (vec && dtype == ISEG_BF16)
-        hipLaunchKernelGGL((mul_colsum_partial_vec_kernel<bf16_t>), dim3(blocks), dim3(256), mc_slab_bytes(C), stream,
-                           (const bf16_t*)a, (const bf16_t*)b, rows, C, (float*)ws);
-    else if (vec)
-        hipLaunchKernelGGL((mul_colsum_partial_vec_kernel<float>), dim3(blocks), dim3(256), mc_slab_bytes(C), stream,
-                           (const float*)a, (const float*)b, rows, C, (float*)ws);
-    else if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL((mul_colsum_partial_kernel<bf16_t>), dim3(blocks), dim3(256), 0, stream, (const bf16_t*)a, (const bf16_t*)b,
-                           rows, C, (float*)ws);
-    else
-        hipLaunchKernelGGL((mul_colsum_partial_kernel<float>), dim3(blocks), dim3(256), 0, stream, (const float*)a, (const float*)b, rows,
-                           C, (float*)ws);
+    const int rc = by_dtype(dtype, "iseg_mul_colsum", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((vec ? mul_colsum_partial_vec_kernel<T> : mul_colsum_partial_kernel<T>), dim3(blocks), dim3(256), vec ? mc_slab_bytes(C) : 0,
+                           stream, (const T*)a, (const T*)b, rows, C, (float*)ws);
+    });
+    if (rc != ISEG_OK) return rc;
     launch_reduce_rows((const float*)ws, blocks, C, 0, 1, C, out, nullptr, C, 0, 1.f, accumulate, stream);
     return iseg_check_launch("iseg_mul_colsum");
 }
@@ -1116,19 +1056,13 @@ extern "C" int iseg_scale_cols(const void* x, const float* colscale, void* y, in
     ISEG_REQUIRE(x && colscale && y && rows > 0 && C > 0, "iseg_scale_cols: bad arguments");
     const int64_t n = rows * C;
     const bool vec = C % 8 == 0 && ((uintptr_t)x | (uintptr_t)y) % 16 == 0 && (uintptr_t)colscale % 16 == 0;
-    if (vec && dtype == ISEG_BF16)
-        hipLaunchKernelGGL((scale_cols_vec_kernel<bf16_t>), dim3(lane_blocks(n / 8)), dim3(256), 0, stream, (const bf16_t*)x, colscale,
-                           (bf16_t*)y, n / 8, C);
-    else if (vec)
-        hipLaunchKernelGGL((scale_cols_vec_kernel<float>), dim3(lane_blocks(n / 8)), dim3(256), 0, stream, (const float*)x, colscale,
-                           (float*)y, n / 8, C);
-    else if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL((scale_cols_kernel<bf16_t>), dim3(lane_blocks(n)), dim3(256), 0, stream, (const bf16_t*)x, colscale, (bf16_t*)y,
-                           n, C);
-    else
-        hipLaunchKernelGGL((scale_cols_kernel<float>), dim3(lane_blocks(n)), dim3(256), 0, stream, (const float*)x, colscale, (float*)y, n,
-                           C);
-    return iseg_check_launch("iseg_scale_cols");
+    const int64_t items = vec ? n / 8 : n;
+    return by_dtype(dtype, "iseg_scale_cols", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((vec ? scale_cols_vec_kernel<T> : scale_cols_kernel<T>), dim3(lane_blocks(items)), dim3(256), 0, stream, (const T*)x, colscale,
+                           (T*)y, items, C);
+        return iseg_check_launch("iseg_scale_cols");
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------------
@@ -1267,13 +1201,12 @@ extern "C" int iseg_dcnv2_sample_fwd(const void* x, const void* offset, void* co
     ISEG_REQUIRE(x && offset && col && N > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, "iseg_dcnv2_sample_fwd: bad arguments (C = %d must be a multiple of 8)", C);
     ISEG_REQUIRE((int64_t)N * H * W * 9 * C < (1ll << 40), "iseg_dcnv2_sample_fwd: tensor too large");
     const int64_t lanes = (int64_t)N * H * W * 9 * (C / 8);
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL((dcnv2_sample_fwd_kernel<bf16_t>), dim3(lane_blocks(lanes)), dim3(256), 0, stream, (const bf16_t*)x, (const bf16_t*)offset, (bf16_t*)col,
-                           N, H, W, C);
-    else
-        hipLaunchKernelGGL((dcnv2_sample_fwd_kernel<float>), dim3(lane_blocks(lanes)), dim3(256), 0, stream, (const float*)x, (const float*)offset, (float*)col, N,
-                           H, W, C);
-    return iseg_check_launch("iseg_dcnv2_sample_fwd");
+    return by_dtype(dtype, "iseg_dcnv2_sample_fwd", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((dcnv2_sample_fwd_kernel<T>), dim3(lane_blocks(lanes)), dim3(256), 0, stream, (const T*)x, (const T*)offset, (T*)col, N, H,
+                           W, C);
+        return iseg_check_launch("iseg_dcnv2_sample_fwd");
+    });
 }
 
 extern "C" size_t iseg_dcnv2_sample_bwd_workspace_bytes(int N, int H, int W, int C) {
@@ -1283,22 +1216,20 @@ extern "C" size_t iseg_dcnv2_sample_bwd_workspace_bytes(int N, int H, int W, int
 extern "C" int iseg_dcnv2_sample_bwd(const void* x, const void* offset, const void* dcol, float* dx_f32, void* doffset, int N, int H, int W, int C,
                                      int dtype, void* ws, size_t ws_bytes, hipStream_t stream) {
     ISEG_REQUIRE(x && offset && dcol && dx_f32 && doffset && N > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, "iseg_dcnv2_sample_bwd: bad arguments");
+    ISEG_REQUIRE(dtype == ISEG_BF16 || dtype == ISEG_F32, "iseg_dcnv2_sample_bwd: dtype %d", dtype);      // (before the first launch)
     const size_t need = iseg_dcnv2_sample_bwd_workspace_bytes(N, H, W, C);
-    if (!ws || ws_bytes < need) {
-        iseg_set_error("iseg_dcnv2_sample_bwd: needs %zu workspace bytes, got %zu", need, ws_bytes);
-        return ISEG_ERR_WORKSPACE;
-    }
+    ISEG_NEED_WORKSPACE("iseg_dcnv2_sample_bwd", ws, ws_bytes, need);
     const int64_t nel = (int64_t)N * H * W * C, n16 = (int64_t)(need / 16);
     unsigned long long* acc = (unsigned long long*)ws;
     hipLaunchKernelGGL(dcn_zero_kernel, dim3(lane_blocks(n16)), dim3(256), 0, stream, (uint4*)ws, n16);
     constexpr int LC = 8;
     const int64_t lanes = (int64_t)N * H * W * 9 * LC;
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL((dcnv2_sample_bwd_kernel<bf16_t, LC>), dim3(lane_blocks(lanes)), dim3(256), 0, stream, (const bf16_t*)x, (const bf16_t*)offset,
-                           (const bf16_t*)dcol, acc, (bf16_t*)doffset, N, H, W, C);
-    else
-        hipLaunchKernelGGL((dcnv2_sample_bwd_kernel<float, LC>), dim3(lane_blocks(lanes)), dim3(256), 0, stream, (const float*)x, (const float*)offset,
-                           (const float*)dcol, acc, (float*)doffset, N, H, W, C);
+    const int rc = by_dtype(dtype, "iseg_dcnv2_sample_bwd", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((dcnv2_sample_bwd_kernel<T, LC>), dim3(lane_blocks(lanes)), dim3(256), 0, stream, (const T*)x, (const T*)offset,
+                           (const T*)dcol, acc, (T*)doffset, N, H, W, C);
+    });
+    if (rc != ISEG_OK) return rc;
     hipLaunchKernelGGL(dcn_unfix_kernel<float>, dim3(lane_blocks(nel)), dim3(256), 0, stream, acc, dx_f32, nel, (const int*)nullptr);
     return iseg_check_launch("iseg_dcnv2_sample_bwd");
 }
@@ -1380,23 +1311,22 @@ __global__ __launch_bounds__(256) void split_cols_accumulate_kernel(const float*
 extern "C" int iseg_dcn_mask_softmax_fwd(void* om, int64_t pixels, int G, int P, int64_t ld, int col0, int dtype, hipStream_t stream) {
     ISEG_REQUIRE(om && pixels > 0 && G > 0 && P > 0 && P <= DCN_PMAX && col0 >= 0 && ld >= col0 + (int64_t)G * P && ld < (1 << 30),
                  "iseg_dcn_mask_softmax_fwd: bad arguments (P <= %d)", DCN_PMAX);
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL(dcn_mask_softmax_fwd_kernel<bf16_t>, dim3(lane_blocks(pixels * G)), dim3(256), 0, stream, (bf16_t*)om, pixels, G, P, (int)ld, col0);
-    else
-        hipLaunchKernelGGL(dcn_mask_softmax_fwd_kernel<float>, dim3(lane_blocks(pixels * G)), dim3(256), 0, stream, (float*)om, pixels, G, P, (int)ld, col0);
-    return iseg_check_launch("iseg_dcn_mask_softmax_fwd");
+    return by_dtype(dtype, "iseg_dcn_mask_softmax_fwd", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(dcn_mask_softmax_fwd_kernel<T>, dim3(lane_blocks(pixels * G)), dim3(256), 0, stream, (T*)om, pixels, G, P, (int)ld, col0);
+        return iseg_check_launch("iseg_dcn_mask_softmax_fwd");
+    });
 }
 
 extern "C" int iseg_dcn_mask_softmax_bwd(const void* om, void* dom, int64_t pixels, int G, int P, int64_t ld, int col0, int dtype, hipStream_t stream) {
     ISEG_REQUIRE(om && dom && pixels > 0 && G > 0 && P > 0 && P <= DCN_PMAX && col0 >= 0 && ld >= col0 + (int64_t)G * P && ld < (1 << 30),
                  "iseg_dcn_mask_softmax_bwd: bad arguments (P <= %d)", DCN_PMAX);
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL(dcn_mask_softmax_bwd_kernel<bf16_t>, dim3(lane_blocks(pixels * G)), dim3(256), 0, stream, (const bf16_t*)om, (bf16_t*)dom, pixels, G,
-                           P, (int)ld, col0);
-    else
-        hipLaunchKernelGGL(dcn_mask_softmax_bwd_kernel<float>, dim3(lane_blocks(pixels * G)), dim3(256), 0, stream, (const float*)om, (float*)dom, pixels, G, P,
+    return by_dtype(dtype, "iseg_dcn_mask_softmax_bwd", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(dcn_mask_softmax_bwd_kernel<T>, dim3(lane_blocks(pixels * G)), dim3(256), 0, stream, (const T*)om, (T*)dom, pixels, G, P,
                            (int)ld, col0);
-    return iseg_check_launch("iseg_dcn_mask_softmax_bwd");
+        return iseg_check_launch("iseg_dcn_mask_softmax_bwd");
+    });
 }
 
 // dst0 [rows][n0] += src[:, 0:n0],  dst1 [rows][n1] += src[:, n0:n0+n1]   (src [rows][ld] fp32; a null destination is skipped)

@@ -265,34 +265,18 @@ static size_t da_ws_bytes(int64_t nel) { return ((size_t)nel * sizeof(unsigned l
 extern "C" int iseg_defattn_fwd(const void* value, const void* offset_logits, const void* attn_logits, void* out, int N, int H, int W, int heads,
                                 int P, int Ch, float offset_range_factor, int dtype, hipStream_t stream) {
     ISEG_REQUIRE(value && offset_logits && attn_logits && out, "iseg_defattn_fwd: null pointer");
-    ISEG_REQUIRE(dtype == ISEG_F32 || dtype == ISEG_BF16, "iseg_defattn_fwd: dtype %d", dtype);
     DaGeom g;
     const int rc = da_geom(&g, N, H, W, heads, P, Ch, offset_range_factor, "iseg_defattn_fwd");
     if (rc != ISEG_OK) return rc;
     const bool v8 = Ch % 8 == 0 && (uintptr_t)value % 16 == 0 && (uintptr_t)out % 16 == 0;
-    if (v8) {
-        const int64_t lanes = (int64_t)N * H * W * heads * (Ch / 8);
-#define DA_FWD_VEC(T, PM)                                                                                                             \
-    hipLaunchKernelGGL((defattn_fwd_vec_kernel<T, PM>), dim3(lane_blocks(lanes)), dim3(256), 0, stream, (const T*)value,             \
-                       (const T*)offset_logits, (const T*)attn_logits, (T*)out, g)
-        if (dtype == ISEG_BF16) {
-            if (P <= 4) DA_FWD_VEC(bf16_t, 4);
-            else DA_FWD_VEC(bf16_t, DA_PMAX);
-        } else {
-            if (P <= 4) DA_FWD_VEC(float, 4);
-            else DA_FWD_VEC(float, DA_PMAX);
-        }
-#undef DA_FWD_VEC
-    } else {
-        const int64_t lanes = (int64_t)N * H * W * heads * Ch;
-        if (dtype == ISEG_BF16)
-            hipLaunchKernelGGL((defattn_fwd_kernel<bf16_t>), dim3(lane_blocks(lanes)), dim3(256), 0, stream, (const bf16_t*)value,
-                               (const bf16_t*)offset_logits, (const bf16_t*)attn_logits, (bf16_t*)out, g);
-        else
-            hipLaunchKernelGGL((defattn_fwd_kernel<float>), dim3(lane_blocks(lanes)), dim3(256), 0, stream, (const float*)value,
-                               (const float*)offset_logits, (const float*)attn_logits, (float*)out, g);
-    }
-    return iseg_check_launch("iseg_defattn_fwd");
+    const int64_t lanes = (int64_t)N * H * W * heads * (v8 ? Ch / 8 : Ch);
+    return by_dtype(dtype, "iseg_defattn_fwd", [&](auto t) {
+        using T = decltype(t);
+        const auto kernel = v8 ? (P <= 4 ? defattn_fwd_vec_kernel<T, 4> : defattn_fwd_vec_kernel<T, DA_PMAX>) : defattn_fwd_kernel<T>;
+        hipLaunchKernelGGL(kernel, dim3(lane_blocks(lanes)), dim3(256), 0, stream, (const T*)value, (const T*)offset_logits, (const T*)attn_logits,
+                           (T*)out, g);
+        return iseg_check_launch("iseg_defattn_fwd");
+    });
 }
 
 extern "C" size_t iseg_defattn_bwd_workspace_bytes(int N, int H, int W, int heads, int Ch) {
@@ -304,40 +288,29 @@ extern "C" int iseg_defattn_bwd(const void* value, const void* offset_logits, co
                                 void* doffset_logits, void* dattn_logits, int N, int H, int W, int heads, int P, int Ch, float offset_range_factor,
                                 int dtype, void* ws, size_t ws_bytes, hipStream_t stream) {
     ISEG_REQUIRE(value && offset_logits && attn_logits && dout && dvalue && doffset_logits && dattn_logits, "iseg_defattn_bwd: null pointer");
-    ISEG_REQUIRE(dtype == ISEG_F32 || dtype == ISEG_BF16, "iseg_defattn_bwd: dtype %d", dtype);
+    ISEG_REQUIRE(dtype == ISEG_BF16 || dtype == ISEG_F32, "iseg_defattn_bwd: dtype %d", dtype);      // (before the first launch)
     DaGeom g;
     const int rc = da_geom(&g, N, H, W, heads, P, Ch, offset_range_factor, "iseg_defattn_bwd");
     if (rc != ISEG_OK) return rc;
     const int64_t nel = (int64_t)N * H * W * heads * Ch;
     const size_t need = da_ws_bytes(nel);
-    if (!ws || ws_bytes < need || (uintptr_t)ws % 16 != 0) {
-        iseg_set_error("iseg_defattn_bwd: needs %zu workspace bytes (16-byte aligned), got %zu", need, ws_bytes);
-        return ISEG_ERR_WORKSPACE;
-    }
+    ISEG_NEED_WORKSPACE("iseg_defattn_bwd", ws, ws_bytes, need);
+    ISEG_REQUIRE_WORKSPACE((uintptr_t)ws % 16 == 0, "iseg_defattn_bwd: the workspace must be 16-byte aligned");
     const int64_t n16 = (int64_t)need / 16;      // (accumulators and the flag slot are zeroed by one launch)
     hipLaunchKernelGGL(dcn_zero_kernel, dim3(lane_blocks(n16)), dim3(256), 0, stream, (uint4*)ws, n16);
     unsigned long long* const acc = (unsigned long long*)ws;
     int* const flag = (int*)((char*)ws + need - 16);
     const int64_t items = (int64_t)N * H * W * heads;
-#define DA_BWD(T, LC, PM)                                                                                                             \
-    hipLaunchKernelGGL((defattn_bwd_kernel<T, LC, PM>), dim3(lane_blocks(items * LC)), dim3(256), 0, stream, (const T*)value,        \
-                       (const T*)offset_logits, (const T*)attn_logits, (const T*)dout, acc, (T*)doffset_logits, (T*)dattn_logits, flag, g)
-#define DA_BWD_LC(T, PM)                     \
-    do {                                     \
-        if (Ch <= 4) DA_BWD(T, 4, PM);       \
-        else if (Ch <= 16) DA_BWD(T, 16, PM); \
-        else DA_BWD(T, 64, PM);              \
-    } while (0)
-    if (dtype == ISEG_BF16) {
-        if (P <= 4) DA_BWD_LC(bf16_t, 4);
-        else DA_BWD_LC(bf16_t, DA_PMAX);
-        hipLaunchKernelGGL(dcn_unfix_kernel<bf16_t>, dim3(lane_blocks(nel)), dim3(256), 0, stream, acc, (bf16_t*)dvalue, nel, (const int*)flag);
-    } else {
-        if (P <= 4) DA_BWD_LC(float, 4);
-        else DA_BWD_LC(float, DA_PMAX);
-        hipLaunchKernelGGL(dcn_unfix_kernel<float>, dim3(lane_blocks(nel)), dim3(256), 0, stream, acc, (float*)dvalue, nel, (const int*)flag);
-    }
-#undef DA_BWD_LC
-#undef DA_BWD
-    return iseg_check_launch("iseg_defattn_bwd");
+    return by_dtype(dtype, "iseg_defattn_bwd", [&](auto t) {
+        using T = decltype(t);
+        auto launch = [&](auto kernel4, auto kernel, int lc) {
+            hipLaunchKernelGGL((P <= 4 ? kernel4 : kernel), dim3(lane_blocks(items * lc)), dim3(256), 0, stream, (const T*)value, (const T*)offset_logits,
+                               (const T*)attn_logits, (const T*)dout, acc, (T*)doffset_logits, (T*)dattn_logits, flag, g);
+        };
+        if (Ch <= 4) launch(defattn_bwd_kernel<T, 4, 4>, defattn_bwd_kernel<T, 4, DA_PMAX>, 4);
+        else if (Ch <= 16) launch(defattn_bwd_kernel<T, 16, 4>, defattn_bwd_kernel<T, 16, DA_PMAX>, 16);
+        else launch(defattn_bwd_kernel<T, 64, 4>, defattn_bwd_kernel<T, 64, DA_PMAX>, 64);
+        hipLaunchKernelGGL(dcn_unfix_kernel<T>, dim3(lane_blocks(nel)), dim3(256), 0, stream, acc, (T*)dvalue, nel, (const int*)flag);
+        return iseg_check_launch("iseg_defattn_bwd");
+    });
 }

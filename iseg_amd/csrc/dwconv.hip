@@ -1115,17 +1115,16 @@ extern "C" int iseg_dwconv2d_fwd(const void* x, const float* w, const float* bia
     ISEG_REQUIRE(K == 3 || K == 5 || K == 7, "iseg_dwconv2d_fwd: kernel size %d unsupported (3,5,7)", K);
     ISEG_REQUIRE(dil >= 1, "iseg_dwconv2d_fwd: dilation must be >= 1");
     ISEG_REQUIRE((int64_t)N * H * W * C < (1ll << 31), "iseg_dwconv2d_fwd: more than 2^31 elements");
-#define DW_FWD(T)                                                                                             \
-    (K == 7   ? launch_fwd_cv<T, 7>(x, w, bias, add, y, N, H, W, C, dil, pad_t, pad_l, flip, stream)          \
-     : K == 5 ? launch_fwd_cv<T, 5>(x, w, bias, add, y, N, H, W, C, dil, pad_t, pad_l, flip, stream)          \
-              : launch_fwd_cv<T, 3>(x, w, bias, add, y, N, H, W, C, dil, pad_t, pad_l, flip, stream))
     // 7 x 7, bf16, C % 32 == 0: the banded products on the matrix cores where dwconv_mfma.hip finds them faster (round 5)
     if (dtype == ISEG_BF16 && iseg_dwconv7_mfma_launch(x, w, bias, add, y, N, H, W, C, K, dil, pad_t, pad_l, flip, stream))
         return iseg_check_launch("iseg_dwconv2d (mfma)");
     if (dtype == ISEG_BF16 && launch_fwd_dma(x, w, bias, add, y, N, H, W, C, K, dil, pad_t, pad_l, flip, stream))
         return iseg_check_launch("iseg_dwconv2d");
-    return dtype == ISEG_BF16 ? DW_FWD(bf16_t) : DW_FWD(float);
-#undef DW_FWD
+    return by_dtype(dtype, "iseg_dwconv2d_fwd", [&](auto t) {
+        using T = decltype(t);
+        const auto launch = K == 7 ? launch_fwd_cv<T, 7> : K == 5 ? launch_fwd_cv<T, 5> : launch_fwd_cv<T, 3>;
+        return launch(x, w, bias, add, y, N, H, W, C, dil, pad_t, pad_l, flip, stream);
+    });
 }
 
 int iseg_dwconv7_wgrad_mfma_blocks(int N, int H, int W, int C, int K, int dil);      // dwconv_wgrad_mfma.hip
@@ -1162,6 +1161,7 @@ extern "C" int iseg_dwconv2d_bwd_weight(const void* x, const void* dy, float* dw
     ISEG_REQUIRE(x && dy && dw, "iseg_dwconv2d_bwd_weight: null pointer");
     ISEG_REQUIRE(C % 8 == 0, "iseg_dwconv2d_bwd_weight: C=%d must be a multiple of 8", C);
     ISEG_REQUIRE(K == 3 || K == 5 || K == 7, "iseg_dwconv2d_bwd_weight: kernel size %d unsupported", K);
+    ISEG_REQUIRE(dtype == ISEG_BF16 || dtype == ISEG_F32, "iseg_dwconv2d_bwd_weight: dtype %d", dtype);      // (the routes below are picked by it)
     ISEG_REQUIRE((int64_t)N * H * W * C < (1ll << 31), "iseg_dwconv2d_bwd_weight: more than 2^31 elements");
     const BwDmaGeom gd = bw_dma_geom(N, H, W, C, K, dil, dtype == ISEG_BF16 ? 2 : 4);
     BwGeom g = bw_geom(N, H, W, C, K, dil, dtype == ISEG_BF16 ? 2 : 4);
@@ -1173,10 +1173,7 @@ extern "C" int iseg_dwconv2d_bwd_weight(const void* x, const void* dy, float* dw
     // the caller is held to iseg_dwconv2d_bwd_weight_workspace_bytes (the bound over every route), not to the chosen route's smaller count:
     // what the header tells a caller to ask for is then also what is checked, whichever route a later change picks
     const size_t promised = iseg_dwconv2d_bwd_weight_workspace_bytes(N, H, W, C, K);
-    if (!ws || ws_bytes < need || ws_bytes < promised) {
-        iseg_set_error("iseg_dwconv2d_bwd_weight: needs %zu workspace bytes, got %zu", need > promised ? need : promised, ws_bytes);
-        return ISEG_ERR_WORKSPACE;
-    }
+    ISEG_NEED_WORKSPACE("iseg_dwconv2d_bwd_weight", ws, ws_bytes, need > promised ? need : promised);
     float* const arena = iseg_deferred_partials(need, dw, db, accumulate, stream);      // (see common.h: deferred reductions)
     if (arena) ws = arena;
     if (bm) {
@@ -1194,14 +1191,12 @@ extern "C" int iseg_dwconv2d_bwd_weight(const void* x, const void* dy, float* dw
         else if (K == 5) DW_BWL(5);
         else DW_BWL(3);
 #undef DW_BWL
-    } else if (dtype == ISEG_BF16) {
-        if (K == 7) launch_bw<bf16_t, 7>(x, dy, (float*)ws, N, H, W, C, dil, pad_t, pad_l, g, stream);
-        else if (K == 5) launch_bw<bf16_t, 5>(x, dy, (float*)ws, N, H, W, C, dil, pad_t, pad_l, g, stream);
-        else launch_bw<bf16_t, 3>(x, dy, (float*)ws, N, H, W, C, dil, pad_t, pad_l, g, stream);
     } else {
-        if (K == 7) launch_bw<float, 7>(x, dy, (float*)ws, N, H, W, C, dil, pad_t, pad_l, g, stream);
-        else if (K == 5) launch_bw<float, 5>(x, dy, (float*)ws, N, H, W, C, dil, pad_t, pad_l, g, stream);
-        else launch_bw<float, 3>(x, dy, (float*)ws, N, H, W, C, dil, pad_t, pad_l, g, stream);
+        by_dtype(dtype, "iseg_dwconv2d_bwd_weight", [&](auto t) {
+            using T = decltype(t);
+            const auto launch = K == 7 ? launch_bw<T, 7> : K == 5 ? launch_bw<T, 5> : launch_bw<T, 3>;
+            launch(x, dy, (float*)ws, N, H, W, C, dil, pad_t, pad_l, g, stream);
+        });
     }
     const int n = (K * K + 1) * C;
     if (arena) iseg_deferred_push((const float*)ws, g.bx, n, n, dw, db, K * K * C, 1.f, stream);

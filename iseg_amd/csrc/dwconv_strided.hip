@@ -145,16 +145,13 @@ bool geom_ok(int N, int H, int W, int C, int K, int s, int d, int Ho, int Wo) {
            (int64_t)N * H * W * C < (1ll << 31);
 }
 
-template <class F> int by_dtype_k(int dtype, int K, F&& f) {
+template <class F> int by_dtype_k(int dtype, int K, const char* who, F&& f) {
     // (generic lambdas over <T, K> keep the six instantiations in one place)
-    if (dtype == ISEG_BF16) {
-        if (K == 3) return f(bf16_t{}, std::integral_constant<int, 3>{});
-        if (K == 5) return f(bf16_t{}, std::integral_constant<int, 5>{});
-        return f(bf16_t{}, std::integral_constant<int, 7>{});
-    }
-    if (K == 3) return f(float{}, std::integral_constant<int, 3>{});
-    if (K == 5) return f(float{}, std::integral_constant<int, 5>{});
-    return f(float{}, std::integral_constant<int, 7>{});
+    return by_dtype(dtype, who, [&](auto t) {
+        if (K == 3) return f(t, IntC<3>{});
+        if (K == 5) return f(t, IntC<5>{});
+        return f(t, IntC<7>{});
+    });
 }
 
 }  // namespace
@@ -163,11 +160,10 @@ extern "C" int iseg_dwconv2d_strided_fwd(const void* x, const float* w, const fl
                                          int dil, int pad_t, int pad_l, int Ho, int Wo, int dtype, hipStream_t stream) {
     ISEG_REQUIRE(x && w && y, "iseg_dwconv2d_strided_fwd: null pointer");
     ISEG_REQUIRE(geom_ok(N, H, W, C, K, stride, dil, Ho, Wo), "iseg_dwconv2d_strided_fwd: needs C %% 8 == 0 and K in (3, 5, 7) (C %d, K %d)", C, K);
-    ISEG_REQUIRE(dtype == ISEG_BF16 || dtype == ISEG_F32, "iseg_dwconv2d_strided_fwd: dtype %d", dtype);
     const SGeom g{N, H, W, C, Ho, Wo, stride, dil, pad_t, pad_l};
     const int64_t total = (int64_t)N * Ho * Wo * (C / 8);
-    const unsigned grid = (unsigned)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-    return by_dtype_k(dtype, K, [&](auto t, auto k) {
+    const unsigned grid = grid_cap(total, 256, 16384);
+    return by_dtype_k(dtype, K, "iseg_dwconv2d_strided_fwd", [&](auto t, auto k) {
         using T = decltype(t);
         hipLaunchKernelGGL((dws_fwd_kernel<T, decltype(k)::value>), dim3(grid), dim3(256), 0, stream, (const T*)x, w, bias, (T*)y, g, total);
         return iseg_check_launch("iseg_dwconv2d_strided_fwd");
@@ -178,11 +174,10 @@ extern "C" int iseg_dwconv2d_strided_bwd_data(const void* dy, const float* w, vo
                                               int pad_t, int pad_l, int Ho, int Wo, int dtype, hipStream_t stream) {
     ISEG_REQUIRE(dy && w && dx, "iseg_dwconv2d_strided_bwd_data: null pointer");
     ISEG_REQUIRE(geom_ok(N, H, W, C, K, stride, dil, Ho, Wo), "iseg_dwconv2d_strided_bwd_data: needs C %% 8 == 0 and K in (3, 5, 7) (C %d, K %d)", C, K);
-    ISEG_REQUIRE(dtype == ISEG_BF16 || dtype == ISEG_F32, "iseg_dwconv2d_strided_bwd_data: dtype %d", dtype);
     const SGeom g{N, H, W, C, Ho, Wo, stride, dil, pad_t, pad_l};
     const int64_t total = (int64_t)N * H * W * (C / 8);
-    const unsigned grid = (unsigned)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-    return by_dtype_k(dtype, K, [&](auto t, auto k) {
+    const unsigned grid = grid_cap(total, 256, 16384);
+    return by_dtype_k(dtype, K, "iseg_dwconv2d_strided_bwd_data", [&](auto t, auto k) {
         using T = decltype(t);
         hipLaunchKernelGGL((dws_bwd_data_kernel<T, decltype(k)::value>), dim3(grid), dim3(256), 0, stream, (const T*)dy, w, (T*)dx, g, total);
         return iseg_check_launch("iseg_dwconv2d_strided_bwd_data");
@@ -199,16 +194,12 @@ extern "C" int iseg_dwconv2d_strided_bwd_weight(const void* x, const void* dy, f
                                                 size_t ws_bytes, hipStream_t stream) {
     ISEG_REQUIRE(x && dy && dw, "iseg_dwconv2d_strided_bwd_weight: null pointer");
     ISEG_REQUIRE(geom_ok(N, H, W, C, K, stride, dil, Ho, Wo), "iseg_dwconv2d_strided_bwd_weight: needs C %% 8 == 0 and K in (3, 5, 7) (C %d, K %d)", C, K);
-    ISEG_REQUIRE(dtype == ISEG_BF16 || dtype == ISEG_F32, "iseg_dwconv2d_strided_bwd_weight: dtype %d", dtype);
     const int64_t pixels = (int64_t)N * Ho * Wo;
     const int parts = bw_partitions(pixels, C);
     const size_t need = (size_t)parts * (K * K + 1) * C * sizeof(float);
-    if (!ws || ws_bytes < need) {
-        iseg_set_error("iseg_dwconv2d_strided_bwd_weight: needs %zu workspace bytes, got %zu", need, ws_bytes);
-        return ISEG_ERR_WORKSPACE;
-    }
+    ISEG_NEED_WORKSPACE("iseg_dwconv2d_strided_bwd_weight", ws, ws_bytes, need);
     const SGeom g{N, H, W, C, Ho, Wo, stride, dil, pad_t, pad_l};
-    const int rc = by_dtype_k(dtype, K, [&](auto t, auto k) {
+    const int rc = by_dtype_k(dtype, K, "iseg_dwconv2d_strided_bwd_weight", [&](auto t, auto k) {
         using T = decltype(t);
         hipLaunchKernelGGL((dws_bwd_weight_kernel<T, decltype(k)::value>), dim3(parts, (C + 31) / 32), dim3(256), 0, stream, (const T*)x, (const T*)dy,
                            (float*)ws, g, pixels);

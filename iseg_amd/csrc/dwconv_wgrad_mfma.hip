@@ -298,10 +298,7 @@ extern "C" int iseg_dwconv2d7_bwd_weight_mfma(const void* x, const void* dy, flo
     size_t need = (size_t)blocks * NT * C * sizeof(float);
     const size_t promised = iseg_dwconv2d_bwd_weight_workspace_bytes(N, H, W, C, KS);      // (what the header tells the caller to ask for)
     if (promised > need) need = promised;
-    if (blocks > 0 && (!ws || ws_bytes < need)) {
-        iseg_set_error("iseg_dwconv2d7_bwd_weight_mfma: needs %zu workspace bytes, got %zu", need, ws_bytes);
-        return ISEG_ERR_WORKSPACE;
-    }
+    if (blocks > 0) ISEG_NEED_WORKSPACE("iseg_dwconv2d7_bwd_weight_mfma", ws, ws_bytes, need);
     if (!iseg_dwconv7_wgrad_mfma_launch(x, dy, (float*)ws, N, H, W, C, pad_t, pad_l, blocks, stream)) {
         iseg_set_error("iseg_dwconv2d7_bwd_weight_mfma: needs bf16 storage, C %% 32 == 0 (C = %d) and 16-byte aligned tensors", C);
         return ISEG_ERR_UNSUPPORTED;

@@ -8,12 +8,7 @@
 
 namespace {
 
-static inline unsigned cap_blocks(int64_t work_items, int per_block = 256) {
-    int64_t b = ceil_div64(work_items, per_block);
-    if (b > 256 * 8) b = 256 * 8;
-    if (b < 1) b = 1;
-    return (unsigned)b;
-}
+static inline unsigned cap_blocks(int64_t work_items, int per_block = 256) { return grid_cap(work_items, per_block, 256 * 8); }
 
 template <class TI, class TO>
 __global__ void cast_kernel(const TI* __restrict__ src, TO* __restrict__ dst, int64_t n) {
@@ -189,10 +184,7 @@ static int colsum_blocks(int64_t rows, int C, int V) {
     const int nch = C / V;
     const int tpc = nch < 256 ? nch : 256;
     const int rpi = 256 / tpc;
-    int64_t b = ceil_div64(rows, (int64_t)rpi * 8);
-    if (b > 256) b = 256;
-    if (b < 1) b = 1;
-    return (int)b;
+    return (int)grid_cap(rows, (int64_t)rpi * 8, 256);
 }
 
 // y[b][r][c] (+)= scale * v[b][c]     (broadcast a per-sample vector over R rows; y row stride ldy, batch stride bsy)
@@ -679,32 +671,25 @@ extern "C" int iseg_cast(const void* src, int src_dtype, void* dst, int dst_dtyp
     ISEG_REQUIRE(src && dst && n >= 0, "iseg_cast: bad arguments");
     if (n == 0) return ISEG_OK;
     const unsigned blocks = cap_blocks(ceil_div64(n, 8));
-    if (src_dtype == ISEG_F32 && dst_dtype == ISEG_BF16)
-        hipLaunchKernelGGL((cast_kernel<float, bf16_t>), dim3(blocks), dim3(256), 0, stream, (const float*)src, (bf16_t*)dst, n);
-    else if (src_dtype == ISEG_BF16 && dst_dtype == ISEG_F32)
-        hipLaunchKernelGGL((cast_kernel<bf16_t, float>), dim3(blocks), dim3(256), 0, stream, (const bf16_t*)src, (float*)dst, n);
-    else if (src_dtype == ISEG_F32 && dst_dtype == ISEG_F32)
-        hipLaunchKernelGGL((cast_kernel<float, float>), dim3(blocks), dim3(256), 0, stream, (const float*)src, (float*)dst, n);
-    else if (src_dtype == ISEG_BF16 && dst_dtype == ISEG_BF16)
-        hipLaunchKernelGGL((cast_kernel<bf16_t, bf16_t>), dim3(blocks), dim3(256), 0, stream, (const bf16_t*)src, (bf16_t*)dst, n);
-    else {
-        iseg_set_error("iseg_cast: bad dtypes %d -> %d", src_dtype, dst_dtype);
-        return ISEG_ERR_ARG;
-    }
-    return iseg_check_launch("iseg_cast");
+    return by_dtype(src_dtype, "iseg_cast", [&](auto ti) {
+        return by_dtype(dst_dtype, "iseg_cast", [&](auto to) {
+            using TI = decltype(ti);
+            using TO = decltype(to);
+            hipLaunchKernelGGL((cast_kernel<TI, TO>), dim3(blocks), dim3(256), 0, stream, (const TI*)src, (TO*)dst, n);
+            return iseg_check_launch("iseg_cast");
+        });
+    });
 }
 
 extern "C" int iseg_scale_cols_cast(const float* src, const float* colscale, void* dst, int64_t rows, int cols, int dst_dtype,
                                     hipStream_t stream) {
     ISEG_REQUIRE(src && colscale && dst && rows > 0 && cols > 0, "iseg_scale_cols_cast: bad arguments");
     const unsigned blocks = cap_blocks(rows * cols);
-    if (dst_dtype == ISEG_BF16)
-        hipLaunchKernelGGL((scale_cols_cast_kernel<bf16_t>), dim3(blocks), dim3(256), 0, stream, src, colscale, (bf16_t*)dst, rows,
-                           cols);
-    else
-        hipLaunchKernelGGL((scale_cols_cast_kernel<float>), dim3(blocks), dim3(256), 0, stream, src, colscale, (float*)dst, rows,
-                           cols);
-    return iseg_check_launch("iseg_scale_cols_cast");
+    return by_dtype(dst_dtype, "iseg_scale_cols_cast", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((scale_cols_cast_kernel<T>), dim3(blocks), dim3(256), 0, stream, src, colscale, (T*)dst, rows, cols);
+        return iseg_check_launch("iseg_scale_cols_cast");
+    });
 }
 
 extern "C" int iseg_im2col(const void* x, int in_dtype, void* col, int out_dtype, int N, int H, int W, int C, int KH, int KW,
@@ -718,26 +703,26 @@ extern "C" int iseg_im2col(const void* x, int in_dtype, void* col, int out_dtype
     const bool runs = !vec && dw == 1 && (KW * C) % 4 == 0 && ldc % 4 == 0 && ((int64_t)W * C) % 4 == 0 && (sw * C) % 4 == 0 && (pl * C) % 4 == 0 &&
                       ((uintptr_t)x % 16 == 0) && ((uintptr_t)col % 16 == 0);
     const unsigned blocks = cap_blocks(runs ? M * KH * (KW * C / 4) : M * KH * KW * (vec ? C / 8 : C));
-#define IM2COL(TI, TO)                                                                                                        \
-    do {                                                                                                                      \
-        if (runs)                                                                                                             \
-            hipLaunchKernelGGL((im2col_runs_kernel<TI, TO>), dim3(blocks), dim3(256), 0, stream, (const TI*)x, (TO*)col, N, H, W, C, \
-                               KH, KW, sh, sw, dh, pt, pl, Ho, Wo, ldc);                                                      \
-        else if (vec)                                                                                                              \
-            hipLaunchKernelGGL((im2col_kernel<TI, TO, 8>), dim3(blocks), dim3(256), 0, stream, (const TI*)x, (TO*)col, N, H, W, C, \
-                               KH, KW, sh, sw, dh, dw, pt, pl, Ho, Wo, ldc);                                                  \
-        else                                                                                                                  \
-            hipLaunchKernelGGL((im2col_kernel<TI, TO, 1>), dim3(blocks), dim3(256), 0, stream, (const TI*)x, (TO*)col, N, H, W, C, \
-                               KH, KW, sh, sw, dh, dw, pt, pl, Ho, Wo, ldc);                                                  \
-        if (ldc > K)                                                                                                          \
-            hipLaunchKernelGGL((zero_pad_cols_kernel<TO>), dim3(cap_blocks(M * (ldc - K))), dim3(256), 0, stream, (TO*)col, M, K, \
-                               ldc);                                                                                          \
-    } while (0)
-    if (in_dtype == ISEG_F32 && out_dtype == ISEG_F32) IM2COL(float, float);
-    else if (in_dtype == ISEG_F32 && out_dtype == ISEG_BF16) IM2COL(float, bf16_t);
-    else IM2COL(bf16_t, bf16_t);
-#undef IM2COL
-    return iseg_check_launch("iseg_im2col");
+    return by_dtype(in_dtype, "iseg_im2col", [&](auto ti) {
+        return by_dtype(out_dtype, "iseg_im2col", [&](auto to) {
+            using TI = decltype(ti);
+            using TO = decltype(to);
+            if constexpr (!(std::is_same_v<TI, bf16_t> && std::is_same_v<TO, float>)) {      // (refused above: no such kernel)
+                auto im2col = [&](auto kernel) {
+                    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, stream, (const TI*)x, (TO*)col, N, H, W, C, KH, KW, sh, sw, dh, dw, pt, pl,
+                                       Ho, Wo, ldc);
+                };
+                if (runs)
+                    hipLaunchKernelGGL((im2col_runs_kernel<TI, TO>), dim3(blocks), dim3(256), 0, stream, (const TI*)x, (TO*)col, N, H, W, C, KH, KW, sh,
+                                       sw, dh, pt, pl, Ho, Wo, ldc);
+                else if (vec) im2col(im2col_kernel<TI, TO, 8>);
+                else im2col(im2col_kernel<TI, TO, 1>);
+                if (ldc > K)
+                    hipLaunchKernelGGL((zero_pad_cols_kernel<TO>), dim3(cap_blocks(M * (ldc - K))), dim3(256), 0, stream, (TO*)col, M, K, ldc);
+            }
+            return iseg_check_launch("iseg_im2col");
+        });
+    });
 }
 
 extern "C" int iseg_col2im(const void* dcol, void* dx, int N, int H, int W, int C, int KH, int KW, int sh, int sw, int dh, int dw,
@@ -745,19 +730,12 @@ extern "C" int iseg_col2im(const void* dcol, void* dx, int N, int H, int W, int 
     ISEG_REQUIRE(dcol && dx, "iseg_col2im: null pointer");
     const bool vec = (C % 8 == 0) && (ldc % 8 == 0);
     const unsigned blocks = cap_blocks((int64_t)N * H * W * (vec ? C / 8 : C));
-#define COL2IM(T)                                                                                                              \
-    do {                                                                                                                       \
-        if (vec)                                                                                                               \
-            hipLaunchKernelGGL((col2im_kernel<T, 8>), dim3(blocks), dim3(256), 0, stream, (const T*)dcol, (T*)dx, N, H, W, C, KH, \
-                               KW, sh, sw, dh, dw, pt, pl, Ho, Wo, ldc);                                                       \
-        else                                                                                                                   \
-            hipLaunchKernelGGL((col2im_kernel<T, 1>), dim3(blocks), dim3(256), 0, stream, (const T*)dcol, (T*)dx, N, H, W, C, KH, \
-                               KW, sh, sw, dh, dw, pt, pl, Ho, Wo, ldc);                                                       \
-    } while (0)
-    if (dtype == ISEG_BF16) COL2IM(bf16_t);
-    else COL2IM(float);
-#undef COL2IM
-    return iseg_check_launch("iseg_col2im");
+    return by_dtype(dtype, "iseg_col2im", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((vec ? col2im_kernel<T, 8> : col2im_kernel<T, 1>), dim3(blocks), dim3(256), 0, stream, (const T*)dcol, (T*)dx, N, H, W, C, KH,
+                           KW, sh, sw, dh, dw, pt, pl, Ho, Wo, ldc);
+        return iseg_check_launch("iseg_col2im");
+    });
 }
 
 extern "C" size_t iseg_colsum_workspace_bytes(int batch, int64_t rows, int C) {
@@ -768,28 +746,21 @@ extern "C" size_t iseg_colsum_workspace_bytes(int batch, int64_t rows, int C) {
 extern "C" int iseg_colsum(const void* x, int64_t ldx, int64_t batch_stride, int batch, int64_t rows, int C, float* out,
                            float scale, int accumulate, int dtype, void* ws, size_t ws_bytes, hipStream_t stream) {
     ISEG_REQUIRE(x && out && batch > 0 && rows > 0 && C > 0, "iseg_colsum: bad arguments");
+    ISEG_REQUIRE(dtype == ISEG_BF16 || dtype == ISEG_F32, "iseg_colsum: dtype %d", dtype);      // (before the first launch)
     const bool vec = (C % 8 == 0) && (ldx % 8 == 0) && (batch_stride % 8 == 0) && ((uintptr_t)x % 16 == 0);
     const int V = vec ? 8 : 1;
     const int P = colsum_blocks(rows, C, V);
     const size_t need = (size_t)batch * P * C * sizeof(float);
-    if (!ws || ws_bytes < need) {
-        iseg_set_error("iseg_colsum: needs %zu workspace bytes, got %zu", need, ws_bytes);
-        return ISEG_ERR_WORKSPACE;
-    }
+    ISEG_NEED_WORKSPACE("iseg_colsum", ws, ws_bytes, need);
     float* const arena = batch == 1 ? iseg_deferred_partials(need, out, nullptr, accumulate, stream) : nullptr;      // (see common.h: deferred reductions)
     if (arena) ws = arena;
     const size_t lds = colsum_slab_bytes(C, V);
-#define COLSUM(T, VV)                                                                                                  \
-    hipLaunchKernelGGL((colsum_partial_kernel<T, VV>), dim3(P, batch), dim3(256), lds, stream, (const T*)x, ldx, batch_stride, \
-                       (float*)ws, rows, C)
-    if (dtype == ISEG_BF16) {
-        if (vec) COLSUM(bf16_t, 8);
-        else COLSUM(bf16_t, 1);
-    } else {
-        if (vec) COLSUM(float, 8);
-        else COLSUM(float, 1);
-    }
-#undef COLSUM
+    const int rc = by_dtype(dtype, "iseg_colsum", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((vec ? colsum_partial_kernel<T, 8> : colsum_partial_kernel<T, 1>), dim3(P, batch), dim3(256), lds, stream, (const T*)x, ldx,
+                           batch_stride, (float*)ws, rows, C);
+    });
+    if (rc != ISEG_OK) return rc;
     if (arena) iseg_deferred_push((const float*)ws, P, C, C, out, nullptr, C, scale, stream);
     else launch_reduce_rows((const float*)ws, P, C, (int64_t)P * C, batch, C, out, nullptr, C, C, scale, accumulate, stream);
     return iseg_check_launch("iseg_colsum");
@@ -799,18 +770,20 @@ extern "C" int iseg_broadcast_rows(const void* v, int v_dtype, void* y, int64_t 
                                    int C, float scale, int accumulate, int dtype, hipStream_t stream) {
     ISEG_REQUIRE(v && y && C % 8 == 0 && ldy % 8 == 0 && batch_stride % 8 == 0, "iseg_broadcast_rows: bad arguments");
     const unsigned blocks = cap_blocks((int64_t)batch * rows * (C / 8));
-#define BC(T, TV)                                                                                                           \
-    hipLaunchKernelGGL((broadcast_rows_kernel<T, TV>), dim3(blocks), dim3(256), 0, stream, (const TV*)v, (T*)y, ldy, batch_stride, \
-                       batch, rows, C, scale, accumulate)
-    if (dtype == ISEG_BF16) {
-        if (v_dtype == ISEG_BF16) BC(bf16_t, bf16_t);
-        else BC(bf16_t, float);
-    } else {
-        ISEG_REQUIRE(v_dtype == ISEG_F32, "iseg_broadcast_rows: f32 output needs f32 vector");
-        BC(float, float);
-    }
-#undef BC
-    return iseg_check_launch("iseg_broadcast_rows");
+    return by_dtype(dtype, "iseg_broadcast_rows", [&](auto t) {
+        return by_dtype(v_dtype, "iseg_broadcast_rows", [&](auto tv) {
+            using T = decltype(t);
+            using TV = decltype(tv);
+            if constexpr (std::is_same_v<T, float> && std::is_same_v<TV, bf16_t>) {      // (no such kernel)
+                iseg_set_error("iseg_broadcast_rows: f32 output needs f32 vector");
+                return ISEG_ERR_ARG;
+            } else {
+                hipLaunchKernelGGL((broadcast_rows_kernel<T, TV>), dim3(blocks), dim3(256), 0, stream, (const TV*)v, (T*)y, ldy, batch_stride, batch,
+                                   rows, C, scale, accumulate);
+                return iseg_check_launch("iseg_broadcast_rows");
+            }
+        });
+    });
 }
 
 extern "C" int iseg_axpby(const void* a, const void* b, void* y, float alpha, float beta, int64_t n, int dtype,
@@ -818,13 +791,11 @@ extern "C" int iseg_axpby(const void* a, const void* b, void* y, float alpha, fl
     ISEG_REQUIRE(a && y && n >= 0, "iseg_axpby: bad arguments");
     if (n == 0) return ISEG_OK;
     const unsigned blocks = cap_blocks(ceil_div64(n, 8));
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL((axpby_kernel<bf16_t>), dim3(blocks), dim3(256), 0, stream, (const bf16_t*)a, (const bf16_t*)b,
-                           (bf16_t*)y, alpha, beta, n);
-    else
-        hipLaunchKernelGGL((axpby_kernel<float>), dim3(blocks), dim3(256), 0, stream, (const float*)a, (const float*)b, (float*)y,
-                           alpha, beta, n);
-    return iseg_check_launch("iseg_axpby");
+    return by_dtype(dtype, "iseg_axpby", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((axpby_kernel<T>), dim3(blocks), dim3(256), 0, stream, (const T*)a, (const T*)b, (T*)y, alpha, beta, n);
+        return iseg_check_launch("iseg_axpby");
+    });
 }
 
 extern "C" int iseg_accumulate_pair(const float* src, int n, float* dst0, float* dst1, hipStream_t stream) {
@@ -838,24 +809,21 @@ extern "C" int iseg_rowscale(const void* x, const float* s, void* y, int64_t row
                              hipStream_t stream) {
     ISEG_REQUIRE(x && s && y && C % 8 == 0 && rows_per_group > 0, "iseg_rowscale: bad arguments");
     const unsigned blocks = cap_blocks(rows * (C / 8));
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL((rowscale_kernel<bf16_t>), dim3(blocks), dim3(256), 0, stream, (const bf16_t*)x, s, (bf16_t*)y, rows, C,
-                           rows_per_group);
-    else
-        hipLaunchKernelGGL((rowscale_kernel<float>), dim3(blocks), dim3(256), 0, stream, (const float*)x, s, (float*)y, rows, C,
-                           rows_per_group);
-    return iseg_check_launch("iseg_rowscale");
+    return by_dtype(dtype, "iseg_rowscale", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((rowscale_kernel<T>), dim3(blocks), dim3(256), 0, stream, (const T*)x, s, (T*)y, rows, C, rows_per_group);
+        return iseg_check_launch("iseg_rowscale");
+    });
 }
 
 extern "C" int iseg_dropout(const void* x, void* y, int64_t n, float rate, uint64_t seed, const uint64_t* seed_offset, int dtype, hipStream_t stream) {
     ISEG_REQUIRE(x && y && rate >= 0.f && rate < 1.f, "iseg_dropout: bad arguments");
     const unsigned blocks = cap_blocks(ceil_div64(n, 8));
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL((dropout_kernel<bf16_t>), dim3(blocks), dim3(256), 0, stream, (const bf16_t*)x, (bf16_t*)y, n, rate,
-                           seed, seed_offset);
-    else
-        hipLaunchKernelGGL((dropout_kernel<float>), dim3(blocks), dim3(256), 0, stream, (const float*)x, (float*)y, n, rate, seed, seed_offset);
-    return iseg_check_launch("iseg_dropout");
+    return by_dtype(dtype, "iseg_dropout", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((dropout_kernel<T>), dim3(blocks), dim3(256), 0, stream, (const T*)x, (T*)y, n, rate, seed, seed_offset);
+        return iseg_check_launch("iseg_dropout");
+    });
 }
 
 extern "C" int iseg_drop_path_mask(float* s, int n, float keep_prob, uint64_t seed, const uint64_t* seed_offset, hipStream_t stream) {
@@ -898,10 +866,7 @@ extern "C" int iseg_layerscale_grads(const float* Z, const float* W2, const floa
     const size_t need = (size_t)P * N * sizeof(float);
     // (the caller is held to the query, which also covers the slab form's finer strips: one rule for both forms)
     const size_t promised = iseg_layerscale_grads_workspace_bytes(K, N);
-    if (!ws || ws_bytes < need || ws_bytes < promised) {
-        iseg_set_error("iseg_layerscale_grads: needs %zu workspace bytes, got %zu", need > promised ? need : promised, ws_bytes);
-        return ISEG_ERR_WORKSPACE;
-    }
+    ISEG_NEED_WORKSPACE("iseg_layerscale_grads", ws, ws_bytes, need > promised ? need : promised);
     float* const arena = iseg_deferred_partials(need, dgamma, nullptr, accumulate, stream);      // (see common.h: deferred reductions)
     if (arena) ws = arena;
     hipLaunchKernelGGL(layerscale_stage1_kernel, dim3((N + 63) / 64, P), dim3(256), 0, stream, Z, W2, gamma, b2, S, dW2, db2, (float*)ws, K, N,
@@ -949,10 +914,7 @@ static int layerscale_grads_slabs_impl(const float* slabs, int nslabs, const flo
     const size_t need = (size_t)P * N * sizeof(float);
     // (a buffer smaller than the query answers is refused, not served with coarser strips)
     const size_t promised = iseg_layerscale_grads_workspace_bytes(K, N);
-    if (!ws || ws_bytes < need || ws_bytes < promised) {
-        iseg_set_error("iseg_layerscale_grads_slabs: needs %zu workspace bytes, got %zu", need > promised ? need : promised, ws_bytes);
-        return ISEG_ERR_WORKSPACE;
-    }
+    ISEG_NEED_WORKSPACE("iseg_layerscale_grads_slabs", ws, ws_bytes, need > promised ? need : promised);
     float* const arena = iseg_deferred_partials(need, dgamma, nullptr, accumulate, stream);
     if (arena) ws = arena;
     const int64_t slab_stride = (int64_t)(K + 1) * N;
@@ -974,24 +936,22 @@ extern "C" int iseg_act_fwd(const void* x, void* y, int64_t n, int act, int dtyp
     ISEG_REQUIRE(x && y && (act == ISEG_ACT_RELU || act == ISEG_ACT_GELU || act == ISEG_ACT_SIGMOID || act == ISEG_ACT_SWISH), "iseg_act_fwd: bad arguments (act = %d)", act);
     if (n == 0) return ISEG_OK;
     const unsigned blocks = cap_blocks(ceil_div64(n, 8));
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL((act_fwd_kernel<bf16_t>), dim3(blocks), dim3(256), 0, stream, (const bf16_t*)x, (bf16_t*)y, n, act);
-    else
-        hipLaunchKernelGGL((act_fwd_kernel<float>), dim3(blocks), dim3(256), 0, stream, (const float*)x, (float*)y, n, act);
-    return iseg_check_launch("iseg_act_fwd");
+    return by_dtype(dtype, "iseg_act_fwd", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((act_fwd_kernel<T>), dim3(blocks), dim3(256), 0, stream, (const T*)x, (T*)y, n, act);
+        return iseg_check_launch("iseg_act_fwd");
+    });
 }
 
 extern "C" int iseg_act_bwd(const void* dy, const void* aux, void* dx, int64_t n, int act, int dtype, hipStream_t stream) {
     ISEG_REQUIRE(dy && aux && dx && (act == ISEG_ACT_RELU || act == ISEG_ACT_GELU || act == ISEG_ACT_SIGMOID || act == ISEG_ACT_SWISH), "iseg_act_bwd: bad arguments (act = %d)", act);
     if (n == 0) return ISEG_OK;
     const unsigned blocks = cap_blocks(ceil_div64(n, 8));
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL((act_bwd_kernel<bf16_t>), dim3(blocks), dim3(256), 0, stream, (const bf16_t*)dy, (const bf16_t*)aux,
-                           (bf16_t*)dx, n, act);
-    else
-        hipLaunchKernelGGL((act_bwd_kernel<float>), dim3(blocks), dim3(256), 0, stream, (const float*)dy, (const float*)aux,
-                           (float*)dx, n, act);
-    return iseg_check_launch("iseg_act_bwd");
+    return by_dtype(dtype, "iseg_act_bwd", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((act_bwd_kernel<T>), dim3(blocks), dim3(256), 0, stream, (const T*)dy, (const T*)aux, (T*)dx, n, act);
+        return iseg_check_launch("iseg_act_bwd");
+    });
 }
 
 extern "C" int iseg_copy2d(const void* src, int64_t ld_src, void* dst, int64_t ld_dst, int64_t rows, int cols, int dtype,
@@ -999,24 +959,22 @@ extern "C" int iseg_copy2d(const void* src, int64_t ld_src, void* dst, int64_t l
     ISEG_REQUIRE(src && dst && rows > 0 && cols > 0, "iseg_copy2d: bad arguments");
     ISEG_REQUIRE(cols % 8 == 0 && ld_src % 8 == 0 && ld_dst % 8 == 0, "iseg_copy2d: cols/ld must be multiples of 8");
     const unsigned blocks = cap_blocks(rows * (cols / 8));
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL((copy2d_kernel<bf16_t>), dim3(blocks), dim3(256), 0, stream, (const bf16_t*)src, ld_src, (bf16_t*)dst,
-                           ld_dst, rows, cols);
-    else
-        hipLaunchKernelGGL((copy2d_kernel<float>), dim3(blocks), dim3(256), 0, stream, (const float*)src, ld_src, (float*)dst,
-                           ld_dst, rows, cols);
-    return iseg_check_launch("iseg_copy2d");
+    return by_dtype(dtype, "iseg_copy2d", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((copy2d_kernel<T>), dim3(blocks), dim3(256), 0, stream, (const T*)src, ld_src, (T*)dst, ld_dst, rows, cols);
+        return iseg_check_launch("iseg_copy2d");
+    });
 }
 
 extern "C" int iseg_scale_dev(const void* x, const float* s_dev, void* y, int64_t n, int dtype, hipStream_t stream) {
     ISEG_REQUIRE(x && s_dev && y && n >= 0, "iseg_scale_dev: bad arguments");
     if (n == 0) return ISEG_OK;
     const unsigned blocks = cap_blocks(ceil_div64(n, 8));
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL((scale_dev_kernel<bf16_t>), dim3(blocks), dim3(256), 0, stream, (const bf16_t*)x, s_dev, (bf16_t*)y, n);
-    else
-        hipLaunchKernelGGL((scale_dev_kernel<float>), dim3(blocks), dim3(256), 0, stream, (const float*)x, s_dev, (float*)y, n);
-    return iseg_check_launch("iseg_scale_dev");
+    return by_dtype(dtype, "iseg_scale_dev", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((scale_dev_kernel<T>), dim3(blocks), dim3(256), 0, stream, (const T*)x, s_dev, (T*)y, n);
+        return iseg_check_launch("iseg_scale_dev");
+    });
 }
 
 // ---- sliding-window accumulation (core_inference.py:254-301 of the reference): fp32, arbitrary widths ----

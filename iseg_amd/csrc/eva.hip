@@ -159,10 +159,7 @@ __global__ __launch_bounds__(256) void glu_bwd_any_kernel(const T* __restrict__ 
     }
 }
 
-unsigned eva_blocks(int64_t work) {
-    int64_t b = (work + 255) / 256;
-    return (unsigned)(b < 1 ? 1 : (b > 16384 ? 16384 : b));
-}
+unsigned eva_blocks(int64_t work) { return grid_cap(work, 256, 16384); }
 
 }  // namespace
 
@@ -174,13 +171,12 @@ extern "C" int iseg_qkv_rope(const void* qkv, void* out, const float* q_bias, co
     ISEG_REQUIRE((((uintptr_t)qkv | (uintptr_t)out | (uintptr_t)q_bias | (uintptr_t)v_bias | (uintptr_t)emb) & 15) == 0, "iseg_qkv_rope: operands must be 16-byte aligned");
     if (!q_bias && !v_bias && !emb && qkv == out) return ISEG_OK;
     const unsigned blocks = eva_blocks(rows * (3 * C / 8));
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL((qkv_rope_kernel<bf16_t>), dim3(blocks), dim3(256), 0, stream, (const bf16_t*)qkv, (bf16_t*)out, q_bias, v_bias, emb, rows, tokens, prefix, C, head_dim,
-                           inverse);
-    else
-        hipLaunchKernelGGL((qkv_rope_kernel<float>), dim3(blocks), dim3(256), 0, stream, (const float*)qkv, (float*)out, q_bias, v_bias, emb, rows, tokens, prefix, C, head_dim,
-                           inverse);
-    return iseg_check_launch("iseg_qkv_rope");
+    return by_dtype(dtype, "iseg_qkv_rope", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((qkv_rope_kernel<T>), dim3(blocks), dim3(256), 0, stream, (const T*)qkv, (T*)out, q_bias, v_bias, emb, rows, tokens,
+                           prefix, C, head_dim, inverse);
+        return iseg_check_launch("iseg_qkv_rope");
+    });
 }
 
 static bool glu_act_ok(int act) { return act == ISEG_ACT_GELU || act == ISEG_ACT_SWISH || act == ISEG_ACT_SIGMOID; }
@@ -190,22 +186,20 @@ extern "C" int iseg_glu_fwd(const void* gate, int64_t ld_gate, const void* x, in
     ISEG_REQUIRE(gate && x && out && rows > 0 && cols > 0 && glu_act_ok(act), "iseg_glu_fwd: bad arguments (act = %d)", act);
     if (cols % 8 || ld_gate % 8 || ld_x % 8 || ld_out % 8 || (((uintptr_t)gate | (uintptr_t)x | (uintptr_t)out) & 15)) {      // no 16-byte pieces: the scalar form
         const unsigned nb = eva_blocks(rows * cols);
-        if (dtype == ISEG_BF16)
-            hipLaunchKernelGGL((glu_fwd_any_kernel<bf16_t>), dim3(nb), dim3(256), 0, stream, (const bf16_t*)gate, ld_gate, (const bf16_t*)x, ld_x, (bf16_t*)out,
-                               ld_out, rows, cols, act);
-        else
-            hipLaunchKernelGGL((glu_fwd_any_kernel<float>), dim3(nb), dim3(256), 0, stream, (const float*)gate, ld_gate, (const float*)x, ld_x, (float*)out, ld_out,
+        return by_dtype(dtype, "iseg_glu_fwd", [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL((glu_fwd_any_kernel<T>), dim3(nb), dim3(256), 0, stream, (const T*)gate, ld_gate, (const T*)x, ld_x, (T*)out, ld_out,
                                rows, cols, act);
-        return iseg_check_launch("iseg_glu_fwd");
+            return iseg_check_launch("iseg_glu_fwd");
+        });
     }
     const unsigned blocks = eva_blocks(rows * (cols / 8));
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL((glu_fwd_kernel<bf16_t>), dim3(blocks), dim3(256), 0, stream, (const bf16_t*)gate, ld_gate, (const bf16_t*)x, ld_x, (bf16_t*)out,
-                           ld_out, rows, cols, act);
-    else
-        hipLaunchKernelGGL((glu_fwd_kernel<float>), dim3(blocks), dim3(256), 0, stream, (const float*)gate, ld_gate, (const float*)x, ld_x, (float*)out, ld_out,
-                           rows, cols, act);
-    return iseg_check_launch("iseg_glu_fwd");
+    return by_dtype(dtype, "iseg_glu_fwd", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((glu_fwd_kernel<T>), dim3(blocks), dim3(256), 0, stream, (const T*)gate, ld_gate, (const T*)x, ld_x, (T*)out, ld_out, rows,
+                           cols, act);
+        return iseg_check_launch("iseg_glu_fwd");
+    });
 }
 
 extern "C" int iseg_glu_bwd(const void* dout, int64_t ld_dout, const void* gate, int64_t ld_gate, const void* x, int64_t ld_x, void* dgate,
@@ -214,20 +208,18 @@ extern "C" int iseg_glu_bwd(const void* dout, int64_t ld_dout, const void* gate,
     if (cols % 8 || ld_dout % 8 || ld_gate % 8 || ld_x % 8 || ld_dgate % 8 || ld_dx % 8 ||
         (((uintptr_t)dout | (uintptr_t)gate | (uintptr_t)x | (uintptr_t)dgate | (uintptr_t)dx) & 15)) {      // no 16-byte pieces: the scalar form
         const unsigned nb = eva_blocks(rows * cols);
-        if (dtype == ISEG_BF16)
-            hipLaunchKernelGGL((glu_bwd_any_kernel<bf16_t>), dim3(nb), dim3(256), 0, stream, (const bf16_t*)dout, ld_dout, (const bf16_t*)gate, ld_gate,
-                               (const bf16_t*)x, ld_x, (bf16_t*)dgate, ld_dgate, (bf16_t*)dx, ld_dx, rows, cols, act);
-        else
-            hipLaunchKernelGGL((glu_bwd_any_kernel<float>), dim3(nb), dim3(256), 0, stream, (const float*)dout, ld_dout, (const float*)gate, ld_gate,
-                               (const float*)x, ld_x, (float*)dgate, ld_dgate, (float*)dx, ld_dx, rows, cols, act);
-        return iseg_check_launch("iseg_glu_bwd");
+        return by_dtype(dtype, "iseg_glu_bwd", [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL((glu_bwd_any_kernel<T>), dim3(nb), dim3(256), 0, stream, (const T*)dout, ld_dout, (const T*)gate, ld_gate, (const T*)x,
+                               ld_x, (T*)dgate, ld_dgate, (T*)dx, ld_dx, rows, cols, act);
+            return iseg_check_launch("iseg_glu_bwd");
+        });
     }
     const unsigned blocks = eva_blocks(rows * (cols / 8));
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL((glu_bwd_kernel<bf16_t>), dim3(blocks), dim3(256), 0, stream, (const bf16_t*)dout, ld_dout, (const bf16_t*)gate, ld_gate,
-                           (const bf16_t*)x, ld_x, (bf16_t*)dgate, ld_dgate, (bf16_t*)dx, ld_dx, rows, cols, act);
-    else
-        hipLaunchKernelGGL((glu_bwd_kernel<float>), dim3(blocks), dim3(256), 0, stream, (const float*)dout, ld_dout, (const float*)gate, ld_gate, (const float*)x,
-                           ld_x, (float*)dgate, ld_dgate, (float*)dx, ld_dx, rows, cols, act);
-    return iseg_check_launch("iseg_glu_bwd");
+    return by_dtype(dtype, "iseg_glu_bwd", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((glu_bwd_kernel<T>), dim3(blocks), dim3(256), 0, stream, (const T*)dout, ld_dout, (const T*)gate, ld_gate, (const T*)x,
+                           ld_x, (T*)dgate, ld_dgate, (T*)dx, ld_dx, rows, cols, act);
+        return iseg_check_launch("iseg_glu_bwd");
+    });
 }

@@ -546,10 +546,8 @@ extern "C" int iseg_attention_bwd(const void* qkv, const void* out, const void* 
     ISEG_REQUIRE(((uintptr_t)qkv | (uintptr_t)out | (uintptr_t)dout | (uintptr_t)dqkv | (uintptr_t)lse2) % 16 == 0,
                  "iseg_attention_bwd: operands must be 16-byte aligned");
     const size_t need = iseg_attention_bwd_workspace_bytes(batch, T, heads);
-    if (!ws || ws_bytes < need || (uintptr_t)ws % 16) {
-        iseg_set_error("iseg_attention_bwd: needs %zu aligned workspace bytes, got %zu", need, ws_bytes);
-        return ISEG_ERR_WORKSPACE;
-    }
+    ISEG_NEED_WORKSPACE("iseg_attention_bwd", ws, ws_bytes, need);
+    ISEG_REQUIRE_WORKSPACE((uintptr_t)ws % 16 == 0, "iseg_attention_bwd: the workspace must be 16-byte aligned");
     float* dsum = (float*)ws;
     const int qtiles = (T + FQ - 1) / FQ;
     const int Tp = qtiles * FQ;

@@ -234,10 +234,7 @@ extern "C" int iseg_gemm(const iseg_gemm_args* g, void* ws, size_t ws_bytes, hip
     int64_t kps = g->K;
     if (nsplit > 1) {
         const size_t need = (size_t)nsplit * slab_rows * g->N * sizeof(float);
-        if (!ws || ws_bytes < need) {
-            iseg_set_error("iseg_gemm: split-K needs %zu workspace bytes, got %zu", need, ws_bytes);
-            return ISEG_ERR_WORKSPACE;
-        }
+        ISEG_NEED_WORKSPACE("iseg_gemm", ws, ws_bytes, need);
         slabs = (float*)ws;
         kps = ceil_div64(ceil_div64(g->K, nsplit), 128) * 128;
     }
@@ -305,10 +302,8 @@ extern "C" int iseg_gemm_tn_pair(const iseg_gemm_args* g0, void* ws0, size_t ws0
     ISEG_REQUIRE(!g0->bias && !g1->bias && g0->act == ISEG_ACT_NONE && g1->act == ISEG_ACT_NONE && g0->out_dtype == ISEG_F32 && g1->out_dtype == ISEG_F32,
                  "iseg_gemm_tn_pair: plain fp32 weight gradients only");
     const size_t need0 = iseg_gemm_workspace_bytes(g0), need1 = iseg_gemm_workspace_bytes(g1);
-    if (!ws0 || ws0_bytes < need0 || !ws1 || ws1_bytes < need1) {
-        iseg_set_error("iseg_gemm_tn_pair: needs %zu + %zu workspace bytes, got %zu + %zu", need0, need1, ws0_bytes, ws1_bytes);
-        return ISEG_ERR_WORKSPACE;
-    }
+    ISEG_NEED_WORKSPACE("iseg_gemm_tn_pair", ws0, ws0_bytes, need0);
+    ISEG_NEED_WORKSPACE("iseg_gemm_tn_pair", ws1, ws1_bytes, need1);
     const int64_t kps = ceil_div64(ceil_div64(g0->K, s), 128) * 128;
     const int eff = (int)ceil_div64(g0->K, kps);
     iseg_mm::gemm_bf16_tn_pair(g0, (float*)ws0, g1, (float*)ws1, eff, kps, stream);
@@ -322,10 +317,7 @@ extern "C" int iseg_gemm_reduce(const iseg_gemm_args* g, void* ws, size_t ws_byt
     if (nsplit <= 1) return ISEG_OK;
     const int64_t slab_rows = g->M + (g->colsum_out ? 1 : 0);
     const size_t need = (size_t)nsplit * slab_rows * g->N * sizeof(float);
-    if (!ws || ws_bytes < need) {
-        iseg_set_error("iseg_gemm_reduce: needs %zu workspace bytes, got %zu", need, ws_bytes);
-        return ISEG_ERR_WORKSPACE;
-    }
+    ISEG_NEED_WORKSPACE("iseg_gemm_reduce", ws, ws_bytes, need);
     const int64_t kps = ceil_div64(ceil_div64(g->K, nsplit), 128) * 128;
     const int eff_split = (int)ceil_div64(g->K, kps);
     Epi epi{g->bias, g->colscale, g->rowscale, g->rows_per_group, g->residual, g->ldr, g->aux, g->ldaux, g->pre_out, g->ldp,

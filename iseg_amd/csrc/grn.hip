@@ -285,12 +285,8 @@ int grn_parts(int64_t N, int64_t HW, int C) {
     const int nch = C / 8;
     const int tpc = nch < 256 ? nch : 256;
     const int rpi = 256 / tpc;
-    int64_t P = ceil_div64(HW, (int64_t)rpi * 8);      // >= 8 rows per lane
     const int64_t cap = N >= 2048 ? 1 : 2048 / N;      // ~2048 workgroups over the samples
-    if (P > cap) P = cap;
-    if (P > 256) P = 256;
-    if (P < 1) P = 1;
-    return (int)P;
+    return (int)grid_cap(HW, (int64_t)rpi * 8, cap < 256 ? cap : 256);      // >= 8 rows per lane
 }
 
 size_t align256(size_t b) { return (b + 255) / 256 * 256; }
@@ -306,39 +302,38 @@ extern "C" size_t iseg_grn_workspace_bytes(int64_t N, int64_t HW, int C) {
 extern "C" int iseg_grn_fwd(const void* x, const float* gamma, const float* beta, void* y, float* nx, float* gx, int64_t N, int64_t HW,
                             int C, float eps, int dtype, void* ws, size_t ws_bytes, hipStream_t stream) {
     ISEG_REQUIRE(x && nx && gx && N > 0 && HW > 0 && C > 0 && (!y || (gamma && beta)), "iseg_grn_fwd: bad arguments");
-    ISEG_REQUIRE((dtype == ISEG_BF16 || dtype == ISEG_F32) && C % 8 == 0, "iseg_grn_fwd: C %% 8 == 0 required (got dtype %d, C %d)", dtype, C);
+    ISEG_REQUIRE(C % 8 == 0, "iseg_grn_fwd: C %% 8 == 0 required (got C %d)", C);
     ISEG_REQUIRE(N <= 65535, "iseg_grn_fwd: at most 65535 samples");
-    ISEG_REQUIRE_WORKSPACE(ws && ws_bytes >= iseg_grn_workspace_bytes(N, HW, C), "iseg_grn_fwd: workspace too small");
+    ISEG_NEED_WORKSPACE("iseg_grn_fwd", ws, ws_bytes, iseg_grn_workspace_bytes(N, HW, C));
     const int P = grn_parts(N, HW, C);
     float* parts = (float*)ws;
     float* sumsq = (float*)((char*)ws + align256((size_t)N * P * 2 * C * sizeof(float)));
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL((grn_colsum_kernel<bf16_t, false>), dim3(P, (unsigned)N), dim3(256), 0, stream, (const bf16_t*)x,
-                           (const bf16_t*)nullptr, parts, HW, C);
-    else
-        hipLaunchKernelGGL((grn_colsum_kernel<float, false>), dim3(P, (unsigned)N), dim3(256), 0, stream, (const float*)x, (const float*)nullptr,
-                           parts, HW, C);
+    const int rc = by_dtype(dtype, "iseg_grn_fwd", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((grn_colsum_kernel<T, false>), dim3(P, (unsigned)N), dim3(256), 0, stream, (const T*)x, (const T*)nullptr, parts, HW, C);
+    });
+    if (rc != ISEG_OK) return rc;
     launch_reduce_rows(parts, P, C, (int64_t)P * C, (int)N, C, sumsq, nullptr, C, C, 1.f, 0, stream);
     hipLaunchKernelGGL(grn_stats_kernel, dim3((unsigned)N), dim3(256), 0, stream, (const float*)sumsq, nx, gx, C, eps);
     if (!y) return iseg_check_launch("iseg_grn_fwd");      // statistics only: the caller folds gamma*nx + 1 into the next layer's kernel
     const int64_t chunks = N * HW * (C / 8);
-    const unsigned blocks = (unsigned)(ceil_div64(chunks, 256) < 8192 ? ceil_div64(chunks, 256) : 8192);
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL((grn_apply_kernel<bf16_t, false>), dim3(blocks), dim3(256), 0, stream, (const bf16_t*)x, (const bf16_t*)nullptr,
-                           gamma, beta, (const float*)nx, (const float*)nullptr, (const bf16_t*)nullptr, (bf16_t*)y, HW, C, chunks);
-    else
-        hipLaunchKernelGGL((grn_apply_kernel<float, false>), dim3(blocks), dim3(256), 0, stream, (const float*)x, (const float*)nullptr, gamma,
-                           beta, (const float*)nx, (const float*)nullptr, (const float*)nullptr, (float*)y, HW, C, chunks);
-    return iseg_check_launch("iseg_grn_fwd");
+    const unsigned blocks = grid_cap(chunks, 256, 8192);
+    return by_dtype(dtype, "iseg_grn_fwd", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((grn_apply_kernel<T, false>), dim3(blocks), dim3(256), 0, stream, (const T*)x, (const T*)nullptr, gamma, beta,
+                           (const float*)nx, (const float*)nullptr, (const T*)nullptr, (T*)y, HW, C, chunks);
+        return iseg_check_launch("iseg_grn_fwd");
+    });
 }
 
 extern "C" int iseg_grn_bwd(const void* dy, const void* x, const float* gamma, const float* nx, const float* gx, const void* mul, void* dx,
                             float* dgamma, float* dbeta, int accumulate, int64_t N, int64_t HW, int C, float eps, int dtype, void* ws, size_t ws_bytes,
                             hipStream_t stream) {
     ISEG_REQUIRE(dy && x && gamma && nx && gx && dx && dgamma && dbeta && N > 0 && HW > 0 && C > 0, "iseg_grn_bwd: bad arguments");
-    ISEG_REQUIRE((dtype == ISEG_BF16 || dtype == ISEG_F32) && C % 8 == 0, "iseg_grn_bwd: C %% 8 == 0 required (got dtype %d, C %d)", dtype, C);
+    ISEG_REQUIRE(C % 8 == 0, "iseg_grn_bwd: C %% 8 == 0 required (got C %d)", C);
     ISEG_REQUIRE(N <= 65535, "iseg_grn_bwd: at most 65535 samples");
-    ISEG_REQUIRE_WORKSPACE(ws && ws_bytes >= iseg_grn_workspace_bytes(N, HW, C), "iseg_grn_bwd: workspace too small");
+    ISEG_REQUIRE(dtype == ISEG_BF16 || dtype == ISEG_F32, "iseg_grn_bwd: dtype %d", dtype);      // (before the first launch)
+    ISEG_NEED_WORKSPACE("iseg_grn_bwd", ws, ws_bytes, iseg_grn_workspace_bytes(N, HW, C));
     const int P = grn_parts(N, HW, C);
     const size_t side = align256((size_t)N * 2 * C * sizeof(float));
     float* parts = (float*)ws;
@@ -347,33 +342,31 @@ extern "C" int iseg_grn_bwd(const void* dy, const void* x, const float* gamma, c
     // per-sample rows (D*nx | sum dy) are the partials of the parameter gradients: they go to the trainer's arena when its queue is open
     float* arena = iseg_deferred_partials((size_t)N * 2 * C * sizeof(float), dgamma, dbeta, accumulate, stream);
     if (arena) buf = arena;
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL((grn_colsum_kernel<bf16_t, true>), dim3(P, (unsigned)N), dim3(256), 0, stream, (const bf16_t*)x, (const bf16_t*)dy,
-                           parts, HW, C);
-    else
-        hipLaunchKernelGGL((grn_colsum_kernel<float, true>), dim3(P, (unsigned)N), dim3(256), 0, stream, (const float*)x, (const float*)dy, parts,
-                           HW, C);
+    const int rc = by_dtype(dtype, "iseg_grn_bwd", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((grn_colsum_kernel<T, true>), dim3(P, (unsigned)N), dim3(256), 0, stream, (const T*)x, (const T*)dy, parts, HW, C);
+    });
+    if (rc != ISEG_OK) return rc;
     launch_reduce_rows(parts, P, 2 * (int64_t)C, (int64_t)P * 2 * C, (int)N, 2 * (int64_t)C, buf, nullptr, 2 * (int64_t)C, 2 * (int64_t)C, 1.f,
                        0, stream);
     hipLaunchKernelGGL(grn_bwd_stats_kernel, dim3((unsigned)N), dim3(256), 0, stream, buf, 2 * (int64_t)C, gamma, nx, gx, t, C, eps);
     if (arena) iseg_deferred_push(buf, (int)N, 2 * (int64_t)C, 2 * (int64_t)C, dgamma, dbeta, C, 1.f, stream);
     else launch_reduce_rows(buf, (int)N, 2 * (int64_t)C, 0, 1, 2 * (int64_t)C, dgamma, dbeta, C, 0, 1.f, accumulate, stream);
     const int64_t chunks = N * HW * (C / 8);
-    const unsigned blocks = (unsigned)(ceil_div64(chunks, 256) < 8192 ? ceil_div64(chunks, 256) : 8192);
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL((grn_apply_kernel<bf16_t, true>), dim3(blocks), dim3(256), 0, stream, (const bf16_t*)x, (const bf16_t*)dy, gamma,
-                           (const float*)nullptr, nx, (const float*)t, (const bf16_t*)mul, (bf16_t*)dx, HW, C, chunks);
-    else
-        hipLaunchKernelGGL((grn_apply_kernel<float, true>), dim3(blocks), dim3(256), 0, stream, (const float*)x, (const float*)dy, gamma,
-                           (const float*)nullptr, nx, (const float*)t, (const float*)mul, (float*)dx, HW, C, chunks);
-    return iseg_check_launch("iseg_grn_bwd");
+    const unsigned blocks = grid_cap(chunks, 256, 8192);
+    return by_dtype(dtype, "iseg_grn_bwd", [&](auto st) {
+        using T = decltype(st);
+        hipLaunchKernelGGL((grn_apply_kernel<T, true>), dim3(blocks), dim3(256), 0, stream, (const T*)x, (const T*)dy, gamma, (const float*)nullptr,
+                           nx, (const float*)t, (const T*)mul, (T*)dx, HW, C, chunks);
+        return iseg_check_launch("iseg_grn_bwd");
+    });
 }
 
 extern "C" int iseg_grn_fold_weights(const void* wt, const float* gamma, const float* nx, void* out, int64_t N, int Cout, int C4,
                                      hipStream_t stream) {
     ISEG_REQUIRE(wt && gamma && nx && out && N > 0 && Cout > 0 && C4 > 0 && C4 % 8 == 0, "iseg_grn_fold_weights: bad arguments");
     const int64_t chunks = N * Cout * (C4 / 8);
-    const unsigned blocks = (unsigned)(ceil_div64(chunks, 256) < 4096 ? ceil_div64(chunks, 256) : 4096);
+    const unsigned blocks = grid_cap(chunks, 256, 4096);
     hipLaunchKernelGGL(grn_fold_weights_kernel, dim3(blocks), dim3(256), 0, stream, (const bf16_t*)wt, gamma, nx, (bf16_t*)out, Cout, C4, chunks);
     return iseg_check_launch("iseg_grn_fold_weights");
 }
@@ -405,19 +398,19 @@ extern "C" int iseg_grn_bwd_folded(const void* dy, const void* x, const float* g
                                    float* dstats, void* dx, float* dgamma, float* dbeta, int accumulate, int64_t N, int64_t HW, int C, float eps,
                                    int dtype, void* ws, size_t ws_bytes, hipStream_t stream) {
     ISEG_REQUIRE(dy && x && gamma && nx && gx && dstats && dx && dgamma && dbeta && N > 0 && HW > 0 && C > 0, "iseg_grn_bwd_folded: bad arguments");
-    ISEG_REQUIRE((dtype == ISEG_BF16 || dtype == ISEG_F32) && C % 8 == 0, "iseg_grn_bwd_folded: C %% 8 == 0 required (got dtype %d, C %d)", dtype, C);
+    ISEG_REQUIRE(C % 8 == 0, "iseg_grn_bwd_folded: C %% 8 == 0 required (got C %d)", C);
     ISEG_REQUIRE(N <= 65535, "iseg_grn_bwd_folded: at most 65535 samples");
-    ISEG_REQUIRE_WORKSPACE(ws && ws_bytes >= iseg_grn_workspace_bytes(N, HW, C), "iseg_grn_bwd_folded: workspace too small");
+    ISEG_REQUIRE(dtype == ISEG_BF16 || dtype == ISEG_F32, "iseg_grn_bwd_folded: dtype %d", dtype);      // (before the first launch)
+    ISEG_NEED_WORKSPACE("iseg_grn_bwd_folded", ws, ws_bytes, iseg_grn_workspace_bytes(N, HW, C));
     float* t = (float*)ws;
     hipLaunchKernelGGL(grn_bwd_stats_kernel, dim3((unsigned)N), dim3(256), 0, stream, dstats, 2 * (int64_t)C, gamma, nx, gx, t, C, eps);
     launch_reduce_rows(dstats, (int)N, 2 * (int64_t)C, 0, 1, 2 * (int64_t)C, dgamma, dbeta, C, 0, 1.f, accumulate, stream);
     const int64_t chunks = N * HW * (C / 8);
-    const unsigned blocks = (unsigned)(ceil_div64(chunks, 256) < 8192 ? ceil_div64(chunks, 256) : 8192);
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL((grn_apply_kernel<bf16_t, true>), dim3(blocks), dim3(256), 0, stream, (const bf16_t*)x, (const bf16_t*)dy, gamma,
-                           (const float*)nullptr, nx, (const float*)t, (const bf16_t*)mul, (bf16_t*)dx, HW, C, chunks);
-    else
-        hipLaunchKernelGGL((grn_apply_kernel<float, true>), dim3(blocks), dim3(256), 0, stream, (const float*)x, (const float*)dy, gamma,
-                           (const float*)nullptr, nx, (const float*)t, (const float*)mul, (float*)dx, HW, C, chunks);
-    return iseg_check_launch("iseg_grn_bwd_folded");
+    const unsigned blocks = grid_cap(chunks, 256, 8192);
+    return by_dtype(dtype, "iseg_grn_bwd_folded", [&](auto st) {
+        using T = decltype(st);
+        hipLaunchKernelGGL((grn_apply_kernel<T, true>), dim3(blocks), dim3(256), 0, stream, (const T*)x, (const T*)dy, gamma, (const float*)nullptr,
+                           nx, (const float*)t, (const T*)mul, (T*)dx, HW, C, chunks);
+        return iseg_check_launch("iseg_grn_bwd_folded");
+    });
 }

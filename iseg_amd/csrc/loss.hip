@@ -412,10 +412,7 @@ static int launch_softmax_ce(const float* logits, const int32_t* labels, const f
     float* bs = nullptr;
     if (loss_sum) {
         const size_t need = (size_t)blocks * sizeof(float);
-        if (!ws || ws_bytes < need) {
-            iseg_set_error("%s: needs %zu workspace bytes, got %zu", who, need, ws_bytes);
-            return ISEG_ERR_WORKSPACE;
-        }
+        ISEG_NEED_WORKSPACE(who, ws, ws_bytes, need);
         bs = (float*)ws;
     }
     const int use_hist = (cm != nullptr) && ((size_t)C * C * 4 <= 16 * 1024);
@@ -487,46 +484,38 @@ extern "C" int iseg_upsample_ce(const void* z, int dtype, const int32_t* labels,
                                 int C, int ignore_label, float* loss_sum, float loss_sum_scale, void* dz, float grad_scale, uint64_t* cm,
                                 void* ws, size_t ws_bytes, hipStream_t stream) {
     ISEG_REQUIRE(z && labels && loss_sum && N > 0, "iseg_upsample_ce: bad arguments");
-    ISEG_REQUIRE(dtype == ISEG_F32 || dtype == ISEG_BF16, "iseg_upsample_ce: bad dtype %d", dtype);
     int sy, sx;
     ISEG_REQUIRE(upsample_ce_geometry(Hi, Wi, Ho, Wo, C, sy, sx),
                  "iseg_upsample_ce: needs an integer upsampling factor (rows: even; columns: a power of two <= 64) and num_class <= 32; got "
                  "%dx%d -> %dx%d, %d classes (use iseg_resize_bilinear_fwd + iseg_softmax_ce_ignore)", Hi, Wi, Ho, Wo, C);
     ISEG_REQUIRE((int64_t)N * Ho * Wo < (1ll << 31), "iseg_upsample_ce: too many pixels");
     const size_t need = iseg_upsample_ce_workspace_bytes(N, Hi, Wi, Ho, Wo, C);
-    if (!ws || ws_bytes < need) {
-        iseg_set_error("iseg_upsample_ce: needs %zu workspace bytes, got %zu", need, ws_bytes);
-        return ISEG_ERR_WORKSPACE;
-    }
+    ISEG_NEED_WORKSPACE("iseg_upsample_ce", ws, ws_bytes, need);
     const int nwc = ((Wi + 1) * sx + 63) / 64;
     const int ns = upsample_ce_nsplit(N, Hi, nwc, sy);
     const int items = N * (Hi + 1) * ns * nwc;
     float* item_loss = (float*)ws;
     float* partial = dz ? item_loss + (items + 3) / 4 * 4 : nullptr;
     const int blocks = (items + 3) / 4;
-#define UCE(TI, CMAX, EXACT)                                                                                                            \
-    hipLaunchKernelGGL((upsample_ce_kernel<TI, CMAX, EXACT>), dim3(blocks), dim3(256), 0, stream, (const TI*)z, labels, class_w, N, Hi, Wi, Ho, \
-                       Wo, C, sy, sx, nwc, ns, ignore_label, grad_scale, item_loss, partial, (unsigned long long*)cm)
-#define UCE_T(TI)                          \
-    do {                                   \
-        if (C == 21) UCE(TI, 21, true);    \
-        else if (C == 19) UCE(TI, 19, true); \
-        else if (C <= 8) UCE(TI, 8, false);  \
-        else if (C <= 24) UCE(TI, 24, false); \
-        else UCE(TI, 32, false);             \
-    } while (0)
-    if (dtype == ISEG_BF16) UCE_T(bf16_t);
-    else UCE_T(float);
-#undef UCE_T
-#undef UCE
+    const int rc = by_dtype(dtype, "iseg_upsample_ce", [&](auto t) {
+        using TI = decltype(t);
+        const auto kernel = C == 21   ? upsample_ce_kernel<TI, 21, true>
+                            : C == 19 ? upsample_ce_kernel<TI, 19, true>
+                            : C <= 8  ? upsample_ce_kernel<TI, 8, false>
+                            : C <= 24 ? upsample_ce_kernel<TI, 24, false>
+                                      : upsample_ce_kernel<TI, 32, false>;
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, stream, (const TI*)z, labels, class_w, N, Hi, Wi, Ho, Wo, C, sy, sx, nwc, ns, ignore_label,
+                           grad_scale, item_loss, partial, (unsigned long long*)cm);
+    });
+    if (rc != ISEG_OK) return rc;
     hipLaunchKernelGGL(sum_blocks_kernel, dim3(1), dim3(256), 0, stream, (const float*)item_loss, items, loss_sum, loss_sum_scale);
     if (dz) {
         const int64_t total = (int64_t)N * Hi * Wi * C;
-        const int gb = (int)(ceil_div64(total, 256) < 1024 ? ceil_div64(total, 256) : 1024);
-        if (dtype == ISEG_BF16)
-            hipLaunchKernelGGL((upsample_ce_gather_kernel<bf16_t>), dim3(gb), dim3(256), 0, stream, (const float*)partial, (bf16_t*)dz, N, Hi, Wi, C, ns);
-        else
-            hipLaunchKernelGGL((upsample_ce_gather_kernel<float>), dim3(gb), dim3(256), 0, stream, (const float*)partial, (float*)dz, N, Hi, Wi, C, ns);
+        const unsigned gb = grid_cap(total, 256, 1024);
+        by_dtype(dtype, "iseg_upsample_ce", [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL((upsample_ce_gather_kernel<T>), dim3(gb), dim3(256), 0, stream, (const float*)partial, (T*)dz, N, Hi, Wi, C, ns);
+        });
     }
     return iseg_check_launch("iseg_upsample_ce");
 }

@@ -313,10 +313,7 @@ extern "C" int iseg_mask_loss(const float* logits, const int32_t* labels, int B,
     ISEG_REQUIRE((int64_t)B * ceil_div64(HW, mask_loss_pix(C)) < (1ll << 31), "iseg_mask_loss: too many tiles");
     const Layout l = mask_loss_layout(B, HW, C);
     const size_t need = l.total * sizeof(float);
-    if (!ws || ws_bytes < need) {
-        iseg_set_error("iseg_mask_loss: needs %zu workspace bytes, got %zu", need, ws_bytes);
-        return ISEG_ERR_WORKSPACE;
-    }
+    ISEG_NEED_WORKSPACE("iseg_mask_loss", ws, ws_bytes, need);
     float* partials = (float*)ws;
     float* img = partials + l.off_img;
     float* glob = partials + l.off_glob;
@@ -336,7 +333,7 @@ extern "C" int iseg_mask_loss(const float* logits, const int32_t* labels, int B,
         hipLaunchKernelGGL(mask_loss_finalize_kernel, dim3(1), dim3(1024), 0, stream, (const float*)partials, B, l.tpi, dice_coef, dice,      \
                            grad_px ? 1 : 0, grad_scale, loss_scale, img, glob, loss_mean);                                                     \
         if (loss_px && dice)                                                                                                                  \
-            hipLaunchKernelGGL(mask_loss_px_dice_kernel, dim3((unsigned)(ceil_div64(l.P, 256) < 2048 ? ceil_div64(l.P, 256) : 2048)),         \
+            hipLaunchKernelGGL(mask_loss_px_dice_kernel, dim3(grid_cap(l.P, 256, 2048)),         \
                                dim3(256), 0, stream, loss_px, labels, (const float*)img, HW, l.P, ignore_label);                               \
         if (dlogits)                                                                                                                          \
             hipLaunchKernelGGL((mask_loss_pass2_kernel<S, D, E>), grid, block, lds, stream, logits, labels, HW, C, ignore_label, l.tpi,       \

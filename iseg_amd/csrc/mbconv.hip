@@ -507,13 +507,11 @@ extern "C" int iseg_bn_swish_se_squeeze(const void* x, const float* mean, const 
     ISEG_REQUIRE(partials_bytes >= iseg_mbconv_partials_bytes(N, HW, C, 0), "iseg_bn_swish_se_squeeze: partials buffer too small");
     const MbTile t = mb_tile(HW, C);
     const dim3 grid(t.parts, t.slabs, N);
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL(mb_squeeze_kernel<bf16_t>, grid, dim3(MB_THREADS), 0, stream, (const bf16_t*)x, mean, rstd, gamma, beta, partials,
-                           HW, C, t);
-    else
-        hipLaunchKernelGGL(mb_squeeze_kernel<float>, grid, dim3(MB_THREADS), 0, stream, (const float*)x, mean, rstd, gamma, beta, partials,
-                           HW, C, t);
-    return iseg_check_launch("iseg_bn_swish_se_squeeze");
+    return by_dtype(dtype, "iseg_bn_swish_se_squeeze", [&](auto st) {
+        using T = decltype(st);
+        hipLaunchKernelGGL(mb_squeeze_kernel<T>, grid, dim3(MB_THREADS), 0, stream, (const T*)x, mean, rstd, gamma, beta, partials, HW, C, t);
+        return iseg_check_launch("iseg_bn_swish_se_squeeze");
+    });
 }
 
 extern "C" int iseg_se_excite_fwd(const float* partials, int N, int HW, int C, int Cse, const float* W1, const float* b1, const float* W2,
@@ -534,13 +532,11 @@ extern "C" int iseg_bn_swish_gate_fwd(const void* x, const float* mean, const fl
         MB_UNSUPPORTED("iseg_bn_swish_gate_fwd", N, HW, C, 0);
     const MbTile t = mb_tile(HW, C);
     const dim3 grid(t.parts, t.slabs, N);
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL(mb_gate_fwd_kernel<bf16_t>, grid, dim3(MB_THREADS), 0, stream, (const bf16_t*)x, mean, rstd, gamma, beta, g,
-                           (bf16_t*)out, HW, C, t);
-    else
-        hipLaunchKernelGGL(mb_gate_fwd_kernel<float>, grid, dim3(MB_THREADS), 0, stream, (const float*)x, mean, rstd, gamma, beta, g,
-                           (float*)out, HW, C, t);
-    return iseg_check_launch("iseg_bn_swish_gate_fwd");
+    return by_dtype(dtype, "iseg_bn_swish_gate_fwd", [&](auto st) {
+        using T = decltype(st);
+        hipLaunchKernelGGL(mb_gate_fwd_kernel<T>, grid, dim3(MB_THREADS), 0, stream, (const T*)x, mean, rstd, gamma, beta, g, (T*)out, HW, C, t);
+        return iseg_check_launch("iseg_bn_swish_gate_fwd");
+    });
 }
 
 extern "C" int iseg_bn_swish_gate_bwd_reduce(const void* dO, const void* x, const float* mean, const float* rstd, const float* gamma,
@@ -553,13 +549,12 @@ extern "C" int iseg_bn_swish_gate_bwd_reduce(const void* dO, const void* x, cons
     ISEG_REQUIRE(partials_bytes >= iseg_mbconv_partials_bytes(N, HW, C, 1), "iseg_bn_swish_gate_bwd_reduce: partials buffer too small");
     const MbTile t = mb_tile(HW, C);
     const dim3 grid(t.parts, t.slabs, N);
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL(mb_bwd_reduce_kernel<bf16_t>, grid, dim3(MB_THREADS), 0, stream, (const bf16_t*)dO, (const bf16_t*)x, mean, rstd,
-                           gamma, beta, partials, HW, C, t);
-    else
-        hipLaunchKernelGGL(mb_bwd_reduce_kernel<float>, grid, dim3(MB_THREADS), 0, stream, (const float*)dO, (const float*)x, mean, rstd,
-                           gamma, beta, partials, HW, C, t);
-    return iseg_check_launch("iseg_bn_swish_gate_bwd_reduce");
+    return by_dtype(dtype, "iseg_bn_swish_gate_bwd_reduce", [&](auto st) {
+        using T = decltype(st);
+        hipLaunchKernelGGL(mb_bwd_reduce_kernel<T>, grid, dim3(MB_THREADS), 0, stream, (const T*)dO, (const T*)x, mean, rstd, gamma, beta, partials,
+                           HW, C, t);
+        return iseg_check_launch("iseg_bn_swish_gate_bwd_reduce");
+    });
 }
 
 extern "C" int iseg_se_excite_bwd(const float* partials, int N, int HW, int C, int Cse, const float* W1, const float* W2, const float* m,
@@ -567,7 +562,7 @@ extern "C" int iseg_se_excite_bwd(const float* partials, int N, int HW, int C, i
                                   float* sums, void* ws, size_t ws_bytes, hipStream_t stream) {
     ISEG_REQUIRE(partials && W1 && W2 && m && hpre && g && dmh && sums && ws, "iseg_se_excite_bwd: null pointer");
     if (!mb_shape_ok(N, HW, C, Cse)) MB_UNSUPPORTED("iseg_se_excite_bwd", N, HW, C, Cse);
-    ISEG_REQUIRE_WORKSPACE(ws_bytes >= iseg_se_excite_bwd_workspace_bytes(N, C, Cse), "iseg_se_excite_bwd: workspace too small");
+    ISEG_NEED_WORKSPACE("iseg_se_excite_bwd", ws, ws_bytes, iseg_se_excite_bwd_workspace_bytes(N, C, Cse));
     const MbTile t = mb_tile(HW, C);
     float* S = (float*)ws;
     float* de = S + (int64_t)N * 5 * C;
@@ -593,11 +588,10 @@ extern "C" int iseg_bn_swish_gate_bwd_apply(const void* dO, const void* x, const
         MB_UNSUPPORTED("iseg_bn_swish_gate_bwd_apply", N, HW, C, 0);
     const MbTile t = mb_tile(HW, C);
     const dim3 grid(t.parts, t.slabs, N);
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL(mb_bwd_apply_kernel<bf16_t>, grid, dim3(MB_THREADS), 0, stream, (const bf16_t*)dO, (const bf16_t*)x, mean, rstd,
-                           gamma, beta, g, dmh, sums, inv_n, train, (bf16_t*)dx, dgamma, dbeta, HW, C, t);
-    else
-        hipLaunchKernelGGL(mb_bwd_apply_kernel<float>, grid, dim3(MB_THREADS), 0, stream, (const float*)dO, (const float*)x, mean, rstd,
-                           gamma, beta, g, dmh, sums, inv_n, train, (float*)dx, dgamma, dbeta, HW, C, t);
-    return iseg_check_launch("iseg_bn_swish_gate_bwd_apply");
+    return by_dtype(dtype, "iseg_bn_swish_gate_bwd_apply", [&](auto st) {
+        using T = decltype(st);
+        hipLaunchKernelGGL(mb_bwd_apply_kernel<T>, grid, dim3(MB_THREADS), 0, stream, (const T*)dO, (const T*)x, mean, rstd, gamma, beta, g, dmh,
+                           sums, inv_n, train, (T*)dx, dgamma, dbeta, HW, C, t);
+        return iseg_check_launch("iseg_bn_swish_gate_bwd_apply");
+    });
 }

@@ -261,12 +261,7 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const T* __restrict__ 
         partials[(int64_t)blockIdx.x * C + c] = (slab[c] + slab[C + c]) + (slab[2 * C + c] + slab[3 * C + c]);
 }
 
-static inline int rms_blocks(int64_t rows) {
-    int64_t b = ceil_div64(rows, 4 * 8);
-    if (b > 512) b = 512;
-    if (b < 1) b = 1;
-    return (int)b;
-}
+static inline int rms_blocks(int64_t rows) { return (int)grid_cap(rows, 4 * 8, 512); }
 
 // ---- pooling, padding="SAME" -----------------------------------------------------------------------------------------
 // mode 0: max (padding never wins), mode 1: average over the valid cells only (tf.nn.avg_pool2d SAME)
@@ -440,62 +435,45 @@ __global__ __launch_bounds__(256) void add_relu_kernel(const T* __restrict__ a, 
     }
 }
 
-static inline unsigned ew_blocks(int64_t n) {
-    int64_t b = ceil_div64(n, 256);
-    if (b > 256 * 16) b = 256 * 16;
-    if (b < 1) b = 1;
-    return (unsigned)b;
-}
+static inline unsigned ew_blocks(int64_t n) { return grid_cap(n, 256, 256 * 16); }
 
 }  // namespace
 
 extern "C" int iseg_replace_nan_or_inf(const void* x, void* y, int64_t n, float nan_value, int dtype, void* ws, size_t ws_bytes,
                                        hipStream_t stream) {
     ISEG_REQUIRE(x && y && n > 0, "iseg_replace_nan_or_inf: bad arguments");
-    if (!ws || ws_bytes < 8) {
-        iseg_set_error("iseg_replace_nan_or_inf: needs 8 workspace bytes, got %zu", ws_bytes);
-        return ISEG_ERR_WORKSPACE;
-    }
+    ISEG_REQUIRE(dtype == ISEG_BF16 || dtype == ISEG_F32, "iseg_replace_nan_or_inf: dtype %d", dtype);      // (before the first launch)
+    ISEG_NEED_WORKSPACE("iseg_replace_nan_or_inf", ws, ws_bytes, 8);
     unsigned* mm = (unsigned*)ws;
     hipLaunchKernelGGL(minmax_init_kernel, dim3(1), dim3(1), 0, stream, mm);
     // the min / max pass: at most four workgroups per CU (each ends in up to two atomics on the same two words), eight elements per lane and trip
-    int64_t rb = ceil_div64(ceil_div64(n, 8), 256);
-    if (rb > 1024) rb = 1024;
-    const unsigned red_blocks = (unsigned)rb;
-    if (dtype == ISEG_BF16) {
-        hipLaunchKernelGGL((finite_minmax_kernel<bf16_t>), dim3(red_blocks), dim3(256), 0, stream, (const bf16_t*)x, n, nan_value, mm);
-        hipLaunchKernelGGL((sanitize_apply_kernel<bf16_t>), dim3(ew_blocks(n)), dim3(256), 0, stream, (const bf16_t*)x, (bf16_t*)y, n,
-                           nan_value, mm);
-    } else {
-        hipLaunchKernelGGL((finite_minmax_kernel<float>), dim3(red_blocks), dim3(256), 0, stream, (const float*)x, n, nan_value, mm);
-        hipLaunchKernelGGL((sanitize_apply_kernel<float>), dim3(ew_blocks(n)), dim3(256), 0, stream, (const float*)x, (float*)y, n,
-                           nan_value, mm);
-    }
-    return iseg_check_launch("iseg_replace_nan_or_inf");
+    const unsigned red_blocks = grid_cap(ceil_div64(n, 8), 256, 1024);
+    return by_dtype(dtype, "iseg_replace_nan_or_inf", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((finite_minmax_kernel<T>), dim3(red_blocks), dim3(256), 0, stream, (const T*)x, n, nan_value, mm);
+        hipLaunchKernelGGL((sanitize_apply_kernel<T>), dim3(ew_blocks(n)), dim3(256), 0, stream, (const T*)x, (T*)y, n, nan_value, mm);
+        return iseg_check_launch("iseg_replace_nan_or_inf");
+    });
 }
 
 extern "C" int iseg_replace_nan_or_inf_bwd(const void* x, const void* dy, void* dx, int64_t n, int dtype, hipStream_t stream) {
     ISEG_REQUIRE(x && dy && dx && n > 0, "iseg_replace_nan_or_inf_bwd: bad arguments");
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL((sanitize_bwd_kernel<bf16_t>), dim3(ew_blocks(n)), dim3(256), 0, stream, (const bf16_t*)x, (const bf16_t*)dy,
-                           (bf16_t*)dx, n);
-    else
-        hipLaunchKernelGGL((sanitize_bwd_kernel<float>), dim3(ew_blocks(n)), dim3(256), 0, stream, (const float*)x, (const float*)dy,
-                           (float*)dx, n);
-    return iseg_check_launch("iseg_replace_nan_or_inf_bwd");
+    return by_dtype(dtype, "iseg_replace_nan_or_inf_bwd", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((sanitize_bwd_kernel<T>), dim3(ew_blocks(n)), dim3(256), 0, stream, (const T*)x, (const T*)dy, (T*)dx, n);
+        return iseg_check_launch("iseg_replace_nan_or_inf_bwd");
+    });
 }
 
 extern "C" int iseg_groupnorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, int N,
                                   int HW, int C, int G, float eps, int dtype, hipStream_t stream) {
     ISEG_REQUIRE(x && y && mean && rstd, "iseg_groupnorm_fwd: null pointer");
     ISEG_REQUIRE(N > 0 && HW > 0 && C > 0 && G > 0 && C % G == 0, "iseg_groupnorm_fwd: C=%d is not a multiple of groups=%d", C, G);
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL((groupnorm_fwd_kernel<bf16_t>), dim3(N * G), dim3(256), 0, stream, (const bf16_t*)x, gamma, beta, (bf16_t*)y,
-                           mean, rstd, HW, C, G, eps);
-    else
-        hipLaunchKernelGGL((groupnorm_fwd_kernel<float>), dim3(N * G), dim3(256), 0, stream, (const float*)x, gamma, beta, (float*)y,
-                           mean, rstd, HW, C, G, eps);
-    return iseg_check_launch("iseg_groupnorm_fwd");
+    return by_dtype(dtype, "iseg_groupnorm_fwd", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((groupnorm_fwd_kernel<T>), dim3(N * G), dim3(256), 0, stream, (const T*)x, gamma, beta, (T*)y, mean, rstd, HW, C, G, eps);
+        return iseg_check_launch("iseg_groupnorm_fwd");
+    });
 }
 
 extern "C" size_t iseg_groupnorm_bwd_workspace_bytes(int N, int C) { return (size_t)N * 2 * C * sizeof(float); }
@@ -507,16 +485,13 @@ extern "C" int iseg_groupnorm_bwd(const void* dy, const void* x, const float* ga
     ISEG_REQUIRE(N > 0 && HW > 0 && C > 0 && G > 0 && C % G == 0, "iseg_groupnorm_bwd: C=%d is not a multiple of groups=%d", C, G);
     ISEG_REQUIRE(C / G <= 256, "iseg_groupnorm_bwd: %d channels per group (max 256)", C / G);
     const size_t need = iseg_groupnorm_bwd_workspace_bytes(N, C);
-    if (!ws || ws_bytes < need) {
-        iseg_set_error("iseg_groupnorm_bwd: needs %zu workspace bytes, got %zu", need, ws_bytes);
-        return ISEG_ERR_WORKSPACE;
-    }
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL((groupnorm_bwd_kernel<bf16_t>), dim3(N * G), dim3(256), 0, stream, (const bf16_t*)dy, (const bf16_t*)x, gamma,
-                           mean, rstd, (bf16_t*)dx, (float*)ws, HW, C, G);
-    else
-        hipLaunchKernelGGL((groupnorm_bwd_kernel<float>), dim3(N * G), dim3(256), 0, stream, (const float*)dy, (const float*)x, gamma,
-                           mean, rstd, (float*)dx, (float*)ws, HW, C, G);
+    ISEG_NEED_WORKSPACE("iseg_groupnorm_bwd", ws, ws_bytes, need);
+    const int rc = by_dtype(dtype, "iseg_groupnorm_bwd", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((groupnorm_bwd_kernel<T>), dim3(N * G), dim3(256), 0, stream, (const T*)dy, (const T*)x, gamma, mean, rstd, (T*)dx,
+                           (float*)ws, HW, C, G);
+    });
+    if (rc != ISEG_OK) return rc;
     if (dgamma || dbeta) {
         if (dgamma) launch_reduce_rows((const float*)ws, N, 2 * C, 0, 1, C, dgamma, nullptr, C, 0, 1.f, accumulate_param_grads, stream);
         if (dbeta) launch_reduce_rows((const float*)ws + C, N, 2 * C, 0, 1, C, dbeta, nullptr, C, 0, 1.f, accumulate_param_grads, stream);
@@ -528,13 +503,11 @@ extern "C" int iseg_rmsnorm_fwd(const void* x, const float* scale, void* y, floa
                                 hipStream_t stream) {
     ISEG_REQUIRE(x && scale && y && rows > 0 && C > 0, "iseg_rmsnorm_fwd: bad arguments");
     const int blocks = rms_blocks(rows);
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL((rmsnorm_fwd_kernel<bf16_t>), dim3(blocks), dim3(256), 0, stream, (const bf16_t*)x, scale, (bf16_t*)y, rstd,
-                           rows, C, eps);
-    else
-        hipLaunchKernelGGL((rmsnorm_fwd_kernel<float>), dim3(blocks), dim3(256), 0, stream, (const float*)x, scale, (float*)y, rstd, rows,
-                           C, eps);
-    return iseg_check_launch("iseg_rmsnorm_fwd");
+    return by_dtype(dtype, "iseg_rmsnorm_fwd", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((rmsnorm_fwd_kernel<T>), dim3(blocks), dim3(256), 0, stream, (const T*)x, scale, (T*)y, rstd, rows, C, eps);
+        return iseg_check_launch("iseg_rmsnorm_fwd");
+    });
 }
 
 extern "C" size_t iseg_rmsnorm_bwd_workspace_bytes(int64_t rows, int C) { return (size_t)rms_blocks(rows) * C * sizeof(float); }
@@ -546,17 +519,14 @@ extern "C" int iseg_rmsnorm_bwd(const void* dy, const void* x, const float* scal
     ISEG_REQUIRE(C <= 8192, "iseg_rmsnorm_bwd: C=%d too wide (max 8192)", C);
     const int blocks = rms_blocks(rows);
     const size_t need = (size_t)blocks * C * sizeof(float);
-    if (!ws || ws_bytes < need) {
-        iseg_set_error("iseg_rmsnorm_bwd: needs %zu workspace bytes, got %zu", need, ws_bytes);
-        return ISEG_ERR_WORKSPACE;
-    }
+    ISEG_NEED_WORKSPACE("iseg_rmsnorm_bwd", ws, ws_bytes, need);
     const size_t lds = (size_t)4 * C * sizeof(float);
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL((rmsnorm_bwd_kernel<bf16_t>), dim3(blocks), dim3(256), lds, stream, (const bf16_t*)dy, (const bf16_t*)x, scale,
-                           rstd, (bf16_t*)dx, (float*)ws, rows, C);
-    else
-        hipLaunchKernelGGL((rmsnorm_bwd_kernel<float>), dim3(blocks), dim3(256), lds, stream, (const float*)dy, (const float*)x, scale,
-                           rstd, (float*)dx, (float*)ws, rows, C);
+    const int rc = by_dtype(dtype, "iseg_rmsnorm_bwd", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((rmsnorm_bwd_kernel<T>), dim3(blocks), dim3(256), lds, stream, (const T*)dy, (const T*)x, scale, rstd, (T*)dx, (float*)ws,
+                           rows, C);
+    });
+    if (rc != ISEG_OK) return rc;
     launch_reduce_rows((const float*)ws, blocks, C, 0, 1, C, dscale, nullptr, C, 0, 1.f, accumulate_param_grads, stream);
     return iseg_check_launch("iseg_rmsnorm_bwd");
 }
@@ -569,13 +539,12 @@ extern "C" int iseg_pool2d_fwd(const void* x, void* y, int N, int H, int W, int 
                  "iseg_pool2d_fwd: bad window geometry");
     ISEG_REQUIRE((Ho - 1) * sh - pad_t < H && (Wo - 1) * sw - pad_l < W, "iseg_pool2d_fwd: output window outside the input");
     const int64_t total = (int64_t)N * Ho * Wo * C;
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL((pool2d_fwd_kernel<bf16_t>), dim3(ew_blocks(total)), dim3(256), 0, stream, (const bf16_t*)x, (bf16_t*)y, N, H, W,
-                           C, kh, kw, sh, sw, pad_t, pad_l, Ho, Wo, mode);
-    else
-        hipLaunchKernelGGL((pool2d_fwd_kernel<float>), dim3(ew_blocks(total)), dim3(256), 0, stream, (const float*)x, (float*)y, N, H, W, C,
-                           kh, kw, sh, sw, pad_t, pad_l, Ho, Wo, mode);
-    return iseg_check_launch("iseg_pool2d_fwd");
+    return by_dtype(dtype, "iseg_pool2d_fwd", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((pool2d_fwd_kernel<T>), dim3(ew_blocks(total)), dim3(256), 0, stream, (const T*)x, (T*)y, N, H, W, C, kh, kw, sh, sw,
+                           pad_t, pad_l, Ho, Wo, mode);
+        return iseg_check_launch("iseg_pool2d_fwd");
+    });
 }
 
 extern "C" size_t iseg_pool2d_bwd_workspace_bytes(int N, int Ho, int Wo, int C, int mode) {
@@ -593,41 +562,31 @@ extern "C" int iseg_pool2d_bwd(const void* x, const void* dy, void* dx, int N, i
     const size_t need = iseg_pool2d_bwd_workspace_bytes(N, Ho, Wo, C, mode);
     const bool aligned = (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx) & 15) == 0 && ((uintptr_t)ws & 7) == 0;
     if (need > 0 && kh * kw < 255 && aligned) {
-        if (!ws || ws_bytes < need) {
-            iseg_set_error("iseg_pool2d_bwd: needs %zu workspace bytes, got %zu", need, ws_bytes);
-            return ISEG_ERR_WORKSPACE;
-        }
+        ISEG_NEED_WORKSPACE("iseg_pool2d_bwd", ws, ws_bytes, need);
         unsigned char* idx = (unsigned char*)ws;
         const int64_t n_out = (int64_t)N * Ho * Wo * (C / 8), n_in = total / 8;
-        if (dtype == ISEG_BF16) {
-            hipLaunchKernelGGL((pool_argmax_kernel<bf16_t>), dim3(ew_blocks(n_out)), dim3(256), 0, stream, (const bf16_t*)x, idx, N, H, W, C,
-                               kh, kw, sh, sw, pad_t, pad_l, Ho, Wo);
-            hipLaunchKernelGGL((pool_max_bwd_idx_kernel<bf16_t>), dim3(ew_blocks(n_in)), dim3(256), 0, stream, idx, (const bf16_t*)dy,
-                               (bf16_t*)dx, N, H, W, C, kh, kw, sh, sw, pad_t, pad_l, Ho, Wo);
-        } else {
-            hipLaunchKernelGGL((pool_argmax_kernel<float>), dim3(ew_blocks(n_out)), dim3(256), 0, stream, (const float*)x, idx, N, H, W, C,
-                               kh, kw, sh, sw, pad_t, pad_l, Ho, Wo);
-            hipLaunchKernelGGL((pool_max_bwd_idx_kernel<float>), dim3(ew_blocks(n_in)), dim3(256), 0, stream, idx, (const float*)dy,
-                               (float*)dx, N, H, W, C, kh, kw, sh, sw, pad_t, pad_l, Ho, Wo);
-        }
-        return iseg_check_launch("iseg_pool2d_bwd");
+        return by_dtype(dtype, "iseg_pool2d_bwd", [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL((pool_argmax_kernel<T>), dim3(ew_blocks(n_out)), dim3(256), 0, stream, (const T*)x, idx, N, H, W, C, kh, kw, sh, sw, pad_t,
+                               pad_l, Ho, Wo);
+            hipLaunchKernelGGL((pool_max_bwd_idx_kernel<T>), dim3(ew_blocks(n_in)), dim3(256), 0, stream, idx, (const T*)dy, (T*)dx, N, H, W, C, kh, kw,
+                               sh, sw, pad_t, pad_l, Ho, Wo);
+            return iseg_check_launch("iseg_pool2d_bwd");
+        });
     }
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL((pool2d_bwd_kernel<bf16_t>), dim3(ew_blocks(total)), dim3(256), 0, stream, (const bf16_t*)x, (const bf16_t*)dy,
-                           (bf16_t*)dx, N, H, W, C, kh, kw, sh, sw, pad_t, pad_l, Ho, Wo, mode);
-    else
-        hipLaunchKernelGGL((pool2d_bwd_kernel<float>), dim3(ew_blocks(total)), dim3(256), 0, stream, (const float*)x, (const float*)dy,
-                           (float*)dx, N, H, W, C, kh, kw, sh, sw, pad_t, pad_l, Ho, Wo, mode);
-    return iseg_check_launch("iseg_pool2d_bwd");
+    return by_dtype(dtype, "iseg_pool2d_bwd", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((pool2d_bwd_kernel<T>), dim3(ew_blocks(total)), dim3(256), 0, stream, (const T*)x, (const T*)dy, (T*)dx, N, H, W, C, kh,
+                           kw, sh, sw, pad_t, pad_l, Ho, Wo, mode);
+        return iseg_check_launch("iseg_pool2d_bwd");
+    });
 }
 
 extern "C" int iseg_add_relu(const void* a, const void* b, void* y, int64_t n, int dtype, hipStream_t stream) {
     ISEG_REQUIRE(a && b && y && n > 0 && n % 8 == 0, "iseg_add_relu: n=%lld must be a positive multiple of 8", (long long)n);
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL((add_relu_kernel<bf16_t>), dim3(ew_blocks(n / 8)), dim3(256), 0, stream, (const bf16_t*)a, (const bf16_t*)b,
-                           (bf16_t*)y, n / 8);
-    else
-        hipLaunchKernelGGL((add_relu_kernel<float>), dim3(ew_blocks(n / 8)), dim3(256), 0, stream, (const float*)a, (const float*)b,
-                           (float*)y, n / 8);
-    return iseg_check_launch("iseg_add_relu");
+    return by_dtype(dtype, "iseg_add_relu", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((add_relu_kernel<T>), dim3(ew_blocks(n / 8)), dim3(256), 0, stream, (const T*)a, (const T*)b, (T*)y, n / 8);
+        return iseg_check_launch("iseg_add_relu");
+    });
 }

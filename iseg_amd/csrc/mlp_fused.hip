@@ -781,10 +781,7 @@ extern "C" int iseg_convnext_mlp_bwd_data_ln(const void* y1, const float* mean, 
     ISEG_REQUIRE((((uintptr_t)y1 | (uintptr_t)dout | (uintptr_t)bw_tiled | (uintptr_t)b1 | (uintptr_t)dy1 | (uintptr_t)ln_gamma | (uintptr_t)ln_beta) & 15) == 0,
                  "iseg_convnext_mlp_bwd_data_ln: operands must be 16-byte aligned");
     const size_t need = iseg_convnext_mlp_bwd_data_ln_workspace_bytes(M, C);
-    if (!ws || ws_bytes < need) {
-        iseg_set_error("iseg_convnext_mlp_bwd_data_ln: needs %zu workspace bytes, got %zu", need, ws_bytes);
-        return ISEG_ERR_WORKSPACE;
-    }
+    ISEG_NEED_WORKSPACE("iseg_convnext_mlp_bwd_data_ln", ws, ws_bytes, need);
     const MlpLayerNorm ln{ln_gamma, ln_beta, const_cast<float*>(mean), const_cast<float*>(rstd), 0.f};
     // dgamma | dbeta: the workgroups' partial rows, summed in fixed order into the gradient buffers (queued when the caller defers reductions)
     float* partials = (float*)ws;

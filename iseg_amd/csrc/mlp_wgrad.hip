@@ -424,10 +424,7 @@ extern "C" int iseg_convnext_mlp_wgrad(const void* y, const float* mean, const f
                  "iseg_convnext_mlp_wgrad: operands must be 16-byte aligned");
     int nchunk;
     const size_t need = wgrad_ws_floats(C, M, &nchunk) * sizeof(float);
-    if (!ws || ws_bytes < need) {
-        iseg_set_error("iseg_convnext_mlp_wgrad: needs %zu workspace bytes, got %zu", need, ws_bytes);
-        return ISEG_ERR_WORKSPACE;
-    }
+    ISEG_NEED_WORKSPACE("iseg_convnext_mlp_wgrad", ws, ws_bytes, need);
     float* const wsf = (float*)ws;
     int rc = C == 96 ? launch_wgrad<96>(y, mean, rstd, ln_gamma, ln_beta, dout, rowscale, rows_per_group, bw_tiled, b1, wsf, M, stream)
                      : launch_wgrad<192>(y, mean, rstd, ln_gamma, ln_beta, dout, rowscale, rows_per_group, bw_tiled, b1, wsf, M, stream);

@@ -126,7 +126,7 @@ extern "C" int iseg_projective_transform_batch(const float* images, const int32_
     k.has_replace = replace != nullptr;
     for (int c = 0; c < C && replace; ++c) k.replace[c] = replace[c];
     const int64_t tiles = (int64_t)B * ceil_div64(Hs, TILE_H) * ceil_div64(Ws, TILE_W);
-    const unsigned blocks = (unsigned)(tiles < 16384 ? tiles : 16384);
+    const unsigned blocks = grid_cap(tiles, 1, 16384);
     switch (C) {
         case 1: launch<1>(image_interp, blocks, stream, images, labels, transforms, sizes, out_images, out_labels, B, Hs, Ws, image_fill, k, label_fill); break;
         case 2: launch<2>(image_interp, blocks, stream, images, labels, transforms, sizes, out_images, out_labels, B, Hs, Ws, image_fill, k, label_fill); break;

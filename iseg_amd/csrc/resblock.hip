@@ -384,23 +384,9 @@ RbGeom rb_geom(int N, int H, int W, int C, int stride) {
         return ISEG_ERR_UNSUPPORTED;                                                                                                 \
     } while (0)
 
-// kernel<T, S, BN0> from the runtime (dtype, stride, bn0)
-#define RB_DISPATCH(KERNEL, GRID, LDS, STREAM, dtype, stride, bn0, ...)                                                                \
-    do {                                                                                                                           \
-        if (dtype == ISEG_BF16) {                                                                                                  \
-            typedef bf16_t T;                                                                                                      \
-            if (stride == 1 && bn0) hipLaunchKernelGGL((KERNEL<T, 1, true>), GRID, dim3(RB_THREADS), LDS, STREAM, __VA_ARGS__);   \
-            else if (stride == 1) hipLaunchKernelGGL((KERNEL<T, 1, false>), GRID, dim3(RB_THREADS), LDS, STREAM, __VA_ARGS__);    \
-            else if (bn0) hipLaunchKernelGGL((KERNEL<T, 2, true>), GRID, dim3(RB_THREADS), LDS, STREAM, __VA_ARGS__);             \
-            else hipLaunchKernelGGL((KERNEL<T, 2, false>), GRID, dim3(RB_THREADS), LDS, STREAM, __VA_ARGS__);                     \
-        } else {                                                                                                                   \
-            typedef float T;                                                                                                       \
-            if (stride == 1 && bn0) hipLaunchKernelGGL((KERNEL<T, 1, true>), GRID, dim3(RB_THREADS), LDS, STREAM, __VA_ARGS__);   \
-            else if (stride == 1) hipLaunchKernelGGL((KERNEL<T, 1, false>), GRID, dim3(RB_THREADS), LDS, STREAM, __VA_ARGS__);    \
-            else if (bn0) hipLaunchKernelGGL((KERNEL<T, 2, true>), GRID, dim3(RB_THREADS), LDS, STREAM, __VA_ARGS__);             \
-            else hipLaunchKernelGGL((KERNEL<T, 2, false>), GRID, dim3(RB_THREADS), LDS, STREAM, __VA_ARGS__);                     \
-        }                                                                                                                          \
-    } while (0)
+// kernel<T, S, BN0> from the runtime (stride, bn0)
+#define RB_KERNEL(KERNEL, T, stride, bn0) \
+    (stride == 1 ? (bn0 ? KERNEL<T, 1, true> : KERNEL<T, 1, false>) : (bn0 ? KERNEL<T, 2, true> : KERNEL<T, 2, false>))
 
 }  // namespace
 
@@ -421,16 +407,19 @@ extern "C" int iseg_resblock_tail_fwd(const void* z2, const float* mean2, const 
     ISEG_REQUIRE(z2 && mean2 && rstd2 && gamma2 && beta2 && sc && out, "iseg_resblock_tail_fwd: null pointer");
     const bool bn0 = mean0 != nullptr;
     ISEG_REQUIRE(!bn0 || (rstd0 && gamma0 && beta0), "iseg_resblock_tail_fwd: BN0 needs mean0, rstd0, gamma0 and beta0");
-    if (!rb_shape_ok(N, H, W, C, stride) || !iseg_resblock_tail_supported(C, stride, dtype) || !rb_aligned(z2) || !rb_aligned(sc) ||
+    if (!rb_shape_ok(N, H, W, C, stride) || !rb_aligned(z2) || !rb_aligned(sc) ||
         !rb_aligned(out) || !rb_aligned(mean2) || !rb_aligned(rstd2) || !rb_aligned(gamma2) || !rb_aligned(beta2) ||
         (bn0 && (!rb_aligned(mean0) || !rb_aligned(rstd0) || !rb_aligned(gamma0) || !rb_aligned(beta0))))
         RB_UNSUPPORTED("iseg_resblock_tail_fwd", N, H, W, C, stride);
     const RbGeom g = rb_geom(N, H, W, C, stride);
     const RbTile t = rb_tile(g.P, C);
     const dim3 grid(t.parts, t.slabs);
-    RB_DISPATCH(rb_fwd_kernel, grid, 0, stream, dtype, stride, bn0, (const T*)z2, mean2, rstd2, gamma2, beta2, (const T*)sc, mean0, rstd0,
-                gamma0, beta0, (T*)out, g, t);
-    return iseg_check_launch("iseg_resblock_tail_fwd");
+    return by_dtype(dtype, "iseg_resblock_tail_fwd", [&](auto st) {
+        using T = decltype(st);
+        hipLaunchKernelGGL(RB_KERNEL(rb_fwd_kernel, T, stride, bn0), grid, dim3(RB_THREADS), 0, stream, (const T*)z2, mean2, rstd2, gamma2, beta2,
+                           (const T*)sc, mean0, rstd0, gamma0, beta0, (T*)out, g, t);
+        return iseg_check_launch("iseg_resblock_tail_fwd");
+    });
 }
 
 extern "C" int iseg_resblock_tail_bwd_reduce(const void* dout, const void* out, const void* z2, const float* mean2, const float* rstd2,
@@ -439,15 +428,19 @@ extern "C" int iseg_resblock_tail_bwd_reduce(const void* dout, const void* out, 
     ISEG_REQUIRE(dout && out && z2 && mean2 && rstd2 && sums && ws, "iseg_resblock_tail_bwd_reduce: null pointer");
     const bool bn0 = z0 != nullptr;
     ISEG_REQUIRE(!bn0 || (mean0 && rstd0), "iseg_resblock_tail_bwd_reduce: BN0 needs mean0 and rstd0");
-    if (!rb_shape_ok(N, H, W, C, stride) || !iseg_resblock_tail_supported(C, stride, dtype) || !rb_aligned(dout) || !rb_aligned(out) ||
+    if (!rb_shape_ok(N, H, W, C, stride) || !rb_aligned(dout) || !rb_aligned(out) ||
         !rb_aligned(z2) || !rb_aligned(mean2) || !rb_aligned(rstd2) || (bn0 && (!rb_aligned(z0) || !rb_aligned(mean0) || !rb_aligned(rstd0))))
         RB_UNSUPPORTED("iseg_resblock_tail_bwd_reduce", N, H, W, C, stride);
-    ISEG_REQUIRE_WORKSPACE(ws_bytes >= iseg_resblock_tail_workspace_bytes(N, H, W, C, stride, bn0), "iseg_resblock_tail_bwd_reduce: workspace too small");
+    ISEG_NEED_WORKSPACE("iseg_resblock_tail_bwd_reduce", ws, ws_bytes, iseg_resblock_tail_workspace_bytes(N, H, W, C, stride, bn0));
     const RbGeom g = rb_geom(N, H, W, C, stride);
     const RbTile t = rb_tile(g.P, C);
     float* partials = (float*)ws;
-    RB_DISPATCH(rb_bwd_reduce_kernel, dim3(t.parts, t.slabs), 0, stream, dtype, stride, bn0, (const T*)dout, (const T*)out, (const T*)z2, mean2,
-                rstd2, (const T*)z0, mean0, rstd0, partials, g, t);
+    const int rc = by_dtype(dtype, "iseg_resblock_tail_bwd_reduce", [&](auto st) {
+        using T = decltype(st);
+        hipLaunchKernelGGL(RB_KERNEL(rb_bwd_reduce_kernel, T, stride, bn0), dim3(t.parts, t.slabs), dim3(RB_THREADS), 0, stream, (const T*)dout,
+                           (const T*)out, (const T*)z2, mean2, rstd2, (const T*)z0, mean0, rstd0, partials, g, t);
+    });
+    if (rc != ISEG_OK) return rc;
     const int NQ = bn0 ? 3 : 2;
     const int cols_per_block = RB_THREADS / RBF_PART_LANES;
     hipLaunchKernelGGL(rb_bwd_sums_kernel, dim3((unsigned)ceil_div64((int64_t)NQ * C, cols_per_block)), dim3(RB_THREADS), 0, stream, partials,
@@ -463,7 +456,7 @@ extern "C" int iseg_resblock_tail_bwd_apply(const void* dout, const void* out, c
     ISEG_REQUIRE(dout && out && z2 && mean2 && rstd2 && gamma2 && sums && dz2 && dsc, "iseg_resblock_tail_bwd_apply: null pointer");
     const bool bn0 = z0 != nullptr;
     ISEG_REQUIRE(!bn0 || (mean0 && rstd0 && gamma0), "iseg_resblock_tail_bwd_apply: BN0 needs mean0, rstd0 and gamma0");
-    if (!rb_shape_ok(N, H, W, C, stride) || !iseg_resblock_tail_supported(C, stride, dtype) || !rb_aligned(dout) || !rb_aligned(out) ||
+    if (!rb_shape_ok(N, H, W, C, stride) || !rb_aligned(dout) || !rb_aligned(out) ||
         !rb_aligned(z2) || !rb_aligned(dz2) || !rb_aligned(dsc) || !rb_aligned(mean2) || !rb_aligned(rstd2) || !rb_aligned(gamma2) ||
         !rb_aligned(sums) || (bn0 && (!rb_aligned(z0) || !rb_aligned(mean0) || !rb_aligned(rstd0) || !rb_aligned(gamma0))) ||
         (dgamma2 && !rb_aligned(dgamma2)) || (dbeta2 && !rb_aligned(dbeta2)) || (dgamma0 && !rb_aligned(dgamma0)) ||
@@ -471,8 +464,11 @@ extern "C" int iseg_resblock_tail_bwd_apply(const void* dout, const void* out, c
         RB_UNSUPPORTED("iseg_resblock_tail_bwd_apply", N, H, W, C, stride);
     const RbGeom g = rb_geom(N, H, W, C, stride);
     const RbTile t = rb_tile(g.P, C);
-    RB_DISPATCH(rb_bwd_apply_kernel, dim3(t.parts, t.slabs), 0, stream, dtype, stride, bn0, (const T*)dout, (const T*)out, (const T*)z2, mean2,
-                rstd2, gamma2, (const T*)z0, mean0, rstd0, gamma0, sums, inv_n2, inv_n0, train, (T*)dz2, (T*)dsc, dgamma2, dbeta2,
-                bn0 ? dgamma0 : nullptr, bn0 ? dbeta0 : nullptr, g, t);
-    return iseg_check_launch("iseg_resblock_tail_bwd_apply");
+    return by_dtype(dtype, "iseg_resblock_tail_bwd_apply", [&](auto st) {
+        using T = decltype(st);
+        hipLaunchKernelGGL(RB_KERNEL(rb_bwd_apply_kernel, T, stride, bn0), dim3(t.parts, t.slabs), dim3(RB_THREADS), 0, stream, (const T*)dout,
+                           (const T*)out, (const T*)z2, mean2, rstd2, gamma2, (const T*)z0, mean0, rstd0, gamma0, sums, inv_n2, inv_n0, train, (T*)dz2,
+                           (T*)dsc, dgamma2, dbeta2, bn0 ? dgamma0 : nullptr, bn0 ? dbeta0 : nullptr, g, t);
+        return iseg_check_launch("iseg_resblock_tail_bwd_apply");
+    });
 }

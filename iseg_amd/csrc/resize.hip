@@ -472,12 +472,7 @@ __global__ void resize_nearest_i32_kernel(const int32_t* __restrict__ x, int32_t
     }
 }
 
-static inline unsigned cap_blocks(int64_t items) {
-    int64_t b = ceil_div64(items, 256);
-    if (b > 256 * 8) b = 256 * 8;
-    if (b < 1) b = 1;
-    return (unsigned)b;
-}
+static inline unsigned cap_blocks(int64_t items) { return grid_cap(items, 256, 256 * 8); }
 
 }  // namespace
 
@@ -487,53 +482,23 @@ extern "C" int iseg_resize_bilinear_fwd(const void* x, int in_dtype, void* y, in
     ISEG_REQUIRE((int64_t)Wo * C < (1ll << 30) && (int64_t)Wi * C < (1ll << 30) && (int64_t)N * Ho < (1ll << 31),
                  "iseg_resize_bilinear_fwd: row too long");
     const float sy = (float)Hi / (float)Ho, sx = (float)Wi / (float)Wo;
-    int64_t blocks = (int64_t)N * Ho;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-#define RS(TI, TO)                                                                                                                    \
-    hipLaunchKernelGGL((resize_bilinear_fwd_kernel<TI, TO>), dim3((unsigned)blocks), dim3(256), 0, stream, (const TI*)x, (TO*)y, N, Hi, \
-                       Wi, Ho, Wo, C, sy, sx)
+    const unsigned blocks = grid_cap((int64_t)N * Ho, 1, 256 * 16);
     const size_t lds = ((size_t)2 * Wi * C + (size_t)3 * Wo) * sizeof(float);
-    if (lds <= 48 * 1024 && (int64_t)Wo * C >= 1024) {   // small source rows, long output rows: LDS-resident sources
-#define RSL(TI, TO)                                                                                                                   \
-    hipLaunchKernelGGL((resize_bilinear_fwd_lds_kernel<TI, TO>), dim3((unsigned)blocks), dim3(256), lds, stream, (const TI*)x, (TO*)y, \
-                       N, Hi, Wi, Ho, Wo, C, sy, sx)
-        if (in_dtype == ISEG_F32 && out_dtype == ISEG_F32) RSL(float, float);
-        else if (in_dtype == ISEG_BF16 && out_dtype == ISEG_F32) RSL(bf16_t, float);
-        else if (in_dtype == ISEG_BF16 && out_dtype == ISEG_BF16) RSL(bf16_t, bf16_t);
-        else if (in_dtype == ISEG_F32 && out_dtype == ISEG_BF16) RSL(float, bf16_t);
-        else {
-            iseg_set_error("iseg_resize_bilinear_fwd: bad dtypes");
-            return ISEG_ERR_ARG;
-        }
-#undef RSL
-        return iseg_check_launch("iseg_resize_bilinear_fwd");
-    }
-    if (C % 8 == 0 && ((uintptr_t)x | (uintptr_t)y) % 16 == 0) {
-        const unsigned vb = cap_blocks((int64_t)N * Ho * Wo * (C / 8));
-#define RSV(TI, TO)                                                                                                                  \
-    hipLaunchKernelGGL((resize_bilinear_fwd_vec_kernel<TI, TO>), dim3(vb), dim3(256), 0, stream, (const TI*)x, (TO*)y, N, Hi, Wi, Ho, \
-                       Wo, C, sy, sx)
-        if (in_dtype == ISEG_F32 && out_dtype == ISEG_F32) RSV(float, float);
-        else if (in_dtype == ISEG_BF16 && out_dtype == ISEG_F32) RSV(bf16_t, float);
-        else if (in_dtype == ISEG_BF16 && out_dtype == ISEG_BF16) RSV(bf16_t, bf16_t);
-        else if (in_dtype == ISEG_F32 && out_dtype == ISEG_BF16) RSV(float, bf16_t);
-        else {
-            iseg_set_error("iseg_resize_bilinear_fwd: bad dtypes");
-            return ISEG_ERR_ARG;
-        }
-#undef RSV
-        return iseg_check_launch("iseg_resize_bilinear_fwd");
-    }
-    if (in_dtype == ISEG_F32 && out_dtype == ISEG_F32) RS(float, float);
-    else if (in_dtype == ISEG_BF16 && out_dtype == ISEG_F32) RS(bf16_t, float);
-    else if (in_dtype == ISEG_BF16 && out_dtype == ISEG_BF16) RS(bf16_t, bf16_t);
-    else if (in_dtype == ISEG_F32 && out_dtype == ISEG_BF16) RS(float, bf16_t);
-    else {
-        iseg_set_error("iseg_resize_bilinear_fwd: bad dtypes");
-        return ISEG_ERR_ARG;
-    }
-#undef RS
-    return iseg_check_launch("iseg_resize_bilinear_fwd");
+    const bool lds_rows = lds <= 48 * 1024 && (int64_t)Wo * C >= 1024;      // small source rows, long output rows: LDS-resident sources
+    const bool vec = C % 8 == 0 && ((uintptr_t)x | (uintptr_t)y) % 16 == 0;
+    return by_dtype(in_dtype, "iseg_resize_bilinear_fwd", [&](auto ti) {
+        return by_dtype(out_dtype, "iseg_resize_bilinear_fwd", [&](auto to) {
+            using TI = decltype(ti);
+            using TO = decltype(to);
+            auto launch = [&](auto kernel, unsigned grid, size_t shared) {
+                hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), shared, stream, (const TI*)x, (TO*)y, N, Hi, Wi, Ho, Wo, C, sy, sx);
+            };
+            if (lds_rows) launch(resize_bilinear_fwd_lds_kernel<TI, TO>, blocks, lds);
+            else if (vec) launch(resize_bilinear_fwd_vec_kernel<TI, TO>, cap_blocks((int64_t)N * Ho * Wo * (C / 8)), 0);
+            else launch(resize_bilinear_fwd_kernel<TI, TO>, blocks, 0);
+            return iseg_check_launch("iseg_resize_bilinear_fwd");
+        });
+    });
 }
 
 extern "C" int iseg_bn_relu_upsample_add(const void* z, const float* mean, const float* rstd, const float* gamma, const float* beta, const void* x,
@@ -551,15 +516,13 @@ extern "C" int iseg_bn_relu_upsample_add(const void* z, const float* mean, const
     const int tpc = C8 < 256 ? C8 : 256;
     const int rpi = 256 / tpc;
     const int threads = tpc * rpi;
-    int64_t blocks = ceil_div64((int64_t)N * Ho * Wo, (int64_t)rpi * 4);
-    if (blocks > 4096) blocks = 4096;
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL((bn_relu_upsample_add_kernel<bf16_t>), dim3((unsigned)blocks), dim3(threads), 0, stream, (const bf16_t*)z, mean, rstd, gamma,
-                           beta, (const bf16_t*)x, (bf16_t*)out, N, Hi, Wi, Ho, Wo, C, sy, sx, tpc);
-    else
-        hipLaunchKernelGGL((bn_relu_upsample_add_kernel<float>), dim3((unsigned)blocks), dim3(threads), 0, stream, (const float*)z, mean, rstd, gamma,
-                           beta, (const float*)x, (float*)out, N, Hi, Wi, Ho, Wo, C, sy, sx, tpc);
-    return iseg_check_launch("iseg_bn_relu_upsample_add");
+    const unsigned blocks = grid_cap((int64_t)N * Ho * Wo, (int64_t)rpi * 4, 4096);
+    return by_dtype(dtype, "iseg_bn_relu_upsample_add", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((bn_relu_upsample_add_kernel<T>), dim3(blocks), dim3(threads), 0, stream, (const T*)z, mean, rstd, gamma, beta,
+                           (const T*)x, (T*)out, N, Hi, Wi, Ho, Wo, C, sy, sx, tpc);
+        return iseg_check_launch("iseg_bn_relu_upsample_add");
+    });
 }
 
 extern "C" size_t iseg_resize_bilinear_bwd_workspace_bytes(int N, int Hi, int Wi, int Ho, int Wo, int C) {
@@ -572,66 +535,48 @@ extern "C" size_t iseg_resize_bilinear_bwd_workspace_bytes(int N, int Hi, int Wi
 extern "C" int iseg_resize_bilinear_bwd(const void* dy, int dy_dtype, void* dx, int dx_dtype, const void* dx_add, int N, int Hi,
                                         int Wi, int Ho, int Wo, int C, void* ws, size_t ws_bytes, hipStream_t stream) {
     ISEG_REQUIRE(dy && dx, "iseg_resize_bilinear_bwd: null pointer");
+    ISEG_REQUIRE(dx_dtype == ISEG_BF16 || dx_dtype == ISEG_F32, "iseg_resize_bilinear_bwd: dtype %d", dx_dtype);      // (before the first launch)
     const size_t need = iseg_resize_bilinear_bwd_workspace_bytes(N, Hi, Wi, Ho, Wo, C);
-    if (!ws || ws_bytes < need) {
-        iseg_set_error("iseg_resize_bilinear_bwd: needs %zu workspace bytes, got %zu", need, ws_bytes);
-        return ISEG_ERR_WORKSPACE;
-    }
+    ISEG_NEED_WORKSPACE("iseg_resize_bilinear_bwd", ws, ws_bytes, need);
     float* tmp = (float*)ws;
     const float sy = (float)Hi / (float)Ho, sx = (float)Wi / (float)Wo;
     // exact x2 up-sampling with 16-byte channel chunks: one pass, no intermediate
     if (Ho == 2 * Hi && Wo == 2 * Wi && C % 8 == 0 && dy_dtype == dx_dtype && (int64_t)N * Hi * Wi * (C / 8) < (1ll << 31) &&
         (((uintptr_t)dy | (uintptr_t)dx | (uintptr_t)dx_add) & 15) == 0) {
         const unsigned vb = cap_blocks((int64_t)N * Hi * Wi * (C / 8));
-        if (dy_dtype == ISEG_BF16)
-            hipLaunchKernelGGL((resize_bwd_x2_vec_kernel<bf16_t, bf16_t>), dim3(vb), dim3(256), 0, stream, (const bf16_t*)dy, (bf16_t*)dx, N, Hi, Wi, C,
-                               (const bf16_t*)dx_add);
-        else
-            hipLaunchKernelGGL((resize_bwd_x2_vec_kernel<float, float>), dim3(vb), dim3(256), 0, stream, (const float*)dy, (float*)dx, N, Hi, Wi, C,
-                               (const float*)dx_add);
-        return iseg_check_launch("iseg_resize_bilinear_bwd");
+        return by_dtype(dy_dtype, "iseg_resize_bilinear_bwd", [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL((resize_bwd_x2_vec_kernel<T, T>), dim3(vb), dim3(256), 0, stream, (const T*)dy, (T*)dx, N, Hi, Wi, C,
+                               (const T*)dx_add);
+            return iseg_check_launch("iseg_resize_bilinear_bwd");
+        });
     }
     // X pass: [N*Ho, Wo, C] -> [N*Ho, Wi, C]
     const int64_t t1 = (int64_t)N * Ho * Wi * C;
     const size_t row_bytes = ((size_t)Wo * C + (size_t)3 * Wo) * sizeof(float);   // gradient row + destination lerp table
-    if (row_bytes <= 64 * 1024 && (int64_t)N * Ho < (1ll << 31)) {
-        int64_t blocks = (int64_t)N * Ho;
-        if (blocks > 256 * 8) blocks = 256 * 8;
-        if (dy_dtype == ISEG_BF16)
-            hipLaunchKernelGGL((resize_bwd_x_lds_kernel<bf16_t>), dim3((unsigned)blocks), dim3(256), row_bytes, stream, (const bf16_t*)dy,
-                               tmp, N * Ho, Wo, Wi, C, sx);
+    const bool lds_x = row_bytes <= 64 * 1024 && (int64_t)N * Ho < (1ll << 31);
+    const bool vec_x = C % 8 == 0 && (uintptr_t)dy % 16 == 0;
+    int64_t blocks = (int64_t)N * Ho;      // (no lower clamp: an empty problem stays a launch error)
+    if (blocks > 256 * 8) blocks = 256 * 8;
+    const int rc = by_dtype(dy_dtype, "iseg_resize_bilinear_bwd", [&](auto t) {
+        using T = decltype(t);
+        if (lds_x)
+            hipLaunchKernelGGL((resize_bwd_x_lds_kernel<T>), dim3((unsigned)blocks), dim3(256), row_bytes, stream, (const T*)dy, tmp, N * Ho, Wo, Wi,
+                               C, sx);
         else
-            hipLaunchKernelGGL((resize_bwd_x_lds_kernel<float>), dim3((unsigned)blocks), dim3(256), row_bytes, stream, (const float*)dy,
-                               tmp, N * Ho, Wo, Wi, C, sx);
-    } else if (C % 8 == 0 && (uintptr_t)dy % 16 == 0 && dy_dtype == ISEG_BF16) {
-        hipLaunchKernelGGL((resize_bwd_axis_vec_kernel<bf16_t, float>), dim3(cap_blocks(t1 / 8)), dim3(256), 0, stream, (const bf16_t*)dy,
-                           tmp, (int64_t)N * Ho, Wo, Wi, (int64_t)C, sx, (const float*)nullptr);
-    } else if (C % 8 == 0 && (uintptr_t)dy % 16 == 0) {
-        hipLaunchKernelGGL((resize_bwd_axis_vec_kernel<float, float>), dim3(cap_blocks(t1 / 8)), dim3(256), 0, stream, (const float*)dy,
-                           tmp, (int64_t)N * Ho, Wo, Wi, (int64_t)C, sx, (const float*)nullptr);
-    } else if (dy_dtype == ISEG_BF16) {
-        hipLaunchKernelGGL((resize_bwd_axis_kernel<bf16_t, float>), dim3(cap_blocks(t1)), dim3(256), 0, stream, (const bf16_t*)dy,
-                           tmp, (int64_t)N * Ho, Wo, Wi, (int64_t)C, sx, (const float*)nullptr);
-    } else {
-        hipLaunchKernelGGL((resize_bwd_axis_kernel<float, float>), dim3(cap_blocks(t1)), dim3(256), 0, stream, (const float*)dy, tmp,
-                           (int64_t)N * Ho, Wo, Wi, (int64_t)C, sx, (const float*)nullptr);
-    }
+            hipLaunchKernelGGL((vec_x ? resize_bwd_axis_vec_kernel<T, float> : resize_bwd_axis_kernel<T, float>), dim3(cap_blocks(vec_x ? t1 / 8 : t1)),
+                               dim3(256), 0, stream, (const T*)dy, tmp, (int64_t)N * Ho, Wo, Wi, (int64_t)C, sx, (const float*)nullptr);
+    });
+    if (rc != ISEG_OK) return rc;
     // Y pass: [N, Ho, Wi*C] -> [N, Hi, Wi*C]
     const int64_t t2 = (int64_t)N * Hi * Wi * C;
     const bool vec_y = ((int64_t)Wi * C) % 8 == 0 && ((uintptr_t)dx | (uintptr_t)dx_add) % 16 == 0;
-    if (vec_y && dx_dtype == ISEG_BF16)
-        hipLaunchKernelGGL((resize_bwd_axis_vec_kernel<float, bf16_t>), dim3(cap_blocks(t2 / 8)), dim3(256), 0, stream, (const float*)tmp,
-                           (bf16_t*)dx, (int64_t)N, Ho, Hi, (int64_t)Wi * C, sy, (const bf16_t*)dx_add);
-    else if (vec_y)
-        hipLaunchKernelGGL((resize_bwd_axis_vec_kernel<float, float>), dim3(cap_blocks(t2 / 8)), dim3(256), 0, stream, (const float*)tmp,
-                           (float*)dx, (int64_t)N, Ho, Hi, (int64_t)Wi * C, sy, (const float*)dx_add);
-    else if (dx_dtype == ISEG_BF16)
-        hipLaunchKernelGGL((resize_bwd_axis_kernel<float, bf16_t>), dim3(cap_blocks(t2)), dim3(256), 0, stream, (const float*)tmp,
-                           (bf16_t*)dx, (int64_t)N, Ho, Hi, (int64_t)Wi * C, sy, (const bf16_t*)dx_add);
-    else
-        hipLaunchKernelGGL((resize_bwd_axis_kernel<float, float>), dim3(cap_blocks(t2)), dim3(256), 0, stream, (const float*)tmp,
-                           (float*)dx, (int64_t)N, Ho, Hi, (int64_t)Wi * C, sy, (const float*)dx_add);
-    return iseg_check_launch("iseg_resize_bilinear_bwd");
+    return by_dtype(dx_dtype, "iseg_resize_bilinear_bwd", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((vec_y ? resize_bwd_axis_vec_kernel<float, T> : resize_bwd_axis_kernel<float, T>), dim3(cap_blocks(vec_y ? t2 / 8 : t2)),
+                           dim3(256), 0, stream, (const float*)tmp, (T*)dx, (int64_t)N, Ho, Hi, (int64_t)Wi * C, sy, (const T*)dx_add);
+        return iseg_check_launch("iseg_resize_bilinear_bwd");
+    });
 }
 
 // tf.compat.v1.image.resize(x, size, method="bilinear", align_corners=True) (backbones/hrnet.py:303-304,523-524): generic gather kernels with
@@ -642,48 +587,40 @@ extern "C" int iseg_resize_bilinear_ac_fwd(const void* x, int in_dtype, void* y,
     ISEG_REQUIRE((int64_t)Wo * C < (1ll << 30) && (int64_t)Wi * C < (1ll << 30) && (int64_t)N * Ho < (1ll << 31),
                  "iseg_resize_bilinear_ac_fwd: row too long");
     const float sy = Ho > 1 ? (float)(Hi - 1) / (float)(Ho - 1) : 0.f, sx = Wo > 1 ? (float)(Wi - 1) / (float)(Wo - 1) : 0.f;
-    int64_t blocks = (int64_t)N * Ho;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-#define RSA(TI, TO)                                                                                                                         \
-    hipLaunchKernelGGL((resize_bilinear_fwd_kernel<TI, TO, true>), dim3((unsigned)blocks), dim3(256), 0, stream, (const TI*)x, (TO*)y, N, Hi, \
-                       Wi, Ho, Wo, C, sy, sx)
-    if (in_dtype == ISEG_F32 && out_dtype == ISEG_F32) RSA(float, float);
-    else if (in_dtype == ISEG_BF16 && out_dtype == ISEG_F32) RSA(bf16_t, float);
-    else if (in_dtype == ISEG_BF16 && out_dtype == ISEG_BF16) RSA(bf16_t, bf16_t);
-    else if (in_dtype == ISEG_F32 && out_dtype == ISEG_BF16) RSA(float, bf16_t);
-    else {
-        iseg_set_error("iseg_resize_bilinear_ac_fwd: bad dtypes");
-        return ISEG_ERR_ARG;
-    }
-#undef RSA
-    return iseg_check_launch("iseg_resize_bilinear_ac_fwd");
+    const unsigned blocks = grid_cap((int64_t)N * Ho, 1, 256 * 16);
+    return by_dtype(in_dtype, "iseg_resize_bilinear_ac_fwd", [&](auto ti) {
+        return by_dtype(out_dtype, "iseg_resize_bilinear_ac_fwd", [&](auto to) {
+            using TI = decltype(ti);
+            using TO = decltype(to);
+            hipLaunchKernelGGL((resize_bilinear_fwd_kernel<TI, TO, true>), dim3(blocks), dim3(256), 0, stream, (const TI*)x, (TO*)y, N, Hi, Wi, Ho, Wo, C,
+                               sy, sx);
+            return iseg_check_launch("iseg_resize_bilinear_ac_fwd");
+        });
+    });
 }
 
 extern "C" int iseg_resize_bilinear_ac_bwd(const void* dy, int dy_dtype, void* dx, int dx_dtype, const void* dx_add, int N, int Hi, int Wi,
                                            int Ho, int Wo, int C, void* ws, size_t ws_bytes, hipStream_t stream) {
     ISEG_REQUIRE(dy && dx && N > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && C > 0, "iseg_resize_bilinear_ac_bwd: bad arguments");
+    ISEG_REQUIRE(dx_dtype == ISEG_BF16 || dx_dtype == ISEG_F32, "iseg_resize_bilinear_ac_bwd: dtype %d", dx_dtype);      // (before the first launch)
     const size_t need = iseg_resize_bilinear_bwd_workspace_bytes(N, Hi, Wi, Ho, Wo, C);
-    if (!ws || ws_bytes < need) {
-        iseg_set_error("iseg_resize_bilinear_ac_bwd: needs %zu workspace bytes, got %zu", need, ws_bytes);
-        return ISEG_ERR_WORKSPACE;
-    }
+    ISEG_NEED_WORKSPACE("iseg_resize_bilinear_ac_bwd", ws, ws_bytes, need);
     float* tmp = (float*)ws;
     const float sy = Ho > 1 ? (float)(Hi - 1) / (float)(Ho - 1) : 0.f, sx = Wo > 1 ? (float)(Wi - 1) / (float)(Wo - 1) : 0.f;
     const int64_t t1 = (int64_t)N * Ho * Wi * C, t2 = (int64_t)N * Hi * Wi * C;
     // X pass: [N*Ho, Wo, C] -> [N*Ho, Wi, C] (fp32), then Y pass: [N, Ho, Wi*C] -> [N, Hi, Wi*C]
-    if (dy_dtype == ISEG_BF16)
-        hipLaunchKernelGGL((resize_bwd_axis_kernel<bf16_t, float, true>), dim3(cap_blocks(t1)), dim3(256), 0, stream, (const bf16_t*)dy, tmp,
-                           (int64_t)N * Ho, Wo, Wi, (int64_t)C, sx, (const float*)nullptr);
-    else
-        hipLaunchKernelGGL((resize_bwd_axis_kernel<float, float, true>), dim3(cap_blocks(t1)), dim3(256), 0, stream, (const float*)dy, tmp,
-                           (int64_t)N * Ho, Wo, Wi, (int64_t)C, sx, (const float*)nullptr);
-    if (dx_dtype == ISEG_BF16)
-        hipLaunchKernelGGL((resize_bwd_axis_kernel<float, bf16_t, true>), dim3(cap_blocks(t2)), dim3(256), 0, stream, (const float*)tmp,
-                           (bf16_t*)dx, (int64_t)N, Ho, Hi, (int64_t)Wi * C, sy, (const bf16_t*)dx_add);
-    else
-        hipLaunchKernelGGL((resize_bwd_axis_kernel<float, float, true>), dim3(cap_blocks(t2)), dim3(256), 0, stream, (const float*)tmp,
-                           (float*)dx, (int64_t)N, Ho, Hi, (int64_t)Wi * C, sy, (const float*)dx_add);
-    return iseg_check_launch("iseg_resize_bilinear_ac_bwd");
+    const int rc = by_dtype(dy_dtype, "iseg_resize_bilinear_ac_bwd", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((resize_bwd_axis_kernel<T, float, true>), dim3(cap_blocks(t1)), dim3(256), 0, stream, (const T*)dy, tmp, (int64_t)N * Ho,
+                           Wo, Wi, (int64_t)C, sx, (const float*)nullptr);
+    });
+    if (rc != ISEG_OK) return rc;
+    return by_dtype(dx_dtype, "iseg_resize_bilinear_ac_bwd", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((resize_bwd_axis_kernel<float, T, true>), dim3(cap_blocks(t2)), dim3(256), 0, stream, (const float*)tmp, (T*)dx,
+                           (int64_t)N, Ho, Hi, (int64_t)Wi * C, sy, (const T*)dx_add);
+        return iseg_check_launch("iseg_resize_bilinear_ac_bwd");
+    });
 }
 
 extern "C" int iseg_resize_nearest_i32(const int32_t* x, int32_t* y, int N, int Hi, int Wi, int Ho, int Wo, int C,

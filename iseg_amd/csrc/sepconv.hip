@@ -413,46 +413,36 @@ extern "C" size_t iseg_relu_dwconv3_stats_workspace_bytes(int N, int H, int W, i
 extern "C" int iseg_relu_dwconv3_stats(const void* x, const float* w, void* z, float* packed, int N, int H, int W, int C, int stride, int dil,
                                        int dtype, void* ws, size_t ws_bytes, hipStream_t stream) {
     ISEG_REQUIRE(x && w && z, "iseg_relu_dwconv3_stats: null pointer");
-    if (!iseg_sepconv_supported(N, H, W, C, stride, dil, dtype) || !sc_aligned(x) || !sc_aligned(w) || !sc_aligned(z))
+    if (!sc_shape_ok(N, H, W, C, stride, dil) || !sc_aligned(x) || !sc_aligned(w) || !sc_aligned(z))
         SC_UNSUPPORTED("iseg_relu_dwconv3_stats", N, H, W, C, stride, dil);
     const ScGeom g = sc_geom(N, H, W, C, stride, dil);
     const ScTile t = sc_tile(g, false);
     const dim3 grid(t.tiles_w * t.hsteps, N, t.groups);
     const size_t lds = sc_lds_bytes(t);
     float* part = (float*)ws;
-    if (packed) {
-        ISEG_REQUIRE_WORKSPACE(ws && ws_bytes >= iseg_relu_dwconv3_stats_workspace_bytes(N, H, W, C, stride, dil),
-                               "iseg_relu_dwconv3_stats: workspace too small");
-        if (dtype == ISEG_BF16)
-            hipLaunchKernelGGL((sc_fwd_kernel<bf16_t, true>), grid, dim3(SC_THREADS), lds, stream, (const bf16_t*)x, w, (bf16_t*)z, part,
-                               packed + 2 * C, g, t);
-        else
-            hipLaunchKernelGGL((sc_fwd_kernel<float, true>), grid, dim3(SC_THREADS), lds, stream, (const float*)x, w, (float*)z, part,
-                               packed + 2 * C, g, t);
-        launch_reduce_rows(part, (int)sc_parts(g, t), 2 * (int64_t)C, 0, 1, 2 * (int64_t)C, packed, nullptr, 2 * (int64_t)C, 0, 1.f, 0, stream);
-    } else if (dtype == ISEG_BF16) {
-        hipLaunchKernelGGL((sc_fwd_kernel<bf16_t, false>), grid, dim3(SC_THREADS), lds, stream, (const bf16_t*)x, w, (bf16_t*)z, nullptr,
-                           nullptr, g, t);
-    } else {
-        hipLaunchKernelGGL((sc_fwd_kernel<float, false>), grid, dim3(SC_THREADS), lds, stream, (const float*)x, w, (float*)z, nullptr, nullptr,
-                           g, t);
-    }
+    if (packed) ISEG_NEED_WORKSPACE("iseg_relu_dwconv3_stats", ws, ws_bytes, iseg_relu_dwconv3_stats_workspace_bytes(N, H, W, C, stride, dil));
+    const int rc = by_dtype(dtype, "iseg_relu_dwconv3_stats", [&](auto st) {
+        using T = decltype(st);
+        hipLaunchKernelGGL((packed ? sc_fwd_kernel<T, true> : sc_fwd_kernel<T, false>), grid, dim3(SC_THREADS), lds, stream, (const T*)x, w, (T*)z,
+                           packed ? part : nullptr, packed ? packed + 2 * C : nullptr, g, t);
+    });
+    if (rc != ISEG_OK) return rc;
+    if (packed) launch_reduce_rows(part, (int)sc_parts(g, t), 2 * (int64_t)C, 0, 1, 2 * (int64_t)C, packed, nullptr, 2 * (int64_t)C, 0, 1.f, 0, stream);
     return iseg_check_launch("iseg_relu_dwconv3_stats");
 }
 
 extern "C" int iseg_sepconv_fold(const float* W, const float* mean, const float* rstd, const float* gamma, const float* beta, void* Wt, void* Wn,
                                  float* bias, int Cin, int Cout, int dtype, hipStream_t stream) {
     ISEG_REQUIRE(W && mean && rstd && gamma && beta && (Wt || Wn) && bias, "iseg_sepconv_fold: null pointer");
-    ISEG_REQUIRE(Cin > 0 && Cout > 0 && (dtype == ISEG_F32 || dtype == ISEG_BF16), "iseg_sepconv_fold: bad shape or dtype");
+    ISEG_REQUIRE(Cin > 0 && Cout > 0, "iseg_sepconv_fold: bad shape");
     const int tiles_o = (Cout + 63) / 64, tiles = tiles_o * ((Cin + 63) / 64);
     const dim3 grid(tiles + (Cout + SC_BIAS_COLS - 1) / SC_BIAS_COLS);
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL(sc_fold_kernel<bf16_t>, grid, dim3(SC_THREADS), 0, stream, W, mean, rstd, gamma, beta, (bf16_t*)Wt, (bf16_t*)Wn, bias,
-                           Cin, Cout, tiles_o, tiles);
-    else
-        hipLaunchKernelGGL(sc_fold_kernel<float>, grid, dim3(SC_THREADS), 0, stream, W, mean, rstd, gamma, beta, (float*)Wt, (float*)Wn, bias,
-                           Cin, Cout, tiles_o, tiles);
-    return iseg_check_launch("iseg_sepconv_fold");
+    return by_dtype(dtype, "iseg_sepconv_fold", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(sc_fold_kernel<T>, grid, dim3(SC_THREADS), 0, stream, W, mean, rstd, gamma, beta, (T*)Wt, (T*)Wn, bias, Cin, Cout, tiles_o,
+                           tiles);
+        return iseg_check_launch("iseg_sepconv_fold");
+    });
 }
 
 extern "C" int iseg_sepconv_fold_bwd(const float* G, const float* S, const float* W, const float* mean, const float* rstd, const float* gamma,
@@ -473,23 +463,23 @@ extern "C" size_t iseg_bnfold_dwconv3_relu_bwd_workspace_bytes(int N, int H, int
 extern "C" int iseg_bnfold_dwconv3_relu_bwd(const void* D, const void* z, const void* x, const float* w, const float* mean, const float* rstd,
                                             const float* gamma, const float* sums, float inv_n, int train, void* dx, float* dw, int N, int H,
                                             int W, int C, int stride, int dil, int dtype, void* ws, size_t ws_bytes, hipStream_t stream) {
-    ISEG_REQUIRE(D && z && x && w && dx && dw && ws, "iseg_bnfold_dwconv3_relu_bwd: null pointer");
+    ISEG_REQUIRE(D && z && x && w && dx && dw, "iseg_bnfold_dwconv3_relu_bwd: null pointer");
     ISEG_REQUIRE(!train || (mean && rstd && gamma && sums), "iseg_bnfold_dwconv3_relu_bwd: training statistics need mean, rstd, gamma, sums");
-    if (!iseg_sepconv_supported(N, H, W, C, stride, dil, dtype) || !sc_aligned(D) || !sc_aligned(z) || !sc_aligned(x) || !sc_aligned(w) ||
+    if (!sc_shape_ok(N, H, W, C, stride, dil) || !sc_aligned(D) || !sc_aligned(z) || !sc_aligned(x) || !sc_aligned(w) ||
         !sc_aligned(dx))
         SC_UNSUPPORTED("iseg_bnfold_dwconv3_relu_bwd", N, H, W, C, stride, dil);
-    ISEG_REQUIRE_WORKSPACE(ws_bytes >= iseg_bnfold_dwconv3_relu_bwd_workspace_bytes(N, H, W, C, stride, dil), "iseg_bnfold_dwconv3_relu_bwd: workspace too small");
+    ISEG_NEED_WORKSPACE("iseg_bnfold_dwconv3_relu_bwd", ws, ws_bytes, iseg_bnfold_dwconv3_relu_bwd_workspace_bytes(N, H, W, C, stride, dil));
     const ScGeom g = sc_geom(N, H, W, C, stride, dil);
     const ScTile t = sc_tile(g, true);
     const dim3 grid(t.tiles_w * t.hsteps, N, t.groups);
     const size_t lds = sc_lds_bytes(t);
     float* part = (float*)ws;
-    if (dtype == ISEG_BF16)
-        hipLaunchKernelGGL(sc_bwd_kernel<bf16_t>, grid, dim3(SC_THREADS), lds, stream, (const bf16_t*)D, (const bf16_t*)z, (const bf16_t*)x, w,
-                           mean, rstd, gamma, sums, inv_n, train, (bf16_t*)dx, part, g, t);
-    else
-        hipLaunchKernelGGL(sc_bwd_kernel<float>, grid, dim3(SC_THREADS), lds, stream, (const float*)D, (const float*)z, (const float*)x, w, mean,
-                           rstd, gamma, sums, inv_n, train, (float*)dx, part, g, t);
+    const int rc = by_dtype(dtype, "iseg_bnfold_dwconv3_relu_bwd", [&](auto st) {
+        using T = decltype(st);
+        hipLaunchKernelGGL(sc_bwd_kernel<T>, grid, dim3(SC_THREADS), lds, stream, (const T*)D, (const T*)z, (const T*)x, w, mean, rstd, gamma, sums,
+                           inv_n, train, (T*)dx, part, g, t);
+    });
+    if (rc != ISEG_OK) return rc;
     launch_reduce_rows(part, (int)sc_parts(g, t), 9 * (int64_t)C, 0, 1, 9 * (int64_t)C, dw, nullptr, 9 * (int64_t)C, 0, 1.f, 1, stream);
     return iseg_check_launch("iseg_bnfold_dwconv3_relu_bwd");
 }

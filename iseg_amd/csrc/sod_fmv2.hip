@@ -417,10 +417,8 @@ extern "C" int iseg_sod_fmv2(const void* pred, int pred_is_u8, const uint8_t* gt
         modes |= modes_h[h];
     }
     const Layout l = fmv2_layout(B, H, W, n_handlers);
-    if (!ws || ws_bytes < l.total || ((uintptr_t)ws & 15)) {
-        iseg_set_error("iseg_sod_fmv2: needs %zu workspace bytes (16-byte aligned), got %zu", l.total, ws_bytes);
-        return ISEG_ERR_WORKSPACE;
-    }
+    ISEG_NEED_WORKSPACE("iseg_sod_fmv2", ws, ws_bytes, l.total);
+    ISEG_REQUIRE_WORKSPACE(((uintptr_t)ws & 15) == 0, "iseg_sod_fmv2: the workspace must be 16-byte aligned");
     char* base = (char*)ws;
     int32_t* ints = (int32_t*)base;
     int32_t* raw = (int32_t*)(base + l.off_raw);

@@ -643,10 +643,8 @@ extern "C" int iseg_sod_metrics(const void* pred, int pred_is_u8, const uint8_t*
     ISEG_REQUIRE(!(flags & ISEG_SOD_WFM) || W <= 8192, "iseg_sod_metrics: the weighted F-measure keeps one row of 2 W ints in 64 KiB of LDS: W <= 8192");
     ISEG_REQUIRE((state != nullptr) == (count != nullptr), "iseg_sod_metrics: state and count go together");
     const Layout l = sod_layout(B, H, W, flags);
-    if (!ws || ws_bytes < l.total || ((uintptr_t)ws & 15)) {
-        iseg_set_error("iseg_sod_metrics: needs %zu workspace bytes (16-byte aligned), got %zu", l.total, ws_bytes);
-        return ISEG_ERR_WORKSPACE;
-    }
+    ISEG_NEED_WORKSPACE("iseg_sod_metrics", ws, ws_bytes, l.total);
+    ISEG_REQUIRE_WORKSPACE(((uintptr_t)ws & 15) == 0, "iseg_sod_metrics: the workspace must be 16-byte aligned");
     const bool wfm = (flags & ISEG_SOD_WFM) != 0;
     ISEG_REQUIRE(wfm || (!dist2_out && !nearest_out), "iseg_sod_metrics: distances are only computed with ISEG_SOD_WFM");
     char* base = (char*)ws;

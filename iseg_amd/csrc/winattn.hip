@@ -420,10 +420,7 @@ extern "C" int iseg_window_attention_bwd(const void* qkv, const float* table, co
     const int64_t pairs = windows * heads;
     const int waves = bwd_waves(pairs, heads);
     const size_t need = (size_t)waves * T * T * sizeof(float);
-    if (!ws || ws_bytes < need) {
-        iseg_set_error("iseg_window_attention_bwd: needs %zu workspace bytes, got %zu", need, ws_bytes);
-        return ISEG_ERR_WORKSPACE;
-    }
+    ISEG_NEED_WORKSPACE("iseg_window_attention_bwd", ws, ws_bytes, need);
     const size_t lds = (size_t)2 * (WT * PS_STRIDE + 3 * WT * QK_STRIDE) * sizeof(bf16_t);
     hipLaunchKernelGGL(win_attn_bwd_kernel, dim3(waves / 2), dim3(128), lds, stream, (const bf16_t*)qkv, table, (const bf16_t*)dout,
                        (bf16_t*)dqkv, (float*)ws, pairs, T, heads, table_windows, scale);

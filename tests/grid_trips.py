@@ -24,8 +24,8 @@ full trips at all; the budget exists to bound memory and host time, which bytes 
 storage only (a `shapes` table with the one key), and say why next to the entry.
 
 Completeness -- every `gridDim` use and every cap helper in iseg_amd/csrc (searched: gridDim, cap_blocks, ew_blocks, row_blocks, lane_blocks,
-eva_blocks, mc_blocks, rms_blocks, colsum_blocks, strip_grid, bn_blocks, bn_strip_blocks, ln_bwd_blocks, ln_any_bwd_blocks, grn_parts,
-bw_partitions and the inline `< CAP ? ... : CAP` grids).  strip_grid (norm.hip) has no caller left: bn_blocks / bn_strip_blocks took its place.
+eva_blocks, mc_blocks, rms_blocks, colsum_blocks, bn_blocks, bn_strip_blocks, ln_bwd_blocks, ln_any_bwd_blocks, grn_parts, bw_partitions
+and the direct `grid_cap(items, per_block, cap)` grids; each helper is one grid_cap call of common.h with its own constants).
 
 (a) IN THE TABLE (file: entry points)
   elementwise.hip  cast, scale_cols_cast, im2col (16-byte; scalar + zero_pad_cols; contiguous-run form), col2im (16-byte, scalar), colsum
