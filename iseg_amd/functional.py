@@ -21,6 +21,13 @@ def _grad(p):
     return p.grad
 
 
+def _param_grad(p, *shape):
+    """the gradient buffer of a trainable Parameter (viewed as `shape` when given); None for an absent or a frozen one"""
+    if p is None or not p.requires_grad:
+        return None
+    return _grad(p).reshape(shape) if shape else _grad(p)
+
+
 def _c(t):
     return t if t.is_contiguous() else t.contiguous()
 
@@ -172,12 +179,12 @@ class _MlpGeluFn(Function):
         if ctx.rowscale is not None:
             dy2 = K.rowscale(dy2, ctx.rowscale, ctx.rpg)
         if W2.requires_grad:
-            K.dense_wgrad(g, dy2, _grad(W2), bias_grad=(_grad(b2) if b2 is not None and b2.requires_grad else None))
+            K.dense_wgrad(g, dy2, _grad(W2), bias_grad=_param_grad(b2))
         elif b2 is not None and b2.requires_grad:
             K.colsum(dy2, N, 0, 1, dy2.shape[0], N, _grad(b2), accumulate=True)
         dh = K.dense_dgrad(dy2, nn.w(W2), act=K.ACT_MUL_AUX, aux=d)            # (dy W2^T) * gelu'(h)
         if W1.requires_grad:
-            K.dense_wgrad(x2, dh, _grad(W1), bias_grad=(_grad(b1) if b1 is not None and b1.requires_grad else None))
+            K.dense_wgrad(x2, dh, _grad(W1), bias_grad=_param_grad(b1))
         elif b1 is not None and b1.requires_grad:
             K.colsum(dh, dh.shape[1], 0, 1, dh.shape[0], dh.shape[1], _grad(b1), accumulate=True)
         dx = None
@@ -714,43 +721,92 @@ def layer_norm(x, gamma, beta, eps):
 
 
 # ---------------------------------------------------------------------------------------------------------
-# (Sync)BatchNormalization over all axes but the last, optional fused ReLU
+# (Sync)BatchNormalization over all axes but the last, optional fused ReLU.  The statistics exchange of every tape node that carries a
+# BatchNorm is stated here once: _bn_batch_stats (forward), _bn_exchange_sums (backward), _bn_frozen_stats (moving statistics).
 # ---------------------------------------------------------------------------------------------------------
+def _bn_batch_stats(x2s, sync):
+    """packed [sum | sumsq | count] ([2C+1] floats) of every [rows, C] tensor in x2s, summed over the replicas when `sync`: ONE message for all
+    of them (and one instead of the reference's three per layer) -- the exposed latency of a small RCCL message is paid once (hard
+    part 4)"""
+    if len(x2s) == 1:
+        rows, C = x2s[0].shape
+        msg = K.bn_stats(x2s[0], C, rows, C)
+        slots = [msg]
+    else:
+        offs = [0]
+        for x2 in x2s:
+            offs.append(offs[-1] + 2 * x2.shape[1] + 4)      # 3 floats of padding: every layer's slot stays 16-byte aligned
+        msg = torch.zeros(offs[-1], dtype=torch.float32, device=x2s[0].device)
+        slots = []
+        for x2, off in zip(x2s, offs):
+            rows, C = x2.shape
+            slots.append(K.bn_stats(x2, C, rows, C, out=msg[off:off + 2 * C + 1]))
+    if sync:
+        dist.all_reduce_sum(msg)
+    return slots
+
+
+def _bn_frozen_stats(moving_mean, moving_var, eps):
+    """(mean, rstd) of a call on the moving statistics.  The mean is a copy: the backward reads the statistics of THIS call, and a later
+    training-mode call updates the buffer in place through a raw pointer, which autograd's version counter cannot see"""
+    return moving_mean.clone(), K.rsqrt_eps(moving_var, eps)
+
+
+def _bn_exchange_sums(sums, layers, sync):
+    """`sums`: the [dbeta | dgamma] blocks ([2C] each, back to back) that the backward reductions of `layers` ((gamma, beta) pairs) left for this
+    replica.  Returns (sums, world, own); the input gradient takes 1 / (rows * world) for its mean over the batch.
+
+    own: no exchange -- the sums are this replica's, so the caller's apply kernel books dgamma / dbeta itself and the caller reports
+    dist.grads_ready after that launch.
+    not own: the local parameter gradients are booked here (the gradient all-reduce sums them over the ranks later) and reported BEFORE the
+    statistics message, so that a gradient bucket can go out before that message is waited for; then a copy of the sums is summed over the
+    replicas.  A caller whose reduction has already booked its parameter gradients passes no layers."""
+    if not (sync and dist.active()):
+        return sums, 1, True
+    off = 0
+    for gamma, beta in layers:
+        C = gamma.shape[0]
+        K.accumulate_pair(sums[off:off + 2 * C], C, _param_grad(beta), _param_grad(gamma))
+        off += 2 * C
+    dist.grads_ready(*[p for layer in layers for p in layer])
+    sums = sums.clone()
+    dist.all_reduce_sum(sums)
+    return sums, dist.world_size(), False
+
+
+def _aligned16(tensors, vectors):
+    """the 16-byte alignment the fused kernels' vector accesses need: of an activation when it is passed as is (a non-contiguous one is copied
+    into a fresh, aligned buffer first) and of the per-channel vectors and kernels they read directly, which must be contiguous as well"""
+    return (not any(t.is_contiguous() and t.data_ptr() % 16 for t in tensors)
+            and not any(v.data_ptr() % 16 or not v.is_contiguous() for v in vectors))
+
+
 class _BatchNormTrainFn(Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, moving_mean, moving_var, eps, momentum, relu, sync):
         C = x.shape[-1]
         x2 = _c(x).reshape(-1, C)
         rows = x2.shape[0]
-        packed = K.bn_stats(x2, C, rows, C)
-        if sync:
-            dist.all_reduce_sum(packed)          # ONE [2C+1] message (sum, sumsq, count) instead of the reference's three
+        (packed,) = _bn_batch_stats([x2], sync)
         y = torch.empty_like(x2)
         mean, rstd = K.bn_finalize_apply(packed, x2, C, gamma.data, beta.data, y, C, rows, C, eps, momentum, moving_mean, moving_var, relu)
         ctx.gamma, ctx.beta, ctx.relu, ctx.sync = gamma, beta, relu, sync
-        ctx.save_for_backward(x2, y if relu else None, mean, rstd, packed)
+        ctx.save_for_backward(x2, y if relu else None, mean, rstd)
         return y.reshape(x.shape)
 
     @staticmethod
     def backward(ctx, dy):
-        x2, y, mean, rstd, packed = ctx.saved_tensors
+        x2, y, mean, rstd = ctx.saved_tensors
+        gamma, beta = ctx.gamma, ctx.beta
         rows, C = x2.shape
         dy2, lddy = _rows2d(dy)
         sums = K.bn_bwd_reduce(dy2, lddy, x2, C, y, C, mean, rstd, rows, C, ctx.relu)
-        dbeta = _grad(ctx.beta) if ctx.beta.requires_grad else None
-        dgamma = _grad(ctx.gamma) if ctx.gamma.requires_grad else None
+        sums, world, own = _bn_exchange_sums(sums, [(gamma, beta)], ctx.sync)
         dx = torch.empty_like(x2)
-        if ctx.sync and dist.active():
-            # local parameter gradients first (the gradient all-reduce sums them over ranks later), then the statistics of all replicas
-            K.accumulate_pair(sums, C, dbeta, dgamma)
-            dist.grads_ready(ctx.gamma, ctx.beta)
-            sums = sums.clone()
-            dist.all_reduce_sum(sums)
-            K.bn_bwd_apply(dy2, lddy, x2, C, y, C, mean, rstd, ctx.gamma.data, sums, 1.0 / (rows * dist.world_size()), dx, C, rows, C, ctx.relu)
-        else:      # the sums are this replica's own: the apply kernel books dbeta | dgamma itself
-            K.bn_bwd_apply(dy2, lddy, x2, C, y, C, mean, rstd, ctx.gamma.data, sums, 1.0 / rows, dx, C, rows, C, ctx.relu, dgamma=dgamma,
-                           dbeta=dbeta)
-            dist.grads_ready(ctx.gamma, ctx.beta)
+        K.bn_bwd_apply(dy2, lddy, x2, C, y, C, mean, rstd, gamma.data, sums, 1.0 / (rows * world), dx, C, rows, C, ctx.relu,
+                       dgamma=_param_grad(gamma) if own else None, dbeta=_param_grad(beta) if own else None)
+        if own:
+            dist.grads_ready(gamma, beta)
         return dx.reshape(dy.shape), None, None, None, None, None, None, None, None
 
 
@@ -761,13 +817,10 @@ class _BnReluUpsampleAddFn(Function):
 
     @staticmethod
     def forward(ctx, z, x, gamma, beta, moving_mean, moving_var, eps, momentum, sync):
-        N, Ho, Wo, C = z.shape
+        C = z.shape[-1]
         zc, xc = _c(z), _c(x)
         z2 = zc.reshape(-1, C)
-        rows = z2.shape[0]
-        packed = K.bn_stats(z2, C, rows, C)
-        if sync:
-            dist.all_reduce_sum(packed)
+        (packed,) = _bn_batch_stats([z2], sync)
         mean, rstd = K.bn_finalize(packed, C, eps, momentum, moving_mean, moving_var)
         out = K.bn_relu_upsample_add(zc, mean, rstd, gamma.data, beta.data, xc)
         ctx.gamma, ctx.beta, ctx.sync, ctx.x_shape, ctx.x_dtype = gamma, beta, sync, x.shape, x.dtype
@@ -777,29 +830,23 @@ class _BnReluUpsampleAddFn(Function):
     @staticmethod
     def backward(ctx, dout):
         z2, mean, rstd = ctx.saved_tensors
+        gamma, beta = ctx.gamma, ctx.beta
         rows, C = z2.shape
         dc = _c(dout)
         d2 = dc.reshape(rows, C)
         dx = K.resize_bilinear_bwd(dc, ctx.x_shape[1], ctx.x_shape[2], ctx.x_dtype) if ctx.needs_input_grad[1] else None
         dz = None
-        g, b = ctx.gamma.data, ctx.beta.data
-        sums = K.bn_bwd_reduce_remask(d2, C, z2, C, mean, rstd, g, b, rows, C)
-        dbeta = _grad(ctx.beta) if ctx.beta.requires_grad else None
-        dgamma = _grad(ctx.gamma) if ctx.gamma.requires_grad else None
-        if ctx.sync and dist.active():
+        sums = K.bn_bwd_reduce_remask(d2, C, z2, C, mean, rstd, gamma.data, beta.data, rows, C)
+        sums, world, own = _bn_exchange_sums(sums, [(gamma, beta)], ctx.sync)
+        dgamma, dbeta = (_param_grad(gamma), _param_grad(beta)) if own else (None, None)
+        if ctx.needs_input_grad[0]:
+            dz = K.bn_bwd_apply_remask(d2, C, z2, C, mean, rstd, gamma.data, beta.data, sums, 1.0 / (rows * world), torch.empty_like(z2), C, rows, C,
+                                       dgamma=dgamma, dbeta=dbeta).reshape(dout.shape)
+        elif own:      # no apply launch to book them
             K.accumulate_pair(sums, C, dbeta, dgamma)
-            dist.grads_ready(ctx.gamma, ctx.beta)
-            sums = sums.clone()
-            dist.all_reduce_sum(sums)
-            if ctx.needs_input_grad[0]:
-                dz = K.bn_bwd_apply_remask(d2, C, z2, C, mean, rstd, g, b, sums, 1.0 / (rows * dist.world_size()), torch.empty_like(z2), C, rows, C)
-        else:
-            if ctx.needs_input_grad[0]:
-                dz = K.bn_bwd_apply_remask(d2, C, z2, C, mean, rstd, g, b, sums, 1.0 / rows, torch.empty_like(z2), C, rows, C, dgamma=dgamma, dbeta=dbeta)
-            else:
-                K.accumulate_pair(sums, C, dbeta, dgamma)
-            dist.grads_ready(ctx.gamma, ctx.beta)
-        return (dz.reshape(dout.shape) if dz is not None else None), dx, None, None, None, None, None, None, None
+        if own:
+            dist.grads_ready(gamma, beta)
+        return dz, dx, None, None, None, None, None, None, None
 
 
 def batch_norm_relu_upsample_add(z, x, gamma, beta, moving_mean, moving_var, eps, momentum, sync=True):
@@ -812,41 +859,32 @@ def batch_norm_relu_upsample_add(z, x, gamma, beta, moving_mean, moving_var, eps
 
 class _BatchNormGroupFn(Function):
     """Several independent SyncBN layers whose inputs all exist before any of them is normalised (the five ASPP branches,
-    layers/aspp.py:57-71): their packed statistics travel in ONE all-reduce forward and ONE backward instead of one per layer --
-    the exposed latency of a small RCCL message is paid once (hard part 4).  Arithmetic per layer is _BatchNormTrainFn's."""
+    layers/aspp.py:57-71): their statistics travel in ONE all-reduce forward and ONE backward instead of one per layer.  Arithmetic per
+    layer is _BatchNormTrainFn's."""
 
     @staticmethod
     def forward(ctx, n, relu, layers, *tensors):
         xs, gammas, betas = tensors[:n], tensors[n:2 * n], tensors[2 * n:3 * n]
         x2s = [_c(x).reshape(-1, x.shape[-1]) for x in xs]
-        Cs = [x2.shape[1] for x2 in x2s]
-        offs = [0]
-        for C in Cs:
-            offs.append(offs[-1] + 2 * C + 4)      # [sum | sumsq | count] + 3 floats of padding: every layer's slot stays 16-byte aligned
-        msg = torch.zeros(offs[-1], dtype=torch.float32, device=x2s[0].device)
-        for i, x2 in enumerate(x2s):
-            K.bn_stats(x2, Cs[i], x2.shape[0], Cs[i], out=msg[offs[i]:offs[i] + 2 * Cs[i] + 1])
-        dist.all_reduce_sum(msg)
         ys, saved = [], []
-        for i, x2 in enumerate(x2s):
-            L = layers[i]
+        for x, x2, packed, gamma, beta, L in zip(xs, x2s, _bn_batch_stats(x2s, True), gammas, betas, layers):
+            rows, C = x2.shape
             y = torch.empty_like(x2)
-            mean, rstd = K.bn_finalize_apply(msg[offs[i]:offs[i] + 2 * Cs[i] + 1], x2, Cs[i], gammas[i].data, betas[i].data, y, Cs[i], x2.shape[0], Cs[i],
-                                             L["eps"], L["momentum"], L["moving_mean"], L["moving_var"], relu)
-            ys.append(y.reshape(xs[i].shape))
+            mean, rstd = K.bn_finalize_apply(packed, x2, C, gamma.data, beta.data, y, C, rows, C, L["eps"], L["momentum"], L["moving_mean"],
+                                             L["moving_var"], relu)
+            ys.append(y.reshape(x.shape))
             saved += [x2, y if relu else None, mean, rstd]
-        ctx.n, ctx.relu, ctx.gammas, ctx.betas = n, relu, gammas, betas
+        ctx.relu, ctx.layers = relu, list(zip(gammas, betas))
         ctx.save_for_backward(*saved)
         return tuple(ys)
 
     @staticmethod
     def backward(ctx, *dys):
-        n, relu = ctx.n, ctx.relu
-        sv = ctx.saved_tensors
-        Cs = [sv[4 * i].shape[1] for i in range(n)]
+        relu, layers, sv = ctx.relu, ctx.layers, ctx.saved_tensors
+        n = len(layers)
         offs = [0]
-        for C in Cs:
-            offs.append(offs[-1] + 2 * C)
+        for gamma, _ in layers:
+            offs.append(offs[-1] + 2 * gamma.shape[0])
         msg = torch.empty(offs[-1], dtype=torch.float32, device=sv[0].device)
         dy2s = []
         for i in range(n):
@@ -854,24 +892,18 @@ class _BatchNormGroupFn(Function):
             rows, C = x2.shape
             dy2, lddy = _rows2d(dys[i])
             dy2s.append((dy2, lddy))
-            sums = K.bn_bwd_reduce(dy2, lddy, x2, C, y, C, mean, rstd, rows, C, relu, out=msg[offs[i]:offs[i + 1]])
-            # local parameter gradients (the gradient all-reduce sums them over ranks later)
-            K.accumulate_pair(sums, C, _grad(ctx.betas[i]) if ctx.betas[i].requires_grad else None,
-                              _grad(ctx.gammas[i]) if ctx.gammas[i].requires_grad else None)
-            dist.grads_ready(ctx.gammas[i], ctx.betas[i])
-        world = 1
-        if dist.active():
-            msg = msg.clone()
-            dist.all_reduce_sum(msg)
-            world = dist.world_size()
+            K.bn_bwd_reduce(dy2, lddy, x2, C, y, C, mean, rstd, rows, C, relu, out=msg[offs[i]:offs[i + 1]])
+        msg, world, own = _bn_exchange_sums(msg, layers, True)
         dxs = []
-        for i in range(n):
+        for i, (gamma, beta) in enumerate(layers):
             x2, y, mean, rstd = sv[4 * i:4 * i + 4]
             rows, C = x2.shape
             dx = torch.empty_like(x2)
-            K.bn_bwd_apply(dy2s[i][0], dy2s[i][1], x2, C, y, C, mean, rstd, ctx.gammas[i].data, msg[offs[i]:offs[i + 1]], 1.0 / (rows * world),
-                           dx, C, rows, C, relu)
+            K.bn_bwd_apply(dy2s[i][0], dy2s[i][1], x2, C, y, C, mean, rstd, gamma.data, msg[offs[i]:offs[i + 1]], 1.0 / (rows * world),
+                           dx, C, rows, C, relu, dgamma=_param_grad(gamma) if own else None, dbeta=_param_grad(beta) if own else None)
             dxs.append(dx.reshape(dys[i].shape))
+        if own:
+            dist.grads_ready(*[p for layer in layers for p in layer])
         return (None, None, None) + tuple(dxs) + (None,) * (2 * n)
 
 
@@ -886,12 +918,15 @@ class _BatchNormInferFn(Function):
     def forward(ctx, x, gamma, beta, moving_mean, moving_var, eps, relu):
         C = x.shape[-1]
         x2 = _c(x).reshape(-1, C)
-        rstd = K.rsqrt_eps(moving_var, eps)
-        y = torch.empty_like(x2)
-        K.bn_apply_fwd(x2, C, moving_mean, rstd, gamma.data, beta.data, y, C, x2.shape[0], C, relu)
-        ctx.gamma, ctx.beta, ctx.relu = gamma, beta, relu
         want_param_grads = gamma.requires_grad or beta.requires_grad
-        ctx.save_for_backward(y if relu else None, rstd, x2 if want_param_grads else None, moving_mean if want_param_grads else None)
+        if want_param_grads:      # the backward reads the mean again
+            mean, rstd = _bn_frozen_stats(moving_mean, moving_var, eps)
+        else:
+            mean, rstd = moving_mean, K.rsqrt_eps(moving_var, eps)
+        y = torch.empty_like(x2)
+        K.bn_apply_fwd(x2, C, mean, rstd, gamma.data, beta.data, y, C, x2.shape[0], C, relu)
+        ctx.gamma, ctx.beta, ctx.relu = gamma, beta, relu
+        ctx.save_for_backward(y if relu else None, rstd, x2 if want_param_grads else None, mean if want_param_grads else None)
         return y.reshape(x.shape)
 
     @staticmethod
@@ -903,18 +938,15 @@ class _BatchNormInferFn(Function):
         dy2 = _c(dy).reshape(-1, C)
         if x2 is not None:
             sums = K.bn_bwd_reduce(dy2, C, x2, C, y, C, mean, rstd, x2.shape[0], C, ctx.relu)
-            K.accumulate_pair(sums, C, _grad(ctx.beta) if ctx.beta.requires_grad else None,
-                              _grad(ctx.gamma) if ctx.gamma.requires_grad else None)
+            K.accumulate_pair(sums, C, _param_grad(ctx.beta), _param_grad(ctx.gamma))
             dist.grads_ready(ctx.gamma, ctx.beta)
         if ctx.relu:
             dy2 = K.act_bwd(dy2, y, K.ACT_RELU)
         scale = K.axpby(ctx.gamma.data, None, 1.0, 0.0)
-        # dx = dy2 * (gamma*rstd) per column: reuse bn_apply with mean=0,rstd=1,beta=0, gamma=gamma*rstd
+        # dx = dy2 * (gamma * rstd) per column: bn_apply with mean = 0 and beta = 0
         zeros = torch.zeros(C, dtype=torch.float32, device=dy.device)
-        ones = torch.ones(C, dtype=torch.float32, device=dy.device)
         dx = torch.empty_like(dy2)
         K.bn_apply_fwd(dy2, C, zeros, rstd, scale, zeros, dx, C, dy2.shape[0], C, False)
-        del ones
         return dx.reshape(dy.shape), None, None, None, None, None, None
 
 
@@ -929,7 +961,7 @@ def batch_norm(x, gamma, beta, moving_mean, moving_var, eps, momentum, training,
 
 # ---------------------------------------------------------------------------------------------------------
 # EfficientNet MBConv tail (backbones/efficientnet.py:214-255): (Sync)BN -> swish -> squeeze-excite -> gate as one tape node
-# (csrc/mbconv.hip).  The un-gated activation is never written; statistics and their all-reduce messages are _BatchNormTrainFn's.
+# (csrc/mbconv.hip).  The un-gated activation is never written.
 # ---------------------------------------------------------------------------------------------------------
 def _se_params(W1, b1, W2, b2):
     C, Cse = W1.shape[-2], W1.shape[-1]
@@ -938,56 +970,21 @@ def _se_params(W1, b1, W2, b2):
 
 def _se_grads(W1, b1, W2, b2):
     C, Cse = W1.shape[-2], W1.shape[-1]
-    return ((_grad(W1).reshape(C, Cse) if W1.requires_grad else None), (_grad(b1) if b1.requires_grad else None),
-            (_grad(W2).reshape(Cse, C) if W2.requires_grad else None), (_grad(b2) if b2.requires_grad else None))
+    return _param_grad(W1, C, Cse), _param_grad(b1), _param_grad(W2, Cse, C), _param_grad(b2)
 
 
-class _BnSwishSETrainFn(Function):
+class _BnSwishSEFn(Function):
     @staticmethod
-    def forward(ctx, x, gamma, beta, moving_mean, moving_var, W1, b1, W2, b2, eps, momentum, sync):
+    def forward(ctx, x, gamma, beta, moving_mean, moving_var, W1, b1, W2, b2, eps, momentum, training, sync):
         C = x.shape[-1]
         xc = _c(x)
-        x2 = xc.reshape(-1, C)
-        packed = K.bn_stats(x2, C, x2.shape[0], C)
-        if sync:
-            dist.all_reduce_sum(packed)          # the packed [2C+1] statistics message of _BatchNormTrainFn
-        mean, rstd = K.bn_finalize(packed, C, eps, momentum, moving_mean, moving_var)
-        out, m, hpre, g = K.bn_swish_se_fwd(xc, mean, rstd, gamma.data, beta.data, *_se_params(W1, b1, W2, b2))
-        ctx.params, ctx.sync = (gamma, beta, W1, b1, W2, b2), sync
-        ctx.save_for_backward(xc, mean, rstd, m, hpre, g)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        xc, mean, rstd, m, hpre, g = ctx.saved_tensors
-        gamma, beta, W1, b1, W2, b2 = ctx.params
-        rows, C = xc.numel() // xc.shape[-1], xc.shape[-1]
-        dO = _c(dout)
-        W1d, _, W2d, _ = _se_params(W1, b1, W2, b2)
-        sums, dmh = K.bn_swish_se_bwd_sums(dO, xc, mean, rstd, gamma.data, beta.data, W1d, W2d, m, hpre, g, *_se_grads(W1, b1, W2, b2))
-        dist.grads_ready(W1, b1, W2, b2)
-        dbeta = _grad(beta) if beta.requires_grad else None
-        dgamma = _grad(gamma) if gamma.requires_grad else None
-        if ctx.sync and dist.active():
-            K.accumulate_pair(sums, C, dbeta, dgamma)
-            dist.grads_ready(gamma, beta)
-            sums = sums.clone()
-            dist.all_reduce_sum(sums)           # the [2C] sums message of _BatchNormTrainFn's backward
-            dx = K.bn_swish_gate_bwd_apply(dO, xc, mean, rstd, gamma.data, beta.data, g, dmh, sums, 1.0 / (rows * dist.world_size()), True)
+        if training:
+            (packed,) = _bn_batch_stats([xc.reshape(-1, C)], sync)
+            mean, rstd = K.bn_finalize(packed, C, eps, momentum, moving_mean, moving_var)
         else:
-            dx = K.bn_swish_gate_bwd_apply(dO, xc, mean, rstd, gamma.data, beta.data, g, dmh, sums, 1.0 / rows, True, dgamma=dgamma, dbeta=dbeta)
-            dist.grads_ready(gamma, beta)
-        return dx, None, None, None, None, None, None, None, None, None, None, None
-
-
-class _BnSwishSEInferFn(Function):
-    @staticmethod
-    def forward(ctx, x, gamma, beta, moving_mean, moving_var, W1, b1, W2, b2, eps):
-        xc = _c(x)
-        rstd = K.rsqrt_eps(moving_var, eps)
-        mean = moving_mean.clone()      # the backward reads the statistics of THIS call: a later training-mode call updates the buffer in place
+            mean, rstd = _bn_frozen_stats(moving_mean, moving_var, eps)
         out, m, hpre, g = K.bn_swish_se_fwd(xc, mean, rstd, gamma.data, beta.data, *_se_params(W1, b1, W2, b2))
-        ctx.params = (gamma, beta, W1, b1, W2, b2)
+        ctx.params, ctx.training, ctx.sync = (gamma, beta, W1, b1, W2, b2), training, training and sync
         ctx.save_for_backward(xc, mean, rstd, m, hpre, g)
         return out
 
@@ -995,14 +992,18 @@ class _BnSwishSEInferFn(Function):
     def backward(ctx, dout):
         xc, mean, rstd, m, hpre, g = ctx.saved_tensors
         gamma, beta, W1, b1, W2, b2 = ctx.params
+        rows = xc.numel() // xc.shape[-1]
         dO = _c(dout)
         W1d, _, W2d, _ = _se_params(W1, b1, W2, b2)
         sums, dmh = K.bn_swish_se_bwd_sums(dO, xc, mean, rstd, gamma.data, beta.data, W1d, W2d, m, hpre, g, *_se_grads(W1, b1, W2, b2))
         dist.grads_ready(W1, b1, W2, b2)
-        dx = K.bn_swish_gate_bwd_apply(dO, xc, mean, rstd, gamma.data, beta.data, g, dmh, sums, 0.0, False,
-                                       dgamma=_grad(gamma) if gamma.requires_grad else None, dbeta=_grad(beta) if beta.requires_grad else None)
-        dist.grads_ready(gamma, beta)
-        return dx, None, None, None, None, None, None, None, None, None
+        sums, world, own = _bn_exchange_sums(sums, [(gamma, beta)], ctx.sync)
+        inv_n = 1.0 / (rows * world) if ctx.training else 0.0
+        dx = K.bn_swish_gate_bwd_apply(dO, xc, mean, rstd, gamma.data, beta.data, g, dmh, sums, inv_n, ctx.training,
+                                       dgamma=_param_grad(gamma) if own else None, dbeta=_param_grad(beta) if own else None)
+        if own:
+            dist.grads_ready(gamma, beta)
+        return (dx,) + (None,) * 12
 
 
 def mbconv_fused_enabled():
@@ -1011,14 +1012,9 @@ def mbconv_fused_enabled():
 
 
 def bn_swish_se_supported(x, se_filters, *vectors):
-    """the shape rules of csrc/mbconv.hip, and the 16-byte alignment its vector accesses need: of x when it is passed as is (a non-contiguous
-    x is copied into a fresh, aligned buffer first) and of the per-channel vectors (gamma, beta, moving statistics) it reads directly"""
+    """the shape rules of csrc/mbconv.hip, and _aligned16 of x and the per-channel vectors (gamma, beta, moving statistics)"""
     N, H, W, C = x.shape
-    if x.is_contiguous() and x.data_ptr() % 16:
-        return False
-    if any(v.data_ptr() % 16 or not v.is_contiguous() for v in vectors):
-        return False
-    return K.mbconv_supported(N, H * W, C, se_filters)
+    return _aligned16((x,), vectors) and K.mbconv_supported(N, H * W, C, se_filters)
 
 
 def bn_swish_se(x, gamma, beta, moving_mean, moving_var, eps, momentum, training, W1, b1, W2, b2, sync=True):
@@ -1027,15 +1023,13 @@ def bn_swish_se(x, gamma, beta, moving_mean, moving_var, eps, momentum, training
     _check_act_dtype(x)
     if nn.dry_run():
         return _dry(x.shape, x)
-    if training:
-        return _BnSwishSETrainFn.apply(x, gamma, beta, moving_mean, moving_var, W1, b1, W2, b2, float(eps), float(momentum), bool(sync))
-    return _BnSwishSEInferFn.apply(x, gamma, beta, moving_mean, moving_var, W1, b1, W2, b2, float(eps))
+    return _BnSwishSEFn.apply(x, gamma, beta, moving_mean, moving_var, W1, b1, W2, b2, float(eps), float(momentum), bool(training), bool(sync))
 
 
 # ---------------------------------------------------------------------------------------------------------
 # Xception separable unit, activation=False (backbones/xception_common.py:14-78): relu -> depthwise 3x3 -> (Sync)BN -> pointwise 1x1 as one
 # tape node (csrc/sepconv.hip).  The BN is folded into the pointwise GEMM (v = z diag(a) W + c^T W), so neither relu(x) nor the BN output is
-# written; the statistics and gradient-sum messages are _BatchNormTrainFn's, so the SyncBN all-reduces carry them unchanged.
+# written.
 # ---------------------------------------------------------------------------------------------------------
 def _sepconv_pointwise(z2, pwk, mean, rstd, gamma, beta, need_grad):
     """fold the BN into the pointwise kernel and run the GEMM; returns (v, Wn) -- Wn [Cin, Cout], the data gradient's operand, only when
@@ -1050,75 +1044,52 @@ def _sepconv_pointwise(z2, pwk, mean, rstd, gamma, beta, need_grad):
     return v, Wn
 
 
-def _sepconv_backward(ctx, dv, train, inv_n):
-    """wgrad GEMM + colsum -> fold_bwd -> (all-reduce of the BN sums) -> dgrad GEMM -> fused depthwise / BN / ReLU backward"""
-    xc, z, mean, rstd, Wn = ctx.saved_tensors
-    dwk, gamma, beta, pwk = ctx.params
-    C, Cout = Wn.shape
-    dv2 = _c(dv).reshape(-1, Cout)
-    z2 = z.reshape(-1, C)
-    G = torch.empty((C, Cout), dtype=torch.float32, device=dv.device)
-    S = torch.empty(Cout, dtype=torch.float32, device=dv.device)
-    if z2.dtype == torch.bfloat16 and C % 8 == 0:
-        # S rides the weight-gradient GEMM as its ones-row at every width here: at Cin = 64 / 128 / 256 (where dense_wgrad runs a separate
-        # column-sum pass) that measured 90 / 102 / 41 us against 93 / 142 / 60 us for the Xception shapes of a 16 x 512^2 batch
-        M = z2.shape[0]
-        K.gemm(z2, dv2, G, C, Cout, M, lda=C, ldb=Cout, ldd=Cout, a_kcontig=0, b_kcontig=0, accumulate=False, colsum_out=S, colsum_accumulate=False)
-    else:
-        K.dense_wgrad(z2, dv2, G, accumulate=False, bias_grad=S)
-    # this replica's dgamma / dbeta are booked by the same launch, before the sums go to the all-reduce (as _BatchNormTrainFn books them)
-    sums = K.sepconv_fold_bwd(G, S, pwk.data.reshape(C, Cout), mean, rstd, gamma.data, beta.data,
-                              dW=_grad(pwk).reshape(C, Cout) if pwk.requires_grad else None,
-                              dgamma=_grad(gamma) if gamma.requires_grad else None, dbeta=_grad(beta) if beta.requires_grad else None)
-    dist.grads_ready(pwk, gamma, beta)
-    if train and ctx.sync and dist.active():
-        sums = sums.clone()
-        dist.all_reduce_sum(sums)           # the [2C] sums message of _BatchNormTrainFn's backward
-    D = K.dense_dgrad(dv2, Wn).reshape(z.shape)
-    dw = _grad(dwk).reshape(9, C) if dwk.requires_grad else torch.zeros((9, C), dtype=torch.float32, device=dv.device)
-    dx = K.bnfold_dwconv3_relu_bwd(D, z, xc, dwk.data.reshape(9, C), mean, rstd, gamma.data, sums, inv_n, train, dw, ctx.stride, ctx.dil)
-    dist.grads_ready(dwk)
-    return dx
-
-
-class _SepConvTrainFn(Function):
+class _SepConvFn(Function):
     @staticmethod
-    def forward(ctx, x, dwk, gamma, beta, pwk, moving_mean, moving_var, eps, momentum, stride, dil, sync):
+    def forward(ctx, x, dwk, gamma, beta, pwk, moving_mean, moving_var, eps, momentum, stride, dil, training, sync):
         C, Cout = x.shape[-1], pwk.shape[-1]
         xc = _c(x)
-        z, packed = K.relu_dwconv3_stats(xc, dwk.data.reshape(9, C), stride, dil, stats=True)
-        if sync:
-            dist.all_reduce_sum(packed)          # the packed [2C+1] statistics message of _BatchNormTrainFn
-        mean, rstd = K.bn_finalize(packed, C, eps, momentum, moving_mean, moving_var)
+        z, packed = K.relu_dwconv3_stats(xc, dwk.data.reshape(9, C), stride, dil, stats=training)
+        if training:
+            if sync:
+                dist.all_reduce_sum(packed)          # _bn_batch_stats' one-tensor message, written by the depthwise launch itself
+            mean, rstd = K.bn_finalize(packed, C, eps, momentum, moving_mean, moving_var)
+        else:
+            mean, rstd = _bn_frozen_stats(moving_mean, moving_var, eps)
         v, Wn = _sepconv_pointwise(z.reshape(-1, C), pwk, mean, rstd, gamma, beta, any(ctx.needs_input_grad))
-        ctx.params, ctx.sync, ctx.stride, ctx.dil = (dwk, gamma, beta, pwk), sync, stride, dil
+        ctx.params, ctx.training, ctx.sync, ctx.stride, ctx.dil = (dwk, gamma, beta, pwk), training, training and sync, stride, dil
         ctx.save_for_backward(xc, z, mean, rstd, Wn)
         return v.reshape(*z.shape[:-1], Cout)
 
     @staticmethod
     def backward(ctx, dv):
-        z = ctx.saved_tensors[1]
-        rows = z.numel() // z.shape[-1]
-        world = dist.world_size() if ctx.sync and dist.active() else 1
-        return (_sepconv_backward(ctx, dv, True, 1.0 / (rows * world)),) + (None,) * 11
-
-
-class _SepConvInferFn(Function):
-    @staticmethod
-    def forward(ctx, x, dwk, gamma, beta, pwk, moving_mean, moving_var, eps, stride, dil):
-        C, Cout = x.shape[-1], pwk.shape[-1]
-        xc = _c(x)
-        z, _ = K.relu_dwconv3_stats(xc, dwk.data.reshape(9, C), stride, dil, stats=False)
-        rstd = K.rsqrt_eps(moving_var, eps)
-        mean = moving_mean.clone()      # the backward reads the statistics of THIS call: a later training-mode call updates the buffer in place
-        v, Wn = _sepconv_pointwise(z.reshape(-1, C), pwk, mean, rstd, gamma, beta, any(ctx.needs_input_grad))
-        ctx.params, ctx.sync, ctx.stride, ctx.dil = (dwk, gamma, beta, pwk), False, stride, dil
-        ctx.save_for_backward(xc, z, mean, rstd, Wn)
-        return v.reshape(*z.shape[:-1], Cout)
-
-    @staticmethod
-    def backward(ctx, dv):
-        return (_sepconv_backward(ctx, dv, False, 0.0),) + (None,) * 9
+        """wgrad GEMM + colsum -> fold_bwd -> (all-reduce of the BN sums) -> dgrad GEMM -> fused depthwise / BN / ReLU backward"""
+        xc, z, mean, rstd, Wn = ctx.saved_tensors
+        dwk, gamma, beta, pwk = ctx.params
+        C, Cout = Wn.shape
+        dv2 = _c(dv).reshape(-1, Cout)
+        z2 = z.reshape(-1, C)
+        rows = z2.shape[0]
+        G = torch.empty((C, Cout), dtype=torch.float32, device=dv.device)
+        S = torch.empty(Cout, dtype=torch.float32, device=dv.device)
+        if z2.dtype == torch.bfloat16 and C % 8 == 0:
+            # S rides the weight-gradient GEMM as its ones-row at every width here: at Cin = 64 / 128 / 256 (where dense_wgrad runs a separate
+            # column-sum pass) that measured 90 / 102 / 41 us against 93 / 142 / 60 us for the Xception shapes of a 16 x 512^2 batch
+            K.gemm(z2, dv2, G, C, Cout, rows, lda=C, ldb=Cout, ldd=Cout, a_kcontig=0, b_kcontig=0, accumulate=False, colsum_out=S,
+                   colsum_accumulate=False)
+        else:
+            K.dense_wgrad(z2, dv2, G, accumulate=False, bias_grad=S)
+        # this launch books the replica's own dgamma / dbeta whether or not the sums are exchanged: _bn_exchange_sums gets no layers
+        sums = K.sepconv_fold_bwd(G, S, pwk.data.reshape(C, Cout), mean, rstd, gamma.data, beta.data, dW=_param_grad(pwk, C, Cout),
+                                  dgamma=_param_grad(gamma), dbeta=_param_grad(beta))
+        dist.grads_ready(pwk, gamma, beta)
+        sums, world, _ = _bn_exchange_sums(sums, (), ctx.sync)
+        D = K.dense_dgrad(dv2, Wn).reshape(z.shape)
+        dw = _grad(dwk).reshape(9, C) if dwk.requires_grad else torch.zeros((9, C), dtype=torch.float32, device=dv.device)
+        dx = K.bnfold_dwconv3_relu_bwd(D, z, xc, dwk.data.reshape(9, C), mean, rstd, gamma.data, sums, 1.0 / (rows * world) if ctx.training else 0.0,
+                                       ctx.training, dw, ctx.stride, ctx.dil)
+        dist.grads_ready(dwk)
+        return (dx,) + (None,) * 12
 
 
 def sepconv_fused_enabled():
@@ -1127,15 +1098,11 @@ def sepconv_fused_enabled():
 
 
 def sepconv_supported(x, dw_kernel, bn, pw_kernel, strides=1, dilation=1):
-    """the shape rules of csrc/sepconv.hip, and the 16-byte alignment its vector accesses need: of x when it is passed as is (a non-contiguous
-    x is copied into a fresh, aligned buffer first) and of the vectors and kernels it reads directly"""
+    """the shape rules of csrc/sepconv.hip, and _aligned16 of x and the vectors and kernels it reads directly"""
     N, H, W, C = x.shape
     if tuple(dw_kernel.shape) != (3, 3, C, 1) or pw_kernel.shape[-2] != C or pw_kernel.dim() != 4 or tuple(pw_kernel.shape[:2]) != (1, 1):
         return False
-    if x.is_contiguous() and x.data_ptr() % 16:
-        return False
-    vectors = (dw_kernel, pw_kernel, bn.gamma, bn.beta, bn.moving_mean, bn.moving_variance)
-    if any(v.data_ptr() % 16 or not v.is_contiguous() for v in vectors):
+    if not _aligned16((x,), (dw_kernel, pw_kernel, bn.gamma, bn.beta, bn.moving_mean, bn.moving_variance)):
         return False
     return K.sepconv_supported(N, H, W, C, int(strides), int(dilation), x.dtype)
 
@@ -1151,101 +1118,50 @@ def sepconv_unit(x, dw_kernel, bn, pw_kernel, training, strides=1, dilation=1):
         z = depthwise_conv2d(relu(x), dw_kernel, None, dilation=d, strides=s)
         u = batch_norm(z, bn.gamma, bn.beta, bn.moving_mean, bn.moving_variance, bn.epsilon, bn.momentum, bn_training, sync=bn.synchronized)
         return conv2d(u, pw_kernel, None, (1, 1), (1, 1), "same")
-    if bn_training:
-        return _SepConvTrainFn.apply(x, dw_kernel, bn.gamma, bn.beta, pw_kernel, bn.moving_mean, bn.moving_variance, float(bn.epsilon),
-                                     float(bn.momentum), s, d, bool(bn.synchronized))
-    return _SepConvInferFn.apply(x, dw_kernel, bn.gamma, bn.beta, pw_kernel, bn.moving_mean, bn.moving_variance, float(bn.epsilon), s, d)
+    return _SepConvFn.apply(x, dw_kernel, bn.gamma, bn.beta, pw_kernel, bn.moving_mean, bn.moving_variance, float(bn.epsilon), float(bn.momentum),
+                            s, d, bn_training, bool(bn.synchronized))
 
 
 # ---------------------------------------------------------------------------------------------------------
 # ResNet-9 / 10 / 18 basic-block tail (backbones/resnet_blocks_small.py:84-119): relu(bn2(z2) + avg_pool_s(bn0(z0) or x)) as one tape node
-# (csrc/resblock.hip).  Neither BN output nor the pooled shortcut is written; the statistics and gradient-sum messages are
-# _BatchNormTrainFn's (both layers' in one message), so the SyncBN all-reduces carry them unchanged.
+# (csrc/resblock.hip).  Neither BN output nor the pooled shortcut is written; both layers' statistics travel in one message each way.
 # ---------------------------------------------------------------------------------------------------------
-def _bn_vecs(gamma, beta):
-    return gamma.data, beta.data
-
-
-def _resblock_backward(ctx, dout, train, inv_n2, inv_n0):
-    """reduce -> (all-reduce of both layers' [2C] sums in one message) -> apply; returns (dz2, dsc)"""
-    out, z2, z0, mean2, rstd2, mean0, rstd0 = ctx.saved_tensors
-    gamma2, beta2, gamma0, beta0 = ctx.params
-    C = z2.shape[-1]
-    bn0 = z0 is not None
-    dO = _c(dout)
-    sums = K.resblock_tail_bwd_reduce(dO, out, z2, mean2, rstd2, ctx.sc_shape, ctx.stride, z0, mean0, rstd0)
-    pg = [_grad(p) if p is not None and p.requires_grad else None for p in (gamma2, beta2, gamma0, beta0)]
-    own = dict(dgamma2=pg[0], dbeta2=pg[1], dgamma0=pg[2], dbeta0=pg[3])
-    if train and ctx.sync and dist.active():
-        # local parameter gradients first (the gradient all-reduce sums them over ranks later), then the sums of all replicas
-        K.accumulate_pair(sums[:2 * C], C, pg[1], pg[0])
-        if bn0:
-            K.accumulate_pair(sums[2 * C:], C, pg[3], pg[2])
-        dist.grads_ready(gamma2, beta2, gamma0, beta0)
-        sums = sums.clone()
-        dist.all_reduce_sum(sums)           # [2C] per layer: the sums message of _BatchNormTrainFn's backward
-        w = dist.world_size()
-        inv_n2, inv_n0 = inv_n2 / w, inv_n0 / w
-        own = {}
-    g0 = gamma0.data if bn0 else None
-    dz2, dsc = K.resblock_tail_bwd_apply(dO, out, z2, mean2, rstd2, gamma2.data, sums, inv_n2, inv_n0, train, ctx.sc_shape, ctx.stride, z0, mean0,
-                                         rstd0, g0, **own)
-    if own:
-        dist.grads_ready(gamma2, beta2, gamma0, beta0)
-    return dz2, (dsc if ctx.needs_input_grad[1] else None)
-
-
-class _ResBlockTailTrainFn(Function):
+class _ResBlockTailFn(Function):
     @staticmethod
-    def forward(ctx, z2, sc, gamma2, beta2, gamma0, beta0, moving2, moving0, eps, momentum, stride, sync):
+    def forward(ctx, z2, sc, gamma2, beta2, gamma0, beta0, moving2, moving0, eps, momentum, stride, training, sync):
         C = z2.shape[-1]
         z2c, scc = _c(z2), _c(sc)
         bn0 = gamma0 is not None
-        r2, r0 = z2c.numel() // C, scc.numel() // C
-        if bn0:
-            # one message for both layers: [sum | sumsq | count] of z2, 3 floats of padding (16-byte aligned slots), then z0's
-            msg = torch.empty(4 * C + 5, dtype=torch.float32, device=z2.device)
-            K.bn_stats(z2c.reshape(r2, C), C, r2, C, out=msg[:2 * C + 1])
-            K.bn_stats(scc.reshape(r0, C), C, r0, C, out=msg[2 * C + 4:])
+        x2s = [z2c.reshape(-1, C)] + ([scc.reshape(-1, C)] if bn0 else [])
+        moving = (moving2, moving0)
+        if training:
+            stats = [K.bn_finalize(packed, C, eps[i], momentum[i], *moving[i]) for i, packed in enumerate(_bn_batch_stats(x2s, sync))]
         else:
-            msg = K.bn_stats(z2c.reshape(r2, C), C, r2, C)
-        if sync:
-            dist.all_reduce_sum(msg)          # the packed statistics message of _BatchNormTrainFn
-        mean2, rstd2 = K.bn_finalize(msg[:2 * C + 1], C, eps[0], momentum[0], moving2[0], moving2[1])
-        mean0 = rstd0 = None
-        if bn0:
-            mean0, rstd0 = K.bn_finalize(msg[2 * C + 4:], C, eps[1], momentum[1], moving0[0], moving0[1])
-        out = K.resblock_tail_fwd(z2c, mean2, rstd2, *_bn_vecs(gamma2, beta2), scc, stride,
-                                  (mean0, rstd0) + _bn_vecs(gamma0, beta0) if bn0 else None)
-        ctx.params, ctx.sync, ctx.stride, ctx.sc_shape, ctx.rows = (gamma2, beta2, gamma0, beta0), sync, stride, tuple(sc.shape), (r2, r0)
+            stats = [_bn_frozen_stats(*moving[i], eps[i]) for i in range(len(x2s))]
+        (mean2, rstd2), (mean0, rstd0) = stats[0], stats[1] if bn0 else (None, None)
+        out = K.resblock_tail_fwd(z2c, mean2, rstd2, gamma2.data, beta2.data, scc, stride,
+                                  (mean0, rstd0, gamma0.data, beta0.data) if bn0 else None)
+        ctx.params, ctx.training, ctx.sync = (gamma2, beta2, gamma0, beta0), training, training and sync
+        ctx.stride, ctx.sc_shape, ctx.rows = stride, tuple(sc.shape), (z2c.numel() // C, scc.numel() // C)
         ctx.save_for_backward(out, z2c, scc if bn0 else None, mean2, rstd2, mean0, rstd0)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        r2, r0 = ctx.rows
-        return _resblock_backward(ctx, dout, True, 1.0 / r2, 1.0 / r0) + (None,) * 10
-
-
-class _ResBlockTailInferFn(Function):
-    @staticmethod
-    def forward(ctx, z2, sc, gamma2, beta2, gamma0, beta0, moving2, moving0, eps, stride):
-        z2c, scc = _c(z2), _c(sc)
-        bn0 = gamma0 is not None
-        # the backward reads the statistics of THIS call: a later training-mode call updates the buffers in place
-        mean2, rstd2 = moving2[0].clone(), K.rsqrt_eps(moving2[1], eps[0])
-        mean0 = rstd0 = None
-        if bn0:
-            mean0, rstd0 = moving0[0].clone(), K.rsqrt_eps(moving0[1], eps[1])
-        out = K.resblock_tail_fwd(z2c, mean2, rstd2, *_bn_vecs(gamma2, beta2), scc, stride,
-                                  (mean0, rstd0) + _bn_vecs(gamma0, beta0) if bn0 else None)
-        ctx.params, ctx.sync, ctx.stride, ctx.sc_shape = (gamma2, beta2, gamma0, beta0), False, stride, tuple(sc.shape)
-        ctx.save_for_backward(out, z2c, scc if bn0 else None, mean2, rstd2, mean0, rstd0)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        return _resblock_backward(ctx, dout, False, 0.0, 0.0) + (None,) * 8
+        """reduce -> (all-reduce of both layers' [2C] sums in one message) -> apply"""
+        out, z2, z0, mean2, rstd2, mean0, rstd0 = ctx.saved_tensors
+        gamma2, beta2, gamma0, beta0 = ctx.params
+        bn0 = z0 is not None
+        dO = _c(dout)
+        sums = K.resblock_tail_bwd_reduce(dO, out, z2, mean2, rstd2, ctx.sc_shape, ctx.stride, z0, mean0, rstd0)
+        sums, world, own = _bn_exchange_sums(sums, [(gamma2, beta2)] + ([(gamma0, beta0)] if bn0 else []), ctx.sync)
+        booked = dict(dgamma2=_param_grad(gamma2), dbeta2=_param_grad(beta2), dgamma0=_param_grad(gamma0), dbeta0=_param_grad(beta0)) if own else {}
+        inv_n2, inv_n0 = [1.0 / (r * world) if ctx.training else 0.0 for r in ctx.rows]
+        dz2, dsc = K.resblock_tail_bwd_apply(dO, out, z2, mean2, rstd2, gamma2.data, sums, inv_n2, inv_n0, ctx.training, ctx.sc_shape, ctx.stride,
+                                             z0, mean0, rstd0, gamma0.data if bn0 else None, **booked)
+        if own:
+            dist.grads_ready(gamma2, beta2, gamma0, beta0)
+        return (dz2, dsc if ctx.needs_input_grad[1] else None) + (None,) * 11
 
 
 def resblock_fused_enabled():
@@ -1254,19 +1170,15 @@ def resblock_fused_enabled():
 
 
 def resblock_tail_supported(z2, sc, bn2, bn0=None, strides=1):
-    """the shape rules of csrc/resblock.hip, and the 16-byte alignment its vector accesses need: of z2 / sc when they are passed as is (a
-    non-contiguous tensor is copied into a fresh, aligned buffer first) and of the per-channel vectors it reads directly"""
+    """the shape rules of csrc/resblock.hip, and _aligned16 of z2 / sc and the per-channel vectors it reads directly"""
     sh, sw = (strides, strides) if isinstance(strides, int) else tuple(strides)
     if sh != sw or sh not in (1, 2) or z2.dim() != 4 or sc.dim() != 4 or z2.dtype != sc.dtype:
         return False
     N, H, W, C = sc.shape
     if tuple(z2.shape) != (N, -(-H // sh), -(-W // sh), C):
         return False
-    if any(t.is_contiguous() and t.data_ptr() % 16 for t in (z2, sc)):
-        return False
     layers = (bn2,) if bn0 is None else (bn2, bn0)
-    vectors = [v for b in layers for v in (b.gamma, b.beta, b.moving_mean, b.moving_variance)]
-    if any(v.data_ptr() % 16 or not v.is_contiguous() for v in vectors):
+    if not _aligned16((z2, sc), [v for b in layers for v in (b.gamma, b.beta, b.moving_mean, b.moving_variance)]):
         return False
     return K.resblock_tail_supported(C, sh, z2.dtype)
 
@@ -1290,15 +1202,12 @@ def resblock_tail(z2, bn2, sc, bn0, strides, training):
         if st[0] > 1 or st[1] > 1:
             sc = avg_pool2d(sc, st, st, "same")
         return add_relu(sc, bn2(z2, training=training))
-    s = st[0]
     eps = (float(bn2.epsilon), float(bn0.epsilon) if bn0 is not None else 0.0)
+    momentum = (float(bn2.momentum), float(bn0.momentum) if bn0 is not None else 0.0)
     moving2 = (bn2.moving_mean, bn2.moving_variance)
     moving0 = (bn0.moving_mean, bn0.moving_variance) if bn0 is not None else (None, None)
     g0, b0 = (bn0.gamma, bn0.beta) if bn0 is not None else (None, None)
-    if modes.pop():
-        momentum = (float(bn2.momentum), float(bn0.momentum) if bn0 is not None else 0.0)
-        return _ResBlockTailTrainFn.apply(z2, sc, bn2.gamma, bn2.beta, g0, b0, moving2, moving0, eps, momentum, s, syncs.pop())
-    return _ResBlockTailInferFn.apply(z2, sc, bn2.gamma, bn2.beta, g0, b0, moving2, moving0, eps, s)
+    return _ResBlockTailFn.apply(z2, sc, bn2.gamma, bn2.beta, g0, b0, moving2, moving0, eps, momentum, st[0], modes.pop(), syncs.pop())
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -2167,8 +2076,7 @@ class _GroupNormFn(Function):
         x3, mean, rstd = ctx.saved_tensors
         g, b = ctx.gamma, ctx.beta
         dx = K.groupnorm_bwd(_c(dy).reshape(x3.shape), x3, g.data if g is not None else None, mean, rstd, ctx.groups,
-                             _grad(g) if g is not None and g.requires_grad else None,
-                             _grad(b) if b is not None and b.requires_grad else None)
+                             _param_grad(g), _param_grad(b))
         dist.grads_ready(g, b)
         return dx.reshape(dy.shape), None, None, None, None
 
@@ -3001,14 +2909,12 @@ class _DcnJointFn(Function):
             dW = torch.empty((Cin, ld), dtype=torch.float32, device=dom.device)
             db = torch.empty(ld, dtype=torch.float32, device=dom.device) if want_b else None
             K.dense_wgrad(x2, dom, dW, accumulate=False, bias_grad=db)
-            K.split_cols_accumulate(dW, _grad(W_off).reshape(Cin, na) if W_off.requires_grad else None, na,
-                                    _grad(W_mask).reshape(Cin, nb) if W_mask.requires_grad else None, nb)
+            K.split_cols_accumulate(dW, _param_grad(W_off, Cin, na), na, _param_grad(W_mask, Cin, nb), nb)
         elif want_b:
             db = torch.empty(ld, dtype=torch.float32, device=dom.device)
             K.colsum(dom, ld, 0, 1, dom.shape[0], ld, db, accumulate=False)
         if want_b:
-            K.split_cols_accumulate(db, _grad(b_off).reshape(-1) if b_off.requires_grad else None, na,
-                                    _grad(b_mask).reshape(-1) if b_mask.requires_grad else None, nb)
+            K.split_cols_accumulate(db, _param_grad(b_off, -1), na, _param_grad(b_mask, -1), nb)
         dx1 = None
         if ctx.needs_input_grad[1]:
             dx1 = K.dense_dgrad(dom, rowcat).reshape(ctx.x1_shape)
