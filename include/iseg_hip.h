@@ -123,8 +123,8 @@ int iseg_gemm_splits(const iseg_gemm_args* args_h);
  * into multiples of 128 -- for a consumer that sums the slabs itself (iseg_layerscale_grads_slabs) */
 int iseg_gemm_slabs(const iseg_gemm_args* args_h);
 /* which main loop iseg_gemm runs for this problem (profiling labels): 0 = register-staged gemm_bf16_kernel / fp32 kernel,
-   1..4 = LDS-DMA pipeline gemm_bf16_dma_kernel with tile 128x64 / 256x128 / 128x128 (2 stages) / 128x128 (3 stages),
-   6 = 256x192 (2 stages),
+   K-contiguous A and B on the LDS-DMA pipeline gemm_bf16_dma_kernel: 1 = 128x64 tiles, 2 = 256x128, 4 = 128x128 (3 stages), 6 = 256x192
+   (2 stages), 8 = 128x192, 9 = 64x192 (3 and 5 are unused: 128x128 with 2 stages could not be planned, a persistent 256x128 form was dropped),
    7 / 8 = the weight-gradient orientation (a_kcontig = b_kcontig = 0, split over K: Dense / 1x1-conv kernel gradients,
    layers' `kernel` of backbones/convnext.py:51-55, backbones/swin.py:17-43) on the LDS-DMA pipeline gemm_bf16_dma_tn_kernel with
    256x128 / 128x256 tiles (M, N multiples of 8 and >= 128 -- or one of them 64..127 when the other is >= 320 --, any K >= 2048, aligned operands) */

@@ -29,8 +29,6 @@
 
 using namespace iseg_mm;
 
-int gemm_reduce(const iseg_gemm_args* g, const Epi& epi, float* slabs, int eff_split, int64_t slab_rows, hipStream_t stream);
-
 namespace {
 
 struct ConvP {
@@ -343,51 +341,40 @@ int conv_splits(int64_t M, int64_t N, int64_t K, int groups) {
     return (int)(want < 1 ? 1 : want);
 }
 
+// conv_splits' answer for one group, cut at multiples of 64 (the K-tile of every pass), slabs of M x N
+SplitPlan conv_plan(int64_t M, int64_t N, int64_t K) { return split_plan(K, conv_splits(M, N, K, 1), 64, M, N); }
+
+// output tiles of the register-staged passes: 128 x 128 (8 wavefronts of 64 x 32), 128 x 64 for narrow outputs
+struct T128 { enum { WM = 2, WN = 4, FM = 4, FN = 2 }; };
+struct T64 { enum { WM = 4, WN = 2, FM = 2, FN = 2 }; };
+template <class F> void with_tile(int64_t N, F&& launch) {
+    if (N <= 64) launch(T64{});
+    else launch(T128{});
+}
+
 template <int PASS, class TO> int run(const Problem& q, void* ws, size_t ws_bytes, hipStream_t stream, const char* what) {
-    const int nsplit = q.groups > 1 ? 1 : conv_splits(q.M, q.N, q.K, 1);      // grouped layers are small: one pass, no slabs
-    int64_t kps = q.K;
+    // grouped layers are small: one pass, no slabs (so split problems have one group)
+    const SplitPlan plan = q.groups > 1 ? split_plan(q.K, 1, 64, q.M, q.N) : conv_plan(q.M, q.N, q.K);
     float* slabs = nullptr;
-    if (nsplit > 1) {
-        const size_t need = (size_t)nsplit * q.groups * q.M * q.N * sizeof(float);
-        ISEG_NEED_WORKSPACE(what, ws, ws_bytes, need);
+    if (plan.nsplit > 1) {
+        ISEG_NEED_WORKSPACE(what, ws, ws_bytes, plan.slab_bytes);
         slabs = (float*)ws;
-        kps = ceil_div64(ceil_div64(q.K, nsplit), 64) * 64;
     }
-    const int eff = (int)ceil_div64(q.K, kps);
-    Epi epi{};
-    epi.bias = q.bias;
-    epi.alpha = 1.f;
-    epi.accumulate = q.accumulate;
-    epi.batch_inner = 1;
+    const Epi epi = plain_epi(q.bias, q.accumulate);
     const int vecD = ((uintptr_t)q.D % 16 == 0) && (q.ldd % 8 == 0) && (q.d_group_stride % 8 == 0) && (!q.bias || (uintptr_t)q.bias % 16 == 0) &&
                      (q.N % 4 == 0);
-    const int64_t slab_group_stride = 0;      // (split problems have one group)
-    auto launch = [&](auto tile) {
+    const int64_t slab_group_stride = 0;
+    with_tile(q.N, [&](auto tile) {
         constexpr int WM = decltype(tile)::WM, WN = decltype(tile)::WN, FM = decltype(tile)::FM, FN = decltype(tile)::FN;
         constexpr int BM = WM * FM * 16, BN = WN * FN * 16;
         const int tiles_m = (int)ceil_div64(q.M, BM), tiles_n = (int)ceil_div64(q.N, BN);
-        hipLaunchKernelGGL((conv_igemm_kernel<WM, WN, FM, FN, PASS, 64, TO>), dim3(tiles_m * tiles_n, eff, q.groups), dim3(WM * WN * 64), 0, stream, q.p,
-                           q.B, q.ldb, q.b_group_stride, q.tap_stride, (TO*)q.D, q.ldd, q.d_group_stride, q.M, q.N, q.K, tiles_n, tiles_m * tiles_n,
-                           kps, slabs, slab_group_stride, epi, vecD, NoPhases{});
-    };
-    struct T128 { enum { WM = 2, WN = 4, FM = 4, FN = 2 }; };
-    struct T64 { enum { WM = 4, WN = 2, FM = 2, FN = 2 }; };
-    if (q.N <= 64) launch(T64{});
-    else launch(T128{});
+        hipLaunchKernelGGL((conv_igemm_kernel<WM, WN, FM, FN, PASS, 64, TO>), dim3(tiles_m * tiles_n, plan.eff_split, q.groups), dim3(WM * WN * 64), 0,
+                           stream, q.p, q.B, q.ldb, q.b_group_stride, q.tap_stride, (TO*)q.D, q.ldd, q.d_group_stride, q.M, q.N, q.K, tiles_n,
+                           tiles_m * tiles_n, plan.kps, slabs, slab_group_stride, epi, vecD, NoPhases{});
+    });
     if (!slabs) return iseg_check_launch(what);
     // slab-order sum + epilogue through the GEMM reducer (deterministic)
-    iseg_gemm_args ga{};
-    ga.M = q.M;
-    ga.N = q.N;
-    ga.K = q.K;
-    ga.D = q.D;
-    ga.ldd = q.ldd;
-    ga.in_dtype = ISEG_BF16;
-    ga.out_dtype = q.out_dtype;
-    ga.alpha = 1.f;
-    ga.accumulate = q.accumulate;
-    ga.bias = q.bias;
-    return gemm_reduce(&ga, epi, slabs, eff, q.M, stream);
+    return gemm_reduce(epi, q.D, q.ldd, q.out_dtype, q.M, q.N, slabs, plan, stream);
 }
 
 // pass 3: every stride phase of a strided data gradient in one launch (grid.y = phase, grid.z = group); phases no tap reaches (kernel
@@ -426,22 +413,16 @@ int run_phases(const Problem& q, const iseg_conv_geom* g, hipStream_t stream, co
         }
     }
     if (count == 0) return ISEG_OK;
-    Epi epi{};
-    epi.alpha = 1.f;
-    epi.batch_inner = 1;
+    const Epi epi = plain_epi(nullptr, 0);
     const int vecD = ((uintptr_t)q.D % 16 == 0) && (q.ldd % 8 == 0) && (q.d_group_stride % 8 == 0) && (q.N % 4 == 0);
-    auto launch = [&](auto tile) {
+    with_tile(q.N, [&](auto tile) {
         constexpr int WM = decltype(tile)::WM, WN = decltype(tile)::WN, FM = decltype(tile)::FM, FN = decltype(tile)::FN;
         constexpr int BM = WM * FM * 16, BN = WN * FN * 16;
         const int tiles_m = (int)ceil_div64(maxM, BM), tiles_n = (int)ceil_div64(q.N, BN);
         hipLaunchKernelGGL((conv_igemm_kernel<WM, WN, FM, FN, 3, 64, bf16_t>), dim3(tiles_m * tiles_n, count, q.groups), dim3(WM * WN * 64), 0, stream,
                            q.p, q.B, q.ldb, q.b_group_stride, q.tap_stride, (bf16_t*)q.D, q.ldd, q.d_group_stride, maxM, q.N, (int64_t)0, tiles_n,
                            tiles_m * tiles_n, (int64_t)0, (float*)nullptr, (int64_t)0, epi, vecD, tab);
-    };
-    struct T128 { enum { WM = 2, WN = 4, FM = 4, FN = 2 }; };
-    struct T64 { enum { WM = 4, WN = 2, FM = 2, FN = 2 }; };
-    if (q.N <= 64) launch(T64{});
-    else launch(T128{});
+    });
     return iseg_check_launch(what);
 }
 
@@ -455,21 +436,13 @@ bool dma_conv_eligible(const Problem& q, const iseg_conv_geom* g, int pass) {
 }
 
 template <int PASS> int run_dma(const Problem& q, void* ws, size_t ws_bytes, hipStream_t stream, const char* what) {
-    const int nsplit = conv_splits(q.M, q.N, q.K, 1);
-    int64_t kps = q.K;
+    const SplitPlan plan = conv_plan(q.M, q.N, q.K);
     float* slabs = nullptr;
-    if (nsplit > 1) {
-        const size_t need = (size_t)nsplit * q.M * q.N * sizeof(float);
-        ISEG_NEED_WORKSPACE(what, ws, ws_bytes, need);
+    if (plan.nsplit > 1) {
+        ISEG_NEED_WORKSPACE(what, ws, ws_bytes, plan.slab_bytes);
         slabs = (float*)ws;
-        kps = ceil_div64(ceil_div64(q.K, nsplit), 64) * 64;
     }
-    const int eff = (int)ceil_div64(q.K, kps);
-    Epi epi{};
-    epi.bias = q.bias;
-    epi.alpha = 1.f;
-    epi.accumulate = q.accumulate;
-    epi.batch_inner = 1;
+    const Epi epi = plain_epi(q.bias, q.accumulate);
     auto launch = [&](auto tile) {
         constexpr int WM = decltype(tile)::WM, WN = decltype(tile)::WN, NS = decltype(tile)::NS;
         constexpr int BM = WM * 64, BN = WN * 64;
@@ -480,26 +453,15 @@ template <int PASS> int run_dma(const Problem& q, void* ws, size_t ws_bytes, hip
                                        hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess;
         }();
         (void)raised;
-        hipLaunchKernelGGL((conv_igemm_dma_kernel<WM, WN, NS, PASS, bf16_t>), dim3(tiles_m * tiles_n, eff, 1), dim3(WM * WN * 64), lds, stream, q.p, q.B,
-                           q.ldb, q.tap_stride, (bf16_t*)q.D, q.ldd, q.M, q.N, q.K, tiles_n, tiles_m * tiles_n, kps, slabs, epi);
+        hipLaunchKernelGGL((conv_igemm_dma_kernel<WM, WN, NS, PASS, bf16_t>), dim3(tiles_m * tiles_n, plan.eff_split, 1), dim3(WM * WN * 64), lds, stream,
+                           q.p, q.B, q.ldb, q.tap_stride, (bf16_t*)q.D, q.ldd, q.M, q.N, q.K, tiles_n, tiles_m * tiles_n, plan.kps, slabs, epi);
     };
-    struct T256 { enum { WM = 4, WN = 2, NS = 3 }; };
-    struct T128 { enum { WM = 2, WN = 2, NS = 2 }; };
-    if (ceil_div64(q.M, 256) * ceil_div64(q.N, 128) * eff >= 192) launch(T256{});
-    else launch(T128{});
+    struct D256 { enum { WM = 4, WN = 2, NS = 3 }; };      // the LDS-DMA kernel's tiles: 256 x 128 with three stages, 128 x 128 with two
+    struct D128 { enum { WM = 2, WN = 2, NS = 2 }; };
+    if (ceil_div64(q.M, 256) * ceil_div64(q.N, 128) * plan.eff_split >= 192) launch(D256{});
+    else launch(D128{});
     if (!slabs) return iseg_check_launch(what);
-    iseg_gemm_args ga{};
-    ga.M = q.M;
-    ga.N = q.N;
-    ga.K = q.K;
-    ga.D = q.D;
-    ga.ldd = q.ldd;
-    ga.in_dtype = ISEG_BF16;
-    ga.out_dtype = q.out_dtype;
-    ga.alpha = 1.f;
-    ga.accumulate = q.accumulate;
-    ga.bias = q.bias;
-    return gemm_reduce(&ga, epi, slabs, eff, q.M, stream);
+    return gemm_reduce(epi, q.D, q.ldd, q.out_dtype, q.M, q.N, slabs, plan, stream);
 }
 
 bool geom_ok(const iseg_conv_geom* g) {
@@ -531,8 +493,7 @@ extern "C" size_t iseg_conv2d_igemm_workspace_bytes(const iseg_conv_geom* g, int
     if (pass == 0) M = Mo, N = g->Cout, K = Kd;
     else if (pass == 1) M = Mi, N = g->Cin, K = (int64_t)g->KH * g->KW * g->Cout;
     else M = Kd, N = g->Cout, K = Mo;
-    const int s = conv_splits(M, N, K, 1);
-    return s > 1 ? (size_t)s * M * N * sizeof(float) : 0;
+    return conv_plan(M, N, K).slab_bytes;
 }
 
 #define CONV_COMMON(name)                                                                                                             \
@@ -660,22 +621,6 @@ ConvP branches_shared(const iseg_conv_branches* t, const void* src, int Cs, int 
     return ConvP{(const bf16_t*)src, t->H, t->W, Cs, t->H, t->W, Cg, 1, 1, 1, 1, 1, 0, 0, 1};
 }
 
-// The K-joined data gradient's tile and split.  Flagship (M = 4096, N = 768, K = 7168), kernel only: 256 x 128 tiles, 2 splits + reducer 126 us;
-// 128 x 128 tiles, 2 splits + reducer 132 us; 128 x 128, no split (192 workgroups for 256 CUs) 138 us; 256 x 128, no split 207 us.
-struct DgradPlan {
-    bool big;         // 256 x 128 tiles (8 wavefronts of 64 x 64, 3 stages) instead of 128 x 128 (8 wavefronts of 64 x 32, 2 stages)
-    int nsplit;
-};
-DgradPlan branches_dgrad_plan(int64_t M, int64_t N, int64_t K) { return DgradPlan{M >= 256, conv_splits(M, N, K, 1)}; }
-
-// The K-joined data gradient IS one stride-1 data gradient whose taps are the taps of every branch in a row: its slabs are sized by
-// iseg_conv2d_igemm_workspace_bytes of this geometry (pass 1), here and by the caller.
-iseg_conv_geom branches_joined_geom(const iseg_conv_branches* t) {
-    int taps = 0;
-    for (int i = 0; i < t->count; ++i) taps += t->b[i].KH * t->b[i].KW;
-    return iseg_conv_geom{t->N, t->H, t->W, t->Cin, t->Cout, 1, taps, 1, 1, 1, 1, 0, 0, t->H, t->W, 1};
-}
-
 template <int PASS, class Tile>
 void launch_branches_dma(Tile, const ConvP& p, const BranchTable& tab, int64_t ldb, int64_t tap_stride, bf16_t* D, int64_t ldd, int64_t M, int64_t N,
                          int64_t K, int eff, int64_t kps, float* slabs, const Epi& epi, hipStream_t stream) {
@@ -740,11 +685,8 @@ extern "C" int iseg_conv2d_branches_fwd(const void* x, const iseg_conv_branches*
         d.bias = b.bias;
         d.kw = b.KW, d.dh = b.dh, d.dw = b.dw, d.pt = b.pt, d.pl = b.pl;
     }
-    Epi epi{};
-    epi.alpha = 1.f;
-    epi.batch_inner = 1;
     const ConvP p = branches_shared(t, x, t->Cin, t->Cin);
-    launch_branches_dma<0>(BT128{}, p, tab, 0, 0, nullptr, 0, M, t->Cout, 0, 1, 0, nullptr, epi, stream);
+    launch_branches_dma<0>(BT128{}, p, tab, 0, 0, nullptr, 0, M, t->Cout, 0, 1, 0, nullptr, plain_epi(nullptr, 0), stream);
     return iseg_check_launch("iseg_conv2d_branches_fwd");
 }
 
@@ -771,39 +713,24 @@ extern "C" int iseg_conv2d_branches_bwd_data(const iseg_conv_branches* t, void* 
         d.kw = b.KW, d.dh = b.dh, d.dw = b.dw, d.pt = b.pt, d.pl = b.pl;
     }
     const int64_t N = t->Cin;
-    const DgradPlan plan = branches_dgrad_plan(M, N, K);
-    int64_t kps = K;
+    // The K-joined data gradient IS one stride-1 data gradient whose taps are the taps of every branch in a row: it takes that problem's plan, and
+    // the caller sizes the slabs by iseg_conv2d_igemm_workspace_bytes (pass 1) of that geometry, a 1 x (all taps) kernel over the same maps.
+    // Its tile (256 x 128 from 256 pixels on), flagship (M = 4096, N = 768, K = 7168), kernel only: 256 x 128 tiles, 2 splits + reducer 126 us; 128 x 128 tiles, 2 splits + reducer
+    // 132 us; 128 x 128, no split (192 workgroups for 256 CUs) 138 us; 256 x 128, no split 207 us.
+    const SplitPlan plan = conv_plan(M, N, K);
     float* slabs = nullptr;
     if (plan.nsplit > 1) {
-        const iseg_conv_geom joined = branches_joined_geom(t);
-        const size_t need = iseg_conv2d_igemm_workspace_bytes(&joined, 1);
-        ISEG_NEED_WORKSPACE("iseg_conv2d_branches_bwd_data", ws, ws_bytes, need);
+        ISEG_NEED_WORKSPACE("iseg_conv2d_branches_bwd_data", ws, ws_bytes, plan.slab_bytes);
         slabs = (float*)ws;
-        kps = ceil_div64(ceil_div64(K, plan.nsplit), 64) * 64;
     }
-    const int eff = (int)ceil_div64(K, kps);
-    Epi epi{};
-    epi.alpha = 1.f;
-    epi.batch_inner = 1;
-    epi.residual = residual;
-    epi.ldr = ldr;
+    Epi epi = plain_epi(nullptr, 0);
+    epi.residual = residual, epi.ldr = ldr;
     const ConvP p = branches_shared(t, nullptr, 0, t->Cout);
     const int64_t tap_stride = (int64_t)t->Cin * t->Cout;
-    if (plan.big) launch_branches_dma<1>(BT256{}, p, tab, t->Cout, tap_stride, (bf16_t*)dx, N, M, N, K, eff, kps, slabs, epi, stream);
-    else launch_branches_dma<1>(BT128{}, p, tab, t->Cout, tap_stride, (bf16_t*)dx, N, M, N, K, eff, kps, slabs, epi, stream);
+    if (M >= 256) launch_branches_dma<1>(BT256{}, p, tab, t->Cout, tap_stride, (bf16_t*)dx, N, M, N, K, plan.eff_split, plan.kps, slabs, epi, stream);
+    else launch_branches_dma<1>(BT128{}, p, tab, t->Cout, tap_stride, (bf16_t*)dx, N, M, N, K, plan.eff_split, plan.kps, slabs, epi, stream);
     if (!slabs) return iseg_check_launch("iseg_conv2d_branches_bwd_data");
-    iseg_gemm_args ga{};
-    ga.M = M;
-    ga.N = N;
-    ga.K = K;
-    ga.D = dx;
-    ga.ldd = N;
-    ga.in_dtype = ISEG_BF16;
-    ga.out_dtype = ISEG_BF16;
-    ga.alpha = 1.f;
-    ga.residual = residual;
-    ga.ldr = ldr;
-    return gemm_reduce(&ga, epi, slabs, eff, M, stream);
+    return gemm_reduce(epi, dx, N, ISEG_BF16, M, N, slabs, plan, stream);
 }
 
 extern "C" int iseg_conv2d_branches_bwd_weight(const void* x, const iseg_conv_branches* t, int accumulate, int dtype, void* ws, size_t ws_bytes,
@@ -829,22 +756,15 @@ extern "C" int iseg_conv2d_branches_bwd_weight(const void* x, const iseg_conv_br
         d.kw = b.KW, d.dh = b.dh, d.dw = b.dw, d.pt = b.pt, d.pl = b.pl;
         if (d.K > maxK) maxK = d.K;
     }
-    Epi epi{};
-    epi.alpha = 1.f;
-    epi.accumulate = accumulate;
-    epi.batch_inner = 1;
+    const Epi epi = plain_epi(nullptr, accumulate);
     const ConvP p = branches_shared(t, x, t->Cin, t->Cin);
     const int64_t N = t->Cout;
-    auto launch = [&](auto tile) {
+    with_tile(N, [&](auto tile) {
         constexpr int WM = decltype(tile)::WM, WN = decltype(tile)::WN, FM = decltype(tile)::FM, FN = decltype(tile)::FN;
         constexpr int BM = WM * FM * 16, BN = WN * FN * 16;
         const int tiles_m = (int)ceil_div64(maxK, BM), tiles_n = (int)ceil_div64(N, BN);
         hipLaunchKernelGGL((conv_branches_wgrad_kernel<WM, WN, FM, FN, 64>), dim3(tiles_m * tiles_n, 1, tab.count), dim3(WM * WN * 64), 0, stream, p, tab,
                            N, M, tiles_n, tiles_m * tiles_n, epi, 1);
-    };
-    struct T128 { enum { WM = 2, WN = 4, FM = 4, FN = 2 }; };
-    struct T64 { enum { WM = 4, WN = 2, FM = 2, FN = 2 }; };
-    if (N <= 64) launch(T64{});
-    else launch(T128{});
+    });
     return iseg_check_launch("iseg_conv2d_branches_bwd_weight");
 }

@@ -17,8 +17,6 @@
 
 using namespace iseg_mm;
 
-int gemm_reduce(const iseg_gemm_args* g, const Epi& epi, float* slabs, int eff_split, int64_t slab_rows, hipStream_t stream);
-
 namespace {
 
 const void* const ALIGNED = reinterpret_cast<const void*>(uintptr_t(4096));      // stands for an operand in the geometry-only queries
@@ -95,17 +93,6 @@ int wgrad_form(const iseg_gemm_args& a) {
     return form && dma_tn_split(&a, form) > 1 ? form : 0;
 }
 
-Epi epi_of(const iseg_gemm_args& a) {
-    Epi e{};
-    e.bias = a.bias;
-    e.alpha = 1.f;
-    e.accumulate = a.accumulate;
-    e.colsum_out = a.colsum_out;
-    e.colsum_accumulate = a.colsum_accumulate;
-    e.batch_inner = 1;
-    return e;
-}
-
 }  // namespace
 
 namespace iseg_mm {
@@ -135,7 +122,7 @@ extern "C" int iseg_conv2d_patch_fwd(const void* x, const void* wt, const float*
         iseg_set_error("iseg_conv2d_patch_fwd: not a patchify convolution this route takes (iseg_conv2d_patch_supported(geom, dtype, 0)), or operands not 16-byte aligned");
         return ISEG_ERR_UNSUPPORTED;
     }
-    Epi e = epi_of(a);
+    Epi e = plain_epi(bias, 0);
     set_view(e, g);
     if (bias) dispatch_dma_patch<1, EK_BIAS>(&a, e, stream);
     else dispatch_dma_patch<1, EK_PLAIN>(&a, e, stream);
@@ -151,7 +138,7 @@ extern "C" int iseg_conv2d_patch_bwd_data(const void* dy, const void* w, void* d
         iseg_set_error("iseg_conv2d_patch_bwd_data: not a patchify convolution this route takes (iseg_conv2d_patch_supported(geom, dtype, 1)), or operands not 16-byte aligned");
         return ISEG_ERR_UNSUPPORTED;
     }
-    Epi e = epi_of(a);
+    Epi e = plain_epi(nullptr, 0);
     set_view(e, g);
     dispatch_dma_patch<2, EK_PLAIN>(&a, e, stream);
     return iseg_check_launch("iseg_conv2d_patch_bwd_data");
@@ -166,15 +153,13 @@ extern "C" int iseg_conv2d_patch_bwd_weight(const void* x, const void* dy, float
         iseg_set_error("iseg_conv2d_patch_bwd_weight: not a patchify convolution this route takes (iseg_conv2d_patch_supported(geom, dtype, 2)), or operands not 16-byte aligned");
         return ISEG_ERR_UNSUPPORTED;
     }
-    const int nsplit = iseg_gemm_splits(&a);
-    const int64_t slab_rows = a.M + (a.colsum_out ? 1 : 0);
-    const size_t need = (size_t)nsplit * slab_rows * a.N * sizeof(float);
-    ISEG_NEED_WORKSPACE("iseg_conv2d_patch_bwd_weight", ws, ws_bytes, need);
-    const int64_t kps = ceil_div64(ceil_div64(a.K, nsplit), 128) * 128;
-    const int eff = (int)ceil_div64(a.K, kps);
+    const SplitPlan plan = split_plan(a.K, iseg_gemm_splits(&a), 128, a.M + (dbias ? 1 : 0), a.N);      // iseg_gemm's plan for the same M, N, K
+    ISEG_NEED_WORKSPACE("iseg_conv2d_patch_bwd_weight", ws, ws_bytes, plan.slab_bytes);
     TnPatch pv{g->Wo, g->KW * g->Cin, (int64_t)g->KH * g->W * g->Cin, (int64_t)g->W * g->Cin, 0};
     if (64 % g->Wo == 0) pv.adv = (int64_t)(64 / g->Wo) * pv.group;      // 64 reduction rows = whole pixel rows: a constant per-stage advance
-    if (form == 7) launch_dma_tn_patch<4, 2>(&a, pv, eff, kps, (float*)ws, stream);
-    else launch_dma_tn_patch<2, 4>(&a, pv, eff, kps, (float*)ws, stream);
-    return gemm_reduce(&a, epi_of(a), (float*)ws, eff, slab_rows, stream);
+    if (form == 7) launch_dma_tn_patch<4, 2>(&a, pv, plan.eff_split, plan.kps, (float*)ws, stream);
+    else launch_dma_tn_patch<2, 4>(&a, pv, plan.eff_split, plan.kps, (float*)ws, stream);
+    Epi e = plain_epi(nullptr, accumulate);
+    e.colsum_out = dbias, e.colsum_accumulate = accumulate;
+    return gemm_reduce(e, dw, a.ldd, ISEG_F32, a.M, a.N, (float*)ws, plan, stream);
 }

@@ -160,36 +160,55 @@ int choose_split(const iseg_gemm_args* g, int tile) {
     return (int)(want < 1 ? 1 : want);
 }
 
-}  // namespace
+// choose_split's answer cut at multiples of 128, slabs of M rows (+ the ones-row of a bias gradient): every entry point below takes its numbers here
+SplitPlan plan_of(const iseg_gemm_args* g) { return split_plan(g->K, iseg_gemm_splits(g), 128, g->M + (g->colsum_out ? 1 : 0), g->N); }
 
-int gemm_reduce(const iseg_gemm_args* g, const Epi& epi, float* slabs, int eff_split, int64_t slab_rows, hipStream_t stream);
+Epi make_epi(const iseg_gemm_args* g) {
+    Epi e{};
+    e.bias = g->bias, e.colscale = g->colscale, e.rowscale = g->rowscale, e.rows_per_group = g->rows_per_group;
+    e.residual = g->residual, e.ldr = g->ldr;
+    e.aux = g->aux, e.ldaux = g->ldaux;
+    e.pre_out = g->pre_out, e.ldp = g->ldp, e.pre_deriv = g->pre_deriv;
+    e.act = g->act, e.alpha = g->alpha, e.accumulate = g->accumulate;
+    e.colsum_out = g->colsum_out, e.colsum_accumulate = g->colsum_accumulate;
+    e.batch_inner = g->batch_inner > 0 ? g->batch_inner : 1;
+    e.sa_outer = g->sa_outer, e.sa_inner = g->sa_inner, e.sb_outer = g->sb_outer, e.sb_inner = g->sb_inner;
+    e.sd_outer = g->sd_outer, e.sd_inner = g->sd_inner;
+    e.b_group_rows = g->b_group_rows, e.b_group_stride = g->b_group_stride;
+    return e;
+}
+
+int check_batched(const iseg_gemm_args* g) {
+    if (g->batch <= 1) return ISEG_OK;
+    ISEG_REQUIRE(g->batch <= 65535, "iseg_gemm: batch %d exceeds the grid z limit (65535)", g->batch);
+    ISEG_REQUIRE(!g->bias && !g->colscale && !g->rowscale && !g->residual && !g->aux && !g->pre_out && !g->colsum_out &&
+                     g->act == ISEG_ACT_NONE && g->a_act == ISEG_ACT_NONE,
+                 "iseg_gemm: a batched problem takes only the alpha / accumulate epilogue");
+    return ISEG_OK;
+}
+
+}  // namespace
 
 extern "C" int iseg_gemm_splits(const iseg_gemm_args* g) {
     return choose_split(g, g->in_dtype == ISEG_BF16 ? 128 : 64);
 }
 
 // slabs a split problem really writes: the K range is cut into 128-element multiples, so it can be fewer than iseg_gemm_splits
-extern "C" int iseg_gemm_slabs(const iseg_gemm_args* g) {
-    if (!g) return 0;
-    const int nsplit = iseg_gemm_splits(g);
-    if (nsplit <= 1) return 1;
-    const int64_t kps = ceil_div64(ceil_div64(g->K, nsplit), 128) * 128;
-    return (int)ceil_div64(g->K, kps);
+extern "C" int iseg_gemm_slabs(const iseg_gemm_args* g) { return g ? plan_of(g).eff_split : 0; }
+
+int iseg_mm::gemm_bf16_form(const iseg_gemm_args* g, const SplitPlan& p) {
+    // 7 / 8: the weight-gradient LDS-DMA kernel, for split problems only (it writes slabs)
+    if (!g->a_kcontig && !g->b_kcontig) return p.eff_split > 1 && p.kps % 64 == 0 ? dma_tn_form(g) : 0;
+    if (g->a_kcontig && g->b_kcontig && dma_eligible(g, p.kps)) return dma_form(g, p.eff_split);
+    return 0;
 }
 
 extern "C" int iseg_gemm_variant(const iseg_gemm_args* g) {
     if (!g || g->in_dtype != ISEG_BF16) return 0;
-    const int nsplit = iseg_gemm_splits(g);
-    const int64_t kps = nsplit > 1 ? ceil_div64(ceil_div64(g->K, nsplit), 128) * 128 : g->K;
-    if (nsplit > 1 && iseg_mm::dma_tn_form(g)) return iseg_mm::dma_tn_form(g);      // 7 / 8: the weight-gradient LDS-DMA kernel
-    if (!iseg_mm::dma_eligible(g, kps)) return 0;
-    return iseg_mm::dma_form(g, (int)ceil_div64(g->K, kps));
+    return gemm_bf16_form(g, plan_of(g));
 }
 
-extern "C" size_t iseg_gemm_workspace_bytes(const iseg_gemm_args* g) {
-    const int s = iseg_gemm_splits(g);
-    return s > 1 ? (size_t)s * (size_t)(g->M + (g->colsum_out ? 1 : 0)) * (size_t)g->N * sizeof(float) : 0;
-}
+extern "C" size_t iseg_gemm_workspace_bytes(const iseg_gemm_args* g) { return plan_of(g).slab_bytes; }
 
 extern "C" int iseg_gemm(const iseg_gemm_args* g, void* ws, size_t ws_bytes, hipStream_t stream) {
     ISEG_REQUIRE(g && g->A && g->B && g->D, "iseg_gemm: null operand");
@@ -204,17 +223,9 @@ extern "C" int iseg_gemm(const iseg_gemm_args* g, void* ws, size_t ws_bytes, hip
     ISEG_REQUIRE(g->act >= ISEG_ACT_NONE && g->act <= ISEG_ACT_MUL_AUX, "iseg_gemm: bad act %d", g->act);
     ISEG_REQUIRE(!g->pre_deriv || (g->act == ISEG_ACT_GELU && g->pre_out), "iseg_gemm: pre_deriv needs act = GELU and pre_out");
     ISEG_REQUIRE(g->a_act == ISEG_ACT_NONE || g->a_act == ISEG_ACT_GELU, "iseg_gemm: a_act must be NONE or GELU");
-    Epi epi{g->bias, g->colscale, g->rowscale, g->rows_per_group, g->residual, g->ldr, g->aux, g->ldaux, g->pre_out, g->ldp,
-            g->act, g->alpha, g->accumulate, g->colsum_out, g->colsum_accumulate,
-            g->batch_inner > 0 ? g->batch_inner : 1, g->sa_outer, g->sa_inner, g->sb_outer, g->sb_inner, g->sd_outer, g->sd_inner,
-            g->pre_deriv, g->b_group_rows, g->b_group_stride};
+    const Epi epi = make_epi(g);
     const int batch = g->batch > 1 ? g->batch : 1;
-    if (batch > 1) {
-        ISEG_REQUIRE(batch <= 65535, "iseg_gemm: batch %d exceeds the grid z limit (65535)", batch);
-        ISEG_REQUIRE(!g->bias && !g->colscale && !g->rowscale && !g->residual && !g->aux && !g->pre_out && !g->colsum_out &&
-                         g->act == ISEG_ACT_NONE && g->a_act == ISEG_ACT_NONE,
-                     "iseg_gemm: a batched problem takes only the alpha / accumulate epilogue");
-    }
+    if (const int st = check_batched(g)) return st;
     if (g->b_group_rows > 0) {
         if (!(g->in_dtype == ISEG_BF16 && g->a_kcontig && g->b_kcontig && batch == 1 && g->split_k <= 1 && g->b_group_rows % 256 == 0 &&
               g->b_group_stride % 8 == 0 && iseg_mm::dma_eligible(g, g->K))) {
@@ -227,22 +238,17 @@ extern "C" int iseg_gemm(const iseg_gemm_args* g, void* ws, size_t ws_bytes, hip
         ISEG_REQUIRE(g->in_dtype == ISEG_BF16 && !g->a_kcontig && !g->b_kcontig, "iseg_gemm: colsum_out needs the bf16 wgrad orientation");
         ISEG_REQUIRE(g->M % 8 == 0, "iseg_gemm: colsum_out needs M %% 8 == 0");      // (M %% 128 == 0: the ones-row opens one more tile row)
     }
-    const int64_t slab_rows = g->M + (g->colsum_out ? 1 : 0);
-    const int nsplit = iseg_gemm_splits(g);
-    if (gemm_log_on()) gemm_log(g, nsplit);
+    const SplitPlan plan = plan_of(g);
+    if (gemm_log_on()) gemm_log(g, plan.nsplit);
     float* slabs = nullptr;
-    int64_t kps = g->K;
-    if (nsplit > 1) {
-        const size_t need = (size_t)nsplit * slab_rows * g->N * sizeof(float);
-        ISEG_NEED_WORKSPACE("iseg_gemm", ws, ws_bytes, need);
+    if (plan.nsplit > 1) {
+        ISEG_NEED_WORKSPACE("iseg_gemm", ws, ws_bytes, plan.slab_bytes);
         slabs = (float*)ws;
-        kps = ceil_div64(ceil_div64(g->K, nsplit), 128) * 128;
     }
-    const int eff_split = (int)ceil_div64(g->K, kps);
     if (g->in_dtype == ISEG_BF16) {
-        if (g->a_kcontig && !g->b_kcontig) gemm_bf16_nn(g, epi, eff_split, kps, slabs, stream);
-        else if (g->a_kcontig && g->b_kcontig) gemm_bf16_nt(g, epi, eff_split, kps, slabs, stream);
-        else if (!g->a_kcontig && !g->b_kcontig) gemm_bf16_tn(g, epi, eff_split, kps, slabs, stream);
+        if (g->a_kcontig && !g->b_kcontig) gemm_bf16_nn(g, epi, plan, slabs, stream);
+        else if (g->a_kcontig && g->b_kcontig) gemm_bf16_nt(g, epi, plan, slabs, stream);
+        else if (!g->a_kcontig && !g->b_kcontig) gemm_bf16_tn(g, epi, plan, slabs, stream);
         else {
             iseg_set_error("iseg_gemm: bf16 path does not provide A MN-contiguous x B K-contiguous");
             return ISEG_ERR_UNSUPPORTED;
@@ -251,33 +257,30 @@ extern "C" int iseg_gemm(const iseg_gemm_args* g, void* ws, size_t ws_bytes, hip
         const int tiles_m = (int)ceil_div64(g->M, 64), tiles_n = (int)ceil_div64(g->N, 64);
         const int64_t sam = g->a_kcontig ? g->lda : 1, sak = g->a_kcontig ? 1 : g->lda;
         const int64_t sbk = g->b_kcontig ? 1 : g->ldb, sbn = g->b_kcontig ? g->ldb : 1;
-        hipLaunchKernelGGL((gemm_f32_kernel<float>), dim3(tiles_m * tiles_n, eff_split, batch), dim3(256), 0, stream,
+        hipLaunchKernelGGL((gemm_f32_kernel<float>), dim3(tiles_m * tiles_n, plan.eff_split, batch), dim3(256), 0, stream,
                            (const float*)g->A, sam, sak, (const float*)g->B, sbk, sbn, (float*)g->D, g->ldd, g->M, g->N, g->K,
-                           tiles_n, kps, slabs, epi, g->a_act);
+                           tiles_n, plan.kps, slabs, epi, g->a_act);
     }
     if (g->defer_reduce) return iseg_check_launch("iseg_gemm");   // caller runs iseg_gemm_reduce itself
-    return gemm_reduce(g, epi, slabs, eff_split, slab_rows, stream);
+    return gemm_reduce(epi, g->D, g->ldd, g->out_dtype, g->M, g->N, slabs, plan, stream);
 }
 
-int gemm_reduce(const iseg_gemm_args* g, const Epi& epi, float* slabs, int eff_split, int64_t slab_rows, hipStream_t stream) {
-    const bool plain_epilogue = !g->bias && !g->colscale && !g->rowscale && !g->residual && !g->pre_out && g->act == ISEG_ACT_NONE &&
-                                g->out_dtype == ISEG_F32 && g->ldd == g->N &&
-                                (!g->colsum_out || (g->colsum_accumulate != 0) == (g->accumulate != 0));
+int iseg_mm::gemm_reduce(const Epi& e, void* D, int64_t ldd, int out_dtype, int64_t M, int64_t N, float* slabs, const SplitPlan& p,
+                         hipStream_t stream) {
+    const bool plain_epilogue = !e.bias && !e.colscale && !e.rowscale && !e.residual && !e.pre_out && e.act == ISEG_ACT_NONE &&
+                                out_dtype == ISEG_F32 && ldd == N && (!e.colsum_out || (e.colsum_accumulate != 0) == (e.accumulate != 0));
+    const int64_t total = p.slab_rows * N;
     if (slabs && plain_epilogue) {
         // weight gradients: D (+)= alpha * sum_z slab[z] (and the ones-row -> colsum_out) with the 2-D parallel reducer
-        const int64_t mn = g->M * g->N;
-        launch_reduce_rows(slabs, eff_split, slab_rows * g->N, 0, 1, slab_rows * g->N, (float*)g->D, g->colsum_out, mn, 0, g->alpha,
-                           g->accumulate, stream);
-        (void)mn;
+        launch_reduce_rows(slabs, p.eff_split, total, 0, 1, total, (float*)D, e.colsum_out, M * N, 0, e.alpha, e.accumulate, stream);
     } else if (slabs) {
-        const int64_t total = slab_rows * g->N;
         const int blocks = (int)(ceil_div64(total, 256) < 2048 ? ceil_div64(total, 256) : 2048);
-        if (g->out_dtype == ISEG_BF16)
-            hipLaunchKernelGGL((splitk_reduce_kernel<bf16_t>), dim3(blocks), dim3(256), 0, stream, slabs, eff_split,
-                               (bf16_t*)g->D, g->ldd, g->M, g->N, epi, slab_rows);
+        if (out_dtype == ISEG_BF16)
+            hipLaunchKernelGGL((splitk_reduce_kernel<bf16_t>), dim3(blocks), dim3(256), 0, stream, slabs, p.eff_split, (bf16_t*)D, ldd, M, N, e,
+                               p.slab_rows);
         else
-            hipLaunchKernelGGL((splitk_reduce_kernel<float>), dim3(blocks), dim3(256), 0, stream, slabs, eff_split,
-                               (float*)g->D, g->ldd, g->M, g->N, epi, slab_rows);
+            hipLaunchKernelGGL((splitk_reduce_kernel<float>), dim3(blocks), dim3(256), 0, stream, slabs, p.eff_split, (float*)D, ldd, M, N, e,
+                               p.slab_rows);
     }
     return iseg_check_launch("iseg_gemm");
 }
@@ -301,35 +304,20 @@ extern "C" int iseg_gemm_tn_pair(const iseg_gemm_args* g0, void* ws0, size_t ws0
                  g1->split_k);
     ISEG_REQUIRE(!g0->bias && !g1->bias && g0->act == ISEG_ACT_NONE && g1->act == ISEG_ACT_NONE && g0->out_dtype == ISEG_F32 && g1->out_dtype == ISEG_F32,
                  "iseg_gemm_tn_pair: plain fp32 weight gradients only");
-    const size_t need0 = iseg_gemm_workspace_bytes(g0), need1 = iseg_gemm_workspace_bytes(g1);
-    ISEG_NEED_WORKSPACE("iseg_gemm_tn_pair", ws0, ws0_bytes, need0);
-    ISEG_NEED_WORKSPACE("iseg_gemm_tn_pair", ws1, ws1_bytes, need1);
-    const int64_t kps = ceil_div64(ceil_div64(g0->K, s), 128) * 128;
-    const int eff = (int)ceil_div64(g0->K, kps);
-    iseg_mm::gemm_bf16_tn_pair(g0, (float*)ws0, g1, (float*)ws1, eff, kps, stream);
+    const SplitPlan p0 = plan_of(g0);      // (split_k = s in both and the same K: the two plans differ in their slab sizes only)
+    ISEG_NEED_WORKSPACE("iseg_gemm_tn_pair", ws0, ws0_bytes, p0.slab_bytes);
+    ISEG_NEED_WORKSPACE("iseg_gemm_tn_pair", ws1, ws1_bytes, plan_of(g1).slab_bytes);
+    iseg_mm::gemm_bf16_tn_pair(g0, (float*)ws0, g1, (float*)ws1, p0, stream);
     return iseg_check_launch("iseg_gemm_tn_pair");
 }
 
 // second half of a deferred split-K GEMM (args.defer_reduce = 1): slab-order sum + epilogue.  No-op when the problem is not split.
 extern "C" int iseg_gemm_reduce(const iseg_gemm_args* g, void* ws, size_t ws_bytes, hipStream_t stream) {
     ISEG_REQUIRE(g && g->D, "iseg_gemm_reduce: null argument");
-    const int nsplit = iseg_gemm_splits(g);
-    if (nsplit <= 1) return ISEG_OK;
-    const int64_t slab_rows = g->M + (g->colsum_out ? 1 : 0);
-    const size_t need = (size_t)nsplit * slab_rows * g->N * sizeof(float);
-    ISEG_NEED_WORKSPACE("iseg_gemm_reduce", ws, ws_bytes, need);
-    const int64_t kps = ceil_div64(ceil_div64(g->K, nsplit), 128) * 128;
-    const int eff_split = (int)ceil_div64(g->K, kps);
-    Epi epi{g->bias, g->colscale, g->rowscale, g->rows_per_group, g->residual, g->ldr, g->aux, g->ldaux, g->pre_out, g->ldp,
-            g->act, g->alpha, g->accumulate, g->colsum_out, g->colsum_accumulate,
-            g->batch_inner > 0 ? g->batch_inner : 1, g->sa_outer, g->sa_inner, g->sb_outer, g->sb_inner, g->sd_outer, g->sd_inner,
-            g->pre_deriv, g->b_group_rows, g->b_group_stride};
-    const int batch = g->batch > 1 ? g->batch : 1;
-    if (batch > 1) {
-        ISEG_REQUIRE(batch <= 65535, "iseg_gemm: batch %d exceeds the grid z limit (65535)", batch);
-        ISEG_REQUIRE(!g->bias && !g->colscale && !g->rowscale && !g->residual && !g->aux && !g->pre_out && !g->colsum_out &&
-                         g->act == ISEG_ACT_NONE && g->a_act == ISEG_ACT_NONE,
-                     "iseg_gemm: a batched problem takes only the alpha / accumulate epilogue");
-    }
-    return gemm_reduce(g, epi, (float*)ws, eff_split, slab_rows, stream);
+    const SplitPlan plan = plan_of(g);
+    if (plan.nsplit <= 1) return ISEG_OK;
+    ISEG_NEED_WORKSPACE("iseg_gemm_reduce", ws, ws_bytes, plan.slab_bytes);
+    if (const int st = check_batched(g)) return st;
+    return gemm_reduce(make_epi(g), g->D, g->ldd, g->out_dtype, g->M, g->N, (float*)ws, plan, stream);
 }
+

@@ -371,19 +371,19 @@ void launch_dma(const iseg_gemm_args* g, const Epi& epi, int nsplit, int64_t k_p
                        (const bf16_t*)g->B, g->ldb, (TO*)g->D, g->ldd, g->M, g->N, g->K, tiles_n, ntiles, k_per_split, slabs, epi, vecD);
 }
 
-// 1: 128 x 64 (4-deep ring)   2: 256 x 128 (8 wavefronts, 3-deep ring)   3: 128 x 128, two workgroups per CU (2 stages)
-// 4: 128 x 128, one workgroup per CU with the 3-deep ring.  (dma_form adds the 256 x 192, 128 x 192 and 64 x 192 forms.)  Measured on MI355X (tools/kbench_gemm_ref.py): 256 x 128 once it fills
-// most CUs -- it reads each B panel half as often; otherwise 128 x 128, two per CU when there are enough tiles, the deeper ring when
-// the grid is thin.
+// 1: 128 x 64 (4-deep ring)   2: 256 x 128 (8 wavefronts, 3-deep ring)   4: 128 x 128, one workgroup per CU with the 3-deep ring.
+// (dma_form adds the 256 x 192, 128 x 192 and 64 x 192 forms.)  Measured on MI355X (tools/kbench_gemm_ref.py): 256 x 128 once it fills most
+// CUs -- it reads each B panel half as often; otherwise 128 x 128 with the deeper ring, the grid being thin.
+// (3 was 128 x 128 with two stages, two workgroups per CU, for tiles128 * nsplit >= 384 below the 256 x 128 threshold.  It could not occur:
+//    tiles256 * nsplit < 192, and ceil(M / 128) <= 2 * ceil(M / 256) gives tiles128 <= 2 * tiles256,
+//    so tiles128 * nsplit <= 2 * 191 = 382 < 384.
+//  The number stays unused, like 5.)
 inline int dma_variant(const iseg_gemm_args* g, int nsplit) {
-    // Measured on the flagship step: forcing 128 x 128 tiles, two workgroups per CU (3) for the GEMMs with fused gelu / aux / residual
+    // Measured on the flagship step: forcing 128 x 128 tiles with two stages, two workgroups per CU, for the GEMMs with fused gelu / aux / residual
     // epilogues 10.66 vs 10.69 ms (equal), the deep-ring 128 x 128 (4) 11.28 ms; requesting the fused operands of four row blocks together
     // in the epilogue: equal, +44 registers.  The 13-17 us these epilogues add are VALU (gelu) and un-overlapped operand reads either way.
-    const int64_t tiles256 = ceil_div64(g->M, 256) * ceil_div64(g->N, 128), tiles128 = ceil_div64(g->M, 128) * ceil_div64(g->N, 128);
     if (g->N <= 64) return 1;
-    if (tiles256 * nsplit >= 192) return 2;
-    if (tiles128 * nsplit >= 384) return 3;
-    return 4;
+    return ceil_div64(g->M, 256) * ceil_div64(g->N, 128) * nsplit >= 192 ? 2 : 4;
 }
 
 // number of CUs of the current device (the 192-column forms fill whole rounds of them)
@@ -450,50 +450,53 @@ void launch_dma_kinds(const iseg_gemm_args* g, const Epi& epi, int nsplit, int64
 // 2 = every whole-K problem of the 256 x 128 form, 0 = never
 int dma_bk32();
 
-template <class TO>
-void dispatch_dma(const iseg_gemm_args* g, const Epi& epi, int nsplit, int64_t kps, float* slabs, hipStream_t s) {
-    switch (dma_form(g, nsplit)) {
-        case 1: launch_dma<2, 1, 4, TO>(g, epi, nsplit, kps, slabs, s); break;
-        case 2:      // 256 x 128: the flagship's stage-2 products
-            // measured (tools/kbench_pitch.py, M = 16384, one box): K = 384 with the gelu + gelu' epilogue 44.8 -> 41.2 us, with the x aux epilogue
-            // 39.7 -> 35.7; K = 1536 plain 31.8 -> 34.0, + bias + residual 35.6 -> 34.9 -- the short-K products are epilogue-bound and gain from the
-            // second resident workgroup, the long-K ones pay for twice the barriers: taken for K <= 512 (ISEG_GEMM_DMA_BK32 = 0 never, 2 always)
-            // (128 x 128 tiles with 48 KB rings, THREE workgroups per CU, measured 45.4 / 38.6 us on the two K = 384 launches: the extra fill
-            // traffic of the smaller tile costs more than the third resident workgroup returns)
-            if (dma_bk32() && (dma_bk32() == 2 || g->K <= 512) && g->K % 32 == 0 && g->K >= 96 && (kps == g->K || kps % 64 == 0) && sizeof(TO) == 2)
-                launch_dma_kinds<4, 2, 3, TO, 4, 32>(g, epi, nsplit, kps, slabs, s);
-            else launch_dma_kinds<4, 2, 3, TO, 4>(g, epi, nsplit, kps, slabs, s);
-            break;
-        case 3: launch_dma<2, 2, 2, TO>(g, epi, nsplit, kps, slabs, s); break;
-        case 6: launch_dma_kinds<4, 2, 2, TO, 6>(g, epi, nsplit, kps, slabs, s); break;      // 256 x 192: stage 3
-        case 9: launch_dma_kinds<4, 2, 3, TO, 6, 64, 1>(g, epi, nsplit, kps, slabs, s); break;      // 64 x 192, eight wavefronts of 16 x 96
-        case 8: launch_dma_kinds<4, 2, 3, TO, 6, 64, 2>(g, epi, nsplit, kps, slabs, s); break;      // 128 x 192, eight wavefronts of 32 x 96
-        default: launch_dma_kinds<2, 2, 3, TO, 4>(g, epi, nsplit, kps, slabs, s); break;
+// whether a problem of the 256 x 128 form (2) runs with the 32-deep stages.  Measured (tools/kbench_pitch.py, M = 16384, one box): K = 384 with the
+// gelu + gelu' epilogue 44.8 -> 41.2 us, with the x aux epilogue 39.7 -> 35.7; K = 1536 plain 31.8 -> 34.0, + bias + residual 35.6 -> 34.9 -- the
+// short-K products are epilogue-bound and gain from the second resident workgroup, the long-K ones pay for twice the barriers: taken for K <= 512.
+// (128 x 128 tiles with 48 KB rings, THREE workgroups per CU, measured 45.4 / 38.6 us on the two K = 384 launches: the extra fill traffic of the
+// smaller tile costs more than the third resident workgroup returns)
+inline bool dma_stage32(const iseg_gemm_args* g, int64_t kps) {
+    return dma_bk32() && (dma_bk32() == 2 || g->K <= 512) && g->K % 32 == 0 && g->K >= 96 && (kps == g->K || kps % 64 == 0);
+}
+
+// The K-step (elements per ring stage) an unsplit bf16 problem runs with: a patch-view A needs pv_seg to be a multiple of it
+inline int dma_kstep(const iseg_gemm_args* g) { return dma_form(g, 1) == 2 && dma_stage32(g, g->K) ? 32 : 64; }
+
+// The tile of each form: WM x WN wavefronts of (FM * 16) x (FN * 16) outputs, NS ring stages of BKS elements.  KINDS: bf16 outputs get one
+// instantiation per fused epilogue kind (launch_dma_kinds); the 128 x 64 form keeps the run-time epilogue.
+template <int WM_, int WN_, int NS_, int FN_ = 4, int BKS_ = 64, int FM_ = 4, bool KINDS_ = true> struct DmaTile {
+    enum { WM = WM_, WN = WN_, NS = NS_, FN = FN_, BKS = BKS_, FM = FM_, KINDS = KINDS_ };
+};
+template <class F> void with_dma_tile(int form, bool stage32, F&& f) {
+    switch (form) {
+        case 1: return f(DmaTile<2, 1, 4, 4, 64, 4, false>{});      // 128 x 64
+        case 2: return stage32 ? f(DmaTile<4, 2, 3, 4, 32>{}) : f(DmaTile<4, 2, 3>{});      // 256 x 128: the flagship's stage-2 products
+        case 6: return f(DmaTile<4, 2, 2, 6>{});                    // 256 x 192: stage 3
+        case 8: return f(DmaTile<4, 2, 3, 6, 64, 2>{});             // 128 x 192, eight wavefronts of 32 x 96
+        case 9: return f(DmaTile<4, 2, 3, 6, 64, 1>{});             // 64 x 192, eight wavefronts of 16 x 96
+        default: return f(DmaTile<2, 2, 3>{});                      // 4: 128 x 128
     }
 }
 
-// The K-step (elements per ring stage) dispatch_dma runs an unsplit bf16 problem with: a patch-view A needs pv_seg to be a multiple of it
-inline int dma_kstep(const iseg_gemm_args* g) {
-    return dma_form(g, 1) == 2 && dma_bk32() && (dma_bk32() == 2 || g->K <= 512) && g->K % 32 == 0 && g->K >= 96 ? 32 : 64;
+// form: gemm_bf16_form's answer for the problem under this split
+template <class TO>
+void dispatch_dma(int form, const iseg_gemm_args* g, const Epi& epi, int nsplit, int64_t kps, float* slabs, hipStream_t s) {
+    with_dma_tile(form, dma_stage32(g, kps) && sizeof(TO) == 2, [&](auto tile) {
+        using T = decltype(tile);
+        if constexpr (T::KINDS) launch_dma_kinds<T::WM, T::WN, T::NS, TO, T::FN, T::BKS, T::FM>(g, epi, nsplit, kps, slabs, s);
+        else launch_dma<T::WM, T::WN, T::NS, TO, T::FN, EK_ANY, T::BKS, T::FM>(g, epi, nsplit, kps, slabs, s);
+    });
 }
 
 // dispatch_dma for an unsplit bf16 product with a patch-view operand: the same tile form for the same problem (so the data gradient sums
 // in the order of the plain GEMM it replaces), the epilogue kind fixed by the caller (EK_PLAIN, or EK_BIAS for a forward pass with bias)
 template <int PV, int EK>
 void dispatch_dma_patch(const iseg_gemm_args* g, const Epi& epi, hipStream_t s) {
-    const int64_t kps = g->K;
-    switch (dma_form(g, 1)) {
-        case 1: launch_dma<2, 1, 4, bf16_t, 4, EK, 64, 4, PV>(g, epi, 1, kps, nullptr, s); break;
-        case 2:
-            if (dma_kstep(g) == 32) launch_dma<4, 2, 3, bf16_t, 4, EK, 32, 4, PV>(g, epi, 1, kps, nullptr, s);
-            else launch_dma<4, 2, 3, bf16_t, 4, EK, 64, 4, PV>(g, epi, 1, kps, nullptr, s);
-            break;
-        case 3: launch_dma<2, 2, 2, bf16_t, 4, EK, 64, 4, PV>(g, epi, 1, kps, nullptr, s); break;
-        case 6: launch_dma<4, 2, 2, bf16_t, 6, EK, 64, 4, PV>(g, epi, 1, kps, nullptr, s); break;
-        case 9: launch_dma<4, 2, 3, bf16_t, 6, EK, 64, 1, PV>(g, epi, 1, kps, nullptr, s); break;
-        case 8: launch_dma<4, 2, 3, bf16_t, 6, EK, 64, 2, PV>(g, epi, 1, kps, nullptr, s); break;
-        default: launch_dma<2, 2, 3, bf16_t, 4, EK, 64, 4, PV>(g, epi, 1, kps, nullptr, s); break;
-    }
+    with_dma_tile(dma_form(g, 1), dma_kstep(g) == 32, [&](auto tile) {
+        using T = decltype(tile);
+        launch_dma<T::WM, T::WN, T::NS, bf16_t, T::FN, EK, T::BKS, T::FM, PV>(g, epi, 1, g->K, nullptr, s);
+    });
 }
 
 }  // namespace iseg_mm
+

@@ -286,6 +286,13 @@ __global__ __launch_bounds__(512) void gemm_bf16_dma_tn_pair_kernel(TnProblem p0
 
 bool dma_tn_lds_ok();   // gemm_tn.hip: the 144-KiB dynamic-LDS limit of both tile forms was raised (once per process); false -> the register kernel keeps these problems
 
+// output tiles of a problem in form 7 (256 x 128 tiles) or 8 (128 x 256); tiles_n: how many of them lie side by side
+inline int64_t tn_tiles(const iseg_gemm_args* g, int form, int* tiles_n = nullptr) {
+    const int64_t tn = ceil_div64(g->N, form == 8 ? 256 : 128);
+    if (tiles_n) *tiles_n = (int)tn;
+    return ceil_div64(g->M, form == 8 ? 128 : 256) * tn;
+}
+
 // 0 = not eligible; 7 = 256 x 128 tiles, 8 = 128 x 256 tiles (the codes iseg_gemm_variant reports)
 inline int dma_tn_form(const iseg_gemm_args* g) {
     if (g->in_dtype != ISEG_BF16 || g->a_kcontig || g->b_kcontig || g->a_act != ISEG_ACT_NONE) return 0;
@@ -297,15 +304,13 @@ inline int dma_tn_form(const iseg_gemm_args* g) {
     // 96 x 384 55.0 -> 47.4, 384 x 96 58.0 -> 45.9, 112 x 336 29.9 -> 26.0, 112 x 448 32.9 -> 27.9, but 96 x 288 46.4 -> 51.7 and 96 x 96 23.7 -> 24.4
     if ((g->M < 128 || g->N < 128) && (g->M > g->N ? g->M : g->N) < 320) return 0;
     if (((uintptr_t)g->A % 16) || ((uintptr_t)g->B % 16) || g->lda % 8 || g->ldb % 8) return 0;
-    const int64_t t7 = ceil_div64(g->M, 256) * ceil_div64(g->N, 128), t8 = ceil_div64(g->M, 128) * ceil_div64(g->N, 256);
-    return t8 < t7 ? 8 : 7;
+    return tn_tiles(g, 8) < tn_tiles(g, 7) ? 8 : 7;
 }
 
 // K splits of an eligible problem: one resident round of workgroups (one per CU: the ring takes 144 KiB), at least 512 reduction rows each
 inline int dma_tn_split(const iseg_gemm_args* g, int form) {
     if (g->split_k > 1) return g->split_k;
-    const int64_t tiles = form == 8 ? ceil_div64(g->M, 128) * ceil_div64(g->N, 256) : ceil_div64(g->M, 256) * ceil_div64(g->N, 128);
-    int64_t want = dma_cus() / tiles;
+    int64_t want = dma_cus() / tn_tiles(g, form);
     const int64_t maxs = g->K / 512;
     if (want > maxs) want = maxs;
     return (int)(want < 2 ? 0 : want);      // 0: not worth splitting -> the register kernel's plan
@@ -340,11 +345,7 @@ void launch_dma_tn_patch(const iseg_gemm_args* g, const TnPatch& pv, int nsplit,
 inline int dma_tn_pair_split(const iseg_gemm_args* g0, const iseg_gemm_args* g1) {
     const int f0 = dma_tn_form(g0), f1 = dma_tn_form(g1);
     if (!f0 || !f1 || g0->K != g1->K) return 0;
-    auto tiles = [](const iseg_gemm_args* g, int form) {
-        return form == 8 ? ceil_div64(g->M, 128) * ceil_div64(g->N, 256) : ceil_div64(g->M, 256) * ceil_div64(g->N, 128);
-    };
-    const int64_t t = tiles(g0, f0) + tiles(g1, f1);
-    int64_t want = dma_cus() / t;
+    int64_t want = dma_cus() / (tn_tiles(g0, f0) + tn_tiles(g1, f1));
     const int64_t maxs = g0->K / 512;
     if (want > maxs) want = maxs;
     return (int)(want < 2 ? 0 : want);
@@ -362,8 +363,7 @@ inline void launch_dma_tn_pair(const iseg_gemm_args* g0, float* slabs0, const is
         p.M = g->M;
         p.N = g->N;
         p.slabs = slabs;
-        p.tiles_n = (int)ceil_div64(g->N, p.form == 8 ? 256 : 128);
-        p.ntiles = (int)ceil_div64(g->M, p.form == 8 ? 128 : 256) * p.tiles_n;
+        p.ntiles = (int)tn_tiles(g, p.form, &p.tiles_n);
         p.ones_row = g->colsum_out ? 1 : 0;
         return p;
     };

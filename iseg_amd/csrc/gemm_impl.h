@@ -12,6 +12,7 @@
 //   * accumulators -> per-wave LDS slab (fp32) -> 8-column rows -> fused epilogue -> 16-B coalesced stores.
 #pragma once
 #include "common.h"
+#include "gemm_plan.h"
 #include "iseg_hip.h"
 
 namespace iseg_mm {
@@ -592,10 +593,26 @@ void dispatch_bk(const iseg_gemm_args* g, const Epi& epi, int nsplit, int64_t kp
 }
 
 // implemented in gemm_nn.hip (A K-contig, B N-contig), gemm_nt.hip (both K-contig), gemm_tn.hip (both MN-contig)
-void gemm_bf16_nn(const iseg_gemm_args* g, const Epi& epi, int nsplit, int64_t kps, float* slabs, hipStream_t s);
-void gemm_bf16_nt(const iseg_gemm_args* g, const Epi& epi, int nsplit, int64_t kps, float* slabs, hipStream_t s);
-void gemm_bf16_tn(const iseg_gemm_args* g, const Epi& epi, int nsplit, int64_t kps, float* slabs, hipStream_t s);
+void gemm_bf16_nn(const iseg_gemm_args* g, const Epi& epi, const SplitPlan& p, float* slabs, hipStream_t s);
+void gemm_bf16_nt(const iseg_gemm_args* g, const Epi& epi, const SplitPlan& p, float* slabs, hipStream_t s);
+void gemm_bf16_tn(const iseg_gemm_args* g, const Epi& epi, const SplitPlan& p, float* slabs, hipStream_t s);
 int gemm_bf16_tn_pair_split(const iseg_gemm_args* g0, const iseg_gemm_args* g1);
-void gemm_bf16_tn_pair(const iseg_gemm_args* g0, float* slabs0, const iseg_gemm_args* g1, float* slabs1, int nsplit, int64_t kps, hipStream_t s);
+void gemm_bf16_tn_pair(const iseg_gemm_args* g0, float* slabs0, const iseg_gemm_args* g1, float* slabs1, const SplitPlan& p, hipStream_t s);
+
+// gemm.hip.  The main loop of a bf16 problem under its plan, in iseg_gemm_variant's codes (0 = the register-staged kernel above): what the NT and TN
+// launch paths branch on and what iseg_gemm_variant reports, so the query cannot disagree with the launch
+int gemm_bf16_form(const iseg_gemm_args* g, const SplitPlan& p);
+// slab-order sum of a split problem and its epilogue into D[M, N] (no slabs: nothing to do): the second half of iseg_gemm and of every split convolution
+int gemm_reduce(const Epi& epi, void* D, int64_t ldd, int out_dtype, int64_t M, int64_t N, float* slabs, const SplitPlan& p, hipStream_t stream);
+
+// the epilogue of a convolution pass: (+ bias) (+ what D held); the sites that fuse more set those fields by name
+inline Epi plain_epi(const float* bias, int accumulate) {
+    Epi e{};
+    e.bias = bias;
+    e.alpha = 1.f;
+    e.accumulate = accumulate;
+    e.batch_inner = 1;
+    return e;
+}
 
 }  // namespace iseg_mm

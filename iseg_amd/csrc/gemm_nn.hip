@@ -2,8 +2,8 @@
 #include "gemm_impl.h"
 
 namespace iseg_mm {
-void gemm_bf16_nn(const iseg_gemm_args* g, const Epi& epi, int nsplit, int64_t kps, float* slabs, hipStream_t s) {
-    if (g->out_dtype == ISEG_BF16) dispatch_bk<true, false, bf16_t>(g, epi, nsplit, kps, slabs, s);
-    else dispatch_bk<true, false, float>(g, epi, nsplit, kps, slabs, s);
+void gemm_bf16_nn(const iseg_gemm_args* g, const Epi& epi, const SplitPlan& p, float* slabs, hipStream_t s) {
+    if (g->out_dtype == ISEG_BF16) dispatch_bk<true, false, bf16_t>(g, epi, p.eff_split, p.kps, slabs, s);
+    else dispatch_bk<true, false, float>(g, epi, p.eff_split, p.kps, slabs, s);
 }
 }  // namespace iseg_mm

@@ -16,17 +16,15 @@ bool dma_tn_lds_ok() {
 }
 
 int gemm_bf16_tn_pair_split(const iseg_gemm_args* g0, const iseg_gemm_args* g1) { return dma_tn_pair_split(g0, g1); }
-void gemm_bf16_tn_pair(const iseg_gemm_args* g0, float* slabs0, const iseg_gemm_args* g1, float* slabs1, int nsplit, int64_t kps, hipStream_t s) {
-    launch_dma_tn_pair(g0, slabs0, g1, slabs1, nsplit, kps, s);
+void gemm_bf16_tn_pair(const iseg_gemm_args* g0, float* slabs0, const iseg_gemm_args* g1, float* slabs1, const SplitPlan& p, hipStream_t s) {
+    launch_dma_tn_pair(g0, slabs0, g1, slabs1, p.eff_split, p.kps, s);
 }
 
-void gemm_bf16_tn(const iseg_gemm_args* g, const Epi& epi, int nsplit, int64_t kps, float* slabs, hipStream_t s) {
-    if (slabs && nsplit > 1 && kps % 64 == 0) {
-        const int form = dma_tn_form(g);
-        if (form == 7) return launch_dma_tn<4, 2>(g, nsplit, kps, slabs, s);
-        if (form == 8) return launch_dma_tn<2, 4>(g, nsplit, kps, slabs, s);
-    }
-    if (g->out_dtype == ISEG_BF16) dispatch_bk<false, false, bf16_t>(g, epi, nsplit, kps, slabs, s);
-    else dispatch_bk<false, false, float>(g, epi, nsplit, kps, slabs, s);
+void gemm_bf16_tn(const iseg_gemm_args* g, const Epi& epi, const SplitPlan& p, float* slabs, hipStream_t s) {
+    const int form = gemm_bf16_form(g, p);
+    if (form == 7) return launch_dma_tn<4, 2>(g, p.eff_split, p.kps, slabs, s);
+    if (form == 8) return launch_dma_tn<2, 4>(g, p.eff_split, p.kps, slabs, s);
+    if (g->out_dtype == ISEG_BF16) dispatch_bk<false, false, bf16_t>(g, epi, p.eff_split, p.kps, slabs, s);
+    else dispatch_bk<false, false, float>(g, epi, p.eff_split, p.kps, slabs, s);
 }
 }  // namespace iseg_mm

@@ -118,6 +118,38 @@ class KernelTimer:
 # ---------------------------------------------------------------------------------------------------------
 # GEMM
 # ---------------------------------------------------------------------------------------------------------
+def _gemm_args(A, B, D, M, N, K, *, lda, ldb, ldd, a_kcontig, b_kcontig, **fields):
+    """the iseg_gemm argument block of D[M, N] = A x B; `fields` are further GemmArgs fields by name (pointer fields take a tensor or None)"""
+    g = GemmArgs()
+    g.A, g.lda, g.a_kcontig = ptr(A), lda, int(a_kcontig)
+    g.B, g.ldb, g.b_kcontig = ptr(B), ldb, int(b_kcontig)
+    g.D, g.ldd = ptr(D), ldd
+    g.M, g.N, g.K = M, N, K
+    g.in_dtype, g.out_dtype = dt(A), dt(D)
+    g.alpha, g.batch, g.batch_inner = 1.0, 1, 1
+    for name, v in fields.items():
+        if not hasattr(GemmArgs, name):
+            raise TypeError(f"iseg_gemm_args has no field {name}")
+        setattr(g, name, ptr(v) if isinstance(v, torch.Tensor) else v)
+    return g
+
+
+@contextlib.contextmanager
+def _timed_gemm(g, in_dtype, out_dtype, variant=None):
+    """the launch in its body -- iseg_gemm on g, or the pair launch that g leads (variant 9) -- lies between KERNEL_TIMER's events, under the shape
+    key bench.py indexes: key[13] is the main loop's variant"""
+    timer = KERNEL_TIMER[0]
+    if timer is not None:
+        L = _hip.lib()
+        if variant is None:
+            variant = int(L.iseg_gemm_variant(C.byref(g)))
+        timer.begin(("gemm", g.a_kcontig, g.b_kcontig, g.M, g.N, g.K, g.act, bool(g.pre_out), bool(g.residual), bool(g.aux), in_dtype, out_dtype,
+                     L.iseg_gemm_workspace_bytes(C.byref(g)) > 0, variant) + ((g.batch,) if g.batch > 1 else ()))
+    yield
+    if timer is not None:
+        timer.end()
+
+
 def gemm(A, B, D, M, N, K, *, lda, ldb, ldd, a_kcontig, b_kcontig, bias=None, colscale=None, rowscale=None,
          rows_per_group=0, residual=None, ldr=0, aux=None, ldaux=0, pre_out=None, ldp=0, act=ACT_NONE, alpha=1.0,
          accumulate=False, split_k=0, a_act=ACT_NONE, colsum_out=None, colsum_accumulate=False, batch=1, batch_inner=1,
@@ -127,22 +159,13 @@ def gemm(A, B, D, M, N, K, *, lda, ldb, ldd, a_kcontig, b_kcontig, bias=None, co
     _require_cuda(A, B, D)
     if A.dtype != B.dtype:
         raise TypeError(f"gemm operands differ in dtype: {A.dtype} vs {B.dtype}")
-    g = GemmArgs()
-    g.A, g.lda, g.a_kcontig = ptr(A), lda, int(a_kcontig)
-    g.B, g.ldb, g.b_kcontig = ptr(B), ldb, int(b_kcontig)
-    g.D, g.ldd = ptr(D), ldd
-    g.M, g.N, g.K = M, N, K
-    g.in_dtype, g.out_dtype = dt(A), dt(D)
-    g.bias, g.colscale, g.rowscale, g.rows_per_group = ptr(bias), ptr(colscale), ptr(rowscale), rows_per_group
-    g.residual, g.ldr = ptr(residual), ldr
-    g.aux, g.ldaux = ptr(aux), ldaux
-    g.pre_out, g.ldp = ptr(pre_out), ldp
-    g.act, g.alpha, g.accumulate, g.split_k, g.a_act = act, alpha, int(accumulate), split_k, a_act
-    g.colsum_out, g.colsum_accumulate = ptr(colsum_out), int(colsum_accumulate)
-    g.batch, g.batch_inner = int(batch), int(batch_inner)
-    g.pre_deriv = int(bool(pre_deriv))
-    g.b_group_rows, g.b_group_stride = (int(b_group[0]), int(b_group[1])) if b_group is not None else (0, 0)
-    (g.sa_outer, g.sa_inner), (g.sb_outer, g.sb_inner), (g.sd_outer, g.sd_inner) = sa, sb, sd
+    b_group_rows, b_group_stride = (int(b_group[0]), int(b_group[1])) if b_group is not None else (0, 0)
+    g = _gemm_args(A, B, D, M, N, K, lda=lda, ldb=ldb, ldd=ldd, a_kcontig=a_kcontig, b_kcontig=b_kcontig, bias=bias, colscale=colscale,
+                   rowscale=rowscale, rows_per_group=rows_per_group, residual=residual, ldr=ldr, aux=aux, ldaux=ldaux, pre_out=pre_out, ldp=ldp,
+                   act=act, alpha=alpha, accumulate=int(accumulate), split_k=split_k, a_act=a_act, colsum_out=colsum_out,
+                   colsum_accumulate=int(colsum_accumulate), batch=int(batch), batch_inner=int(batch_inner), pre_deriv=int(bool(pre_deriv)),
+                   b_group_rows=b_group_rows, b_group_stride=b_group_stride, sa_outer=sa[0], sa_inner=sa[1], sb_outer=sb[0], sb_inner=sb[1],
+                   sd_outer=sd[0], sd_inner=sd[1])
     for t in (residual, aux, pre_out):
         if t is not None and t.dtype != D.dtype:
             raise TypeError("gemm residual/aux/pre_out must have the output dtype")
@@ -153,13 +176,8 @@ def gemm(A, B, D, M, N, K, *, lda, ldb, ldd, a_kcontig, b_kcontig, bias=None, co
     need = L.iseg_gemm_workspace_bytes(C.byref(g))
     ws, wsb = workspace(need, A.device)
     g.defer_reduce = 1 if need > 0 else 0
-    timer = KERNEL_TIMER[0]
-    if timer is not None:
-        timer.begin(("gemm", int(a_kcontig), int(b_kcontig), int(M), int(N), int(K), int(act), pre_out is not None, residual is not None,
-                     aux is not None, A.dtype, D.dtype, need > 0, int(L.iseg_gemm_variant(C.byref(g)))) + ((int(batch),) if batch > 1 else ()))
-    _hip.check(L.iseg_gemm(C.byref(g), ptr(ws), wsb, stream()), "iseg_gemm")
-    if timer is not None:
-        timer.end()
+    with _timed_gemm(g, A.dtype, D.dtype):
+        _hip.check(L.iseg_gemm(C.byref(g), ptr(ws), wsb, stream()), "iseg_gemm")
     if need > 0:
         _hip.check(L.iseg_gemm_reduce(C.byref(g), ptr(ws), wsb, stream()), "iseg_gemm_reduce")
     return D
@@ -231,16 +249,8 @@ def dense_wgrad_slabs(x2d, dy2d):
     if not wgrad_can_fuse_bias(x2d) or N % 4 != 0 or x2d.dtype != torch.bfloat16:
         return None
     _require_cuda(x2d, dy2d)
-    g = GemmArgs()
     dummy = torch.empty(1, dtype=torch.float32, device=x2d.device)      # (never written: the problem stops at its slabs)
-    g.A, g.lda, g.a_kcontig = ptr(x2d), x2d.stride(0), 0
-    g.B, g.ldb, g.b_kcontig = ptr(dy2d), dy2d.stride(0), 0
-    g.D, g.ldd = ptr(dummy), N
-    g.M, g.N, g.K = K, N, M
-    g.in_dtype, g.out_dtype = dt(x2d), 0
-    g.alpha, g.accumulate = 1.0, 0
-    g.colsum_out, g.colsum_accumulate = ptr(dummy), 0
-    g.batch, g.batch_inner = 1, 1
+    g = _gemm_args(x2d, dy2d, dummy, K, N, M, lda=x2d.stride(0), ldb=dy2d.stride(0), ldd=N, a_kcontig=0, b_kcontig=0, colsum_out=dummy)
     L = _hip.lib()
     need = L.iseg_gemm_workspace_bytes(C.byref(g))
     if need == 0:
@@ -248,12 +258,8 @@ def dense_wgrad_slabs(x2d, dy2d):
     eff = int(L.iseg_gemm_slabs(C.byref(g)))
     slabs = torch.empty(need // 4, dtype=torch.float32, device=x2d.device)      # (its own buffer: the consumer's partials use the workspace)
     g.defer_reduce = 1
-    timer = KERNEL_TIMER[0]
-    if timer is not None:
-        timer.begin(("gemm", 0, 0, int(K), int(N), int(M), 0, False, False, False, x2d.dtype, torch.float32, True, int(L.iseg_gemm_variant(C.byref(g)))))
-    _hip.check(L.iseg_gemm(C.byref(g), ptr(slabs), need, stream()), "iseg_gemm")
-    if timer is not None:
-        timer.end()
+    with _timed_gemm(g, x2d.dtype, torch.float32):
+        _hip.check(L.iseg_gemm(C.byref(g), ptr(slabs), need, stream()), "iseg_gemm")
     return slabs, int(eff)
 
 
@@ -269,17 +275,8 @@ def dense_wgrad_pair(g2d, dbr2d, x2d, dh2d, dW1, db1, accumulate=True, defer_sec
     dummy = torch.empty(1, dtype=torch.float32, device=g2d.device)
 
     def args(a, b, out, ldd, bias, acc):
-        g = GemmArgs()
-        g.A, g.lda, g.a_kcontig = ptr(a), a.stride(0), 0
-        g.B, g.ldb, g.b_kcontig = ptr(b), b.stride(0), 0
-        g.D, g.ldd = ptr(out), ldd
-        g.M, g.N, g.K = a.shape[1], b.shape[1], rows
-        g.in_dtype, g.out_dtype = dt(a), 0
-        g.alpha, g.accumulate = 1.0, int(acc)
-        g.colsum_out, g.colsum_accumulate = ptr(bias), int(acc)
-        g.batch, g.batch_inner = 1, 1
-        g.defer_reduce = 1
-        return g
+        return _gemm_args(a, b, out, a.shape[1], b.shape[1], rows, lda=a.stride(0), ldb=b.stride(0), ldd=ldd, a_kcontig=0, b_kcontig=0,
+                          accumulate=int(acc), colsum_out=bias, colsum_accumulate=int(acc), defer_reduce=1)
 
     g0 = args(g2d, dbr2d, dummy, Cc, dummy, False)
     g1 = args(x2d, dh2d, dW1, dW1.stride(0), db1, accumulate)
@@ -301,13 +298,9 @@ def dense_wgrad_pair(g2d, dbr2d, x2d, dh2d, dW1, db1, accumulate=True, defer_sec
         wsb1 = need1
     else:
         ws1, wsb1 = workspace(need1, g2d.device)
-    timer = KERNEL_TIMER[0]
-    if timer is not None:
-        # (variant 9 = the pair launch: bench.py models it as two products [4C, C] and [C, 4C] over `rows`)
-        timer.begin(("gemm", 0, 0, int(K4), int(Cc), int(rows), 0, False, False, False, g2d.dtype, torch.float32, True, 9))
-    _hip.check(L.iseg_gemm_tn_pair(C.byref(g0), ptr(slabs0), need0, C.byref(g1), ptr(ws1), wsb1, stream()), "iseg_gemm_tn_pair")
-    if timer is not None:
-        timer.end()
+    # (variant 9 = the pair launch: bench.py models it as two products [4C, C] and [C, 4C] over `rows`)
+    with _timed_gemm(g0, g2d.dtype, torch.float32, variant=9):
+        _hip.check(L.iseg_gemm_tn_pair(C.byref(g0), ptr(slabs0), need0, C.byref(g1), ptr(ws1), wsb1, stream()), "iseg_gemm_tn_pair")
     if defer_second:
         eff1 = int(L.iseg_gemm_slabs(C.byref(g1)))
         return slabs0, eff, (ws1, eff1, n2, dW1, db1, n0, bool(accumulate))

@@ -621,7 +621,7 @@ def test_argmax_confusion_first_max_and_ignore(cuda):
 
 @pytest.mark.parametrize("M,N,Kd,split", [(300, 64, 256, 0),        # 128 x 64 tile, 4-deep ring, ragged M
                                          (1000, 136, 128, 0),      # 128 x 128 thin grid (3-deep ring), ragged M and N % 128 != 0
-                                         (7000, 384, 192, 0),      # 128 x 128, two workgroups per CU (2 stages)
+                                         (7000, 384, 192, 0),      # 128 x 128 again, whole tiles along N
                                          (16384, 512, 128, 0),     # 256 x 128 tile
                                          (25000, 264, 320, 0),     # 256 x 128, ragged both ways
                                          (640, 128, 2048, 4)])     # split-K slabs from the DMA kernel
@@ -682,7 +682,7 @@ def test_gemm_dma_pipeline_k_tail(cuda, M, N, Kd, split):
     g.M, g.N, g.K, g.in_dtype, g.out_dtype, g.batch, g.batch_inner, g.split_k = M, N, Kd, 1, 1, 1, 1, split
     out = torch.empty((M, N), dtype=dt, device="cuda")
     g.D, g.ldd = out.data_ptr(), N
-    assert int(_hip.lib().iseg_gemm_variant(Ct.byref(g))) in (1, 2, 3, 4, 6), "the problem did not plan onto the LDS-DMA kernel"
+    assert int(_hip.lib().iseg_gemm_variant(Ct.byref(g))) in (1, 2, 4, 6), "the problem did not plan onto the LDS-DMA kernel"
     k.gemm(abuf, bbuf, out, M, N, Kd, lda=lda, ldb=ldb, ldd=N, a_kcontig=1, b_kcontig=1, split_k=split)
     close(out, ar @ br.T, dt, "plain")
     bias = rnd((N,), 3).float()
