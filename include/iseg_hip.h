@@ -598,6 +598,29 @@ int iseg_sod_fmv2(const void* pred, int pred_is_u8, const uint8_t* gt, int norma
                   double* per_image_out, void* ws, size_t ws_bytes, iseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * ops/ccl.py: label_components (:28-36) -- connected-components labelling, N images per call, each on its own (tf.map_fn over the batch, :30-34).
+ *   mask   [N,H,W]  int32 (mask_is_u8 = 0) or one byte per pixel (mask_is_u8 = 1: uint8 / bool).  ANY non-zero value is foreground.  The
+ *                   reference takes int32 in {0,1} only and hands every other value back negated (-binary_img is compared with -1 alone,
+ *                   :52, :80), which is no labelling and is not reproduced.
+ *   labels [N,H,W]  0 on the background; on the foreground the number of the pixel's 4-connected component: neighbours up, left, right, down
+ *                   (NEIGHBORS_COORDS :11-16), a neighbour outside the image does not count (:188-201), so rows do not wrap and images never
+ *                   share a component.  Components are numbered 1, 2, 3, ... in the raster order of their first pixel (find_components :75-92:
+ *                   the loop over i = row * width + col, label += 1 at every pixel still unlabelled, then the flood fill search :117-160).
+ *                   The reduce_sum <= 1 shortcut (:48-54) returns the input, which is the labelling of such an image: no special case.
+ *   counts [N]      components per image = the largest label of the image (0 for an empty one)
+ *   row_base [N,H]  scratch, undefined on return
+ * labels doubles as the parent array of a union-find that links the larger root under the smaller one, so a component's root is its first
+ * raster pixel and its number is 1 + the count of roots with a smaller index; mask and labels therefore cannot be the same buffer.  There is
+ * no opaque workspace and no workspace function: all memory is these three typed, shape-sized buffers.  Six launches (tile-local union-find in
+ * LDS, tile seams, flatten + root count per row, per-image scan, in-row rank, finalise), integer atomics only, no floating point, exact
+ * grids, no wait on another workgroup; no host read, no host-to-device copy, no allocation: the call captures into a graph.  The result is
+ * a function of the mask alone (bit-reproducible).  Errors: a null pointer, N outside 1..65535, H or W outside 1..16384 (H * W + 1 has to
+ * fit an int32), mask == labels.
+ * --------------------------------------------------------------------------------------------------------- */
+int iseg_ccl_label(const void* mask, int mask_is_u8, int N, int H, int W, int32_t* labels, int32_t* counts, int32_t* row_base,
+                   iseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * optimizers/modern/adamw.py:13-74, optimizers/modern/sgd.py:12-51 over the flat parameter buffer.
  * Every tensor is padded to a multiple of 256 elements; seg_of_block[b] = tensor index of 256-element block b
  * (-1 = padding).  hp (device): [lr, sqrt(1-b2^t)/(1-b1^t), grad_scale, clipvalue(<=0 off)].

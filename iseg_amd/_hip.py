@@ -241,6 +241,7 @@ SIGNATURES = {
     "iseg_sod_fmv2_workspace_bytes": (_z, [_i, _i, _i, _i]),
     "iseg_sod_fmv2": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), _p, _p, _p, _p, _p, _z,
                            _p]),
+    "iseg_ccl_label": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p]),
     "iseg_argmax_confusion": (_i, [_p, _p, _l, _i, _i, _p, _p, _p]),
     "iseg_grad_sqnorm": (_i, [_p, _p, _p, _p, _p, _p, _i, _p, _p, _p, _l, _i, _p]),
     "iseg_adamw_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _f, _f, _f, _p, _f, _p, _f, _l, _p]),

@@ -1387,6 +1387,32 @@ def sod_fmv2(pred, gt, handlers, *, normalize=False, state=None, count=None, wan
     return ints, per
 
 
+def ccl_label(mask, *, labels=None, counts=None):
+    """connected-components labelling of ops/ccl.py (csrc/ccl.hip): mask [N,H,W] (or [H,W]: one image) int32 / uint8 / bool, any non-zero value
+    foreground.  returns (labels int32 like mask: 0 background, components 1, 2, ... in the raster order of their first pixel, 4-connected;
+    counts [N] int32: components per image)"""
+    if mask.dtype not in (torch.int32, torch.uint8, torch.bool):
+        raise TypeError(f"ccl_label: mask is int32, uint8 or bool, got {mask.dtype}")
+    if mask.dim() not in (2, 3):
+        raise ValueError(f"ccl_label: mask is [N,H,W] or [H,W], got {tuple(mask.shape)}")
+    _require_cuda(mask, labels, counts)
+    if not mask.is_contiguous():
+        raise ValueError("ccl_label: contiguous tensors only")
+    N, H, W = (1,) + tuple(mask.shape) if mask.dim() == 2 else tuple(mask.shape)
+    dev = mask.device
+    if labels is None:
+        labels = torch.empty(mask.shape, dtype=torch.int32, device=dev)
+    elif labels.dtype != torch.int32 or labels.shape != mask.shape or not labels.is_contiguous():
+        raise ValueError("ccl_label: labels is a contiguous int32 tensor of the mask's shape")
+    if counts is None:
+        counts = torch.empty(N, dtype=torch.int32, device=dev)
+    elif counts.dtype != torch.int32 or counts.numel() != N or not counts.is_contiguous():
+        raise ValueError(f"ccl_label: counts is a contiguous int32 [{N}]")
+    row_base = torch.empty(N, H, dtype=torch.int32, device=dev)
+    _hip.call("iseg_ccl_label", ptr(mask), int(mask.dtype != torch.int32), N, H, W, ptr(labels), ptr(counts), ptr(row_base), stream())
+    return labels, counts
+
+
 def upsample_ce_supported(Hi, Wi, Ho, Wo, Cc):
     return bool(_hip.lib().iseg_upsample_ce_supported(int(Hi), int(Wi), int(Ho), int(Wo), int(Cc)))
 
