@@ -505,6 +505,39 @@ int iseg_argmax_confusion(const float* logits, const int32_t* labels, int64_t P,
                           unsigned long long* cm, iseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * losses/ohem.py:11-39 ohem_selector -- online hard example mining on the per-position loss vector, restated literally (the file carries a
+ * "WIP" comment, yet core_model.py:480-514 hands get_ohem_fn(thresh) to the main output's cross-entropy as post_compute_fn).
+ *
+ * iseg_ohem_label_prob: prob [P] = max_c softmax(logits_p)_c * onehot_pc (:18-20) = the labelled class's probability, exactly 0 on a zero row.
+ *   The label-to-row rule is the one of iseg_softmax_ce_ignore (ignore_label == 0 shifts the labels down by one; a class outside [0, C) is
+ *   the zero row), so prob and loss agree on the zero rows.  fp32, max-subtracted, one pass, rows staged through LDS as in the loss kernel.
+ *
+ * iseg_ohem_select: values [P], loss [P] (may be values), min_kept_total = min_kept * batch_size.
+ *   values_are_loss = 0 (thresh given, values = prob, :17-33):  nnz = #{values != 0};  k = min(min_kept_total, nnz - 1);
+ *        min_threshold = sort(values, DESCENDING)[k], or 0 when nnz == 0;  threshold = max(min_threshold, thresh);  keep = values < threshold
+ *   values_are_loss = 1 (thresh None, values = loss, :34-37):   threshold = sort(values, DESCENDING)[min_kept_total];  keep = values > threshold
+ *   keep [P]            1.0f / 0.0f, both compares strict: the grad_px of iseg_softmax_ce_ignore (the threshold is not differentiated)
+ *   loss_out [P]        (optional, may be loss) keep ? loss : 0
+ *   masked_sum [1]      (optional) sum_scale * sum_p loss_out_p, two stages in a fixed order
+ *   threshold_out [1], nnz_out [1]   the threshold compared against and the count of non-zero values
+ *   state [ISEG_OHEM_STATE_INTS] int32 and partials [ISEG_OHEM_PARTIAL_FLOATS] fp32 (needed with masked_sum) are scratch of fixed,
+ *   shape-independent size, zeroed by the call on its stream, undefined on return.  There is no opaque workspace and no workspace function.
+ * The k-th largest value comes from a most-significant-digit radix select instead of the reference's full sort: four 8-bit passes over the
+ * order-preserving unsigned image of the float bits (any finite value, either sign), per-workgroup LDS histograms flushed with integer
+ * atomics, a one-workgroup launch between passes that picks the digit and carries the remaining rank, which lives on the device.  Every
+ * dependency between workgroups is a launch boundary; no floating-point atomics; no host read, no host-to-device copy, no allocation: the
+ * call captures into a graph and is bit-reproducible.  Non-finite values are binned like any other bit pattern.  Errors: a null required
+ * pointer, P outside 1..2^31-1 (int32 counters), C outside 1..256, keep aliasing values / loss / loss_out, min_kept_total < 0, and with
+ * values_are_loss an index min_kept_total >= P.
+ * --------------------------------------------------------------------------------------------------------- */
+#define ISEG_OHEM_STATE_INTS 1032
+#define ISEG_OHEM_PARTIAL_FLOATS 1024
+int iseg_ohem_label_prob(const float* logits, const int32_t* labels, int64_t P, int C, int ignore_label, float* prob, iseg_stream_t stream);
+int iseg_ohem_select(const float* values, const float* loss, int64_t P, int64_t min_kept_total, float thresh, int values_are_loss, float* keep,
+                     float* loss_out, float* masked_sum, float sum_scale, float* threshold_out, int32_t* nnz_out, int32_t* state,
+                     float* partials, iseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * losses/mask_loss.py:10-201 MaskLoss (+ dice(), :159-200) on losses/seg_loss_base.py:12-95 SegLossBase: per-class sigmoid (focal) loss,
  * per-image dice loss and softmax cross-entropy, the ignore label carried as a Keras loss mask (a mean over VALID pixels).
  * logits [B, HW, C] fp32, labels [B, HW] int32 (already at the logits' size), C <= 256.  flags = ISEG_MASKLOSS_* ; at least one term.

@@ -234,6 +234,8 @@ SIGNATURES = {
     "iseg_softmax_ce_ignore": (_i, [_p, _p, _p, _l, _i, _i, _p, _p, _f, _p, _f, _p, _p, _z, _p]),
     "iseg_softmax_ce_confusion": (_i, [_p, _p, _p, _l, _i, _i, _p, _p, _f, _p, _f, _p, _p, _p, _z, _p]),
     "iseg_softmax_focal_ce_ignore": (_i, [_p, _p, _p, _l, _i, _i, _f, _f, _p, _p, _f, _p, _f, _p, _p, _z, _p]),
+    "iseg_ohem_label_prob": (_i, [_p, _p, _l, _i, _i, _p, _p]),
+    "iseg_ohem_select": (_i, [_p, _p, _l, _l, _f, _i, _p, _p, _p, _f, _p, _p, _p, _p, _p]),
     "iseg_mask_loss_workspace_bytes": (_z, [_i, _l, _i]),
     "iseg_mask_loss": (_i, [_p, _p, _i, _l, _i, _i, _i, _f, _f, _f, _p, _p, _f, _p, _f, _p, _p, _z, _p]),
     "iseg_sod_metrics_workspace_bytes": (_z, [_i, _i, _i, _i]),

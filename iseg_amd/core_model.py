@@ -7,6 +7,7 @@ from . import functional as F
 from .core_inference import inference_fn
 from .utils.common import get_scaled_size, resize_image
 from .losses.catecrossentropy_ignore_label import catecrossentropy_ignore_label_loss
+from .losses.ohem import get_ohem_fn
 from .metrics.utils import SegMetricBuilder
 from .nn import Layer
 
@@ -117,8 +118,6 @@ class SegFoundation(SegBase):
         self.focal_loss_gamma = focal_loss_gamma
         self.focal_loss_alpha = focal_loss_alpha
         self.model_class_weights = class_weights
-        if use_ohem:
-            raise NotImplementedError("OHEM is marked 'WIP DO NOT USE' in the reference (losses/ohem.py:6) and is out of scope")
 
     def inputs_process(self, image, label):
         is_label_collection = isinstance(label, (list, tuple, dict))
@@ -171,7 +170,9 @@ class SegFoundation(SegBase):
         if self.custom_main_loss_fn is not None:
             loss_dict = {self._index_to_output_key(0): self.custom_main_loss_fn(**common_kwargs, **kwargs)}
         else:
-            loss_dict = {self._index_to_output_key(0): default_ce_loss(None)}
+            # core_model.py:480-514 of the reference: OHEM on the main output only, auxiliary outputs stay plain
+            ohem_func = get_ohem_fn(thresh=self.ohem_thresh) if self.use_ohem else None
+            loss_dict = {self._index_to_output_key(0): default_ce_loss(ohem_func)}
         if self.custom_aux_loss_fns is None or len(self.custom_aux_loss_fns) == 0:
             for i in range(self.num_aux_loss):
                 loss_dict[self._index_to_output_key(i + 1)] = default_ce_loss(None)

@@ -10,17 +10,10 @@
 // pixel (row stride C words; conflict-free for odd C such as 21), writes its gradient row back into the same
 // LDS slab, and the block streams it out coalesced again.
 #include "common.h"
+#include "ce_rows.h"
 #include "iseg_hip.h"
 
 namespace {
-
-static inline int pixels_per_block(int C) {
-    int pix = (48 * 1024) / (4 * C);
-    pix = (pix / 64) * 64;
-    if (pix > 256) pix = 256;
-    if (pix < 64) pix = 64;
-    return pix;
-}
 
 __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict__ logits, const int32_t* __restrict__ labels,
                                                          const float* __restrict__ class_w, int64_t P, int C, int ignore,
@@ -40,22 +33,14 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict
         const int64_t p0 = tl * pix;
         const int npx = (int)((P - p0 < pix) ? (P - p0) : pix);
         const int64_t nel = (int64_t)npx * C;
-        const float* src = logits + p0 * C;
-        const bool vec = ((p0 * C) % 4 == 0) && (nel % 4 == 0);
-        if (vec) {
-            for (int i = threadIdx.x; i < nel / 4; i += 256)
-                reinterpret_cast<float4*>(tile)[i] = reinterpret_cast<const float4*>(src)[i];
-        } else {
-            for (int i = threadIdx.x; i < nel; i += 256) tile[i] = src[i];
-        }
+        const bool vec = stage_rows(tile, logits + p0 * C, p0 * C, nel);
         __syncthreads();
         float my_loss = 0.f;
         if ((int)threadIdx.x < npx) {
             float* z = tile + threadIdx.x * C;
             int y = labels[p0 + threadIdx.x];
             const bool keep = y != ignore;
-            if (ignore == 0) y -= 1;
-            const bool in_range = y >= 0 && y < C;
+            const bool in_range = label_class(y, ignore, C);
             float w = keep ? 1.f : 0.f;
             if (class_w) w *= in_range ? class_w[y] : 0.f;
             float mx = z[0];
@@ -164,15 +149,8 @@ __global__ __launch_bounds__(256) void argmax_confusion_kernel(const float* __re
         const int64_t p0 = tl * pix;
         const int npx = (int)((P - p0 < pix) ? (P - p0) : pix);
         const int64_t nel = (int64_t)npx * C;
-        const float* src = logits + p0 * C;
-        const bool vec = ((p0 * C) % 4 == 0) && (nel % 4 == 0);
         __syncthreads();  // previous tile fully consumed (and hist zeroed on the first pass)
-        if (vec) {
-            for (int i = threadIdx.x; i < nel / 4; i += 256)
-                reinterpret_cast<float4*>(tile)[i] = reinterpret_cast<const float4*>(src)[i];
-        } else {
-            for (int i = threadIdx.x; i < nel; i += 256) tile[i] = src[i];
-        }
+        stage_rows(tile, logits + p0 * C, p0 * C, nel);
         __syncthreads();
         if ((int)threadIdx.x < npx) {
             const float* z = tile + threadIdx.x * C;

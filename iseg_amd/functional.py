@@ -1890,6 +1890,98 @@ def softmax_ce_per_pixel(logits, labels, num_class, ignore_label, class_w=None, 
 
 
 # ---------------------------------------------------------------------------------------------------------
+# online hard example mining on the per-position loss          losses/ohem.py:11-39
+# ---------------------------------------------------------------------------------------------------------
+def _ohem_rows(logits, labels, num_class):
+    z = _c(logits).reshape(-1, num_class)
+    if z.dtype != torch.float32:
+        z = K.cast(z, torch.float32)
+    y = _c(labels).reshape(-1)
+    if y.dtype != torch.int32:
+        y = y.to(torch.int32)
+    return z, y
+
+
+def _ohem_check_index(min_kept_total, thresh, P):
+    # sorted_loss[batch_min_kept] (:35-36) past the end is an error in the reference as well; refuse it before anything is launched
+    if thresh is None and not 0 <= int(min_kept_total) < P:
+        raise ValueError(f"ohem: index min_kept * batch_size = {int(min_kept_total)} of {P} sorted losses")
+
+
+class _OhemSelectFn(Function):
+    """loss [P] -> loss * keep.  The threshold only enters comparisons (tf.where on seg_prob < threshold, :33, or loss > threshold, :37), so the
+    upstream gradient passes on kept positions and nothing reaches the logits through the probabilities"""
+
+    @staticmethod
+    def forward(ctx, loss, logits, labels, num_class, ignore_label, min_kept_total, thresh):
+        lv = _c(loss).reshape(-1)
+        if lv.dtype != torch.float32:
+            lv = K.cast(lv, torch.float32)
+        values = lv
+        if thresh is not None:
+            z, y = _ohem_rows(logits, labels, num_class)
+            values = K.ohem_label_prob(z, y, ignore_label)
+        keep, out, _, _, _ = K.ohem_select(values, lv, min_kept_total, thresh, want_loss=True)
+        ctx.in_dtype, ctx.in_shape = loss.dtype, loss.shape
+        ctx.save_for_backward(keep)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        (keep,) = ctx.saved_tensors
+        g = _c(dout).reshape(-1, 1)
+        if g.dtype != torch.float32:
+            g = K.cast(g, torch.float32)
+        dl = K.scale_rows(g, keep)
+        if dl.dtype != ctx.in_dtype:
+            dl = K.cast(dl, ctx.in_dtype)
+        return dl.reshape(ctx.in_shape), None, None, None, None, None, None
+
+
+def ohem_select_per_pixel(loss, logits, labels, num_class, ignore_label, min_kept_total, thresh):
+    """ohem_selector on the flattened loss [N*H*W]: labels are the integer labels under the rule of softmax_ce_per_pixel (ignore_label == 0
+    shifts them, a class outside [0, num_class) is a zero row); thresh None selects on the loss itself and reads neither logits nor labels"""
+    _ohem_check_index(min_kept_total, thresh, loss.numel())
+    return _OhemSelectFn.apply(loss, logits, labels, int(num_class), int(ignore_label), int(min_kept_total), thresh)
+
+
+class _OhemCEMeanFn(Function):
+    """mean over ALL positions of the OHEM-selected loss and d(mean)/d(logits): per-position loss, probabilities, selection with the
+    masked sum, then the loss kernel again with grad_px = keep -- nothing is read back"""
+
+    @staticmethod
+    def forward(ctx, logits, labels, num_class, ignore_label, class_w, weight, focal, cm, min_kept_total, thresh):
+        z, y = _ohem_rows(logits, labels, num_class)
+        P = z.shape[0]
+        px, _, _ = K.softmax_ce_ignore(z, y, ignore_label, class_w=class_w, want_px=True, focal=focal, cm=cm)
+        values = px if thresh is None else K.ohem_label_prob(z, y, ignore_label)
+        keep, _, s, _, _ = K.ohem_select(values, px, min_kept_total, thresh, want_sum=True, sum_scale=weight / P)
+        dz = None
+        if ctx.needs_input_grad[0]:
+            _, _, dz = K.softmax_ce_ignore(z, y, ignore_label, class_w=class_w, want_px=False, want_grad=True, grad_scale=weight / P,
+                                           grad_px=keep, focal=focal)
+        ctx.shape, ctx.in_dtype = logits.shape, logits.dtype
+        ctx.save_for_backward(dz)
+        return s.reshape(())
+
+    @staticmethod
+    def backward(ctx, dloss):
+        (dz,) = ctx.saved_tensors
+        if not _UNIT_LOSS_GRAD[0]:      # (see _SoftmaxCEMeanFn.backward)
+            dz = K.scale_dev(dz, _c(dloss).reshape(1).to(torch.float32))
+        if dz.dtype != ctx.in_dtype:
+            dz = K.cast(dz, ctx.in_dtype)
+        return dz.reshape(ctx.shape), None, None, None, None, None, None, None, None, None
+
+
+def ohem_softmax_ce_mean(logits, labels, num_class, ignore_label, min_kept_total, thresh, class_w=None, weight=1.0, focal=None, cm=None):
+    """softmax_ce_mean with the OHEM selection between the loss and its mean; the mean stays over ALL positions (Keras averages the
+    Reduction.NONE vector, zeros included); cm as there (plain cross-entropy only)"""
+    _ohem_check_index(min_kept_total, thresh, logits.numel() // int(num_class))
+    return _OhemCEMeanFn.apply(logits, labels, int(num_class), int(ignore_label), class_w, float(weight), focal, cm, int(min_kept_total), thresh)
+
+
+# ---------------------------------------------------------------------------------------------------------
 # MaskLoss: sigmoid (focal) + dice + cross-entropy under the ignore-label mask          losses/mask_loss.py:10-201
 # ---------------------------------------------------------------------------------------------------------
 def _mask_loss_inputs(logits, labels):

@@ -1295,6 +1295,51 @@ def softmax_ce_ignore(logits2d, labels1d, ignore_label, *, class_w=None, want_px
     return loss_px, loss_sum, dlogits
 
 
+OHEM_STATE_INTS, OHEM_PARTIAL_FLOATS = 1032, 1024      # ISEG_OHEM_STATE_INTS, ISEG_OHEM_PARTIAL_FLOATS of include/iseg_hip.h
+
+
+def ohem_label_prob(logits2d, labels1d, ignore_label, *, prob=None):
+    """losses/ohem.py:18-20 (csrc/ohem.hip): prob [P] fp32 = softmax probability of the labelled class, exactly 0 on a zero row; labels follow
+    the rule of softmax_ce_ignore (ignore_label == 0 shifts them down by one, a class outside [0, C) is the zero row)"""
+    _require_cuda(logits2d, labels1d, prob)
+    if logits2d.dtype != torch.float32 or labels1d.dtype != torch.int32:
+        raise TypeError(f"ohem_label_prob: float32 logits and int32 labels, got {logits2d.dtype} and {labels1d.dtype}")
+    P, Cc = logits2d.shape
+    if labels1d.numel() != P or not (logits2d.is_contiguous() and labels1d.is_contiguous()):
+        raise ValueError(f"ohem_label_prob: contiguous logits [P,C] and labels [P], got {tuple(logits2d.shape)} and {tuple(labels1d.shape)}")
+    if prob is None:
+        prob = torch.empty(P, dtype=torch.float32, device=logits2d.device)
+    elif prob.dtype != torch.float32 or prob.numel() != P or not prob.is_contiguous():
+        raise ValueError(f"ohem_label_prob: prob is a contiguous float32 [{P}]")
+    _hip.call("iseg_ohem_label_prob", ptr(logits2d), ptr(labels1d), P, Cc, int(ignore_label), ptr(prob), stream())
+    return prob
+
+
+def ohem_select(values, loss, min_kept_total, thresh, *, want_loss=False, want_sum=False, sum_scale=1.0):
+    """losses/ohem.py:22-37 (csrc/ohem.hip): thresh a float -> values is the labelled-class probability, keep = values < max(k-th largest, thresh)
+    with k = min(min_kept_total, nnz - 1); thresh None -> values is the loss, keep = values > (min_kept_total-th largest).  loss [P] may be values.
+    returns (keep [P] fp32 0/1, loss_out [P] | None, masked_sum [1] = sum_scale * sum(keep * loss) | None, threshold [1], nnz [1] int32);
+    nothing is read back"""
+    _require_cuda(values, loss)
+    for name, t in (("values", values), ("loss", loss)):
+        if t is not None and (t.dtype != torch.float32 or t.dim() != 1 or not t.is_contiguous() or t.numel() != values.numel()):
+            raise ValueError(f"ohem_select: {name} is a contiguous float32 [P]")
+    P = values.numel()
+    if thresh is None and not 0 <= int(min_kept_total) < P:
+        raise ValueError(f"ohem_select: index {int(min_kept_total)} of {P} sorted losses (min_kept * batch_size must be less than N*H*W)")
+    dev = values.device
+    keep = torch.empty(P, dtype=torch.float32, device=dev)
+    loss_out = torch.empty(P, dtype=torch.float32, device=dev) if want_loss else None
+    masked_sum = torch.empty(1, dtype=torch.float32, device=dev) if want_sum else None
+    threshold = torch.empty(1, dtype=torch.float32, device=dev)
+    nnz = torch.empty(1, dtype=torch.int32, device=dev)
+    state = torch.empty(OHEM_STATE_INTS, dtype=torch.int32, device=dev)
+    partials = torch.empty(OHEM_PARTIAL_FLOATS, dtype=torch.float32, device=dev) if want_sum else None
+    _hip.call("iseg_ohem_select", ptr(values), ptr(loss), P, int(min_kept_total), 0.0 if thresh is None else float(thresh), int(thresh is None),
+              ptr(keep), ptr(loss_out), ptr(masked_sum), float(sum_scale), ptr(threshold), ptr(nnz), ptr(state), ptr(partials), stream())
+    return keep, loss_out, masked_sum, threshold, nnz
+
+
 MASKLOSS_SIGMOID, MASKLOSS_DICE, MASKLOSS_CE, MASKLOSS_FOCAL_SIGMOID, MASKLOSS_FOCAL_CE, MASKLOSS_CLASS_BALANCING = 1, 2, 4, 8, 16, 32
 
 
