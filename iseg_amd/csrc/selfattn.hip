@@ -1,10 +1,9 @@
 // Single-head attention core of the non-local block (layers/self_attention.py:65-93 with get_attention of
 // utils/attention_utils.py:23-40): O = softmax(scale * Q K^T) V for a 64-wide query / key and a WIDE value (dv = 64 .. 1024 in
 // steps of 64), bf16, any T, every operand with its own row pitch (column ranges of one packed projection output or separate
-// tensors; q and k may be one pointer).  The formulation is the one of flashattn.hip -- S^T = K Q^T on v_mfma_f32_16x16x32_bf16,
-// each lane owns one query column, P stays in registers as the B operand of O^T = V^T P^T, online softmax over key tiles of 64 --
-// generalised over value slabs of 64 columns: a work item is (sample, 64-query tile, value slab) and owns one wavefront with the
-// register budget and LDS image of the equal-width kernel; each slab recomputes S^T.  Nothing of size T x T is ever stored.
+// tensors; q and k may be one pointer).  The tile bodies are those of attn_tile.h, run over value slabs of 64 columns: a forward
+// work item is (sample, 64-query tile, value slab) and owns one wavefront with the register budget and LDS image of the
+// equal-width kernel; each slab recomputes S^T.  Nothing of size T x T is ever stored.
 //
 // Training: the forward also returns L[i] = log2 sum_j exp2(c * s_ij) (c = scale * log2 e), written by slab 0; the backward pass
 // recomputes p = exp2(c * s - L) tile by tile.  With D[i] = sum over ALL dv columns of dO[i][.] * O[i][.]:
@@ -14,60 +13,19 @@
 //   * self_attn_dv_kernel     -- (sample, key tile, value slab) walks the query rows 32 at a time: S = Q K^T, dV^T += dO^T P;
 //   * self_attn_dq_kernel     -- (sample, query tile) walks the key tiles in the forward's transposed orientation;
 //   * self_attn_dk_kernel     -- (sample, key tile) walks the query rows 32 at a time in the natural orientation.
-// The dO / V fragments of the full-width dP product do not fit in registers next to the accumulators at dv = 512; they are re-read
-// per tile (16 B per lane, straight into MFMA operand layout) and served by L2.
-// Rows >= T are never read (zero fragments) and never stored; key columns >= T of a ragged last tile get probability exactly 0.
-#include "common.h"
+// The dO / V fragments of the full-width dP product are streamed (attn_tile.h).  Any positive finite scale is accepted, so nothing
+// here leans on an exp2 underflow: key columns >= T of a ragged last tile get probability exactly 0, and the key-owning kernels
+// switch rows and keys past T off explicitly.
+#include "attn_tile.h"
 #include "iseg_hip.h"
 
-#include <float.h>
 #include <limits.h>
 
 namespace {
 
-typedef __attribute__((address_space(3))) bf16x4* lds_bf16x4_ptr;
+using namespace attn;
 
-constexpr int SD = 64;         // query / key width, and the width of one value slab
-constexpr int SQ = 64;         // query rows per wavefront (forward, dQ)
-constexpr int SK = 64;         // keys per tile
-constexpr int SI = 32;         // query rows per inner step of the key-owning kernels (one MFMA k-step)
-constexpr int SSTRIDE = 72;    // LDS image row stride (bf16): 144-B rows
 constexpr int SDV_MAX = 1024;
-
-__device__ __forceinline__ bf16x8 zero8() {
-    bf16x8 v;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = (bf16_t)0.f;
-    return v;
-}
-// MFMA A / B operand fragment straight from global memory: row `row` (zeros past T), columns col0 + 8 * (lane / 16) .. + 7
-__device__ __forceinline__ bf16x8 gfrag(const bf16_t* __restrict__ base, int64_t ld, int row, int T, int col0, int lane) {
-    if (row >= T) return zero8();
-    return *reinterpret_cast<const bf16x8*>(base + (int64_t)row * ld + col0 + 8 * (lane >> 4));
-}
-// staging chunk of a 64-column tile row (zeros past T)
-__device__ __forceinline__ bf16x8 grow8(const bf16_t* __restrict__ base, int64_t ld, int row, int T, int col) {
-    if (row >= T) return zero8();
-    return *reinterpret_cast<const bf16x8*>(base + (int64_t)row * ld + col);
-}
-// transposed fragment (A operand) for columns c0 .. c0+15 of an LDS image [row][col]: this lane's eight k slots are the rows
-// rowA + 4g + 0..3 and rowB + 4g + 0..3 -- the same row set its accumulators of the preceding product hold
-__device__ __forceinline__ bf16x8 ltfrag(const bf16_t* lds, int rowA, int rowB, int c0, int lane) {
-    const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(lds + (rowA + 4 * g + q) * SSTRIDE + c0 + 4 * p));
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(lds + (rowB + 4 * g + q) * SSTRIDE + c0 + 4 * p));
-    bf16x8 f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        f[i] = lo[i];
-        f[4 + i] = hi[i];
-    }
-    return f;
-}
-__device__ __forceinline__ bf16x8 lfrag(const bf16_t* lds, int r0, int k0, int lane) {
-    return *reinterpret_cast<const bf16x8*>(lds + (r0 + (lane & 15)) * SSTRIDE + k0 + 8 * (lane >> 4));
-}
-__device__ __forceinline__ float xorf(float v, int mask) { return __shfl_xor(v, mask, 64); }
 
 // item = ((b * qtiles) + qt) * slabs + slab: the slabs of one query tile are neighbours, their K tiles meet in L2
 __global__ __launch_bounds__(128) void self_attn_fwd_kernel(const bf16_t* __restrict__ q, int64_t ldq, const bf16_t* __restrict__ k,
@@ -76,148 +34,16 @@ __global__ __launch_bounds__(128) void self_attn_fwd_kernel(const bf16_t* __rest
                                                             int64_t items, int T, int qtiles, int slabs, float scale) {
     extern __shared__ __attribute__((aligned(16))) char ssm[];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    bf16_t* Vl = reinterpret_cast<bf16_t*>(ssm) + (size_t)wv * (SK * SSTRIDE);
+    bf16_t* Vl = reinterpret_cast<bf16_t*>(ssm) + (size_t)wv * (AK * ASTRIDE);
     const int64_t item = (int64_t)blockIdx.x * 2 + wv;
     if (item >= items) return;
     const int slab = (int)(item % slabs);
     const int64_t bq = item / slabs;
     const int qt = (int)(bq % qtiles);
     const int64_t b = bq / qtiles;
-    const bf16_t* qb = q + b * T * ldq;
-    const bf16_t* kb = k + b * T * ldk;
-    const bf16_t* vb = v + b * T * ldv + slab * SD;
-    const int q0 = qt * SQ;
-    const int jl = lane & 15, g4 = (lane >> 4) * 4;
-    const float c = scale * 1.4426950408889634f;
-    const int vrow = lane >> 3, vcol = (lane & 7) * 8;      // V staging: chunk = lane + 64*cc -> row vrow + 8*cc
-
-    bf16x8 aq[4][2], kf[4][2], vr[8];
-#pragma unroll
-    for (int ti = 0; ti < 4; ++ti)
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) aq[ti][ks] = gfrag(qb, ldq, q0 + ti * 16 + jl, T, ks * 32, lane);
-#pragma unroll
-    for (int tj = 0; tj < 4; ++tj)
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) kf[tj][ks] = gfrag(kb, ldk, tj * 16 + jl, T, ks * 32, lane);
-#pragma unroll
-    for (int cc = 0; cc < 8; ++cc) vr[cc] = grow8(vb, ldv, vrow + 8 * cc, T, vcol);
-
-    f32x4 o[4][4];      // [td][ti]: O[i = ti*16 + jl][dd = td*16 + g4 + r]
-    float m[4], l[4];
-#pragma unroll
-    for (int ti = 0; ti < 4; ++ti) {
-#pragma unroll
-        for (int td = 0; td < 4; ++td) o[td][ti] = f32x4{0.f, 0.f, 0.f, 0.f};
-        m[ti] = -FLT_MAX;
-        l[ti] = 0.f;
-    }
-
-    for (int k0 = 0; k0 < T; k0 += SK) {
-#pragma unroll
-        for (int cc = 0; cc < 8; ++cc) *reinterpret_cast<bf16x8*>(Vl + (vrow + 8 * cc) * SSTRIDE + vcol) = vr[cc];
-        f32x4 s[4][4];      // [tj][ti]: S[i = ti*16 + jl][key = k0 + tj*16 + g4 + r]
-#pragma unroll
-        for (int tj = 0; tj < 4; ++tj)
-#pragma unroll
-            for (int ti = 0; ti < 4; ++ti) s[tj][ti] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-            for (int tj = 0; tj < 4; ++tj)
-#pragma unroll
-                for (int ti = 0; ti < 4; ++ti) s[tj][ti] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[tj][ks], aq[ti][ks], s[tj][ti], 0, 0, 0);
-        // next tile's K fragments and V rows start their trip now; they land while this tile's softmax and P V run
-        if (k0 + SK < T) {
-            const int n0 = k0 + SK;
-#pragma unroll
-            for (int tj = 0; tj < 4; ++tj)
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) kf[tj][ks] = gfrag(kb, ldk, n0 + tj * 16 + jl, T, ks * 32, lane);
-#pragma unroll
-            for (int cc = 0; cc < 8; ++cc) vr[cc] = grow8(vb, ldv, n0 + vrow + 8 * cc, T, vcol);
-        }
-        const bool ragged = k0 + SK > T;
-        if (ragged) {      // keys past T stay out of the row maximum
-#pragma unroll
-            for (int tj = 0; tj < 4; ++tj)
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    if (k0 + tj * 16 + g4 + r >= T) {
-#pragma unroll
-                        for (int ti = 0; ti < 4; ++ti) s[tj][ti][r] = -FLT_MAX;
-                    }
-        }
-#pragma unroll
-        for (int ti = 0; ti < 4; ++ti) {
-            float mx = s[0][ti][0];
-#pragma unroll
-            for (int tj = 0; tj < 4; ++tj)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[tj][ti][r]);
-            mx = fmaxf(mx, xorf(mx, 16));
-            mx = fmaxf(mx, xorf(mx, 32));
-            const float mnew = fmaxf(m[ti], mx);
-            const float alpha = __builtin_amdgcn_exp2f((m[ti] - mnew) * c);
-            const float mc = mnew * c;
-            m[ti] = mnew;
-            float sum = 0.f;
-#pragma unroll
-            for (int tj = 0; tj < 4; ++tj)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(s[tj][ti][r], c, -mc));
-                    if (ragged && k0 + tj * 16 + g4 + r >= T) pv = 0.f;      // ... and get probability exactly zero
-                    s[tj][ti][r] = pv;
-                    sum += pv;
-                }
-            l[ti] = l[ti] * alpha + sum;      // per-lane partial over this lane's keys; the four key groups are summed once at the end
-#pragma unroll
-            for (int td = 0; td < 4; ++td)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) o[td][ti][r] *= alpha;
-        }
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            bf16x8 bp[4], av[4];
-#pragma unroll
-            for (int ti = 0; ti < 4; ++ti)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    bp[ti][r] = (bf16_t)s[2 * ks][ti][r];
-                    bp[ti][4 + r] = (bf16_t)s[2 * ks + 1][ti][r];
-                }
-#pragma unroll
-            for (int td = 0; td < 4; ++td) av[td] = ltfrag(Vl, 32 * ks, 32 * ks + 16, td * 16, lane);
-#pragma unroll
-            for (int td = 0; td < 4; ++td)
-#pragma unroll
-                for (int ti = 0; ti < 4; ++ti) o[td][ti] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[td], bp[ti], o[td][ti], 0, 0, 0);
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
-    bf16_t* ob = out + b * T * ldo + slab * SD;
-#pragma unroll
-    for (int ti = 0; ti < 4; ++ti) {
-        float lt = l[ti];
-        lt += xorf(lt, 16);
-        lt += xorf(lt, 32);
-        const float inv = __frcp_rn(lt);
-        const int i = q0 + ti * 16 + jl;
-        // training: log2 of the softmax denominator in the exp2 domain of this kernel, rows padded to qtiles*64 (zeros past T);
-        // every slab of a row computes the same value, slab 0 writes it
-        if (lse2 && slab == 0 && g4 == 0) lse2[b * ((int64_t)qtiles * SQ) + i] = i < T ? __builtin_fmaf(m[ti], c, __log2f(lt)) : 0.f;
-        if (i < T) {
-#pragma unroll
-            for (int td = 0; td < 4; ++td) {
-                bf16x4 w;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) w[r] = (bf16_t)(o[td][ti][r] * inv);
-                *reinterpret_cast<bf16x4*>(ob + (int64_t)i * ldo + td * 16 + g4) = w;
-            }
-        }
-    }
+    // every slab of a row computes the same L, slab 0 writes it
+    attn_fwd_tile<true>(q + b * T * ldq, ldq, k + b * T * ldk, ldk, v + b * T * ldv + slab * AD, ldv, out + b * T * ldo, ldo, slab * AD,
+                        lse2 + b * ((int64_t)qtiles * AQ), lse2 && slab == 0, qt, T, scale, Vl, lane);
 }
 
 // D[b * Tp + i] = sum_c dO[b][i][c] * O[b][i][c] over all dv columns: eight lanes per row, lane `sub` takes the 8-column chunks
@@ -258,7 +84,7 @@ __global__ __launch_bounds__(128) void self_attn_dq_kernel(const bf16_t* __restr
                                                            float scale) {
     extern __shared__ __attribute__((aligned(16))) char ssm[];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    bf16_t* Kl = reinterpret_cast<bf16_t*>(ssm) + (size_t)wv * (SK * SSTRIDE);
+    bf16_t* Kl = reinterpret_cast<bf16_t*>(ssm) + (size_t)wv * (AK * ASTRIDE);
     const int64_t item = (int64_t)blockIdx.x * 2 + wv;
     if (item >= items) return;
     const int qt = (int)(item % qtiles);
@@ -267,9 +93,9 @@ __global__ __launch_bounds__(128) void self_attn_dq_kernel(const bf16_t* __restr
     const bf16_t* kb = k + b * T * ldk;
     const bf16_t* vb = v + b * T * ldv;
     const bf16_t* dob = dout + b * T * lddo;
-    const int q0 = qt * SQ;
+    const int q0 = qt * AQ;
     const int jl = lane & 15, g4 = (lane >> 4) * 4;
-    const float c = scale * 1.4426950408889634f;
+    const float c = scale * LOG2E;
     const int vrow = lane >> 3, vcol = (lane & 7) * 8;
 
     bf16x8 aq[4][2], kr[8];
@@ -278,7 +104,7 @@ __global__ __launch_bounds__(128) void self_attn_dq_kernel(const bf16_t* __restr
     for (int ti = 0; ti < 4; ++ti) {
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) aq[ti][ks] = gfrag(qb, ldq, q0 + ti * 16 + jl, T, ks * 32, lane);
-        const int64_t li = b * ((int64_t)qtiles * SQ) + q0 + ti * 16 + jl;
+        const int64_t li = b * ((int64_t)qtiles * AQ) + q0 + ti * 16 + jl;
         L[ti] = lse2[li];
         Dd[ti] = dsum[li];
     }
@@ -290,13 +116,13 @@ __global__ __launch_bounds__(128) void self_attn_dq_kernel(const bf16_t* __restr
 #pragma unroll
         for (int ti = 0; ti < 4; ++ti) dq[td][ti] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    for (int k0 = 0; k0 < T; k0 += SK) {
+    for (int k0 = 0; k0 < T; k0 += AK) {
 #pragma unroll
-        for (int cc = 0; cc < 8; ++cc) *reinterpret_cast<bf16x8*>(Kl + (vrow + 8 * cc) * SSTRIDE + vcol) = kr[cc];
+        for (int cc = 0; cc < 8; ++cc) *reinterpret_cast<bf16x8*>(Kl + (vrow + 8 * cc) * ASTRIDE + vcol) = kr[cc];
         __builtin_amdgcn_wave_barrier();
-        if (k0 + SK < T) {      // next K tile flies during this tile's products
+        if (k0 + AK < T) {      // next K tile flies during this tile's products
 #pragma unroll
-            for (int cc = 0; cc < 8; ++cc) kr[cc] = grow8(kb, ldk, k0 + SK + vrow + 8 * cc, T, vcol);
+            for (int cc = 0; cc < 8; ++cc) kr[cc] = grow8(kb, ldk, k0 + AK + vrow + 8 * cc, T, vcol);
         }
         f32x4 s[4][4], dp[4][4];      // [tj][ti]: key k0 + tj*16 + g4 + r, query q0 + ti*16 + jl
 #pragma unroll
@@ -307,7 +133,7 @@ __global__ __launch_bounds__(128) void self_attn_dq_kernel(const bf16_t* __restr
         for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
             for (int tj = 0; tj < 4; ++tj) {
-                const bf16x8 kf = lfrag(Kl, tj * 16, ks * 32, lane);
+                const bf16x8 kf = row_frag(Kl, ASTRIDE, tj * 16, ks * 32, lane);
 #pragma unroll
                 for (int ti = 0; ti < 4; ++ti) s[tj][ti] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, aq[ti][ks], s[tj][ti], 0, 0, 0);
             }
@@ -325,7 +151,7 @@ __global__ __launch_bounds__(128) void self_attn_dq_kernel(const bf16_t* __restr
 #pragma unroll
                 for (int ti = 0; ti < 4; ++ti) dp[tj][ti] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[tj], ad[ti], dp[tj][ti], 0, 0, 0);
         }
-        const bool ragged = k0 + SK > T;
+        const bool ragged = k0 + AK > T;
 #pragma unroll
         for (int ti = 0; ti < 4; ++ti)
 #pragma unroll
@@ -379,230 +205,33 @@ __global__ __launch_bounds__(128) void self_attn_dk_kernel(const bf16_t* __restr
                                                            float scale) {
     extern __shared__ __attribute__((aligned(16))) char ssm[];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    bf16_t* Ql = reinterpret_cast<bf16_t*>(ssm) + (size_t)wv * (SI * SSTRIDE);
+    bf16_t* Ql = reinterpret_cast<bf16_t*>(ssm) + (size_t)wv * (AI * ASTRIDE);
     const int64_t item = (int64_t)blockIdx.x * 2 + wv;
     if (item >= items) return;
     const int kt = (int)(item % ktiles);
-    const int64_t b = item / ktiles;
-    const bf16_t* qb = q + b * T * ldq;
-    const bf16_t* kb = k + b * T * ldk;
-    const bf16_t* vb = v + b * T * ldv;
-    const bf16_t* dob = dout + b * T * lddo;
-    const float* Lb = lse2 + b * ((int64_t)ktiles * SQ);
-    const float* Db = dsum + b * ((int64_t)ktiles * SQ);
-    const int j0 = kt * SK;
-    const int jl = lane & 15, g4 = (lane >> 4) * 4;
-    const float c = scale * 1.4426950408889634f;
-    const int vrow = lane >> 3, vcol = (lane & 7) * 8;
-
-    bf16x8 kfB[4][2], qr[4];
-#pragma unroll
-    for (int tj = 0; tj < 4; ++tj)
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) kfB[tj][ks] = gfrag(kb, ldk, j0 + tj * 16 + jl, T, ks * 32, lane);
-#pragma unroll
-    for (int cc = 0; cc < 4; ++cc) qr[cc] = grow8(qb, ldq, vrow + 8 * cc, T, vcol);
-    f32x4 dk[4][4];      // [td][tj]: dK[key j0 + tj*16 + jl][d = td*16 + g4 + r]
-#pragma unroll
-    for (int td = 0; td < 4; ++td)
-#pragma unroll
-        for (int tj = 0; tj < 4; ++tj) dk[td][tj] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    for (int i0 = 0; i0 < T; i0 += SI) {
-#pragma unroll
-        for (int cc = 0; cc < 4; ++cc) *reinterpret_cast<bf16x8*>(Ql + (vrow + 8 * cc) * SSTRIDE + vcol) = qr[cc];
-        __builtin_amdgcn_wave_barrier();
-        if (i0 + SI < T) {      // next step's rows fly during this step's MFMAs
-#pragma unroll
-            for (int cc = 0; cc < 4; ++cc) qr[cc] = grow8(qb, ldq, i0 + SI + vrow + 8 * cc, T, vcol);
-        }
-        f32x4 s[2][4], dp[2][4];      // [ti][tj]: query i0 + ti*16 + g4 + r, key j0 + tj*16 + jl
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < 4; ++tj) s[ti][tj] = dp[ti][tj] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-            for (int ti = 0; ti < 2; ++ti) {
-                const bf16x8 qf = lfrag(Ql, ti * 16, ks * 32, lane);
-#pragma unroll
-                for (int tj = 0; tj < 4; ++tj) s[ti][tj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf, kfB[tj][ks], s[ti][tj], 0, 0, 0);
-            }
-        // dP = dO V^T over the whole value width, 32 columns per step
-#pragma unroll 2
-        for (int c0 = 0; c0 < dv; c0 += 32) {
-            bf16x8 df[2], vf[4];
-#pragma unroll
-            for (int ti = 0; ti < 2; ++ti) df[ti] = gfrag(dob, lddo, i0 + ti * 16 + jl, T, c0, lane);
-#pragma unroll
-            for (int tj = 0; tj < 4; ++tj) vf[tj] = gfrag(vb, ldv, j0 + tj * 16 + jl, T, c0, lane);
-#pragma unroll
-            for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-                for (int tj = 0; tj < 4; ++tj) dp[ti][tj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(df[ti], vf[tj], dp[ti][tj], 0, 0, 0);
-        }
-        // query rows past T (zero q / dO, zero L / D) and key columns past T are switched off explicitly
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti) {
-            const float4 Lr = *reinterpret_cast<const float4*>(Lb + i0 + ti * 16 + g4);
-            const float4 Dr = *reinterpret_cast<const float4*>(Db + i0 + ti * 16 + g4);
-            const float Lv[4] = {Lr.x, Lr.y, Lr.z, Lr.w}, Dv[4] = {Dr.x, Dr.y, Dr.z, Dr.w};
-#pragma unroll
-            for (int tj = 0; tj < 4; ++tj) {
-                const bool keyoff = j0 + tj * 16 + jl >= T;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[ti][tj][r], c, -Lv[r]));
-                    const float ds = p * (dp[ti][tj][r] - Dv[r]) * scale;
-                    dp[ti][tj][r] = (keyoff || i0 + ti * 16 + g4 + r >= T) ? 0.f : ds;
-                }
-            }
-        }
-        {
-            bf16x8 bds[4], aqt[4];
-#pragma unroll
-            for (int tj = 0; tj < 4; ++tj)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    bds[tj][r] = (bf16_t)dp[0][tj][r];
-                    bds[tj][4 + r] = (bf16_t)dp[1][tj][r];
-                }
-#pragma unroll
-            for (int td = 0; td < 4; ++td) aqt[td] = ltfrag(Ql, 0, 16, td * 16, lane);
-#pragma unroll
-            for (int td = 0; td < 4; ++td)
-#pragma unroll
-                for (int tj = 0; tj < 4; ++tj) dk[td][tj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aqt[td], bds[tj], dk[td][tj], 0, 0, 0);
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
-    bf16_t* dkb = dk_out + b * T * lddk;
-#pragma unroll
-    for (int tj = 0; tj < 4; ++tj) {
-        const int j = j0 + tj * 16 + jl;
-        if (j < T) {
-#pragma unroll
-            for (int td = 0; td < 4; ++td) {
-                bf16x4 w;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) w[r] = (bf16_t)dk[td][tj][r];
-                *reinterpret_cast<bf16x4*>(dkb + (int64_t)j * lddk + td * 16 + g4) = w;
-            }
-        }
-    }
+    const int64_t b = item / ktiles, row = b * ((int64_t)ktiles * AQ);
+    attn_key_tile<true, false, false, true>(q + b * T * ldq, ldq, k + b * T * ldk, ldk, v + b * T * ldv, ldv, dout + b * T * lddo, lddo,
+                                            lse2 + row, dsum + row, dk_out + b * T * lddk, lddk, nullptr, 0, kt, T, dv, scale, Ql, nullptr,
+                                            lane);
 }
 
-// item = ((b * ktiles) + kt) * slabs + slab
+// item = ((b * ktiles) + kt) * slabs + slab; Q is fed as global fragments, the LDS image holds the slab's dO rows
 __global__ __launch_bounds__(128) void self_attn_dv_kernel(const bf16_t* __restrict__ q, int64_t ldq, const bf16_t* __restrict__ k, int64_t ldk,
                                                            const bf16_t* __restrict__ dout, int64_t lddo, const float* __restrict__ lse2,
                                                            bf16_t* __restrict__ dv_out, int64_t lddv, int64_t items, int T, int ktiles,
                                                            int slabs, float scale) {
     extern __shared__ __attribute__((aligned(16))) char ssm[];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    bf16_t* Ol = reinterpret_cast<bf16_t*>(ssm) + (size_t)wv * (SI * SSTRIDE);
+    bf16_t* Ol = reinterpret_cast<bf16_t*>(ssm) + (size_t)wv * (AI * ASTRIDE);
     const int64_t item = (int64_t)blockIdx.x * 2 + wv;
     if (item >= items) return;
     const int slab = (int)(item % slabs);
     const int64_t bk = item / slabs;
     const int kt = (int)(bk % ktiles);
     const int64_t b = bk / ktiles;
-    const bf16_t* qb = q + b * T * ldq;
-    const bf16_t* kb = k + b * T * ldk;
-    const bf16_t* dob = dout + b * T * lddo + slab * SD;
-    const float* Lb = lse2 + b * ((int64_t)ktiles * SQ);
-    const int j0 = kt * SK;
-    const int jl = lane & 15, g4 = (lane >> 4) * 4;
-    const float c = scale * 1.4426950408889634f;
-    const int vrow = lane >> 3, vcol = (lane & 7) * 8;
-
-    bf16x8 kfB[4][2], qn[2][2], dor[4];
-#pragma unroll
-    for (int tj = 0; tj < 4; ++tj)
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) kfB[tj][ks] = gfrag(kb, ldk, j0 + tj * 16 + jl, T, ks * 32, lane);
-    auto fetch = [&](int i0) {
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) qn[ti][ks] = gfrag(qb, ldq, i0 + ti * 16 + jl, T, ks * 32, lane);
-#pragma unroll
-        for (int cc = 0; cc < 4; ++cc) dor[cc] = grow8(dob, lddo, i0 + vrow + 8 * cc, T, vcol);
-    };
-    fetch(0);
-    f32x4 dvv[4][4];      // [td][tj]: dV[key j0 + tj*16 + jl][slab column td*16 + g4 + r]
-#pragma unroll
-    for (int td = 0; td < 4; ++td)
-#pragma unroll
-        for (int tj = 0; tj < 4; ++tj) dvv[td][tj] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    for (int i0 = 0; i0 < T; i0 += SI) {
-        bf16x8 qf[2][2];
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) qf[ti][ks] = qn[ti][ks];
-#pragma unroll
-        for (int cc = 0; cc < 4; ++cc) *reinterpret_cast<bf16x8*>(Ol + (vrow + 8 * cc) * SSTRIDE + vcol) = dor[cc];
-        __builtin_amdgcn_wave_barrier();
-        if (i0 + SI < T) fetch(i0 + SI);      // next step's rows fly during this step's MFMAs
-        f32x4 s[2][4];      // [ti][tj]: query i0 + ti*16 + g4 + r, key j0 + tj*16 + jl
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < 4; ++tj) s[ti][tj] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-            for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-                for (int tj = 0; tj < 4; ++tj) s[ti][tj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf[ti][ks], kfB[tj][ks], s[ti][tj], 0, 0, 0);
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti) {
-            const float4 Lr = *reinterpret_cast<const float4*>(Lb + i0 + ti * 16 + g4);
-            const float Lv[4] = {Lr.x, Lr.y, Lr.z, Lr.w};
-#pragma unroll
-            for (int tj = 0; tj < 4; ++tj) {
-                const bool keyoff = j0 + tj * 16 + jl >= T;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[ti][tj][r], c, -Lv[r]));
-                    s[ti][tj][r] = (keyoff || i0 + ti * 16 + g4 + r >= T) ? 0.f : p;
-                }
-            }
-        }
-        {
-            bf16x8 bp[4], adot[4];
-#pragma unroll
-            for (int tj = 0; tj < 4; ++tj)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    bp[tj][r] = (bf16_t)s[0][tj][r];
-                    bp[tj][4 + r] = (bf16_t)s[1][tj][r];
-                }
-#pragma unroll
-            for (int td = 0; td < 4; ++td) adot[td] = ltfrag(Ol, 0, 16, td * 16, lane);
-#pragma unroll
-            for (int td = 0; td < 4; ++td)
-#pragma unroll
-                for (int tj = 0; tj < 4; ++tj) dvv[td][tj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(adot[td], bp[tj], dvv[td][tj], 0, 0, 0);
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
-    bf16_t* dvb = dv_out + b * T * lddv + slab * SD;
-#pragma unroll
-    for (int tj = 0; tj < 4; ++tj) {
-        const int j = j0 + tj * 16 + jl;
-        if (j < T) {
-#pragma unroll
-            for (int td = 0; td < 4; ++td) {
-                bf16x4 w;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) w[r] = (bf16_t)dvv[td][tj][r];
-                *reinterpret_cast<bf16x4*>(dvb + (int64_t)j * lddv + td * 16 + g4) = w;
-            }
-        }
-    }
+    attn_key_tile<false, true, false, true>(q + b * T * ldq, ldq, k + b * T * ldk, ldk, nullptr, 0, dout + b * T * lddo + slab * AD, lddo,
+                                            lse2 + b * ((int64_t)ktiles * AQ), nullptr, nullptr, 0, dv_out + b * T * lddv + slab * AD, lddv,
+                                            kt, T, AD, scale, nullptr, Ol, lane);
 }
 
 bool pitch_ok(int64_t ld, int width) { return ld >= width && ld % 8 == 0; }
@@ -610,12 +239,12 @@ bool pitch_ok(int64_t ld, int width) { return ld >= width && ld % 8 == 0; }
 }  // namespace
 
 extern "C" int iseg_self_attention_supported(int dk, int dv, int dtype) {
-    return (dtype == ISEG_BF16 && dk == SD && dv >= SD && dv <= SDV_MAX && dv % SD == 0) ? 1 : 0;
+    return (dtype == ISEG_BF16 && dk == AD && dv >= AD && dv <= SDV_MAX && dv % AD == 0) ? 1 : 0;
 }
 
 extern "C" size_t iseg_self_attention_lse_elems(int64_t batch, int T) {
     if (batch <= 0 || T <= 0) return 0;
-    return (size_t)batch * (size_t)(((int64_t)T + SQ - 1) / SQ * SQ);
+    return (size_t)batch * (size_t)(((int64_t)T + AQ - 1) / AQ * AQ);
 }
 
 #define SELFATTN_UNSUPPORTED(cond, ...)       \
@@ -626,23 +255,29 @@ extern "C" size_t iseg_self_attention_lse_elems(int64_t batch, int T) {
         }                                     \
     } while (0)
 
+// the checks both entry points make after their own argument test and before their pitch test
+static int self_attn_shape_ok(const char* who, int dk, int dv, float scale, int dtype) {
+    SELFATTN_UNSUPPORTED(iseg_self_attention_supported(dk, dv, dtype), "%s: needs bf16, dk 64 and dv a multiple of 64 in 64..1024 (got dk %d, dv %d)",
+                         who, dk, dv);
+    SELFATTN_UNSUPPORTED(scale > 0.f && scale <= FLT_MAX, "%s: needs a positive finite scale", who);
+    return ISEG_OK;
+}
+
 extern "C" int iseg_self_attention_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* out,
                                        int64_t ldo, float* lse2, int64_t batch, int T, int dk, int dv, float scale, int dtype,
                                        hipStream_t stream) {
     const char* who = "iseg_self_attention_fwd";
-    ISEG_REQUIRE(q && k && v && out && batch > 0 && T > 0 && T <= INT_MAX - SQ, "%s: bad arguments", who);
-    SELFATTN_UNSUPPORTED(iseg_self_attention_supported(dk, dv, dtype), "%s: needs bf16, dk 64 and dv a multiple of 64 in 64..1024 (got dk %d, dv %d)",
-                         who, dk, dv);
-    SELFATTN_UNSUPPORTED(scale > 0.f && scale <= FLT_MAX, "%s: needs a positive finite scale", who);
+    ISEG_REQUIRE(q && k && v && out && batch > 0 && T > 0 && T <= INT_MAX - AQ, "%s: bad arguments", who);
+    if (const int rc = self_attn_shape_ok(who, dk, dv, scale, dtype)) return rc;
     SELFATTN_UNSUPPORTED(pitch_ok(ldq, dk) && pitch_ok(ldk, dk) && pitch_ok(ldv, dv) && pitch_ok(ldo, dv),
                          "%s: row pitches must be multiples of 8 elements and cover their rows (got %lld %lld %lld %lld)", who, (long long)ldq,
                          (long long)ldk, (long long)ldv, (long long)ldo);
     SELFATTN_UNSUPPORTED(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out | (uintptr_t)lse2) % 16 == 0,
                          "%s: operands must be 16-byte aligned", who);
-    const int qtiles = (T + SQ - 1) / SQ, slabs = dv / SD;
+    const int qtiles = (T + AQ - 1) / AQ, slabs = dv / AD;
     const int64_t items = batch * qtiles * slabs;
     ISEG_REQUIRE(ceil_div64(items, 2) <= INT_MAX, "%s: too many work items", who);
-    hipLaunchKernelGGL(self_attn_fwd_kernel, dim3((unsigned)ceil_div64(items, 2)), dim3(128), (size_t)2 * SK * SSTRIDE * sizeof(bf16_t), stream,
+    hipLaunchKernelGGL(self_attn_fwd_kernel, dim3((unsigned)ceil_div64(items, 2)), dim3(128), (size_t)2 * AK * ASTRIDE * sizeof(bf16_t), stream,
                        (const bf16_t*)q, ldq, (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, (bf16_t*)out, ldo, lse2, items, T, qtiles, slabs,
                        scale);
     return iseg_check_launch(who);
@@ -653,11 +288,9 @@ extern "C" int iseg_self_attention_bwd(const void* q, int64_t ldq, const void* k
                                        void* dk, int64_t lddk, void* dv, int64_t lddv, int64_t batch, int T, int dk_dim, int dv_dim,
                                        float scale, int dtype, hipStream_t stream) {
     const char* who = "iseg_self_attention_bwd";
-    ISEG_REQUIRE(q && k && v && out && dout && lse2 && dsum && dq && dk && dv && batch > 0 && T > 0 && T <= INT_MAX - SQ, "%s: bad arguments",
+    ISEG_REQUIRE(q && k && v && out && dout && lse2 && dsum && dq && dk && dv && batch > 0 && T > 0 && T <= INT_MAX - AQ, "%s: bad arguments",
                  who);
-    SELFATTN_UNSUPPORTED(iseg_self_attention_supported(dk_dim, dv_dim, dtype),
-                         "%s: needs bf16, dk 64 and dv a multiple of 64 in 64..1024 (got dk %d, dv %d)", who, dk_dim, dv_dim);
-    SELFATTN_UNSUPPORTED(scale > 0.f && scale <= FLT_MAX, "%s: needs a positive finite scale", who);
+    if (const int rc = self_attn_shape_ok(who, dk_dim, dv_dim, scale, dtype)) return rc;
     SELFATTN_UNSUPPORTED(pitch_ok(ldq, dk_dim) && pitch_ok(ldk, dk_dim) && pitch_ok(ldv, dv_dim) && pitch_ok(ldo, dv_dim) &&
                              pitch_ok(lddo, dv_dim) && pitch_ok(lddq, dk_dim) && pitch_ok(lddk, dk_dim) && pitch_ok(lddv, dv_dim),
                          "%s: row pitches must be multiples of 8 elements and cover their rows", who);
@@ -665,19 +298,19 @@ extern "C" int iseg_self_attention_bwd(const void* q, int64_t ldq, const void* k
                           (uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv) % 16 == 0,
                          "%s: operands must be 16-byte aligned", who);
     ISEG_REQUIRE(dq != dk, "%s: dq and dk must be separate buffers (the caller adds them when q and k alias)", who);
-    const int tiles = (T + SQ - 1) / SQ, slabs = dv_dim / SD;
-    const int Tp = tiles * SQ;
+    const int tiles = (T + AQ - 1) / AQ, slabs = dv_dim / AD;
+    const int Tp = tiles * AQ;
     const int64_t items = batch * tiles, rows = batch * T;
     ISEG_REQUIRE(ceil_div64(items * slabs, 2) <= INT_MAX && ceil_div64(rows * 8, 256) <= INT_MAX, "%s: too many work items", who);
     const bf16_t *qp = (const bf16_t*)q, *kp = (const bf16_t*)k, *vp = (const bf16_t*)v, *dop = (const bf16_t*)dout;
     hipMemsetAsync(dsum, 0, iseg_self_attention_lse_elems(batch, T) * sizeof(float), stream);      // rows T .. Tp-1 are read by the tile loops
     hipLaunchKernelGGL(self_attn_rowdot_kernel, dim3((unsigned)ceil_div64(rows * 8, 256)), dim3(256), 0, stream, (const bf16_t*)out, ldo, dop,
                        lddo, dsum, rows, T, Tp, dv_dim);
-    hipLaunchKernelGGL(self_attn_dv_kernel, dim3((unsigned)ceil_div64(items * slabs, 2)), dim3(128), (size_t)2 * SI * SSTRIDE * sizeof(bf16_t),
+    hipLaunchKernelGGL(self_attn_dv_kernel, dim3((unsigned)ceil_div64(items * slabs, 2)), dim3(128), (size_t)2 * AI * ASTRIDE * sizeof(bf16_t),
                        stream, qp, ldq, kp, ldk, dop, lddo, lse2, (bf16_t*)dv, lddv, items * slabs, T, tiles, slabs, scale);
-    hipLaunchKernelGGL(self_attn_dq_kernel, dim3((unsigned)ceil_div64(items, 2)), dim3(128), (size_t)2 * SK * SSTRIDE * sizeof(bf16_t), stream,
+    hipLaunchKernelGGL(self_attn_dq_kernel, dim3((unsigned)ceil_div64(items, 2)), dim3(128), (size_t)2 * AK * ASTRIDE * sizeof(bf16_t), stream,
                        qp, ldq, kp, ldk, vp, ldv, dop, lddo, lse2, dsum, (bf16_t*)dq, lddq, items, T, tiles, dv_dim, scale);
-    hipLaunchKernelGGL(self_attn_dk_kernel, dim3((unsigned)ceil_div64(items, 2)), dim3(128), (size_t)2 * SI * SSTRIDE * sizeof(bf16_t), stream,
+    hipLaunchKernelGGL(self_attn_dk_kernel, dim3((unsigned)ceil_div64(items, 2)), dim3(128), (size_t)2 * AI * ASTRIDE * sizeof(bf16_t), stream,
                        qp, ldq, kp, ldk, vp, ldv, dop, lddo, lse2, dsum, (bf16_t*)dk, lddk, items, T, tiles, dv_dim, scale);
     return iseg_check_launch(who);
 }

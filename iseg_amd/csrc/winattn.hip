@@ -10,32 +10,22 @@
 //
 // MFMA fragment conventions (16x16x32 bf16): an A (or B) fragment = lane holds 8 consecutive k = 8*(lane>>4) .. +7 of row (or
 // column) lane&15; the accumulator holds D[(lane>>4)*4 + r][lane&15], r = 0..3.
-#include "common.h"
+#include "attn_tile.h"
 #include "iseg_hip.h"
-
-#include <float.h>
 
 namespace {
 
-typedef __attribute__((address_space(3))) bf16x4* lds_bf16x4_ptr;
+using attn::gfrag;
+using attn::lds_bf16x4_ptr;
+using attn::row_frag;
+using attn::zero8;
 
 constexpr int WD = 32;            // head dim
 constexpr int WT = 64;            // padded tokens
 constexpr int PS_STRIDE = 72;     // P / dS image [64][72] bf16 (144-B rows: 16-B aligned, 4-bank skew)
 constexpr int QK_STRIDE = 40;     // Q / K / V / dO images [64][40] bf16 (80-B rows)
 
-__device__ __forceinline__ bf16x8 zero8() {
-    bf16x8 v;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = (bf16_t)0.f;
-    return v;
-}
-
-// fragment straight from global memory: row `row` (token) of a [T][ld] matrix, columns col0 + 8*(lane>>4) .. +7
-__device__ __forceinline__ bf16x8 gfrag(const bf16_t* __restrict__ base, int64_t ld, int row, int T, int col0, int lane) {
-    if (row >= T) return zero8();
-    return *reinterpret_cast<const bf16x8*>(base + (int64_t)row * ld + col0 + 8 * (lane >> 4));
-}
+// zero8, gfrag (fragment straight from global memory) and row_frag (LDS image read along the rows) are those of attn_tile.h
 
 // fragment from a row-major LDS image [k][stride] read TRANSPOSED: lane receives k0 + 8*(lane>>4) .. +7 of column r0 + (lane&15)
 __device__ __forceinline__ bf16x8 tr_frag(const bf16_t* lds, int stride, int k0, int r0, int lane) {
@@ -51,11 +41,6 @@ __device__ __forceinline__ bf16x8 tr_frag(const bf16_t* lds, int stride, int k0,
         f[4 + i] = hi[i];
     }
     return f;
-}
-
-// fragment from a row-major LDS image read along the rows: row r0 + (lane&15), k0 + 8*(lane>>4) .. +7   (one ds_read_b128)
-__device__ __forceinline__ bf16x8 row_frag(const bf16_t* lds, int stride, int r0, int k0, int lane) {
-    return *reinterpret_cast<const bf16x8*>(lds + (r0 + (lane & 15)) * stride + k0 + 8 * (lane >> 4));
 }
 
 // max / sum over the 16 lanes that share (lane >> 4), on the DPP cross-lane network (quad_perm xor 1, xor 2, then half-row and

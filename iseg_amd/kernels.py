@@ -1940,7 +1940,7 @@ def colsum_wide(x2d, out, accumulate=False):
 
 
 # ---------------------------------------------------------------------------------------------------------
-# fused window attention (csrc/winattn.hip)
+# fused global attention on packed [q|k|v], head_dim 64 (csrc/flashattn.hip)
 # ---------------------------------------------------------------------------------------------------------
 def attention_fwd_supported(head_dim, dtype):
     return dtype == torch.bfloat16 and bool(_hip.lib().iseg_attention_fwd_supported(int(head_dim), BF16))
@@ -2026,6 +2026,9 @@ def self_attention_bwd(q, k, v, out, dout, lse, scale):
     return dq, dkk, dvv
 
 
+# ---------------------------------------------------------------------------------------------------------
+# fused window attention (csrc/winattn.hip)
+# ---------------------------------------------------------------------------------------------------------
 def window_attention_supported(T, head_dim, dtype):
     return dtype == torch.bfloat16 and bool(_hip.lib().iseg_window_attention_supported(int(T), int(head_dim), BF16))
 

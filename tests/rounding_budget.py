@@ -734,7 +734,7 @@ case("upsample_ce", "x2_dlogits", "upsample_ce", make_upsample_ce, upsample_ce_c
 
 
 # ---- tier 2: attention cores.  The probabilities (and dS) are bf16 MFMA operands that stay in registers / LDS: UNSTORED_MAX_E ------------------------
-ATT_KEY_TILE = 64      # iseg_amd/csrc/flashattn.hip:3 (one wavefront walks the keys in tiles of 64 with the online-softmax recurrence)
+ATT_KEY_TILE = 64      # iseg_amd/csrc/attn_tile.h:9 (attn_fwd_tile: 64 queries, key tiles of 64, the online-softmax recurrence), AK at :30
 LN2 = math.log(2.0)
 
 
@@ -766,7 +766,7 @@ def online_softmax_pv(q, k, v, scale):
         alpha = torch.exp((m - mnew) * scale)
         p = torch.exp((st - mnew) * scale)
         l = l * alpha + p.sum(-1, keepdim=True)
-        o = o * alpha + rb(p) @ v[..., k0:k0 + ATT_KEY_TILE, :]      # iseg_amd/csrc/flashattn.hip:5 (v_mfma_f32_16x16x32_bf16 for V^T P^T: P is a bf16 operand)
+        o = o * alpha + rb(p) @ v[..., k0:k0 + ATT_KEY_TILE, :]      # iseg_amd/csrc/attn_tile.h:11-13 (the probabilities are the bf16 B operand of O^T = V^T P^T on v_mfma_f32_16x16x32_bf16)
         m = mnew
     return o / l
 
@@ -798,7 +798,7 @@ def flash_bwd_compute(i, B, T, heads, scale):
 def recomputed_p_bwd(q, k, v, do, o, L, scale):
     p = torch.exp(q @ k.transpose(-1, -2) * scale - L * LN2)
     ds = p * (do @ v.transpose(-1, -2) - (do * o).sum(-1, keepdim=True)) * scale
-    pb, dsb = rb(p), rb(ds)                            # iseg_amd/csrc/flashattn.hip:217 (P and dS are the B operands of dV^T = dO^T P and dK^T = Q^T dS), :215 (dS^T of dQ^T)
+    pb, dsb = rb(p), rb(ds)                            # iseg_amd/csrc/attn_tile.h:16-17 (P and dS are the B operands of dV^T = dO^T P and dK^T = Q^T dS); iseg_amd/csrc/flashattn.hip:9-10 (dS of dQ)
     return dsb @ k, dsb.transpose(-1, -2) @ q, pb.transpose(-1, -2) @ do
 
 
@@ -808,8 +808,8 @@ case("attention_flash", "t150_h3", "attention_flash", make_flash, lambda i, B, T
 case("attention_flash_bwd", "t150_h3", "attention_flash_bwd", make_flash, flash_bwd_compute, 2, **FLASH)
 
 
-# the single-head core of the non-local block (iseg_amd/csrc/selfattn.hip:4-5: the formulation of flashattn.hip, P stays in registers as the B operand of
-# O^T = V^T P^T; iseg_amd/csrc/selfattn.hip:9-11 for the backward pass), 64-wide q / k and a wide value
+# the single-head core of the non-local block (iseg_amd/csrc/selfattn.hip:4-6: the tile bodies of attn_tile.h over value slabs, so P stays in registers
+# as the B operand of O^T = V^T P^T, iseg_amd/csrc/attn_tile.h:11-13; iseg_amd/csrc/selfattn.hip:8-10 for the backward pass), 64-wide q / k and a wide value
 def make_self(B, T, dv, scale):
     q, k, v = bq((B, T, 64), 1), bq((B, T, 64), 2), bq((B, T, dv), 3)
     q64, k64 = q.to(F64), k.to(F64)
