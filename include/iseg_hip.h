@@ -323,6 +323,31 @@ int iseg_bnfold_dwconv3_relu_bwd(const void* D, const void* z, const void* x, co
                                  int stride, int dil, int dtype, void* ws, size_t ws_bytes, iseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * JointPyramidUpsampling tail (layers/jpu.py:38-59, 79-88): the merged map x [N, H, W, C] feeds four branches DepthwiseConv2D(3, padding="same",
+ * dilation_rate=r, use_bias=True) -> BN -> ConvNormAct(width), r = 1, 2, 4, 8.  Rate-major operands: w [4][9][C], bias [4][C],
+ * z / D [4][N, H, W, C] (dtype fp32 or bf16, NHWC), mean / rstd / gamma [4][C] fp32.  The BN of every branch is folded into its pointwise GEMM
+ * (iseg_sepconv_fold / iseg_sepconv_fold_bwd above), so only the depthwise side is new:
+ *   iseg_jpu_dwconv3x4_stats       z_r = dw3x3_r(x) + bias_r for the four rates from ONE window of x staged in LDS (pixel tile + halo of 8);
+ *                                  packed != NULL: four iseg_bn_stats messages [4][2C+1] = [sum z | sum z^2 | count] of the stored z, from
+ *                                  fixed-order per-tile partials in ws; packed == NULL: z only (ws is not read)
+ *   iseg_jpu_bnfold_dwconv3x4_bwd  dz_r = D_r + alpha_r + beta'_r z_r (train: the BN backward of the all-reduced sums [4][2C] = [dbeta | dgamma]
+ *                                  per rate with inv_n = 1 / global count; train == 0: dz_r = D_r) staged in LDS with its halo of r;
+ *                                  dx = sum_r dw3x3_r^T(dz_r) summed in registers and stored once, dw [4][9][C] += sum x dz_r per tap,
+ *                                  db [4][C] += sum dz_r (fixed-order per-tile partials in ws, 10 rows per rate; train: that sum is
+ *                                  identically zero over the batch of the statistics, and nothing is added).  dz is never written.
+ *   iseg_jpu_partials_bytes        the bytes of ws either launcher needs (backward = 0: the statistics partials, 1: the dw / db partials); a
+ *                                  null or shorter ws returns ISEG_ERR_WORKSPACE and nothing is launched
+ * Stride 1, C % 8 == 0, N <= 65535, 16-byte aligned activations and vectors; anything else returns ISEG_ERR_UNSUPPORTED.
+ * --------------------------------------------------------------------------------------------------------- */
+int iseg_jpu_supported(int N, int H, int W, int C, int dtype);
+size_t iseg_jpu_partials_bytes(int N, int H, int W, int C, int backward);
+int iseg_jpu_dwconv3x4_stats(const void* x, const float* w, const float* bias, void* z, float* packed, int N, int H, int W, int C, int dtype,
+                             void* ws, size_t ws_bytes, iseg_stream_t stream);
+int iseg_jpu_bnfold_dwconv3x4_bwd(const void* D, const void* z, const void* x, const float* w, const float* mean, const float* rstd,
+                                  const float* gamma, const float* sums, float inv_n, int train, void* dx, float* dw, float* db, int N, int H,
+                                  int W, int C, int dtype, void* ws, size_t ws_bytes, iseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * ResNet-9 / 10 / 18 basic-block tail (backbones/resnet_blocks_small.py, BlockType2Small.call :84-119: shortcut_bn :89-90, avg_pool2d of the
  * shortcut :92-98, conv2_bn :105, add + relu :107-108):
  *   out = relu(bn2(z2) + pool_s(sc)),  sc = bn0(z0) (shortcut conv) or x (identity),  bn(v) = (v - mean) * rstd * gamma + beta

@@ -127,6 +127,10 @@ SIGNATURES = {
     "iseg_sepconv_fold_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _p]),
     "iseg_bnfold_dwconv3_relu_bwd_workspace_bytes": (_z, [_i, _i, _i, _i, _i, _i]),
     "iseg_bnfold_dwconv3_relu_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _f, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _z, _p]),
+    "iseg_jpu_supported": (_i, [_i, _i, _i, _i, _i]),
+    "iseg_jpu_partials_bytes": (_z, [_i, _i, _i, _i, _i]),
+    "iseg_jpu_dwconv3x4_stats": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _z, _p]),
+    "iseg_jpu_bnfold_dwconv3x4_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _f, _i, _p, _p, _p, _i, _i, _i, _i, _i, _p, _z, _p]),
     "iseg_resblock_tail_supported": (_i, [_i, _i, _i]),
     "iseg_resblock_tail_workspace_bytes": (_z, [_i, _i, _i, _i, _i, _i]),
     "iseg_resblock_tail_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),

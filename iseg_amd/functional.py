@@ -1123,6 +1123,135 @@ def sepconv_unit(x, dw_kernel, bn, pw_kernel, training, strides=1, dilation=1):
 
 
 # ---------------------------------------------------------------------------------------------------------
+# JointPyramidUpsampling tail (layers/jpu.py:79-88): the merged map through four branches depthwise 3x3 (dilation 1, 2, 4, 8, with bias) ->
+# (Sync)BN -> pointwise 1x1, as one tape node (csrc/jpu.hip for the depthwise side, the sepconv fold and the GEMMs for the rest).  x is read
+# once forward; backward the four transposed depthwise convolutions are summed in registers, so no per-branch input gradient, no BN output and
+# no dz is written.
+# ---------------------------------------------------------------------------------------------------------
+JPU_RATES = (1, 2, 4, 8)
+
+
+class _JpuTailFn(Function):
+    @staticmethod
+    def forward(ctx, x, training, sync, layers, *params):
+        """layers: per rate dict(eps, momentum, moving_mean, moving_var); params: per rate (dwk, dwb, gamma, beta, pwk), rate-major"""
+        R = len(JPU_RATES)
+        C = x.shape[-1]
+        xc = _c(x)
+        groups = [params[5 * r:5 * r + 5] for r in range(R)]
+        w = torch.stack([g[0].data.reshape(9, C) for g in groups])
+        bias = torch.stack([g[1].data for g in groups])
+        z, packed = K.jpu_dwconv3x4_stats(xc, w, bias, stats=training)
+        if training and sync:
+            dist.all_reduce_sum(packed)          # the four [2C+1] messages, written by the depthwise launch itself, travel as one
+        need_grad = any(ctx.needs_input_grad)
+        vs, saved = [], []
+        for r, (L, (dwk, dwb, gamma, beta, pwk)) in enumerate(zip(layers, groups)):
+            if training:
+                mean, rstd = K.bn_finalize(packed[r], C, L["eps"], L["momentum"], L["moving_mean"], L["moving_var"])
+            else:
+                mean, rstd = _bn_frozen_stats(L["moving_mean"], L["moving_var"], L["eps"])
+            v, Wn = _sepconv_pointwise(z[r].reshape(-1, C), pwk, mean, rstd, gamma, beta, need_grad)
+            vs.append(v.reshape(*x.shape[:-1], pwk.shape[-1]))
+            saved += [mean, rstd, Wn]
+        ctx.groups, ctx.training, ctx.sync = groups, training, training and sync
+        ctx.save_for_backward(xc, z, w, *saved)
+        return tuple(vs)
+
+    @staticmethod
+    def backward(ctx, *dvs):
+        """per rate: wgrad GEMM + colsum -> fold_bwd; ONE exchange of the four [2C] sums; per rate the dgrad GEMM into one [4][N,H,W,C]
+        buffer; one depthwise / BN backward launch for all four"""
+        xc, z, w = ctx.saved_tensors[:3]
+        rest = ctx.saved_tensors[3:]
+        R = len(JPU_RATES)
+        C = xc.shape[-1]
+        rows = xc.numel() // C
+        dev = xc.device
+        sums = torch.empty((R, 2 * C), dtype=torch.float32, device=dev)
+        dv2s = []
+        for r, (dwk, dwb, gamma, beta, pwk) in enumerate(ctx.groups):
+            mean, rstd, Wn = rest[3 * r:3 * r + 3]
+            Cout = pwk.shape[-1]
+            dv = dvs[r]
+            dv2 = _c(dv).reshape(-1, Cout) if dv is not None else torch.zeros((rows, Cout), dtype=xc.dtype, device=dev)
+            dv2s.append(dv2)
+            z2 = z[r].reshape(-1, C)
+            G = torch.empty((C, Cout), dtype=torch.float32, device=dev)
+            S = torch.empty(Cout, dtype=torch.float32, device=dev)
+            if z2.dtype == torch.bfloat16 and C % 8 == 0:
+                K.gemm(z2, dv2, G, C, Cout, rows, lda=C, ldb=Cout, ldd=Cout, a_kcontig=0, b_kcontig=0, accumulate=False, colsum_out=S,
+                       colsum_accumulate=False)
+            else:
+                K.dense_wgrad(z2, dv2, G, accumulate=False, bias_grad=S)
+            K.sepconv_fold_bwd(G, S, pwk.data.reshape(C, Cout), mean, rstd, gamma.data, beta.data, dW=_param_grad(pwk, C, Cout),
+                               dgamma=_param_grad(gamma), dbeta=_param_grad(beta), out=sums[r])
+            dist.grads_ready(pwk, gamma, beta)
+        sums, world, _ = _bn_exchange_sums(sums.reshape(-1), (), ctx.sync)
+        D = torch.empty_like(z)
+        for r in range(R):
+            K.dense_dgrad(dv2s[r], rest[3 * r + 2], out=D[r].reshape(rows, C))
+        mean = torch.stack([rest[3 * r] for r in range(R)])
+        rstd = torch.stack([rest[3 * r + 1] for r in range(R)])
+        gamma = torch.stack([g[2].data for g in ctx.groups])
+        dw = torch.zeros((R, 9, C), dtype=torch.float32, device=dev)
+        db = torch.zeros((R, C), dtype=torch.float32, device=dev)
+        dx = K.jpu_bnfold_dwconv3x4_bwd(D, z, xc, w, mean, rstd, gamma, sums, 1.0 / (rows * world) if ctx.training else 0.0, ctx.training, dw, db)
+        for r, (dwk, dwb, _, _, _) in enumerate(ctx.groups):
+            if dwk.requires_grad:
+                K.axpby(_grad(dwk).reshape(9, C), dw[r], 1.0, 1.0, out=_grad(dwk).reshape(9, C))
+            if dwb.requires_grad:
+                K.axpby(_grad(dwb), db[r], 1.0, 1.0, out=_grad(dwb))
+            dist.grads_ready(dwk, dwb)
+        return (dx if ctx.needs_input_grad[0] else None, None, None, None) + (None,) * (5 * R)
+
+
+def jpu_fused_enabled():
+    """ISEG_JPU_FUSED=1 routes the JointPyramidUpsampling tail through csrc/jpu.hip.  Opt-in: at 16 x 64 x 64 x 1536 -> 512 in bf16 the fused
+    forward + backward measured 7.56 ms against 6.18 ms for the composed operators (EXPERIMENTS.md), so those stay the default"""
+    return os.environ.get("ISEG_JPU_FUSED", "0") == "1"
+
+
+def jpu_tail_supported(x, dw_layers, bn_layers, pw_kernels):
+    """the shape rules of csrc/jpu.hip, and _aligned16 of x and the vectors and kernels the fused node reads directly"""
+    if x.dim() != 4 or len(dw_layers) != len(JPU_RATES):
+        return False
+    N, H, W, C = x.shape
+    vectors = []
+    for rate, dw, bn, pwk in zip(JPU_RATES, dw_layers, bn_layers, pw_kernels):
+        if (dw.depthwise_kernel is None or tuple(dw.depthwise_kernel.shape) != (3, 3, C, 1) or dw.bias is None
+                or tuple(dw.dilation_rate) != (rate, rate) or tuple(dw.strides) != (1, 1) or dw.padding != "same"):
+            return False
+        if pwk.dim() != 4 or tuple(pwk.shape[:3]) != (1, 1, C) or bn.gamma is None or bn.gamma.shape[0] != C:
+            return False
+        vectors += [dw.depthwise_kernel, dw.bias, pwk, bn.gamma, bn.beta, bn.moving_mean, bn.moving_variance]
+    if len({bool(bn.synchronized) for bn in bn_layers}) != 1 or len({bool(bn.trainable) for bn in bn_layers}) != 1:
+        return False
+    if not _aligned16((x,), vectors):
+        return False
+    return K.jpu_supported(N, H, W, C, x.dtype)
+
+
+def jpu_tail(x, dw_layers, bn_layers, pw_kernels, training):
+    """[conv1x1(bn_r(depthwise_conv2d(x, dw_r, bias_r, dilation=r)), pw_r) for r in 1, 2, 4, 8]: the four pointwise outputs before their own BN.
+    dw_layers: the DepthwiseConv2D layers (3x3, with bias, built), bn_layers: their BatchNormalization layers (built), pw_kernels [1, 1, C, Cout]
+    (Keras kernels).  Fused with ISEG_JPU_FUSED=1 where jpu_tail_supported accepts the shape and tensors; else the composed operators run."""
+    _check_act_dtype(x)
+    if nn.dry_run() or not jpu_fused_enabled() or not jpu_tail_supported(x, dw_layers, bn_layers, pw_kernels):
+        outs = []
+        for xr, dw, bn, pwk in zip(fork(x, len(dw_layers)), dw_layers, bn_layers, pw_kernels):
+            z = depthwise_conv2d(xr, dw.depthwise_kernel, dw.bias, dilation=dw.dilation_rate[0])
+            u = batch_norm(z, bn.gamma, bn.beta, bn.moving_mean, bn.moving_variance, bn.epsilon, bn.momentum, bool(training) and bn.trainable,
+                           sync=bn.synchronized)
+            outs.append(conv2d(u, pwk, None, (1, 1), (1, 1), "same"))
+        return outs
+    bn_training = bool(training) and bn_layers[0].trainable
+    layers = [dict(eps=float(b.epsilon), momentum=float(b.momentum), moving_mean=b.moving_mean, moving_var=b.moving_variance) for b in bn_layers]
+    params = [p for dw, bn, pwk in zip(dw_layers, bn_layers, pw_kernels) for p in (dw.depthwise_kernel, dw.bias, bn.gamma, bn.beta, pwk)]
+    return list(_JpuTailFn.apply(x, bn_training, bool(bn_layers[0].synchronized), layers, *params))
+
+
+# ---------------------------------------------------------------------------------------------------------
 # ResNet-9 / 10 / 18 basic-block tail (backbones/resnet_blocks_small.py:84-119): relu(bn2(z2) + avg_pool_s(bn0(z0) or x)) as one tape node
 # (csrc/resblock.hip).  Neither BN output nor the pooled shortcut is written; both layers' statistics travel in one message each way.
 # ---------------------------------------------------------------------------------------------------------

@@ -118,6 +118,29 @@ def resnet18_aspp(num_class=21, output_stride=32, build_input_size=(256, 256), d
                     build_input_size)
 
 
+class JPUASPPHead(Layer):
+    """FastFCN's arrangement: the backbone stays undilated (stride 32), JointPyramidUpsampling (layers/jpu.py) makes the stride-8 map from the
+    last three endpoints, and the ASPP head of the stride-8 DeepLab (rates x 4) runs on it -> ConvNormAct(filters, 1x1, dropout)."""
+
+    def __init__(self, filters=256, jpu_width=512, dropout_rate=0.1, name="jpu_aspp_head"):
+        super().__init__(name=name)
+        from .layers.jpu import JointPyramidUpsampling
+
+        self.jpu = JointPyramidUpsampling(width=jpu_width, name=f"{self.name}/jpu")
+        self.aspp = AtrousSpatialPyramidPooling(filters, dilation_rates=[3, 6, 9], dilation_rates_multiplier=4, name=f"{self.name}/aspp")
+        self.end_conv = ConvNormAct(filters, (1, 1), dropout_rate=dropout_rate, name=f"{self.name}/end_conv")
+
+    def call(self, inputs, training=None):
+        x = self.jpu(list(inputs), training=training)
+        x = self.aspp(x, training=training)
+        return self.end_conv(x, training=training)
+
+
+def resnet18_jpu_aspp(num_class=21, build_input_size=(256, 256), jpu_width=512, dropout_rate=0.1):
+    """ResNet-18 at output stride 32 + JointPyramidUpsampling + ASPP (FastFCN)"""
+    return _managed("resnet18", JPUASPPHead(256, jpu_width=jpu_width, dropout_rate=dropout_rate), num_class, 32, build_input_size)
+
+
 def efficientnet_b0_aspp(num_class=21, output_stride=32, build_input_size=(512, 512), dropout_rate=0.1):
     """EfficientNet-B0 (backbones/efficientnet.py, with top_conv) + ASPP"""
     return _managed("efficientnetb0", ASPPHead(256, output_stride=output_stride, dropout_rate=dropout_rate), num_class, output_stride,

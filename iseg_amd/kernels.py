@@ -655,10 +655,11 @@ def sepconv_fold(W, mean, rstd, gamma, beta, dtype, want_t=True, want_n=True):
     return Wt, Wn, bias
 
 
-def sepconv_fold_bwd(G, S, W, mean, rstd, gamma, beta, dW=None, dgamma=None, dbeta=None):
-    """dW (+)= diag(a) G + c S^T; returns sums [2Cin] = [dbeta | dgamma], which the same launch adds into dgamma / dbeta (None: skipped)"""
+def sepconv_fold_bwd(G, S, W, mean, rstd, gamma, beta, dW=None, dgamma=None, dbeta=None, out=None):
+    """dW (+)= diag(a) G + c S^T; returns sums [2Cin] = [dbeta | dgamma], which the same launch adds into dgamma / dbeta (None: skipped);
+    `out`: a [2Cin] slice of a larger message (several layers, one exchange)"""
     Cin, Cout = W.shape
-    sums = torch.empty(2 * Cin, dtype=torch.float32, device=W.device)
+    sums = out if out is not None else torch.empty(2 * Cin, dtype=torch.float32, device=W.device)
     _hip.call("iseg_sepconv_fold_bwd", ptr(G), ptr(S), ptr(W), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(dW), ptr(sums), ptr(dgamma),
               ptr(dbeta), Cin, Cout, stream())
     return sums
@@ -672,6 +673,46 @@ def bnfold_dwconv3_relu_bwd(D, z, x, w, mean, rstd, gamma, sums, inv_n, train, d
     ws, wsb = workspace(_hip.lib().iseg_bnfold_dwconv3_relu_bwd_workspace_bytes(N, H, W, Cc, stride, dil), x.device)
     _hip.call("iseg_bnfold_dwconv3_relu_bwd", ptr(D), ptr(z), ptr(x), ptr(w), ptr(mean), ptr(rstd), ptr(gamma), ptr(sums), float(inv_n), int(train),
               ptr(dx), ptr(dw), N, H, W, Cc, int(stride), int(dil), dt(x), ptr(ws), wsb, stream())
+    return dx
+
+
+# ---------------------------------------------------------------------------------------------------------
+# JointPyramidUpsampling tail: four depthwise 3x3 branches (dilation 1, 2, 4, 8, with bias) over one tensor (csrc/jpu.hip)
+# ---------------------------------------------------------------------------------------------------------
+JPU_RATES = 4
+
+
+def jpu_supported(N, H, W, Cc, dtype):
+    return bool(_hip.lib().iseg_jpu_supported(int(N), int(H), int(W), int(Cc), dt(dtype)))
+
+
+def jpu_dwconv3x4_stats(x, w, bias, stats=True, ws_bytes=None):
+    """z [4][N,H,W,C], z[r] = dw3x3(x, w[r], dilation (1, 2, 4, 8)[r]) + bias[r] (TF 'same'), and with stats the four packed [2C+1] messages of
+    bn_stats over the stored z; x [N,H,W,C], w [4, 9, C], bias [4, C] fp32.  ws_bytes: the workspace size handed to the launcher (tests)"""
+    _require_cuda(x, w, bias)
+    N, H, W, Cc = x.shape
+    z = torch.empty((JPU_RATES, N, H, W, Cc), dtype=x.dtype, device=x.device)
+    packed, ws, wsb = None, None, 0
+    if stats:
+        packed = torch.empty((JPU_RATES, 2 * Cc + 1), dtype=torch.float32, device=x.device)
+        ws, wsb = workspace(_hip.lib().iseg_jpu_partials_bytes(N, H, W, Cc, 0), x.device)
+        if ws_bytes is not None:
+            wsb = ws_bytes
+    _hip.call("iseg_jpu_dwconv3x4_stats", ptr(x), ptr(w), ptr(bias), ptr(z), ptr(packed), N, H, W, Cc, dt(x), ptr(ws), wsb, stream())
+    return z, packed
+
+
+def jpu_bnfold_dwconv3x4_bwd(D, z, x, w, mean, rstd, gamma, sums, inv_n, train, dw, db, ws_bytes=None):
+    """dx = sum_r dw3x3_r^T(dz_r), dw [4, 9, C] += sum x dz_r per tap, db [4, C] += sum dz_r; dz_r = D_r + alpha_r + beta'_r z_r (training
+    statistics; mean / rstd / gamma [4, C], sums [4][2C]) or D_r"""
+    _require_cuda(D, z, x, w, dw, db)
+    N, H, W, Cc = x.shape
+    dx = torch.empty_like(x)
+    ws, wsb = workspace(_hip.lib().iseg_jpu_partials_bytes(N, H, W, Cc, 1), x.device)
+    if ws_bytes is not None:
+        wsb = ws_bytes
+    _hip.call("iseg_jpu_bnfold_dwconv3x4_bwd", ptr(D), ptr(z), ptr(x), ptr(w), ptr(mean), ptr(rstd), ptr(gamma), ptr(sums), float(inv_n), int(train),
+              ptr(dx), ptr(dw), ptr(db), N, H, W, Cc, dt(x), ptr(ws), wsb, stream())
     return dx
 
 

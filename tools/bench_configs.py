@@ -21,6 +21,7 @@ CONFIGS = {
     "cfg4_infer": ("vit_base_simple_decoder", 640, 1, False, "ViT-B/16 + SimpleDecoder 640x640, sliding window 512"),
     "cfg5": ("intern_image_base_aspp", 512, 8, True, "InternImage-B + ASPP 512x512"),
     "hrnet": ("hrnet_w32_aspp", 512, 8, True, "HRNet-W32 + ASPP 512x512 (not a BASELINE configuration)"),
+    "jpu": ("resnet18_jpu_aspp", 512, 16, True, "ResNet-18 + JointPyramidUpsampling + ASPP 512x512 (FastFCN; not a BASELINE configuration; ISEG_JPU_FUSED=1: fused tail)"),
     "v2": ("convnext_v2_tiny_aspp", 512, 16, True, "ConvNeXt-V2-T + ASPP 512x512 (not a BASELINE configuration: the next backbone family)"),
 }
 
