@@ -51,6 +51,7 @@ typedef struct ihipStream_t* iseg_stream_t; /* == hipStream_t */
 #define ISEG_ACT_MUL_AUX 5   /* v *= aux : backward of ISEG_ACT_GELU when the forward saved gelu'(pre) (pre_deriv = 1) */
 #define ISEG_ACT_SIGMOID 6   /* tf.nn.sigmoid (layers/nasfpn.py:304-311 global-attention gate); iseg_act_fwd / iseg_act_bwd only */
 #define ISEG_ACT_SWISH 7     /* tf.nn.silu / keras "swish": x sigmoid(x) (backbones/eva/swiglu.py:13, layers/nasfpn.py:289); iseg_act_fwd / _bwd only */
+#define ISEG_ACT_GELU_TANH 8 /* keras.activations.gelu(approximate=True): 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3))) (nlp/gemma/gemma_decoder_block.py:167-170); iseg_act_* / iseg_glu_* only */
 
 int iseg_version(void);
 /* copies the calling thread's last error message (NUL-terminated) into buf_h; returns its length */
@@ -1146,6 +1147,42 @@ int iseg_convnext_mlp_wgrad(const void* y, const float* mean, const float* rstd,
                             const void* dout, const float* rowscale, int64_t rows_per_group, const void* bw_tiled, const float* b1,
                             const float* W2, const float* b2, const float* gamma, float* dW1, float* db1, float* dW2, float* db2,
                             float* dgamma, int64_t M, int C, int dtype, void* ws, size_t ws_bytes, iseg_stream_t stream);
+
+/* Gemma text backbone (nlp/gemma).
+ * iseg_gemma_rope: rotary embedding of nlp/gemma/gemma_attention.py:96-114 on the packed projection rows qkv [rows = B * T][(nq + 2 nkv) h] =
+ *   [q heads | k heads | v heads] (row pitches ld_in / ld_out in elements; out == qkv: in place).  Per q / k head, with x1 = x[0:h/2], x2 = x[h/2:h]:
+ *   out[2i] = x1[i] cos - x2[i] sin, out[2i+1] = x2[i] cos + x1[i] sin (the reference's stack(..., axis=-1) + reshape: INTERLEAVED).  The v columns
+ *   are copied unchanged.  table fp32 [T][h] = [sin(t / 10000^(2i/h)), i < h/2 | cos(...)]; fp32 arithmetic, one rounding.  inverse = 1 applies
+ *   the transposed rotation (the backward pass: out[i] = g[2i] cos + g[2i+1] sin, out[h/2+i] = g[2i+1] cos - g[2i] sin). */
+int iseg_gemma_rope(const void* qkv, int64_t ld_in, void* out, int64_t ld_out, const float* table, int64_t rows, int T, int nq, int nkv, int h,
+                    int inverse, int dtype, iseg_stream_t stream);
+/* nlp/gemma/gemma_attention.py:116-151, gemma_decoder_block.py:114-136 -- causal grouped-query attention with a key-side padding mask:
+ *   out[b,t,n,:] = sum_s softmax_s(scale * q[b,t,n,:] . k[b,s,n / (nq/nkv),:]) v[b,s,n / (nq/nkv),:], over the keys s <= t with padding_mask[b,s] != 0.
+ * q / out / dout / dq [batch, T, nq h], k / v / dk / dv [batch, T, nkv h]: column ranges of a packed buffer or separate tensors, each with its
+ * row pitch in elements; padding_mask one byte per (b, s) or NULL (all visible).  The nq/nkv query heads of one key/value head are stacked as
+ * (nq/nkv) T query rows of one problem (row t * (nq/nkv) + j); online softmax over key tiles of 64, key tiles wholly above the diagonal are
+ * skipped, the value width is walked in slabs of 64 columns.  Nothing of size T x T is stored, no atomics, fixed summation order.  A query
+ * row with no visible key gives out = 0, lse2 = 0 and dq = 0; masked pairs contribute exactly 0 to dk and dv.
+ * Supported (iseg_gemma_attention_supported): bf16, h % 64 == 0, 64 <= h <= 256, nq % nkv == 0; any T >= 1; pitches multiples of 8 covering
+ * their rows, 16-byte aligned bases, scale > 0.  Anything else returns ISEG_ERR_UNSUPPORTED before any memory is touched.
+ * lse2 (NULL for inference) and the dsum scratch of the backward call hold iseg_gemma_attention_lse_elems floats: per (sample, key/value head)
+ * the stacked rows padded to a multiple of 64. */
+int iseg_gemma_attention_supported(int nq, int nkv, int h, int dtype);
+size_t iseg_gemma_attention_lse_elems(int64_t batch, int T, int nq, int nkv);
+int iseg_gemma_attention_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const uint8_t* padding_mask,
+                             void* out, int64_t ldo, float* lse2, int64_t batch, int T, int nq, int nkv, int h, float scale, int dtype,
+                             iseg_stream_t stream);
+/* gradient of the same lines; dq, dk, dv are overwritten (dk / dv already summed over the query heads of each group, in stacked-row order) */
+int iseg_gemma_attention_bwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const uint8_t* padding_mask,
+                             const void* out, int64_t ldo, const void* dout, int64_t lddo, const float* lse2, float* dsum, void* dq,
+                             int64_t lddq, void* dk, int64_t lddk, void* dv, int64_t lddv, int64_t batch, int T, int nq, int nkv, int h,
+                             float scale, int dtype, iseg_stream_t stream);
+/* nlp/gemma/gemma_backbone.py:152 -- gradient of the token-embedding lookup: dtable[id,:] += scale * sum over the n tokens with that id of dy[token,:],
+ * added in increasing token order.  sorted_ids [n] = the ids in stable ascending order, order [n] = the token each came from (both int64, a
+ * stable sort of the ids); dy [n, d] in `dtype`, dtable fp32 [vocab, d].  One workgroup per run of equal ids owns its row: rows of
+ * absent ids are not touched, no atomics. */
+int iseg_embedding_grad(const void* dy, const int64_t* sorted_ids, const int64_t* order, float* dtable, int64_t n, int64_t vocab, int d,
+                        float scale, int dtype, iseg_stream_t stream);
 
 #ifdef __cplusplus
 }

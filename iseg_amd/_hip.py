@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libiseg_hip.so")
 
 F32, BF16 = 0, 1
-ACT_NONE, ACT_RELU, ACT_GELU, ACT_GELU_GRAD, ACT_RELU_GRAD, ACT_MUL_AUX, ACT_SIGMOID, ACT_SWISH = 0, 1, 2, 3, 4, 5, 6, 7
+ACT_NONE, ACT_RELU, ACT_GELU, ACT_GELU_GRAD, ACT_RELU_GRAD, ACT_MUL_AUX, ACT_SIGMOID, ACT_SWISH, ACT_GELU_TANH = 0, 1, 2, 3, 4, 5, 6, 7, 8
 
 
 class HipLibraryMissing(RuntimeError):
@@ -289,6 +289,12 @@ SIGNATURES = {
     "iseg_convnext_mlp_fwd_ln": (_i, [_p, _p, _p, _f, _p, _p, _p, _p, _p, _p, _p, _l, _p, _p, _l, _i, _i, _p]),
     "iseg_convnext_mlp_wgrad_workspace_bytes": (_z, [_l, _i]),
     "iseg_convnext_mlp_wgrad": (_i, [_p, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _l, _i, _i, _p, _z, _p]),
+    "iseg_gemma_rope": (_i, [_p, _l, _p, _l, _p, _l, _i, _i, _i, _i, _i, _i, _p]),
+    "iseg_gemma_attention_supported": (_i, [_i, _i, _i, _i]),
+    "iseg_gemma_attention_lse_elems": (_z, [_l, _i, _i, _i]),
+    "iseg_gemma_attention_fwd": (_i, [_p, _l, _p, _l, _p, _l, _p, _p, _l, _p, _l, _i, _i, _i, _i, _f, _i, _p]),
+    "iseg_gemma_attention_bwd": (_i, [_p, _l, _p, _l, _p, _l, _p, _p, _l, _p, _l, _p, _p, _p, _l, _p, _l, _p, _l, _l, _i, _i, _i, _i, _f, _i, _p]),
+    "iseg_embedding_grad": (_i, [_p, _p, _p, _p, _l, _l, _i, _f, _i, _p]),
     "iseg_sgd_momentum_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _f, _i, _p, _f, _p, _f, _l, _p]),
 }
 

@@ -362,3 +362,24 @@ __device__ __forceinline__ float gelu_erf_grad(float x) {
     const float pdf = 0.39894228040143267794f * expf(-0.5f * x * x);
     return cdf + x * pdf;
 }
+
+// tanh-form GELU, as keras.activations.gelu(approximate=True) (nlp/gemma/gemma_decoder_block.py:167-170): value and derivative from one tanh
+__device__ __forceinline__ void gelu_tanh_both(float x, float& y, float& dy) {
+    constexpr float K = 0.79788456080286535588f, A = 0.044715f;      // sqrt(2 / pi)
+    const float xc = fminf(fmaxf(x, -10.f), 10.f);      // tanh is +-1 in fp32 long before: no inf * 0 at the ends of the range
+    const float x2 = xc * xc;
+    const float t = tanhf(K * fmaf(A * x2, xc, xc));
+    const float h = 0.5f * (1.0f + t);
+    y = x * h;
+    dy = fmaf(0.5f * xc * (1.0f - t * t), K * fmaf(3.0f * A, x2, 1.0f), h);
+}
+__device__ __forceinline__ float gelu_tanh(float x) {
+    float y, dy;
+    gelu_tanh_both(x, y, dy);
+    return y;
+}
+__device__ __forceinline__ float gelu_tanh_grad(float x) {
+    float y, dy;
+    gelu_tanh_both(x, y, dy);
+    return dy;
+}

@@ -336,6 +336,7 @@ template <bool FAST> __device__ __forceinline__ float act_value(float v, int act
         case ISEG_ACT_RELU: return fmaxf(v, 0.f);
         case ISEG_ACT_SIGMOID: return 1.f / (1.f + expf(-v));
         case ISEG_ACT_SWISH: return v / (1.f + expf(-v));
+        case ISEG_ACT_GELU_TANH: return gelu_tanh(v);
         default: return FAST ? gelu_poly(v) : gelu_erf(v);
     }
 }
@@ -352,6 +353,7 @@ template <bool FAST> __device__ __forceinline__ float act_deriv(float a, int act
             const float s = 1.f / (1.f + expf(-a));
             return s * (1.f + a * (1.f - s));
         }
+        case ISEG_ACT_GELU_TANH: return gelu_tanh_grad(a);
         default: return FAST ? gelu_poly_grad(a) : gelu_erf_grad(a);
     }
 }
@@ -933,7 +935,7 @@ static int layerscale_grads_slabs_impl(const float* slabs, int nslabs, const flo
 }
 
 extern "C" int iseg_act_fwd(const void* x, void* y, int64_t n, int act, int dtype, hipStream_t stream) {
-    ISEG_REQUIRE(x && y && (act == ISEG_ACT_RELU || act == ISEG_ACT_GELU || act == ISEG_ACT_SIGMOID || act == ISEG_ACT_SWISH), "iseg_act_fwd: bad arguments (act = %d)", act);
+    ISEG_REQUIRE(x && y && (act == ISEG_ACT_RELU || act == ISEG_ACT_GELU || act == ISEG_ACT_SIGMOID || act == ISEG_ACT_SWISH || act == ISEG_ACT_GELU_TANH), "iseg_act_fwd: bad arguments (act = %d)", act);
     if (n == 0) return ISEG_OK;
     const unsigned blocks = cap_blocks(ceil_div64(n, 8));
     return by_dtype(dtype, "iseg_act_fwd", [&](auto t) {
@@ -944,7 +946,7 @@ extern "C" int iseg_act_fwd(const void* x, void* y, int64_t n, int act, int dtyp
 }
 
 extern "C" int iseg_act_bwd(const void* dy, const void* aux, void* dx, int64_t n, int act, int dtype, hipStream_t stream) {
-    ISEG_REQUIRE(dy && aux && dx && (act == ISEG_ACT_RELU || act == ISEG_ACT_GELU || act == ISEG_ACT_SIGMOID || act == ISEG_ACT_SWISH), "iseg_act_bwd: bad arguments (act = %d)", act);
+    ISEG_REQUIRE(dy && aux && dx && (act == ISEG_ACT_RELU || act == ISEG_ACT_GELU || act == ISEG_ACT_SIGMOID || act == ISEG_ACT_SWISH || act == ISEG_ACT_GELU_TANH), "iseg_act_bwd: bad arguments (act = %d)", act);
     if (n == 0) return ISEG_OK;
     const unsigned blocks = cap_blocks(ceil_div64(n, 8));
     return by_dtype(dtype, "iseg_act_bwd", [&](auto t) {

@@ -70,6 +70,8 @@ template <bool FAST> __device__ __forceinline__ void glu_act(float g, int act, f
             a = gelu_erf(g);
             da = gelu_erf_grad(g);
         }
+    } else if (act == ISEG_ACT_GELU_TANH) {
+        gelu_tanh_both(g, a, da);
     } else {
         const float s = 1.f / (1.f + expf(-g));
         if (act == ISEG_ACT_SWISH) {
@@ -179,7 +181,7 @@ extern "C" int iseg_qkv_rope(const void* qkv, void* out, const float* q_bias, co
     });
 }
 
-static bool glu_act_ok(int act) { return act == ISEG_ACT_GELU || act == ISEG_ACT_SWISH || act == ISEG_ACT_SIGMOID; }
+static bool glu_act_ok(int act) { return act == ISEG_ACT_GELU || act == ISEG_ACT_SWISH || act == ISEG_ACT_SIGMOID || act == ISEG_ACT_GELU_TANH; }
 
 extern "C" int iseg_glu_fwd(const void* gate, int64_t ld_gate, const void* x, int64_t ld_x, void* out, int64_t ld_out, int64_t rows, int cols, int act,
                             int dtype, hipStream_t stream) {

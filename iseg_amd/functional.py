@@ -2743,7 +2743,7 @@ class _GluFn(Function):
         return dg.reshape(ctx.in_shape), dx.reshape(ctx.in_shape), None, None
 
 
-_GLU_ACTS = {"gelu": K.ACT_GELU, "swish": K.ACT_SWISH, "silu": K.ACT_SWISH, "sigmoid": K.ACT_SIGMOID}
+_GLU_ACTS = {"gelu": K.ACT_GELU, "swish": K.ACT_SWISH, "silu": K.ACT_SWISH, "sigmoid": K.ACT_SIGMOID, "gelu_tanh": K.ACT_GELU_TANH}
 
 
 def glu(gate, x, activation):
@@ -3287,6 +3287,239 @@ def scale_channels(x, gamma):
     if nn.dry_run():
         return _dry(x.shape, x)
     return _ScaleChannelsFn.apply(x, gamma)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# Gemma text backbone (nlp/gemma/*): embedding lookup, packed q | k | v projection, rotary embedding, causal grouped-query attention
+# ---------------------------------------------------------------------------------------------------------
+class _EmbeddingFn(Function):
+    """rows of the embedding table times a scalar (nlp/gemma/gemma_backbone.py:152-153); backward: iseg_embedding_grad over a stable sort of
+    the ids -- repeated tokens are added in token order, one workgroup per vocabulary row, no atomics"""
+
+    @staticmethod
+    def forward(ctx, ids, table, scale):
+        flat = ids.reshape(-1)
+        y = K.gather_rows(nn.w(table), flat.to(torch.int32), flat.numel())
+        if scale != 1.0:
+            y = K.axpby(y, y, alpha=scale, beta=0.0)
+        ctx.table, ctx.scale, ctx.ids = table, scale, flat
+        return y.reshape(*ids.shape, table.shape[1])
+
+    @staticmethod
+    def backward(ctx, dy):
+        table = ctx.table
+        if table.requires_grad:
+            sorted_ids, order = torch.sort(ctx.ids.to(torch.int64), stable=True)
+            K.embedding_grad(_c(dy).reshape(-1, table.shape[1]), sorted_ids, order, _grad(table), ctx.scale)
+            dist.grads_ready(table)
+        return None, None, None
+
+
+def embedding(ids, table, scale=1.0):
+    """table[ids] * scale: ids integer [...], table [vocab, d] parameter -> [..., d] in the compute dtype; `scale` is rounded to that type first
+    (gemma_backbone.py:153 casts sqrt(hidden_dim) to the activation type before the product)"""
+    dtype = nn.compute_dtype()
+    if nn.dry_run():
+        return torch.empty((*ids.shape, table.shape[1]), dtype=dtype, device=table.device)
+    return _EmbeddingFn.apply(ids, table, float(torch.tensor(float(scale)).to(dtype)))
+
+
+class _GemmaQkvFn(Function):
+    """x [B, T, d] against query/kernel [nq, d, h], key/kernel and value/kernel [nkv, d, h] (EinsumDense "btd,ndh->btnh",
+    nlp/gemma/gemma_attention.py:50-75) -> packed [B, T, (nq + 2 nkv) h] = [q heads | k heads | v heads]: strided-batch GEMMs, one problem per head,
+    written straight into their column ranges -- ONE launch when the three compute copies lie back to back in memory, else one per kernel"""
+
+    @staticmethod
+    def forward(ctx, x, Wq, Wk, Wv):
+        d = x.shape[-1]
+        x2 = _c(x).reshape(-1, d)
+        M = x2.shape[0]
+        h = Wq.shape[2]
+        heads = [Wq.shape[0], Wk.shape[0], Wv.shape[0]]
+        width = sum(heads) * h
+        out = torch.empty((M, width), dtype=x2.dtype, device=x2.device)
+        ws = [nn.w(W) for W in (Wq, Wk, Wv)]
+        es = ws[0].element_size()
+        joined = all(a.is_contiguous() for a in ws) and all(ws[i].data_ptr() + ws[i].numel() * es == ws[i + 1].data_ptr() for i in range(2))
+        runs = [(ws[0], sum(heads), 0)] if joined else [(ws[i], heads[i], sum(heads[:i]) * h) for i in range(3)]
+        for Wc, n, col in runs:
+            K.gemm(x2, Wc, out[:, col:], M, h, d, lda=d, ldb=h, ldd=width, a_kcontig=1, b_kcontig=0, batch=n, batch_inner=1, sa=(0, 0),
+                   sb=(d * h, 0), sd=(h, 0))
+        ctx.params = (Wq, Wk, Wv)
+        ctx.save_for_backward(x2)
+        return out.reshape(*x.shape[:-1], width)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x2,) = ctx.saved_tensors
+        M, d = x2.shape
+        dy2 = _c(dy).reshape(M, -1)
+        h = ctx.params[0].shape[2]
+        dx = torch.empty((M, d), dtype=torch.float32, device=x2.device) if ctx.needs_input_grad[0] else None
+        col, first = 0, True
+        for W in ctx.params:      # one head at a time: the weight gradient into its fp32 slice, the data gradient summed in fp32
+            Wc = nn.w(W)
+            for n in range(W.shape[0]):
+                dyn = dy2[:, col:col + h]
+                if W.requires_grad:
+                    K.dense_wgrad(x2, dyn, _grad(W)[n])
+                if dx is not None:
+                    K.dense_dgrad(dyn, Wc[n], out=dx, accumulate=not first)
+                    first = False
+                col += h
+        dist.grads_ready(*ctx.params)
+        if dx is not None:
+            dx = (dx if x2.dtype == torch.float32 else K.cast(dx, x2.dtype)).reshape(*dy.shape[:-1], d)
+        return dx, None, None, None
+
+
+def gemma_qkv(x, Wq, Wk, Wv):
+    _check_act_dtype(x)
+    if nn.dry_run():
+        return _dry((*x.shape[:-1], (Wq.shape[0] + Wk.shape[0] + Wv.shape[0]) * Wq.shape[2]), x)
+    return _GemmaQkvFn.apply(x, Wq, Wk, Wv)
+
+
+_GEMMA_ROPE_TABLES = {}
+
+
+def gemma_rope_table(T, h, device):
+    """fp32 [T, h] = [sin(t / 10000^(2i/h)) | cos(...)], i < h/2 (nlp/gemma/gemma_attention.py:99-107), built once per (T, h, device).  The angles
+    are formed in fp32 whatever the storage type: in bf16 (the reference's compute dtype) positions above 256 are not representable"""
+    key = (int(T), int(h), str(device))
+    tab = _GEMMA_ROPE_TABLES.get(key)
+    if tab is None:
+        exponents = (2.0 / h) * torch.arange(h // 2, dtype=torch.float32)
+        timescale = torch.pow(torch.tensor(10000.0), exponents)
+        radians = torch.arange(T, dtype=torch.float32)[:, None] / timescale[None, :]
+        tab = _GEMMA_ROPE_TABLES[key] = torch.cat([torch.sin(radians), torch.cos(radians)], dim=1).contiguous().to(device)
+    return tab
+
+
+class _GemmaRopeFn(Function):
+    """the interleaved rotary embedding on the q and k heads of packed rows (csrc/gemma.hip; gemma_attention.py:96-114); backward: the transposed
+    rotation on the gradient"""
+
+    @staticmethod
+    def forward(ctx, qkv, table, nq, nkv, h):
+        ctx.table, ctx.geom = table, (qkv.shape[1], nq, nkv, h)
+        src = _c(qkv)
+        return K.gemma_rope(src, table, qkv.shape[1], nq, nkv, h, out=torch.empty_like(src))
+
+    @staticmethod
+    def backward(ctx, d):
+        T, nq, nkv, h = ctx.geom
+        d = _c(d)
+        return K.gemma_rope(d, ctx.table, T, nq, nkv, h, inverse=True, out=torch.empty_like(d)), None, None, None, None
+
+
+def gemma_rope(qkv, nq, nkv, h):
+    """qkv [B, T, (nq + 2 nkv) h], positions 0 .. T-1: out[2i] = x1 cos - x2 sin, out[2i+1] = x2 cos + x1 sin per q / k head, v unchanged"""
+    _check_act_dtype(qkv)
+    if nn.dry_run():
+        return qkv
+    if qkv.dim() != 3 or qkv.shape[2] != (nq + 2 * nkv) * h or h % 2:
+        raise ValueError(f"gemma_rope: {tuple(qkv.shape)} is not [B, T, ({nq} + 2 * {nkv}) * {h}]")
+    return _GemmaRopeFn.apply(qkv, gemma_rope_table(qkv.shape[1], h, qkv.device), int(nq), int(nkv), int(h))
+
+
+class _GemmaAttentionFn(Function):
+    """causal grouped-query attention with a key padding mask on the fused kernels of csrc/gemma.hip: online softmax, one log-sum-exp float per
+    (token, query head), probabilities recomputed in the backward kernels; nothing of size T x T"""
+
+    @staticmethod
+    def forward(ctx, qkv, mask_u8, nq, nkv, h, scale):
+        qkv = _c(qkv)
+        out, lse = K.gemma_attention_fwd(qkv, mask_u8, nq, nkv, h, scale, True)
+        ctx.cfg = (nq, nkv, h, scale)
+        ctx.mask = mask_u8
+        ctx.save_for_backward(qkv, out, lse)
+        return out
+
+    @staticmethod
+    def backward(ctx, dO):
+        qkv, out, lse = ctx.saved_tensors
+        nq, nkv, h, scale = ctx.cfg
+        return K.gemma_attention_bwd(qkv, ctx.mask, out, _c(dO), lse, nq, nkv, h, scale), None, None, None, None, None
+
+
+class _GemmaRepeatKVFn(Function):
+    """packed [q | k | v] with nkv key/value heads -> [q | k' | v'] with nq: query head n gets key/value head n // (nq / nkv) (the composed route's
+    way to the equal-head-count operator); backward: the group's gradients added back in head order"""
+
+    @staticmethod
+    def forward(ctx, qkv, nq, nkv, h):
+        B, T, W = qkv.shape
+        src = _c(qkv).reshape(B * T, W)
+        g, Cq = nq // nkv, nq * h
+        out = torch.empty((B * T, 3 * Cq), dtype=src.dtype, device=src.device)
+        K.copy2d(src, W, out, 3 * Cq, B * T, Cq)
+        for part in range(2):
+            for n in range(nq):
+                K.copy2d(src[:, Cq + (part * nkv + n // g) * h:], W, out[:, (1 + part) * Cq + n * h:], 3 * Cq, B * T, h)
+        ctx.geom = (nq, nkv, h)
+        return out.reshape(B, T, 3 * Cq)
+
+    @staticmethod
+    def backward(ctx, d):
+        nq, nkv, h = ctx.geom
+        B, T, _ = d.shape
+        g, Cq, W = nq // nkv, nq * h, (nq + 2 * nkv) * h
+        d2 = _c(d).reshape(B * T, 3 * Cq)
+        out = torch.empty((B * T, W), dtype=d2.dtype, device=d2.device)
+        K.copy2d(d2, 3 * Cq, out, W, B * T, Cq)
+        for part in range(2):
+            for kv in range(nkv):
+                acc = None
+                for j in range(g):
+                    piece = torch.empty((B * T, h), dtype=d2.dtype, device=d2.device)
+                    K.copy2d(d2[:, (1 + part) * Cq + (kv * g + j) * h:], 3 * Cq, piece, h, B * T, h)
+                    acc = piece if acc is None else K.axpby(acc, piece)
+                K.copy2d(acc, h, out[:, Cq + (part * nkv + kv) * h:], W, B * T, h)
+        return out.reshape(B, T, W), None, None, None
+
+
+def _gemma_visibility(padding_mask, B, T, device):
+    """bool [B, T, T]: key s visible to query t iff s <= t and padding_mask[b, s] != 0 (gemma_decoder_block.py:114-136)"""
+    vis = torch.ones((T, T), dtype=torch.bool, device=device).tril()[None].expand(B, T, T)
+    if padding_mask is not None:
+        vis = vis & (padding_mask.reshape(B, 1, T) != 0)
+    return vis
+
+
+def gemma_attention_fused(nq, nkv, h, dtype):
+    """True where gemma_attention_core takes the fused kernels: supported shape and type, and ISEG_GEMMA_FUSED unset or not "0" """
+    return os.environ.get("ISEG_GEMMA_FUSED", "1") != "0" and nq % max(nkv, 1) == 0 and K.gemma_attention_supported(nq, nkv, h, dtype)
+
+
+def gemma_attention_core(qkv, padding_mask, nq, nkv, h, *, dropout_rate=0.0, training=False):
+    """qkv [B, T, (nq + 2 nkv) h] = [q heads | k heads | v heads] (after the rotary embedding), padding_mask [B, T] (non-zero = real token) or None
+    -> [B, T, nq h]: softmax(h^-0.5 q k^T) v per query head n on key/value head n // (nq / nkv), over the keys s <= t with padding_mask[b, s] != 0,
+    softmax in fp32 (nlp/gemma/gemma_attention.py:116-151); a query row with no visible key gives zeros and passes no gradient (:189-195).
+    Fused route (bf16, h in 64, 128, 192, 256, nq % nkv == 0, no dropout on the probabilities in effect, ISEG_GEMMA_FUSED unset or not "0"):
+    csrc/gemma.hip.  Composed route (everything else, and the yardstick of the fused one): K and V repeated per group, attention_packed with an additive fp32 mask per sample, rows without
+    a visible key wiped."""
+    _check_act_dtype(qkv)
+    if qkv.dim() != 3 or qkv.shape[2] != (nq + 2 * nkv) * h or nq % nkv:
+        raise ValueError(f"gemma_attention_core: {tuple(qkv.shape)} is not [B, T, ({nq} + 2 * {nkv}) * {h}] with nq a multiple of nkv")
+    B, T, _ = qkv.shape
+    if nn.dry_run():
+        return _dry((B, T, nq * h), qkv)
+    scale = float(h) ** -0.5
+    rate = float(dropout_rate) if training else 0.0
+    if rate <= 0 and gemma_attention_fused(nq, nkv, h, qkv.dtype):
+        mask_u8 = None if padding_mask is None else (padding_mask.reshape(B, T) != 0).to(torch.uint8).contiguous()
+        if not (torch.is_grad_enabled() and qkv.requires_grad):
+            return K.gemma_attention_fwd(_c(qkv), mask_u8, int(nq), int(nkv), int(h), scale, False)[0]
+        return _GemmaAttentionFn.apply(qkv, mask_u8, int(nq), int(nkv), int(h), scale)
+    vis = _gemma_visibility(padding_mask, B, T, qkv.device)
+    additive = torch.where(vis, 0.0, -1e30).to(torch.float32).contiguous()
+    wide = _GemmaRepeatKVFn.apply(qkv, int(nq), int(nkv), int(h)) if nkv != nq else qkv
+    y = attention_packed(wide, nq, nq * h, nq * h, scale, mask=additive, windows=B, dropout_rate=rate, training=rate > 0)
+    if padding_mask is None:      # causal only: every row sees itself
+        return y
+    alive = vis.any(dim=-1).to(torch.float32).reshape(B * T).contiguous()
+    return _RowScaleFn.apply(y.reshape(B * T, nq * h), alive).reshape(B, T, nq * h)
 
 
 _FLIP_CACHE = {}

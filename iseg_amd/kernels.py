@@ -9,7 +9,7 @@ import ctypes as C
 import torch
 
 from . import _hip
-from ._hip import F32, BF16, ACT_NONE, ACT_RELU, ACT_GELU, ACT_GELU_GRAD, ACT_RELU_GRAD, ACT_MUL_AUX, ACT_SIGMOID, ACT_SWISH, GemmArgs  # noqa: F401
+from ._hip import F32, BF16, ACT_NONE, ACT_RELU, ACT_GELU, ACT_GELU_GRAD, ACT_RELU_GRAD, ACT_MUL_AUX, ACT_SIGMOID, ACT_SWISH, ACT_GELU_TANH, GemmArgs  # noqa: F401
 
 _DT = {torch.float32: F32, torch.bfloat16: BF16}
 
@@ -2135,3 +2135,63 @@ def deferred_reductions(flat_grad, arena_bytes=96 << 20):
 def deferred_flush():
     if _DEFER["active"]:
         _hip.call("iseg_deferred_flush", stream())
+
+
+# ---------------------------------------------------------------------------------------------------------
+# Gemma text backbone (csrc/gemma.hip)
+# ---------------------------------------------------------------------------------------------------------
+def gemma_rope(qkv, table, T, nq, nkv, h, inverse=False, out=None):
+    """packed projection rows [B * T, (nq + 2 nkv) h]: the interleaved rotary embedding of nlp/gemma/gemma_attention.py:96-114 on the q and k
+    heads, v copied; table fp32 [T, h] = [sin | cos]; out=None: in place"""
+    _require_cuda(qkv, table)
+    out = qkv if out is None else out
+    W = (nq + 2 * nkv) * h
+    _hip.call("iseg_gemma_rope", ptr(qkv), W, ptr(out), W, ptr(table), qkv.numel() // W, T, nq, nkv, h, int(inverse), dt(qkv), stream())
+    return out
+
+
+def gemma_attention_supported(nq, nkv, h, dtype):
+    return dtype == torch.bfloat16 and bool(_hip.lib().iseg_gemma_attention_supported(int(nq), int(nkv), int(h), BF16))
+
+
+def _gemma_split(qkv, nq, nkv, h):
+    """column ranges (q, k, v) of a contiguous packed [B, T, (nq + 2 nkv) h] tensor and their common row pitch"""
+    Cq, Ck = nq * h, nkv * h
+    return qkv[:, :, :Cq], qkv[:, :, Cq:Cq + Ck], qkv[:, :, Cq + Ck:], qkv.shape[2]
+
+
+def gemma_attention_fwd(qkv, mask_u8, nq, nkv, h, scale, want_lse):
+    """causal grouped-query attention on packed rows qkv [B, T, (nq + 2 nkv) h] (contiguous), mask_u8 [B, T] uint8 or None -> ([B, T, nq h], lse)"""
+    _require_cuda(qkv)
+    B, T, _ = qkv.shape
+    L = _hip.lib()
+    q, k, v, ld = _gemma_split(qkv, nq, nkv, h)
+    out = torch.empty((B, T, nq * h), dtype=qkv.dtype, device=qkv.device)
+    lse = torch.empty(int(L.iseg_gemma_attention_lse_elems(B, T, nq, nkv)), dtype=torch.float32, device=qkv.device) if want_lse else None
+    _hip.check(L.iseg_gemma_attention_fwd(ptr(q), ld, ptr(k), ld, ptr(v), ld, ptr(mask_u8), ptr(out), nq * h, ptr(lse), B, T, nq, nkv, h, float(scale),
+                                          dt(qkv), stream()), "iseg_gemma_attention_fwd")
+    return out, lse
+
+
+def gemma_attention_bwd(qkv, mask_u8, out, dout, lse, nq, nkv, h, scale):
+    """gradient of gemma_attention_fwd towards the packed rows: [B, T, (nq + 2 nkv) h]"""
+    _require_cuda(qkv, out, dout, lse)
+    B, T, _ = qkv.shape
+    L = _hip.lib()
+    q, k, v, ld = _gemma_split(qkv, nq, nkv, h)
+    dqkv = torch.empty_like(qkv)
+    dq, dk, dv, _ = _gemma_split(dqkv, nq, nkv, h)
+    dsum = torch.empty(int(L.iseg_gemma_attention_lse_elems(B, T, nq, nkv)), dtype=torch.float32, device=qkv.device)
+    _hip.check(L.iseg_gemma_attention_bwd(ptr(q), ld, ptr(k), ld, ptr(v), ld, ptr(mask_u8), ptr(out), nq * h, ptr(dout), nq * h, ptr(lse), ptr(dsum),
+                                          ptr(dq), ld, ptr(dk), ld, ptr(dv), ld, B, T, nq, nkv, h, float(scale), dt(qkv), stream()),
+               "iseg_gemma_attention_bwd")
+    return dqkv
+
+
+def embedding_grad(dy2d, sorted_ids, order, dtable, scale):
+    """dtable[id] += scale * sum of the rows of dy2d whose token has that id, in token order (sorted_ids, order: a stable sort of the ids);
+    rows of absent ids keep their contents"""
+    _require_cuda(dy2d, sorted_ids, order, dtable)
+    n, d = dy2d.shape
+    _hip.call("iseg_embedding_grad", ptr(dy2d), ptr(sorted_ids), ptr(order), ptr(dtable), n, dtable.shape[0], d, float(scale), dt(dy2d), stream())
+    return dtable
