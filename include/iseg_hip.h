@@ -531,6 +531,48 @@ int iseg_argmax_confusion(const float* logits, const int32_t* labels, int64_t P,
                           unsigned long long* cm, iseg_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * metrics/confusion_matrix.py:65-143 confusion_matrix and :146-231 batch_confusion_matrix (tf.scatter_nd of the weights at
+ * [b, label, prediction]), the arithmetic under metrics/mean_iou.py:16-55 get_class_confusion_matrix / get_batch_class_confusion_matrix
+ * and :112-130 MeanIOU.update_state(y_true, y_pred, sample_weight), from label and prediction MAPS (iseg_argmax_confusion takes logits).
+ *   labels, preds [batch, n] int32;  weights [batch, n]: NULL (ISEG_CM_W_NONE), one byte per element (ISEG_CM_W_U8: uint8 / bool) or fp32
+ *   cm [batch, C, C] int64, row = label, column = prediction; accumulate = 0 clears it first (stream-ordered), 1 adds to it
+ *   counters [8] uint64, ADDED to (the caller clears them)
+ * Per element (b, i), in this order:
+ *   - use_ignore and label == ignore_label: skipped, nothing else about it is examined;
+ *   - each of these that holds bumps its counter, and the element then contributes nothing (the reference's assertions :115-132, which
+ *     raise; this entry point counts and goes on):  counters[0] label < 0;  [1] prediction < 0;  [2] label >= C;  [3] prediction >= C;
+ *     [4] (F32) the weight is not finite or |w * 2^w_exp| >= 2^39;
+ *   - counters[5] (F32) w * 2^w_exp is no integer: an element that passed the checks above is still counted, rounded to nearest even;
+ *   - counters[6..7] are not touched;
+ *   - cm[b][label][pred] += 1 (NONE), the byte's value 0..255 (U8), or llrint((double)w * 2^w_exp) (F32).
+ * Integer arithmetic only: the scale is a power of two (exact), the bins are 64-bit, integer sums do not depend on their order.  Two runs,
+ * or any permutation of an image's elements, give the same bits; no floating-point atomic is used.  The caller picks w_exp = 38 - ex with
+ * max |w| = m * 2^ex, m in [0.5, 1) (frexp; 0 when every weight is 0): max |w| * 2^w_exp lies in [2^37, 2^38), and with n <= 2^24 elements
+ * per image no bin reaches 2^62.  The value in fixed point differs from the real sum of a bin's k weights by at most k * 2^-(w_exp + 1),
+ * i.e. k * max|w| * 2^-38.  iseg_confusion_absmax_f32 gives max |w|: max_bits[0] = the largest bit pattern of |w_i| (for non-negative
+ * floats the integer order is the float order, so the integer atomic maximum is exact); a NaN or Inf shows as a pattern >= 0x7f800000.
+ * Limits: 1 <= C <= 256 in every mode; |w_exp| <= 1000; F32: n <= ISEG_CM_F32_MAX_N, else ISEG_STATUS_UNSUPPORTED before any memory is touched;
+ * NONE / U8: a workgroup counts the elements it sees of one image in 32-bit bins, so with gx = min(ceil(n / ISEG_CM_SLICE),
+ * max(1, cap / min(batch, cap))) workgroups per image, ceil(ceil(n / ISEG_CM_SLICE) / gx) * ISEG_CM_SLICE must not exceed
+ * 16 843 009 = floor((2^32 - 1) / 255).  cap is the number of workgroups the 256 CUs hold at once with the histogram's LDS, at most four per CU:
+ * ISEG_CM_GRID_CAP up to C = 101 (C = 71 with fp32 weights), 256 from C = 144 (102) on.  So every n <= 16 842 752 passes at any batch and any C (2^24 + 5 included), and
+ * n <= 2^32 at batch 1; beyond, ISEG_STATUS_UNSUPPORTED.  Argument errors (ISEG_STATUS_ARG, nothing launched): a null labels / preds / cm / counters, batch <= 0, n <= 0,
+ * C outside 1..256, an unknown wmode, weights == NULL with wmode != 0.  No workspace: cm and counters are all the launcher needs.
+ * iseg_confusion_supported is pure host: 1 <= C <= 256 and wmode in {0, 1, 2}.
+ * --------------------------------------------------------------------------------------------------------- */
+#define ISEG_CM_W_NONE 0   /* every element counts 1 */
+#define ISEG_CM_W_U8   1   /* weights: one byte per element, its value (0..255) is added */
+#define ISEG_CM_W_F32  2   /* weights: fp32, accumulated as fixed point (above) */
+#define ISEG_CM_SLICE 4096          /* elements of one image a workgroup consumes per trip of its loop */
+#define ISEG_CM_GRID_CAP 1024       /* workgroups per launch, at most (fewer where a CU holds fewer than four histograms) */
+#define ISEG_CM_F32_MAX_N 16777216  /* 2^24 */
+int iseg_confusion_supported(int C, int wmode);
+int iseg_confusion_absmax_f32(const float* w, int64_t n, uint32_t* max_bits, iseg_stream_t stream);
+int iseg_confusion_batched(const int32_t* labels, const int32_t* preds, const void* weights, int wmode, int w_exp, int64_t batch, int64_t n,
+                           int C, int use_ignore, int ignore_label, long long* cm, int accumulate, unsigned long long* counters,
+                           iseg_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * losses/ohem.py:11-39 ohem_selector -- online hard example mining on the per-position loss vector, restated literally (the file carries a
  * "WIP" comment, yet core_model.py:480-514 hands get_ohem_fn(thresh) to the main output's cross-entropy as post_compute_fn).
  *

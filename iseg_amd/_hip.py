@@ -249,6 +249,9 @@ SIGNATURES = {
                            _p]),
     "iseg_ccl_label": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p]),
     "iseg_argmax_confusion": (_i, [_p, _p, _l, _i, _i, _p, _p, _p]),
+    "iseg_confusion_supported": (_i, [_i, _i]),
+    "iseg_confusion_absmax_f32": (_i, [_p, _l, _p, _p]),
+    "iseg_confusion_batched": (_i, [_p, _p, _p, _i, _i, _l, _l, _i, _i, _i, _p, _i, _p, _p]),
     "iseg_grad_sqnorm": (_i, [_p, _p, _p, _p, _p, _p, _i, _p, _p, _p, _l, _i, _p]),
     "iseg_adamw_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _f, _f, _f, _p, _f, _p, _f, _l, _p]),
     "iseg_augment_params_ints": (_i, []),

@@ -1523,6 +1523,78 @@ def argmax_confusion(logits2d, labels1d, ignore_label, cm=None, want_pred=False)
     return pred
 
 
+CM_W_NONE, CM_W_U8, CM_W_F32 = 0, 1, 2
+CM_SLICE, CM_GRID_CAP, CM_F32_MAX_N = 4096, 1024, 1 << 24      # ISEG_CM_SLICE, ISEG_CM_GRID_CAP, ISEG_CM_F32_MAX_N of the header
+CM_COUNTERS = 8
+
+
+def confusion_supported(Cc, wmode):
+    return bool(_hip.lib().iseg_confusion_supported(int(Cc), int(wmode)))
+
+
+def confusion_weight_exponent(max_abs):
+    """w_exp of iseg_confusion_batched for fp32 weights whose largest magnitude is max_abs (finite, >= 0): 38 - ex with max_abs = m * 2^ex,
+    m in [0.5, 1), so that max_abs * 2^w_exp lies in [2^37, 2^38); 0 when every weight is 0"""
+    import math
+
+    max_abs = float(max_abs)
+    if not math.isfinite(max_abs) or max_abs < 0:
+        raise ValueError(f"confusion_weight_exponent: a finite, non-negative maximum, got {max_abs}")
+    return 38 - math.frexp(max_abs)[1] if max_abs else 0
+
+
+def confusion_absmax(weights):
+    """max |w| of a contiguous fp32 tensor (csrc/confusion.hip: an integer maximum over the bit patterns, exact and order-independent) as a
+    Python float: inf or nan when a weight is not finite.  Reads four bytes back: a host synchronisation."""
+    import struct
+
+    _require_cuda(weights)
+    if weights.dtype != torch.float32 or not weights.is_contiguous():
+        raise TypeError("confusion_absmax: a contiguous float32 tensor")
+    if weights.numel() == 0:
+        return 0.0
+    bits = torch.empty(1, dtype=torch.int32, device=weights.device)
+    _hip.call("iseg_confusion_absmax_f32", ptr(weights), weights.numel(), ptr(bits), stream())
+    return struct.unpack("<f", struct.pack("<I", int(bits.item()) & 0xFFFFFFFF))[0]
+
+
+def confusion_batched(labels, preds, Cc, *, weights=None, w_exp=0, ignore_label=None, cm=None, accumulate=False, counters=None):
+    """iseg_confusion_batched (csrc/confusion.hip): labels, preds [B, n] int32 maps; weights None, [B, n] uint8 / bool (each element adds its
+    byte) or [B, n] float32 (each adds llrint(w * 2^w_exp)); ignore_label None or the label that is skipped without a look at the rest.
+    cm [B, C, C] int64 (any shape of B*C*C elements; made here when None), cleared first unless accumulate; counters [8] int64, added to (zeros
+    when None): labels < 0, predictions < 0, labels >= C, predictions >= C, weights not finite or out of range, weights that were rounded.
+    Nothing is read back.  returns (cm, counters)"""
+    if labels.dim() != 2 or labels.shape != preds.shape:
+        raise ValueError(f"confusion_batched: labels and preds are [B, n] of one shape, got {tuple(labels.shape)} and {tuple(preds.shape)}")
+    _require_cuda(labels, preds, weights, cm, counters)
+    if labels.dtype != torch.int32 or preds.dtype != torch.int32 or not (labels.is_contiguous() and preds.is_contiguous()):
+        raise TypeError("confusion_batched: contiguous int32 labels and preds")
+    B, n = labels.shape
+    wmode = CM_W_NONE
+    if weights is not None:
+        if weights.shape != labels.shape or not weights.is_contiguous():
+            raise ValueError(f"confusion_batched: weights are contiguous and of the labels' shape, got {tuple(weights.shape)}")
+        if weights.dtype in (torch.uint8, torch.bool):
+            wmode = CM_W_U8
+        elif weights.dtype == torch.float32:
+            wmode = CM_W_F32
+        else:
+            raise TypeError(f"confusion_batched: weights are uint8, bool or float32, got {weights.dtype}")
+    dev = labels.device
+    if cm is None:
+        cm = torch.empty(B, Cc, Cc, dtype=torch.int64, device=dev)
+        accumulate = False
+    elif cm.dtype != torch.int64 or cm.numel() != B * Cc * Cc or not cm.is_contiguous():
+        raise ValueError(f"confusion_batched: cm is a contiguous int64 tensor of {B} x {Cc} x {Cc} elements")
+    if counters is None:
+        counters = torch.zeros(CM_COUNTERS, dtype=torch.int64, device=dev)
+    elif counters.dtype != torch.int64 or counters.numel() != CM_COUNTERS or not counters.is_contiguous():
+        raise ValueError(f"confusion_batched: counters is a contiguous int64 [{CM_COUNTERS}]")
+    _hip.call("iseg_confusion_batched", ptr(labels), ptr(preds), ptr(weights), wmode, int(w_exp), B, n, int(Cc), int(ignore_label is not None),
+              int(ignore_label or 0), ptr(cm), int(bool(accumulate)), ptr(counters), stream())
+    return cm, counters
+
+
 # ---------------------------------------------------------------------------------------------------------
 # replace_nan_or_inf, GroupNorm, RMSNorm, pooling (csrc/misc.hip)
 # ---------------------------------------------------------------------------------------------------------
