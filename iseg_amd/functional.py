@@ -21,11 +21,22 @@ def _grad(p):
     return p.grad
 
 
-def _param_grad(p, *shape):
-    """the gradient buffer of a trainable Parameter (viewed as `shape` when given); None for an absent or a frozen one"""
-    if p is None or not p.requires_grad:
+def _param_grad(p, *shape, scratch=False):
+    """where a backward body writes the gradient of Parameter p (viewed as `shape` when given): the gradient buffer of a trainable one.  A
+    frozen (or absent) one receives no gradient: None -- or, for a launcher that takes no null destination (scratch=True), an fp32 tensor
+    that nobody reads"""
+    if p is not None and p.requires_grad:
+        g = _grad(p)
+    elif p is None or not scratch:
         return None
-    return _grad(p).reshape(shape) if shape else _grad(p)
+    else:
+        g = torch.zeros(p.shape, dtype=torch.float32, device=p.device)
+    return g.reshape(shape) if shape else g
+
+
+def _grad_out(p, *shape):
+    """_param_grad for a launcher that takes no null destination"""
+    return _param_grad(p, *shape, scratch=True)
 
 
 def _c(t):
@@ -290,11 +301,13 @@ class _LnMlpResidualFn(Function):
         ln = (mean, rstd, ln_gamma.data, ln_beta.data)
         dx = None
         if ctx.needs_input_grad[0]:
-            dln = K.convnext_mlp_bwd_data_ln(x2, do2, bw, b1.data, ln, _grad(ln_gamma), _grad(ln_beta), rowscale, ctx.rpg)
+            dln = K.convnext_mlp_bwd_data_ln(x2, do2, bw, b1.data, ln, _grad_out(ln_gamma), _grad_out(ln_beta), rowscale, ctx.rpg)
             dx = K.axpby(do2, dln, 1.0, 1.0, out=dln).reshape(dout.shape)      # + the skip connection's share
         else:      # (the LayerNorm parameter gradients come out of the chain kernel's epilogue)
-            K.convnext_mlp_bwd_data_ln(x2, do2, bw, b1.data, ln, _grad(ln_gamma), _grad(ln_beta), rowscale, ctx.rpg)
-        K.convnext_mlp_wgrad(x2, do2, bw, b1.data, W2.data, b2.data, None, _grad(W1), _grad(b1), _grad(W2), _grad(b2), None, rowscale, ctx.rpg, ln=ln)
+            K.convnext_mlp_bwd_data_ln(x2, do2, bw, b1.data, ln, _grad_out(ln_gamma), _grad_out(ln_beta), rowscale, ctx.rpg)
+        if any(p.requires_grad for p in (W1, b1, W2, b2)):
+            K.convnext_mlp_wgrad(x2, do2, bw, b1.data, W2.data, b2.data, None, _grad_out(W1), _grad_out(b1), _grad_out(W2), _grad_out(b2), None, rowscale,
+                                 ctx.rpg, ln=ln)
         dist.grads_ready(ln_gamma, ln_beta, W1, b1, W2, b2)
         return (dx,) + (None,) * 8
 
@@ -601,8 +614,8 @@ class _DWConvFn(Function):
         W, b, dil, pad = ctx.W, ctx.b, ctx.dil, ctx.pad
         Kk, C = W.shape[0], W.shape[2]
         dyc = _c(dy)
-        if W.requires_grad:
-            K.dwconv2d_bwd_weight(xc, dyc, _grad(W).reshape(Kk * Kk, C), _grad(b) if b is not None else None, Kk, dil, pad, pad)
+        if W.requires_grad or (b is not None and b.requires_grad):
+            K.dwconv2d_bwd_weight(xc, dyc, _grad_out(W, Kk * Kk, C), _grad_out(b) if b is not None else None, Kk, dil, pad, pad)
         dx = None
         if ctx.needs_input_grad[0]:
             padb = (Kk - 1) * dil - pad
@@ -630,8 +643,8 @@ class _DWConvStridedFn(Function):
         W, b, dil, stride = ctx.W, ctx.b, ctx.dil, ctx.stride
         Kk, C = W.shape[0], W.shape[2]
         dyc = _c(dy)
-        if W.requires_grad:
-            K.dwconv2d_strided_bwd_weight(xc, dyc, _grad(W).reshape(Kk * Kk, C), _grad(b) if b is not None else None, Kk, stride, dil)
+        if W.requires_grad or (b is not None and b.requires_grad):
+            K.dwconv2d_strided_bwd_weight(xc, dyc, _grad_out(W, Kk * Kk, C), _grad_out(b) if b is not None else None, Kk, stride, dil)
         dx = None
         if ctx.needs_input_grad[0]:
             dx = K.dwconv2d_strided_bwd_data(dyc, W.data.reshape(Kk * Kk, C), Kk, stride, dil, xc.shape[1], xc.shape[2])
@@ -671,7 +684,7 @@ class _LayerNormFn(Function):
     def backward(ctx, dy):
         x2, mean, rstd = ctx.saved_tensors
         C = x2.shape[-1]
-        dx = K.layernorm_bwd(_c(dy).reshape(-1, C), x2, ctx.gamma.data, mean, rstd, _grad(ctx.gamma), _grad(ctx.beta))
+        dx = K.layernorm_bwd(_c(dy).reshape(-1, C), x2, ctx.gamma.data, mean, rstd, _grad_out(ctx.gamma), _grad_out(ctx.beta))
         dist.grads_ready(ctx.gamma, ctx.beta)
         return dx.reshape(dy.shape), None, None, None
 
@@ -698,7 +711,7 @@ class _LayerNormPostFn(Function):
         gamma, beta, colscale = ctx.params
         C = x2.shape[1]
         want_cs = colscale is not None and colscale.requires_grad
-        dx = K.layernorm_post_bwd(_c(dy).reshape(-1, C), x2, gamma.data, beta.data, mean, rstd, _grad(gamma), _grad(beta),
+        dx = K.layernorm_post_bwd(_c(dy).reshape(-1, C), x2, gamma.data, beta.data, mean, rstd, _grad_out(gamma), _grad_out(beta),
                                   colscale=colscale.data if colscale is not None else None, dcolscale=_grad(colscale) if want_cs else None,
                                   rowscale=rowscale, rows_per_group=ctx.rpg)
         dist.grads_ready(gamma, beta, colscale) if colscale is not None else dist.grads_ready(gamma, beta)
@@ -1748,17 +1761,19 @@ class _ConvNeXtBlockFn(Function):
             # and the column sums of dbr ride both (csrc/mlp_wgrad.hip) -- replaces rowscale + colsum + chain + two weight-gradient GEMMs + their
             # split-K sums + layerscale_grads
             y1m, ln = y1.reshape(M, C), (mean, rstd, p.ln_gamma.data, p.ln_beta.data)
-            dy1 = K.convnext_mlp_bwd_data_ln(y1m, do2, h, p.b1.data, ln, _grad(p.ln_gamma), _grad(p.ln_beta), dp_mask, H * W)
-            K.convnext_mlp_wgrad(y1m, do2, h, p.b1.data, p.w2.data, p.b2.data, p.gamma.data if p.gamma is not None else None,
-                                 _grad(p.w1), _grad(p.b1), _grad(p.w2), _grad(p.b2), _grad(p.gamma) if p.gamma is not None else None, dp_mask,
-                                 H * W, ln=ln)
+            dy1 = K.convnext_mlp_bwd_data_ln(y1m, do2, h, p.b1.data, ln, _grad_out(p.ln_gamma), _grad_out(p.ln_beta), dp_mask, H * W)
+            if any(q is not None and q.requires_grad for q in (p.w1, p.b1, p.w2, p.b2, p.gamma)):
+                K.convnext_mlp_wgrad(y1m, do2, h, p.b1.data, p.w2.data, p.b2.data, p.gamma.data if p.gamma is not None else None,
+                                     _grad_out(p.w1), _grad_out(p.b1), _grad_out(p.w2), _grad_out(p.b2),
+                                     _grad_out(p.gamma) if p.gamma is not None else None, dp_mask, H * W, ln=ln)
             del h
         else:
             dy2 = _ConvNeXtBlockFn._mlp_backward_with_hidden(ctx, p, do2, y2, h, g, dp_mask, H, W, C, M, cdt, xc)
             del h, g
-            dy1 = K.layernorm_bwd(dy2, y1.reshape(M, C), p.ln_gamma.data, mean, rstd, _grad(p.ln_gamma), _grad(p.ln_beta))
+            dy1 = K.layernorm_bwd(dy2, y1.reshape(M, C), p.ln_gamma.data, mean, rstd, _grad_out(p.ln_gamma), _grad_out(p.ln_beta))
         dy1 = dy1.reshape(N, H, W, C)
-        K.dwconv2d_bwd_weight(xc, dy1, _grad(p.dw_kernel).reshape(Kk * Kk, C), _grad(p.dw_bias), Kk, dil, pad, pad)
+        if p.dw_kernel.requires_grad or p.dw_bias.requires_grad:
+            K.dwconv2d_bwd_weight(xc, dy1, _grad_out(p.dw_kernel, Kk * Kk, C), _grad_out(p.dw_bias), Kk, dil, pad, pad)
         dx = None
         if ctx.needs_input_grad[0]:
             padb = (Kk - 1) * dil - pad
@@ -1795,20 +1810,22 @@ class _ConvNeXtBlockFn(Function):
             if s_on_gemm and p.b1 is not None:
                 # round 5: both weight-gradient products of the block as ONE launch (36 tiles x 7 splits instead of 2 x 18 x 13): Z stops at its
                 # slabs for the layer-scale kernel; round 6: the slab sum of dW1 / db1 rides the layer-scale launch too
-                pair = K.dense_wgrad_pair(g, dbr, y2, dh, _grad(p.w1), _grad(p.b1), defer_second=True)
+                pair = K.dense_wgrad_pair(g, dbr, y2, dh, _grad_out(p.w1), _grad_out(p.b1), defer_second=True)
             sl = pair if pair is not None else (K.dense_wgrad_slabs(g, dbr) if s_on_gemm else None)
             if sl is not None:      # the layer-scale kernel sums the split-K slabs of Z (and its ones-row S) while it reads them
-                K.layerscale_grads_slabs(sl[0], sl[1], p.w2.data, p.b2.data, p.gamma.data, _grad(p.w2), _grad(p.gamma), _grad(p.b2),
+                K.layerscale_grads_slabs(sl[0], sl[1], p.w2.data, p.b2.data, p.gamma.data, _grad_out(p.w2), _grad_out(p.gamma), _grad_out(p.b2),
                                          extra=sl[2] if len(sl) > 2 else None)
             else:
                 Z = torch.empty((4 * C, C), dtype=torch.float32, device=xc.device)
                 K.dense_wgrad(g, dbr, Z, accumulate=False, bias_grad=S if s_on_gemm else None)      # Z = gelu(h)^T dbr (+ S from its ones-row)
-                K.layerscale_grads(Z, p.w2.data, p.b2.data, p.gamma.data, S, _grad(p.w2), _grad(p.gamma), _grad(p.b2))
+                K.layerscale_grads(Z, p.w2.data, p.b2.data, p.gamma.data, S, _grad_out(p.w2), _grad_out(p.gamma), _grad_out(p.b2))
         else:
-            K.dense_wgrad(g, dbr, _grad(p.w2))
-            K.axpby(S, _grad(p.b2), 1.0, 1.0, out=_grad(p.b2))
+            if p.w2.requires_grad:
+                K.dense_wgrad(g, dbr, _grad(p.w2))
+            if p.b2.requires_grad:
+                K.axpby(S, _grad(p.b2), 1.0, 1.0, out=_grad(p.b2))
         if pair is None:
-            K.dense_wgrad(y2, dh, _grad(p.w1), bias_grad=_grad(p.b1))      # db1 rides the wgrad GEMM (virtual ones-row) when C % 128 != 0
+            K.dense_wgrad(y2, dh, _grad_out(p.w1), bias_grad=_grad_out(p.b1))      # db1 rides the wgrad GEMM (virtual ones-row) when C % 128 != 0
         if not ctx.fused:
             dy2 = K.dense_dgrad(dh, nn.w(p.w1))                                # [M,C]
         return dy2
@@ -1880,7 +1897,8 @@ class _ConvNeXtV2BlockFn(Function):
             # G = g^T dbr per sample (per row chunk where a sample alone would not fill the CUs): dW2, the GRN statistics and dbeta all come
             # from these small products -- no pass over dz for them, and no grn(g) to read
             S = K.colsum(dbr, C, 0, 1, M, C, torch.empty(C, dtype=torch.float32, device=xc.device))
-            K.axpby(S, _grad(p.b2), 1.0, 1.0, out=_grad(p.b2))
+            if p.b2.requires_grad:
+                K.axpby(S, _grad(p.b2), 1.0, 1.0, out=_grad(p.b2))
             tiles = -(-4 * C // 128) * -(-C // 128)
             sps = 1
             while N * sps * tiles < 384 and HW % (2 * sps) == 0 and HW // (2 * sps) >= 512:
@@ -1890,25 +1908,26 @@ class _ConvNeXtV2BlockFn(Function):
             K.gemm(g, dbr, slabs, 4 * C, C, rows, lda=4 * C, ldb=C, ldd=C, a_kcontig=0, b_kcontig=0, batch=N * sps, batch_inner=1,
                    sa=(rows * 4 * C, 0), sb=(rows * C, 0), sd=(4 * C * C, 0))
             dstats = K.grn_fold_wgrad(slabs, sps, p.w2.data.reshape(4 * C, C), p.grn_gamma.data.reshape(-1), p.grn_beta.data.reshape(-1), nx, S,
-                                      _grad(p.w2).reshape(4 * C, C))
+                                      _grad_out(p.w2, 4 * C, C))
             del slabs
             dz = K.dense_dgrad(dbr, nn.w(p.w2))                                       # [M, 4C]
             dh = K.grn_bwd_folded(dz.reshape(N, HW, 4 * C), g.reshape(N, HW, 4 * C), p.grn_gamma.data.reshape(-1), nx, gx, dstats,
-                                  _grad(p.grn_gamma).reshape(-1), _grad(p.grn_beta).reshape(-1), ctx.grn_eps, mul=d).reshape(M, 4 * C)
+                                  _grad_out(p.grn_gamma, -1), _grad_out(p.grn_beta, -1), ctx.grn_eps, mul=d).reshape(M, 4 * C)
         else:
-            K.dense_wgrad(z, dbr, _grad(p.w2), bias_grad=_grad(p.b2))
+            K.dense_wgrad(z, dbr, _grad_out(p.w2), bias_grad=_grad_out(p.b2))
             dz = K.dense_dgrad(dbr, nn.w(p.w2))                                       # [M, 4C]
             del z
             # GRN data gradient times gelu'(h) in one kernel; dgamma | dbeta from the same pass over dz
-            dh = K.grn_bwd(dz.reshape(N, HW, 4 * C), g.reshape(N, HW, 4 * C), p.grn_gamma.data, nx, gx, _grad(p.grn_gamma).reshape(-1),
-                           _grad(p.grn_beta).reshape(-1), ctx.grn_eps, mul=d).reshape(M, 4 * C)
+            dh = K.grn_bwd(dz.reshape(N, HW, 4 * C), g.reshape(N, HW, 4 * C), p.grn_gamma.data, nx, gx, _grad_out(p.grn_gamma, -1),
+                           _grad_out(p.grn_beta, -1), ctx.grn_eps, mul=d).reshape(M, 4 * C)
         del dz, g, d
-        K.dense_wgrad(y2, dh, _grad(p.w1), bias_grad=_grad(p.b1))
+        K.dense_wgrad(y2, dh, _grad_out(p.w1), bias_grad=_grad_out(p.b1))
         dy2 = K.dense_dgrad(dh, nn.w(p.w1))                                            # [M, C]
         del dh
-        dy1 = K.layernorm_bwd(dy2, y1.reshape(M, C), p.ln_gamma.data, mean, rstd, _grad(p.ln_gamma), _grad(p.ln_beta))
+        dy1 = K.layernorm_bwd(dy2, y1.reshape(M, C), p.ln_gamma.data, mean, rstd, _grad_out(p.ln_gamma), _grad_out(p.ln_beta))
         dy1 = dy1.reshape(N, H, W, C)
-        K.dwconv2d_bwd_weight(xc, dy1, _grad(p.dw_kernel).reshape(Kk * Kk, C), _grad(p.dw_bias), Kk, dil, pad, pad)
+        if p.dw_kernel.requires_grad or p.dw_bias.requires_grad:
+            K.dwconv2d_bwd_weight(xc, dy1, _grad_out(p.dw_kernel, Kk * Kk, C), _grad_out(p.dw_bias), Kk, dil, pad, pad)
         dx = None
         if ctx.needs_input_grad[0]:
             padb = (Kk - 1) * dil - pad
@@ -2322,7 +2341,7 @@ class _RMSNormFn(Function):
     @staticmethod
     def backward(ctx, dy):
         x2, rstd = ctx.saved_tensors
-        dx = K.rmsnorm_bwd(_c(dy).reshape(x2.shape), x2, ctx.scale.data, rstd, _grad(ctx.scale))
+        dx = K.rmsnorm_bwd(_c(dy).reshape(x2.shape), x2, ctx.scale.data, rstd, _grad_out(ctx.scale))
         dist.grads_ready(ctx.scale)
         return dx.reshape(dy.shape), None, None
 
@@ -2349,7 +2368,7 @@ class _GRNFn(Function):
     def backward(ctx, dy):
         x3, nx, gx = ctx.saved_tensors
         gamma, beta = ctx.params
-        dx = K.grn_bwd(_c(dy).reshape(x3.shape), x3, gamma.data, nx, gx, _grad(gamma), _grad(beta), ctx.eps)
+        dx = K.grn_bwd(_c(dy).reshape(x3.shape), x3, gamma.data, nx, gx, _grad_out(gamma), _grad_out(beta), ctx.eps)
         dist.grads_ready(gamma, beta)
         return dx.reshape(dy.shape), None, None, None
 
@@ -2809,7 +2828,7 @@ class _LnGatherFn(Function):
         dres = ctx.link.pop("dres", None) if ctx.link is not None else None
         if dres is not None:
             dres = _c(dres).reshape(-1, C)
-        dx = K.layernorm_gather_bwd(_c(dy).reshape(-1, C), ctx.idx_bwd, x2, ctx.gamma.data, mean, rstd, _grad(ctx.gamma), _grad(ctx.beta), dx_add=dres)
+        dx = K.layernorm_gather_bwd(_c(dy).reshape(-1, C), ctx.idx_bwd, x2, ctx.gamma.data, mean, rstd, _grad_out(ctx.gamma), _grad_out(ctx.beta), dx_add=dres)
         dist.grads_ready(ctx.gamma, ctx.beta)
         return (dx.reshape(ctx.in_shape) if ctx.needs_input_grad[0] else None,) + (None,) * 7
 

@@ -81,6 +81,26 @@ class _FlatOptimizer:
     def _build_tables(self):
         raise NotImplementedError
 
+    def _updates(self, p):
+        """p is a variable this optimizer is handed: trainable and routed here.  The reference passes only those to apply_gradients, so only they
+        get a learning-rate multiplier and decay, and only their gradients count in the clipping norms"""
+        return p.requires_grad and self._owns(p)
+
+    def _build_norm_blocks(self):
+        """the block -> variable table of the squared-norm pass: the store's, with -1 (the padding mark, which iseg_grad_sqnorm skips) on the blocks
+        of every variable this optimizer is not handed -- whatever lies in a frozen variable's gradient segment must not enter clipnorm /
+        global_clipnorm.  The store's own table when every variable is handed over"""
+        st = self.store
+        skip = [i for i, p in enumerate(st.params) if not self._updates(p)]
+        if not skip:
+            self._norm_seg_of_block = st.seg_of_block
+            return
+        table = st.seg_of_block.cpu().clone()
+        for i in skip:
+            _, o, n = st.segments[i]
+            table[o // 256:(o + st.padded(n)) // 256] = -1
+        self._norm_seg_of_block = table.to(st.device)
+
     def _push_hp(self, vals):
         slot = self._slot
         self._slot = (slot + 1) % self._ring
@@ -137,7 +157,7 @@ class _FlatOptimizer:
                              torch.empty(len(st.segments), dtype=torch.float32, device=st.device),
                              torch.empty(1, dtype=torch.float32, device=st.device))
         blk, seg_sq, tot = self._norm_ws
-        _hip.call("iseg_grad_sqnorm", K.ptr(st.flat_g), K.ptr(st.flat_w), K.ptr(st.seg_of_block), K.ptr(self._seg_first_block), K.ptr(seg_l2),
+        _hip.call("iseg_grad_sqnorm", K.ptr(st.flat_g), K.ptr(st.flat_w), K.ptr(self._norm_seg_of_block), K.ptr(self._seg_first_block), K.ptr(seg_l2),
                   K.ptr(self.hp), int(self._scrub_nan), K.ptr(blk), K.ptr(seg_sq), K.ptr(tot) if gn > 0 else None, st.nblocks,
                   len(st.segments), K.stream())
         return (seg_sq if cn > 0 else None), cn, (tot if gn > 0 else None), gn
@@ -158,10 +178,11 @@ class AdamW(_FlatOptimizer):
         self.v = getattr(self, "v", None) if getattr(self, "v", None) is not None else torch.zeros_like(st.flat_w)
         if self.amsgrad and getattr(self, "vhat", None) is None:
             self.vhat = torch.zeros_like(st.flat_w)
-        lr_mult = [float(getattr(p, "lr_multiplier", 1.0)) if (p.requires_grad and self._owns(p)) else 0.0 for p in st.params]
-        wd = [float(self.weight_decay or 0.0) if (p.requires_grad and self._owns(p) and self._use_weight_decay(p)) else 0.0 for p in st.params]
+        lr_mult = [float(getattr(p, "lr_multiplier", 1.0)) if self._updates(p) else 0.0 for p in st.params]
+        wd = [float(self.weight_decay or 0.0) if (self._updates(p) and self._use_weight_decay(p)) else 0.0 for p in st.params]
         self.seg_lr_mult = torch.tensor(lr_mult, dtype=torch.float32, device=st.device)
         self.seg_wd = torch.tensor(wd, dtype=torch.float32, device=st.device)
+        self._build_norm_blocks()
 
     def _hp_values(self):
         t = self.iterations + 1
@@ -192,10 +213,11 @@ class SGD(_FlatOptimizer):
     def _build_tables(self):
         st = self.store
         self.m = getattr(self, "m", None) if getattr(self, "m", None) is not None else torch.zeros_like(st.flat_w)
-        lr_mult = [float(getattr(p, "lr_multiplier", 1.0)) if (p.requires_grad and self._owns(p)) else 0.0 for p in st.params]
-        l2 = [float(getattr(p, "l2_regularizer", 0.0)) if (p.requires_grad and self._owns(p)) else 0.0 for p in st.params]
+        lr_mult = [float(getattr(p, "lr_multiplier", 1.0)) if self._updates(p) else 0.0 for p in st.params]
+        l2 = [float(getattr(p, "l2_regularizer", 0.0)) if self._updates(p) else 0.0 for p in st.params]
         self.seg_lr_mult = torch.tensor(lr_mult, dtype=torch.float32, device=st.device)
         self.seg_l2 = torch.tensor(l2, dtype=torch.float32, device=st.device)
+        self._build_norm_blocks()
 
     def _hp_values(self):
         return [self.current_lr(), 0.0, self.grad_scale, self.clipvalue if self.clipvalue else 0.0]
