@@ -52,7 +52,7 @@ __global__ __launch_bounds__(256) void softmax_fwd_kernel(const T* __restrict__ 
                 if (br) v += br[j];
                 if (mr) v += mr[j];
                 out = __expf(v - mx) * inv;
-                if (clip) out = fminf(fmaxf(out, clip_lo), clip_hi);
+                if (clip) out = clip_f32(out, clip_lo, clip_hi);      // (a NaN probability stays NaN, as tf.clip_by_value hands it on)
             }
             pr[j] = from_f32<T>(out);
         }
@@ -135,7 +135,7 @@ __global__ __launch_bounds__(256) void softmax_fwd_reg_kernel(const T* __restric
             const int j = l + k * LPR;
             if (j < ld) {
                 float out = v[k] * inv;
-                if (clip && j < cols) out = fminf(fmaxf(out, clip_lo), clip_hi);
+                if (clip && j < cols) out = clip_f32(out, clip_lo, clip_hi);
                 pr[j] = from_f32<T>(j < cols ? out : 0.f);
             }
         }
@@ -188,7 +188,7 @@ static bool softmax_dispatch(int ld, F16 f16, F64x2 f64x2, F64x8 f64x8, F64x32 f
 template <class T>
 __global__ __launch_bounds__(256) void clip_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t n, float lo, float hi) {
     for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
-        y[i] = from_f32<T>(fminf(fmaxf(to_f32(x[i]), lo), hi));
+        y[i] = from_f32<T>(clip_f32(to_f32(x[i]), lo, hi));
 }
 template <class T>
 __global__ __launch_bounds__(256) void clip_bwd_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __restrict__ dx, int64_t n,

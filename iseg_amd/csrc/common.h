@@ -85,6 +85,11 @@ template <class T> __device__ __forceinline__ T from_f32(float v);
 template <> __device__ __forceinline__ float from_f32<float>(float v) { return v; }
 template <> __device__ __forceinline__ bf16_t from_f32<bf16_t>(float v) { return (bf16_t)v; }
 
+// ReLU and clip of DATA as comparisons: fmaxf / fminf return the operand that is not NaN, so fmaxf(NaN, 0) is 0 where tf.nn.relu and
+// tf.clip_by_value hand the NaN on (both comparisons are false for it).  +-Inf clip like any other value.
+__device__ __forceinline__ float relu_f32(float v) { return v < 0.f ? 0.f : v; }
+__device__ __forceinline__ float clip_f32(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
 // 16-byte vector access: VecN<T>::N elements per 16 B.
 template <class T> struct Vec16;
 template <> struct Vec16<float> {
@@ -355,6 +360,10 @@ __device__ __forceinline__ float gelu_poly_grad(float x) {
     return fmaf(w, r, 0.5f);
 }
 
+// gelu_poly_grad where the pre-activation comes from memory (GEMM epilogue, standalone activation): its clamp01 maps a NaN pre-activation to
+// w = -1/2 and a finite derivative, where the reference's gradient is NaN.  (The fused MLP kernels call gelu_poly_grad on their own accumulators.)
+__device__ __forceinline__ float gelu_poly_grad_keep_nan(float x) { return x != x ? x : gelu_poly_grad(x); }
+
 // exact-erf GELU, as keras.activations.gelu(approximate=False)
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 __device__ __forceinline__ float gelu_erf_grad(float x) {
@@ -366,7 +375,7 @@ __device__ __forceinline__ float gelu_erf_grad(float x) {
 // tanh-form GELU, as keras.activations.gelu(approximate=True) (nlp/gemma/gemma_decoder_block.py:167-170): value and derivative from one tanh
 __device__ __forceinline__ void gelu_tanh_both(float x, float& y, float& dy) {
     constexpr float K = 0.79788456080286535588f, A = 0.044715f;      // sqrt(2 / pi)
-    const float xc = fminf(fmaxf(x, -10.f), 10.f);      // tanh is +-1 in fp32 long before: no inf * 0 at the ends of the range
+    const float xc = clip_f32(x, -10.f, 10.f);      // tanh is +-1 in fp32 long before: no inf * 0 at the ends of the range (NaN stays NaN)
     const float x2 = xc * xc;
     const float t = tanhf(K * fmaf(A * x2, xc, xc));
     const float h = 0.5f * (1.0f + t);

@@ -333,7 +333,7 @@ __global__ void rsqrt_eps_kernel(const float* __restrict__ var, float eps, float
 // layers/nasfpn.py:304-311, backbones/eva/swiglu.py:13) are evaluated with expf in both.
 template <bool FAST> __device__ __forceinline__ float act_value(float v, int act) {
     switch (act) {
-        case ISEG_ACT_RELU: return fmaxf(v, 0.f);
+        case ISEG_ACT_RELU: return relu_f32(v);
         case ISEG_ACT_SIGMOID: return 1.f / (1.f + expf(-v));
         case ISEG_ACT_SWISH: return v / (1.f + expf(-v));
         case ISEG_ACT_GELU_TANH: return gelu_tanh(v);
@@ -354,7 +354,7 @@ template <bool FAST> __device__ __forceinline__ float act_deriv(float a, int act
             return s * (1.f + a * (1.f - s));
         }
         case ISEG_ACT_GELU_TANH: return gelu_tanh_grad(a);
-        default: return FAST ? gelu_poly_grad(a) : gelu_erf_grad(a);
+        default: return FAST ? gelu_poly_grad_keep_nan(a) : gelu_erf_grad(a);
     }
 }
 

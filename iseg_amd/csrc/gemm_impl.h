@@ -57,7 +57,7 @@ __device__ __forceinline__ float epi_apply(const Epi& e, float acc, int64_t m, i
     float v = acc * e.alpha;
     if (e.bias) v += e.bias[n];
     if (e.pre_out) reinterpret_cast<TO*>(e.pre_out)[m * e.ldp + n] = from_f32<TO>(e.pre_deriv ? gelu_erf_grad(v) : v);
-    if (e.act == ISEG_ACT_RELU) v = fmaxf(v, 0.f);
+    if (e.act == ISEG_ACT_RELU) v = relu_f32(v);
     else if (e.act == ISEG_ACT_GELU) v = gelu_erf(v);
     else if (e.act == ISEG_ACT_GELU_GRAD) v *= gelu_erf_grad(to_f32(reinterpret_cast<const TO*>(e.aux)[m * e.ldaux + n]));
     else if (e.act == ISEG_ACT_RELU_GRAD) v = to_f32(reinterpret_cast<const TO*>(e.aux)[m * e.ldaux + n]) > 0.f ? v : 0.f;
@@ -84,7 +84,7 @@ __device__ __forceinline__ void epi_apply8(const Epi& e, float* v, int64_t m, in
     if (e.pre_out && !e.pre_deriv) store8<TO>(reinterpret_cast<TO*>(e.pre_out) + m * e.ldp + n, v);
     if (e.act == ISEG_ACT_RELU) {
 #pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = fmaxf(v[i], 0.f);
+        for (int i = 0; i < 8; ++i) v[i] = relu_f32(v[i]);
     } else if (e.act == ISEG_ACT_GELU) {
         if (e.pre_out && e.pre_deriv) {
             float d[8];
@@ -110,7 +110,7 @@ __device__ __forceinline__ void epi_apply8(const Epi& e, float* v, int64_t m, in
         float a[8];
         load8<TO>(reinterpret_cast<const TO*>(e.aux) + m * e.ldaux + n, a);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] *= FAST ? gelu_poly_grad(a[i]) : gelu_erf_grad(a[i]);
+        for (int i = 0; i < 8; ++i) v[i] *= FAST ? gelu_poly_grad_keep_nan(a[i]) : gelu_erf_grad(a[i]);
     } else if (e.act == ISEG_ACT_RELU_GRAD) {
         float a[8];
         load8<TO>(reinterpret_cast<const TO*>(e.aux) + m * e.ldaux + n, a);
@@ -186,7 +186,7 @@ __device__ __forceinline__ void epi_finish8(const Epi& e, float* v, const EpiPre
     if (e.pre_out && !e.pre_deriv) store8<TO>(reinterpret_cast<TO*>(e.pre_out) + m * e.ldp + n, v);
     if (e.act == ISEG_ACT_RELU) {
 #pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = fmaxf(v[i], 0.f);
+        for (int i = 0; i < 8; ++i) v[i] = relu_f32(v[i]);
     } else if (e.act == ISEG_ACT_GELU) {
         if (e.pre_out && e.pre_deriv) {      // Phi(v) and exp(-v^2/2) serve both gelu(v) and gelu'(v)
             float d[8];
@@ -208,7 +208,7 @@ __device__ __forceinline__ void epi_finish8(const Epi& e, float* v, const EpiPre
         for (int i = 0; i < 8; ++i) v[i] *= pf.aux.get(i);
     } else if (e.act == ISEG_ACT_GELU_GRAD) {
 #pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] *= FAST ? gelu_poly_grad(pf.aux.get(i)) : gelu_erf_grad(pf.aux.get(i));
+        for (int i = 0; i < 8; ++i) v[i] *= FAST ? gelu_poly_grad_keep_nan(pf.aux.get(i)) : gelu_erf_grad(pf.aux.get(i));
     } else if (e.act == ISEG_ACT_RELU_GRAD) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) v[i] = pf.aux.get(i) > 0.f ? v[i] : 0.f;

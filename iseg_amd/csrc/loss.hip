@@ -77,7 +77,7 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict
                 // keras CategoricalFocalCrossentropy(from_logits): p = clip(softmax_y, 1e-7, 1 - 1e-7),
                 // loss = alpha * (1 - p)^gamma * (-log p); the clip passes no gradient outside its range
                 const float py = in_range ? z[y] / se : 1.f;
-                const float pc = fminf(fmaxf(py, 1e-7f), 1.f - 1e-7f);
+                const float pc = clip_f32(py, 1e-7f, 1.f - 1e-7f);      // (a NaN probability stays NaN: loss and gradient of the pixel are NaN)
                 const bool inside = py > 1e-7f && py < 1.f - 1e-7f;
                 // 1 - p_y as (sum of the other terms) / se: for a confident pixel 1 - z[y] / se cancels, and the running sum se = 1 + many
                 // terms of ~1e-6 carries ~5e-7 of rounding, which is 10 % of that pixel's loss.  log p_y = log1p(-(1 - p_y)) on that side.
@@ -308,7 +308,9 @@ __global__ __launch_bounds__(256) void upsample_ce_kernel(const TI* __restrict__
             const float wx1 = xv ? tx : 0.f, wx0 = xv ? 1.f - tx : 0.f;
 #pragma unroll
             for (int c = 0; c < CMAX; ++c) {
-                float q00 = wx0 * a0[c], q01 = wx1 * a0[c], q10 = wx0 * a1[c], q11 = wx1 * a1[c];
+                // (a lane outside the image worked on column 0's logits with weight 0: 0 * NaN must not reach the segment's sum)
+                const float s0 = xv ? a0[c] : 0.f, s1 = xv ? a1[c] : 0.f;
+                float q00 = wx0 * s0, q01 = wx1 * s0, q10 = wx0 * s1, q11 = wx1 * s1;
                 for (int o = sx >> 1; o > 0; o >>= 1) {
                     q00 += __shfl_xor(q00, o, 64);
                     q01 += __shfl_xor(q01, o, 64);

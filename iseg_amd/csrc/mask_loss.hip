@@ -116,7 +116,7 @@ __global__ __launch_bounds__(256) void mask_loss_pass1_kernel(const float* __res
                         v += kc * (lse - zy);
                     } else {
                         // keras CategoricalFocalCrossentropy(from_logits): p = clip(softmax_y, 1e-7, 1 - 1e-7), alpha (1 - p)^2 (-log p)
-                        const float pc = fminf(fmaxf(__expf(zy - lse), 1e-7f), 1.f - 1e-7f);
+                        const float pc = clip_f32(__expf(zy - lse), 1e-7f, 1.f - 1e-7f);      // (NaN stays NaN and meets the scrub below)
                         const float om = 1.f - pc;
                         v += kc * F_ALPHA * (om * om) * (-__logf(pc));
                     }
@@ -236,7 +236,7 @@ __global__ __launch_bounds__(256) void mask_loss_pass2_kernel(const float* __res
             if (CE == 1) kce = in_range ? gc : 0.f;
             if (CE == 2 && in_range) {
                 const float py = __expf(zy - lse);
-                const float pc = fminf(fmaxf(py, 1e-7f), 1.f - 1e-7f);
+                const float pc = fminf(fmaxf(py, 1e-7f), 1.f - 1e-7f);      // (read only where `live`: py inside the clip, never NaN)
                 const float om = 1.f - pc;
                 const float lg = __logf(pc);
                 const bool live = py > 1e-7f && py < 1.f - 1e-7f;      // the clip passes no gradient outside its range

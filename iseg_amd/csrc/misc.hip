@@ -430,7 +430,7 @@ __global__ __launch_bounds__(256) void add_relu_kernel(const T* __restrict__ a, 
         load8<T>(a + i * 8, u);
         load8<T>(b + i * 8, v);
 #pragma unroll
-        for (int k = 0; k < 8; ++k) u[k] = fmaxf(u[k] + v[k], 0.f);
+        for (int k = 0; k < 8; ++k) u[k] = relu_f32(u[k] + v[k]);
         store8<T>(y + i * 8, u);
     }
 }

@@ -459,7 +459,7 @@ __global__ void bn_finalize_kernel(const float* __restrict__ packed, int C, floa
     const float n = packed[2 * C];
     const float m = packed[c] / n;
     float var = packed[C + c] / n - m * m;
-    var = fmaxf(var, 0.f);
+    var = relu_f32(var);      // (cancellation may leave -1e-8; a NaN variance -- a NaN or an infinity in the channel -- stays NaN, as in the reference)
     mean[c] = m;
     rstd[c] = rsqrtf(var + eps);
     if (moving_mean) moving_mean[c] = moving_mean[c] * momentum + m * (1.f - momentum);
@@ -509,7 +509,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const T* __restrict__ x, 
 #pragma unroll
                 for (int u = 0; u < 8; ++u) {
                     float o = (v[k][u] - m[u]) * s[u] * g[u] + b[u];
-                    if (relu) o = fmaxf(o, 0.f);
+                    if (relu) o = relu_f32(o);
                     v[k][u] = o;
                 }
                 store8<T>(y + (r + k * rstep) * ldy + c, v[k]);
@@ -521,7 +521,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const T* __restrict__ x, 
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 float o = (v[u] - m[u]) * s[u] * g[u] + b[u];
-                if (relu) o = fmaxf(o, 0.f);
+                if (relu) o = relu_f32(o);
                 v[u] = o;
             }
             store8<T>(y + r * ldy + c, v);
@@ -551,7 +551,7 @@ __global__ __launch_bounds__(256) void bn_apply_packed_kernel(const T* __restric
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             m[u] = m[u] / n;
-            var[u] = fmaxf(var[u] / n - m[u] * m[u], 0.f);
+            var[u] = relu_f32(var[u] / n - m[u] * m[u]);
             s[u] = rsqrtf(var[u] + eps);
         }
         if (blockIdx.x == 0 && st.tr == 0) {      // the lane that owns row 0 of this chunk
@@ -583,7 +583,7 @@ __global__ __launch_bounds__(256) void bn_apply_packed_kernel(const T* __restric
 #pragma unroll
                 for (int u = 0; u < 8; ++u) {
                     float o = (v[k][u] - m[u]) * s[u] * g[u] + b[u];
-                    if (relu) o = fmaxf(o, 0.f);
+                    if (relu) o = relu_f32(o);
                     v[k][u] = o;
                 }
                 store8<T>(y + (r + k * rstep) * ldy + c, v[k]);
@@ -595,7 +595,7 @@ __global__ __launch_bounds__(256) void bn_apply_packed_kernel(const T* __restric
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 float o = (v[u] - m[u]) * s[u] * g[u] + b[u];
-                if (relu) o = fmaxf(o, 0.f);
+                if (relu) o = relu_f32(o);
                 v[u] = o;
             }
             store8<T>(y + r * ldy + c, v);

@@ -159,7 +159,7 @@ __global__ __launch_bounds__(RB_THREADS) void rb_fwd_kernel(const T* __restrict_
         for (int u = 0; u < 8; ++u) {
             const float sv = BN0 ? s[u] * k0[u] + h0[u] : s[u];
             const float v = z[u] * k2[u] + h2[u] + sv;
-            z[u] = v > 0.f ? v : 0.f;
+            z[u] = relu_f32(v);
         }
         store8<T>(out + r * g.C + c, z);
     }

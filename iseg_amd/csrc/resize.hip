@@ -354,7 +354,7 @@ __global__ __launch_bounds__(256) void bn_relu_upsample_add_kernel(const T* __re
             for (int u = 0; u < 8; ++u) {
                 const float tp = tl[u] + (tr_[u] - tl[u]) * lx.t;
                 const float bt = bl[u] + (br[u] - bl[u]) * lx.t;
-                const float y = fmaxf((v[u] - m[u]) * s[u] * g[u] + b[u], 0.f);
+                const float y = relu_f32((v[u] - m[u]) * s[u] * g[u] + b[u]);
                 v[u] = y + (tp + (bt - tp) * ly.t);
             }
             store8<T>(out + (int64_t)p * C + c, v);
@@ -393,7 +393,13 @@ __global__ __launch_bounds__(256) void resize_bwd_x2_vec_kernel(const TI* __rest
 #pragma unroll
         for (int ky = 0; ky < 4; ++ky)
 #pragma unroll
-            for (int kx = 0; kx < 4; ++kx) load8<TI>(dy + (((int64_t)n * Ho + yy[ky]) * Wo + xx[kx]) * C + c, v[4 * ky + kx]);
+            for (int kx = 0; kx < 4; ++kx) {
+                load8<TI>(dy + (((int64_t)n * Ho + yy[ky]) * Wo + xx[kx]) * C + c, v[4 * ky + kx]);
+                // a destination outside the image was loaded from a clamped address and carries weight 0: 0 * NaN must not reach the sum
+                const bool inside = 2 * jy - 1 + ky >= 0 && 2 * jy - 1 + ky < Ho && 2 * jx - 1 + kx >= 0 && 2 * jx - 1 + kx < Wo;
+#pragma unroll
+                for (int u = 0; u < 8; ++u) v[4 * ky + kx][u] = inside ? v[4 * ky + kx][u] : 0.f;
+            }
         float acc[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u) acc[u] = 0.f;

@@ -161,7 +161,7 @@ __global__ __launch_bounds__(SC_THREADS) void sc_fwd_kernel(const T* __restrict_
             if (ck < t.nchunks && h >= 0 && h < g.H && ww >= 0 && ww < g.W) {
                 load8<T>(xn + ((int64_t)h * g.W + ww) * C + ck * 8, v);
 #pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
+                for (int e = 0; e < 8; ++e) v[e] = relu_f32(v[e]);
             }
             float* dst = win + (size_t)i * 8;
             *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
@@ -366,7 +366,7 @@ __global__ __launch_bounds__(SC_THREADS) void sc_bwd_kernel(const T* __restrict_
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 acc[e] = 0.f;
-                xv[e] = fmaxf(xv[e], 0.f);
+                xv[e] = relu_f32(xv[e]);
             }
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
@@ -378,6 +378,9 @@ __global__ __launch_bounds__(SC_THREADS) void sc_bwd_kernel(const T* __restrict_
                     const int wq = ww + g.pl - j * g.d;
                     if (g.s == 2 && (wq & 1)) continue;
                     const int rw = (g.s == 2 ? (wq >> 1) : wq) - wo_lo;
+                    // a tap whose output pixel lies outside the map holds dz = 0 in the window: it adds nothing, and relu(x) * 0 must not turn
+                    // a NaN or an infinity in x into a NaN of a weight-gradient tap that the reference never pairs it with
+                    if ((unsigned)(rh + ho_lo) >= (unsigned)g.Ho || (unsigned)(rw + wo_lo) >= (unsigned)g.Wo) continue;
                     const float* src = win + (((size_t)rh * t.RW + rw) * CG + c) * 8;
                     const float4 a = *reinterpret_cast<const float4*>(src), b = *reinterpret_cast<const float4*>(src + 4);
                     const float dz[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};

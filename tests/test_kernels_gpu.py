@@ -6,7 +6,8 @@ What close() does not see: it bounds the LARGEST error by tol x the LARGEST elem
 bf16 ulps of the largest output, granted to every element.  A store that truncates instead of rounding to nearest-even, split-K or slab partial
 sums kept in bf16, and an intermediate rounded to bf16 in front of an epilogue all stay inside it.  Whether a bf16 output is the fp32-accurate
 value rounded ONCE is the business of tests/test_rounding_budget_gpu.py (statistic, cases and fp32 restatements: tests/rounding_budget.py; the
-proof that the three defects pass close() and miss the statistic: tests/test_rounding_budget_host.py)."""
+proof that the three defects pass close() and miss the statistic: tests/test_rounding_budget_host.py).  close() also sees only finite inputs: where
+a NaN or an infinity inside an operand must come out is the business of tests/test_nonfinite_gpu.py."""
 import math
 
 import numpy as np
