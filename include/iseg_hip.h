@@ -1225,6 +1225,36 @@ int iseg_gemma_attention_bwd(const void* q, int64_t ldq, const void* k, int64_t 
  * absent ids are not touched, no atomics. */
 int iseg_embedding_grad(const void* dy, const int64_t* sorted_ids, const int64_t* order, float* dtable, int64_t n, int64_t vocab, int d,
                         float scale, int dtype, iseg_stream_t stream);
+/* Gemma with a key/value cache (nlp/gemma/gemma_causal.py:186-226).  A cache is a base pointer, a batch stride and a row pitch in elements: row s
+ * of sample b starts at base + b * batch_stride + s * pitch and holds nkv h elements; one layer's key (value) slice of the reference's
+ * [B, num_layers, 2, S, nkv, h] cache is such a view.
+ * iseg_gemma_rope_cache: nlp/gemma/gemma_attention.py:161-179 -- the rotary embedding at the positions pos0 + t and the dynamic_update_slice of
+ *   the cache.  Reads the packed projection rows qkv [batch * Tn][(nq + 2 nkv) h]; writes the rotated q heads to q_out [batch * Tn][nq h] (pitch
+ *   ldq), the rotated k heads to row pos0 + t of kcache and the unchanged v heads to row pos0 + t of vcache.  table is iseg_gemma_rope's, fp32
+ *   [S][h]; the output is interleaved and rounded once, bit for bit iseg_gemma_rope's.  bf16 and fp32.  Cache rows outside
+ *   [pos0, pos0 + Tn) are not written; pos0 < 0 or pos0 + Tn > S returns ISEG_ERR_ARG before anything is touched. */
+int iseg_gemma_rope_cache(const void* qkv, int64_t ld_in, void* q_out, int64_t ldq, void* kcache, int64_t k_batch, int64_t ldk, void* vcache,
+                          int64_t v_batch, int64_t ldv, const float* table, int64_t batch, int S, int pos0, int Tn, int nq, int nkv, int h,
+                          int dtype, iseg_stream_t stream);
+/* nlp/gemma/gemma_attention.py:116-151 under the mask of gemma_decoder_block.py:114-136 with a cache (no padding mask: compute_causal_mask alone):
+ *   out[b,t,n,:] = sum_{s <= pos0 + t} softmax_s(scale * q[b,t,n,:] . K[b,s,n / (nq/nkv),:]) V[b,s,n / (nq/nkv),:]
+ * for the Tn new tokens at positions pos0 .. pos0 + Tn - 1; q / out [batch, Tn, nq h] with their row pitches.  The (nq/nkv) * Tn query rows of one
+ * (sample, key/value head) are stacked (row t * (nq/nkv) + j).  Pass 1, one workgroup per (sample, key/value head, chunk): the visible keys are
+ * cut into `splits` chunks of whole 64-key tiles, each walked with the online softmax; per stacked row an fp32 partial (maximum, sum, h
+ * accumulators) goes to the workspace.  Pass 2 merges the partials in chunk order and rounds once to bf16.  No atomics: a second call is
+ * bit-identical.  Keys past pos0 + Tn - 1 are never loaded: the cache behind the write position may hold anything.
+ * splits: 0 = the launcher's plan, a function of (batch, pos0, Tn, nkv) alone that iseg_gemma_decode_attention_splits returns; a positive value
+ * is taken, clipped to the number of 64-key tiles that hold a visible key.  The workspace holds iseg_gemma_decode_attention_scratch_bytes
+ * (same `splits` argument); a smaller one returns ISEG_ERR_WORKSPACE.
+ * Supported (iseg_gemma_decode_attention_supported): bf16, h % 64 == 0, 64 <= h <= 256, nq % nkv == 0, (nq/nkv) * Tn <= 16; scale > 0, pitches
+ * and batch strides multiples of 8 elements, 16-byte aligned bases.  Anything else returns ISEG_ERR_UNSUPPORTED, and pos0 < 0 or
+ * pos0 + Tn > S returns ISEG_ERR_ARG, before any memory is touched. */
+int iseg_gemma_decode_attention_supported(int Tn, int nq, int nkv, int h, int dtype);
+int iseg_gemma_decode_attention_splits(int64_t batch, int pos0, int Tn, int nq, int nkv, int h);
+size_t iseg_gemma_decode_attention_scratch_bytes(int64_t batch, int pos0, int Tn, int nq, int nkv, int h, int splits);
+int iseg_gemma_decode_attention(const void* q, int64_t ldq, const void* kcache, int64_t k_batch, int64_t ldk, const void* vcache, int64_t v_batch,
+                                int64_t ldv, void* out, int64_t ldo, void* ws, size_t ws_bytes, int64_t batch, int S, int pos0, int Tn, int nq,
+                                int nkv, int h, float scale, int splits, int dtype, iseg_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -298,6 +298,11 @@ SIGNATURES = {
     "iseg_gemma_attention_fwd": (_i, [_p, _l, _p, _l, _p, _l, _p, _p, _l, _p, _l, _i, _i, _i, _i, _f, _i, _p]),
     "iseg_gemma_attention_bwd": (_i, [_p, _l, _p, _l, _p, _l, _p, _p, _l, _p, _l, _p, _p, _p, _l, _p, _l, _p, _l, _l, _i, _i, _i, _i, _f, _i, _p]),
     "iseg_embedding_grad": (_i, [_p, _p, _p, _p, _l, _l, _i, _f, _i, _p]),
+    "iseg_gemma_rope_cache": (_i, [_p, _l, _p, _l, _p, _l, _l, _p, _l, _l, _p, _l, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "iseg_gemma_decode_attention_supported": (_i, [_i, _i, _i, _i, _i]),
+    "iseg_gemma_decode_attention_splits": (_i, [_l, _i, _i, _i, _i, _i]),
+    "iseg_gemma_decode_attention_scratch_bytes": (_z, [_l, _i, _i, _i, _i, _i, _i]),
+    "iseg_gemma_decode_attention": (_i, [_p, _l, _p, _l, _l, _p, _l, _l, _p, _l, _p, _z, _l, _i, _i, _i, _i, _i, _i, _f, _i, _i, _p]),
     "iseg_sgd_momentum_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _f, _i, _p, _f, _p, _f, _l, _p]),
 }
 

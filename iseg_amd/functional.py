@@ -110,8 +110,19 @@ def _kcontig_kernel(W, x2, Kd, N):
 
 
 class _DenseFn(Function):
+    """rows_out: the kernel is stored [out, in] (the token table read as the logits kernel, F.embedding_logits): y = x @ W^T, no bias, no
+    activation; the gradient is written in that layout into the parameter's one buffer"""
+
     @staticmethod
-    def forward(ctx, x, W, b, act, kshape=None):
+    def forward(ctx, x, W, b, act, kshape=None, rows_out=False):
+        ctx.rows_out = rows_out
+        if rows_out:
+            N, Kd = W.shape
+            x2 = _c(x).reshape(-1, Kd)
+            y = K.dense_fwd_t(x2, nn.w(W))      # the kernel as it lies is the K-contiguous [N, K] operand
+            ctx.act, ctx.W, ctx.b, ctx.kshape = act, W, None, (Kd, N)
+            ctx.save_for_backward(x2, None)
+            return y.reshape(*x.shape[:-1], N)
         Kd, N = kshape if kshape is not None else (W.shape[-2], W.shape[-1])
         x2 = _c(x).reshape(-1, Kd)
         bias = b.data.reshape(-1) if b is not None else None
@@ -134,6 +145,12 @@ class _DenseFn(Function):
         W, b = ctx.W, ctx.b
         Kd, N = ctx.kshape
         dy2 = _c(dy).reshape(-1, N)
+        if ctx.rows_out:
+            if W.requires_grad:
+                K.dense_wgrad(dy2, x2, _grad(W))      # dW [N, Kd] += dY^T X
+            dx = K.dense_fwd(dy2, nn.w(W)).reshape(*dy.shape[:-1], Kd) if ctx.needs_input_grad[0] else None
+            dist.grads_ready(W)
+            return dx, None, None, None, None, None
         if ctx.act in (K.ACT_GELU, K.ACT_RELU):
             dy2 = K.act_bwd(dy2, aux, ctx.act)
         want_b = b is not None and b.requires_grad
@@ -146,7 +163,7 @@ class _DenseFn(Function):
         if ctx.needs_input_grad[0]:
             dx = K.dense_dgrad(dy2, nn.w(W).reshape(Kd, N)).reshape(*dy.shape[:-1], Kd)
         dist.grads_ready(W, b)
-        return dx, None, None, None, None
+        return dx, None, None, None, None, None
 
 
 class _MlpGeluFn(Function):
@@ -3531,6 +3548,12 @@ def gemma_attention_core(qkv, padding_mask, nq, nkv, h, *, dropout_rate=0.0, tra
         if not (torch.is_grad_enabled() and qkv.requires_grad):
             return K.gemma_attention_fwd(_c(qkv), mask_u8, int(nq), int(nkv), int(h), scale, False)[0]
         return _GemmaAttentionFn.apply(qkv, mask_u8, int(nq), int(nkv), int(h), scale)
+    return _gemma_attention_composed(qkv, padding_mask, nq, nkv, h, scale, rate)
+
+
+def _gemma_attention_composed(qkv, padding_mask, nq, nkv, h, scale, rate=0.0):
+    """the composed route of gemma_attention_core"""
+    B, T, _ = qkv.shape
     vis = _gemma_visibility(padding_mask, B, T, qkv.device)
     additive = torch.where(vis, 0.0, -1e30).to(torch.float32).contiguous()
     wide = _GemmaRepeatKVFn.apply(qkv, int(nq), int(nkv), int(h)) if nkv != nq else qkv
@@ -3539,6 +3562,89 @@ def gemma_attention_core(qkv, padding_mask, nq, nkv, h, *, dropout_rate=0.0, tra
         return y
     alive = vis.any(dim=-1).to(torch.float32).reshape(B * T).contiguous()
     return _RowScaleFn.apply(y.reshape(B * T, nq * h), alive).reshape(B, T, nq * h)
+
+
+# ---- Gemma with a key/value cache (nlp/gemma/gemma_causal.py:186-226): inference only, no autograd graph -----------------------------------
+def _no_grad_inputs(who, *ts):
+    for t in ts:
+        if t.requires_grad:
+            raise RuntimeError(f"{who}: the cached path is inference only (an input requires grad); train through the uncached call")
+
+
+def _check_layer_cache(who, cache, B, nkv, h, dtype):
+    if cache.dim() != 5 or cache.shape[0] != B or cache.shape[1] != 2 or cache.shape[3] != nkv or cache.shape[4] != h or cache.dtype != dtype:
+        raise ValueError(f"{who}: a layer's cache is [{B}, 2, S, {nkv}, {h}] {dtype}, got {tuple(cache.shape)} {cache.dtype}")
+
+
+def gemma_rope_cache(qkv, cache, pos0, nq, nkv, h):
+    """qkv [B, Tn, (nq + 2 nkv) h]: packed projections of the tokens at positions pos0 .. pos0 + Tn - 1; cache: ONE layer's [B, 2, S, nkv, h] view of
+    the [B, num_layers, 2, S, nkv, h] cache.  The rotary embedding at those positions (fp32 angles from gemma_rope_table(S, h)) and the
+    dynamic_update_slice of nlp/gemma/gemma_attention.py:161-179 in one pass (csrc/gemma_decode.hip): rows pos0 .. of the cache receive the rotated
+    keys and the values IN PLACE, the rotated queries are returned [B, Tn, nq h]."""
+    _check_act_dtype(qkv)
+    _no_grad_inputs("gemma_rope_cache", qkv, cache)
+    if qkv.dim() != 3 or qkv.shape[2] != (nq + 2 * nkv) * h or h % 2:
+        raise ValueError(f"gemma_rope_cache: {tuple(qkv.shape)} is not [B, Tn, ({nq} + 2 * {nkv}) * {h}]")
+    B, Tn, _ = qkv.shape
+    if nn.dry_run():
+        return _dry((B, Tn, nq * h), qkv)
+    _check_layer_cache("gemma_rope_cache", cache, B, nkv, h, qkv.dtype)
+    S = cache.shape[2]
+    if pos0 < 0 or pos0 + Tn > S:
+        raise ValueError(f"gemma_rope_cache: positions {pos0} .. {pos0 + Tn - 1} do not lie inside a cache of {S} rows")
+    with torch.no_grad():
+        return K.gemma_rope_cache(_c(qkv), cache, gemma_rope_table(S, h, qkv.device), int(pos0), int(nq), int(nkv), int(h))
+
+
+def gemma_cached_attention_fused(Tn, nq, nkv, h, dtype):
+    """True where gemma_cached_attention_core takes the decode kernels: supported shape and type, and ISEG_GEMMA_FUSED unset or not "0" """
+    return os.environ.get("ISEG_GEMMA_FUSED", "1") != "0" and nq % max(nkv, 1) == 0 and K.gemma_decode_attention_supported(Tn, nq, nkv, h, dtype)
+
+
+def gemma_cached_attention_core(q, cache, pos0, nq, nkv, h, *, splits=0):
+    """q [B, Tn, nq h]: rotated queries of the tokens at positions pos0 .. pos0 + Tn - 1; cache [B, 2, S, nkv, h]: one layer's keys and values,
+    rows 0 .. pos0 + Tn - 1 filled (gemma_rope_cache) -> [B, Tn, nq h]: softmax(h^-0.5 q k^T) v over the keys s <= pos0 + t, the mask of
+    gemma_decoder_block.py:114-136 with a cache and no padding mask.
+    Fused route (bf16, h in 64 .. 256, (nq / nkv) * Tn <= 16, ISEG_GEMMA_FUSED unset or not "0"): the split-KV kernels of csrc/gemma_decode.hip;
+    rows of the cache past pos0 + Tn - 1 are never read.
+    Seeding call (pos0 == 0, Tn == S, too many rows for the decode kernels): gemma_attention_core on the packed [q | K | V] rows with no
+    padding mask -- at index 0 with the whole cache the cached mask is the plain causal mask.
+    Composed route (everything else, and the yardstick of the fused one): the new q rows at rows pos0 .. of a zeroed packed [B, S, .] buffer
+    beside the cache's visible K and V rows, the composed route of gemma_attention_core, and the rows sliced out: the causal mask of row
+    pos0 + t is exactly the cached mask."""
+    _check_act_dtype(q)
+    _no_grad_inputs("gemma_cached_attention_core", q, cache)
+    if q.dim() != 3 or q.shape[2] != nq * h or nq % nkv:
+        raise ValueError(f"gemma_cached_attention_core: {tuple(q.shape)} is not [B, Tn, {nq} * {h}] with nq a multiple of nkv")
+    B, Tn, _ = q.shape
+    if nn.dry_run():
+        return _dry(q.shape, q)
+    _check_layer_cache("gemma_cached_attention_core", cache, B, nkv, h, q.dtype)
+    S = cache.shape[2]
+    if pos0 < 0 or pos0 + Tn > S:
+        raise ValueError(f"gemma_cached_attention_core: positions {pos0} .. {pos0 + Tn - 1} do not lie inside a cache of {S} rows")
+    scale = float(h) ** -0.5
+    with torch.no_grad():
+        if gemma_cached_attention_fused(Tn, nq, nkv, h, q.dtype):
+            return K.gemma_decode_attention(_c(q), cache, int(pos0), int(nq), int(nkv), int(h), scale, splits)
+        nvis, Cq, Ck = pos0 + Tn, nq * h, nkv * h
+        packed = torch.zeros((B, S, Cq + 2 * Ck), dtype=q.dtype, device=q.device)
+        packed[:, pos0:nvis, :Cq] = q
+        packed[:, :nvis, Cq:Cq + Ck] = cache[:, 0, :nvis].reshape(B, nvis, Ck)
+        packed[:, :nvis, Cq + Ck:] = cache[:, 1, :nvis].reshape(B, nvis, Ck)
+        if pos0 == 0 and Tn == S:
+            return gemma_attention_core(packed, None, nq, nkv, h)
+        return _c(_gemma_attention_composed(packed, None, int(nq), int(nkv), int(h), scale)[:, pos0:nvis])
+
+
+def embedding_logits(x, table):
+    """x [B, T, d] -> [B, T, vocab] = x @ table^T with the token table [vocab, d]: the reverse use of the tied embedding
+    (ReversibleEmbedding(reverse=True), nlp/gemma/gemma_causal.py:158) on the GEMM launchers -- the dense node with the kernel stored [out, in].
+    The table's gradient from here (dy^T x) and from F.embedding accumulate on the one parameter."""
+    _check_act_dtype(x)
+    if nn.dry_run():
+        return _dry((*x.shape[:-1], table.shape[0]), x)
+    return _DenseFn.apply(x, table, None, K.ACT_NONE, None, True)
 
 
 _FLIP_CACHE = {}

@@ -2267,3 +2267,50 @@ def embedding_grad(dy2d, sorted_ids, order, dtable, scale):
     n, d = dy2d.shape
     _hip.call("iseg_embedding_grad", ptr(dy2d), ptr(sorted_ids), ptr(order), ptr(dtable), n, dtable.shape[0], d, float(scale), dt(dy2d), stream())
     return dtable
+
+
+# ---------------------------------------------------------------------------------------------------------
+# Gemma with a key/value cache (csrc/gemma_decode.hip)
+# ---------------------------------------------------------------------------------------------------------
+def _gemma_cache_views(cache, nkv, h):
+    """one layer's cache [B, 2, S, nkv, h] -> (keys, values, batch stride, row pitch): rows of nkv h contiguous elements, equally spaced"""
+    if cache.dim() != 5 or cache.shape[1] != 2 or cache.shape[3] != nkv or cache.shape[4] != h or cache.stride(4) != 1 or cache.stride(3) != h:
+        raise ValueError(f"a layer's cache is [B, 2, S, {nkv}, {h}] with contiguous rows, got {tuple(cache.shape)} strides {cache.stride()}")
+    return cache[:, 0], cache[:, 1], cache.stride(0), cache.stride(2)
+
+
+def gemma_rope_cache(qkv, cache, table, pos0, nq, nkv, h):
+    """packed projection rows qkv [B, Tn, (nq + 2 nkv) h] (contiguous) of the tokens at positions pos0 .. pos0 + Tn - 1: the interleaved rotary
+    embedding of nlp/gemma/gemma_attention.py:161-179 on q and k; the rotated k heads and the v heads are written into rows pos0 .. of
+    cache [B, 2, S, nkv, h] (in place), the rotated q heads are returned [B, Tn, nq h]; table fp32 [S, h]"""
+    _require_cuda(qkv, cache, table)
+    B, Tn, W = qkv.shape
+    kc, vc, bs, ld = _gemma_cache_views(cache, nkv, h)
+    q = torch.empty((B, Tn, nq * h), dtype=qkv.dtype, device=qkv.device)
+    _hip.call("iseg_gemma_rope_cache", ptr(qkv), W, ptr(q), nq * h, ptr(kc), bs, ld, ptr(vc), bs, ld, ptr(table), B, cache.shape[2], int(pos0), Tn,
+              nq, nkv, h, dt(qkv), stream())
+    return q
+
+
+def gemma_decode_attention_supported(Tn, nq, nkv, h, dtype):
+    return dtype == torch.bfloat16 and bool(_hip.lib().iseg_gemma_decode_attention_supported(int(Tn), int(nq), int(nkv), int(h), BF16))
+
+
+def gemma_decode_attention_splits(B, pos0, Tn, nq, nkv, h):
+    """the chunk count iseg_gemma_decode_attention plans for these arguments"""
+    return int(_hip.lib().iseg_gemma_decode_attention_splits(int(B), int(pos0), int(Tn), int(nq), int(nkv), int(h)))
+
+
+def gemma_decode_attention(q, cache, pos0, nq, nkv, h, scale, splits=0):
+    """attention of the Tn new tokens q [B, Tn, nq h] at positions pos0 .. over the keys s <= pos0 + t of cache [B, 2, S, nkv, h]
+    -> [B, Tn, nq h]; splits = 0: the launcher's plan"""
+    _require_cuda(q, cache)
+    B, Tn, _ = q.shape
+    kc, vc, bs, ld = _gemma_cache_views(cache, nkv, h)
+    L = _hip.lib()
+    out = torch.empty((B, Tn, nq * h), dtype=q.dtype, device=q.device)
+    ws, nbytes = workspace(L.iseg_gemma_decode_attention_scratch_bytes(B, int(pos0), Tn, nq, nkv, h, int(splits)), q.device)
+    _hip.check(L.iseg_gemma_decode_attention(ptr(q), q.stride(1), ptr(kc), bs, ld, ptr(vc), bs, ld, ptr(out), nq * h, ptr(ws), nbytes, B,
+                                             cache.shape[2], int(pos0), Tn, nq, nkv, h, float(scale), int(splits), dt(q), stream()),
+               "iseg_gemma_decode_attention")
+    return out

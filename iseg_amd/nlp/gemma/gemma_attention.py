@@ -6,7 +6,12 @@ rotary embedding (:96-114, interleaved output, fp32 angles -- DESIGN.md) turns i
 the wipe of rows without an attended token :189-195) reads column ranges of it.  The attention mask is not an argument: it is always the causal
 mask merged with the key padding mask (gemma_decoder_block.py:114-136), which the core builds from `padding_mask`.
 
-Out of scope: the KV cache -- `cache=` / a non-zero `cache_update_index` raise NotImplementedError."""
+The KV cache (:161-179) has an entry point of its own, `call_with_cache(x, cache, cache_update_index)`: inference only, on
+F.gemma_rope_cache (rotary embedding at the positions cache_update_index + t, written straight into the cache) and F.gemma_cached_attention_core
+(the split-KV decode kernels of csrc/gemma_decode.hip).  The `cache=` / `cache_update_index=` keywords of `call` raise NotImplementedError and
+name it."""
+import torch
+
 from ... import functional as F
 from ...nn import Layer
 
@@ -35,9 +40,23 @@ class CachedGemmaAttention(Layer):
 
     def call(self, x, padding_mask=None, cache=None, cache_update_index=0, training=None):
         if cache is not None or cache_update_index:
-            raise NotImplementedError("CachedGemmaAttention: the KV cache (cache=, cache_update_index) is not built")
+            raise NotImplementedError("CachedGemmaAttention: call() takes no KV cache (cache=, cache_update_index); use call_with_cache(x, cache, "
+                                      "cache_update_index)")
         nq, nkv, h = self.num_query_heads, self.num_key_value_heads, self.head_dim
         qkv = F.gemma_qkv(x, self.query_kernel, self.key_kernel, self.value_kernel)
         qkv = F.gemma_rope(qkv, nq, nkv, h)
         y = F.gemma_attention_core(qkv, padding_mask, nq, nkv, h, dropout_rate=self.dropout, training=bool(training))
         return F.dense(y, self.attention_output_kernel, kshape=(nq * h, self.hidden_dim))      # "btnh,nhd->btd" (:82-91)
+
+    def call_with_cache(self, x, cache, cache_update_index):
+        """x [B, Tn, d]: the tokens at positions cache_update_index .. + Tn - 1; cache [B, 2, S, nkv, h]: this layer's keys and values -> (out, cache)
+        (:161-201 with a cache; the mask is compute_causal_mask(cache_index) alone, no padding mask).  Inference only.  The cache is updated IN
+        PLACE and the same tensor is returned; the reference builds a new one (dynamic_update_slice, tf.stack)."""
+        if not self.built:
+            raise RuntimeError("CachedGemmaAttention.call_with_cache: build the layer first (one uncached call)")
+        nq, nkv, h = self.num_query_heads, self.num_key_value_heads, self.head_dim
+        with torch.no_grad():
+            qkv = F.gemma_qkv(x, self.query_kernel, self.key_kernel, self.value_kernel)
+            q = F.gemma_rope_cache(qkv, cache, int(cache_update_index), nq, nkv, h)
+            y = F.gemma_cached_attention_core(q, cache, int(cache_update_index), nq, nkv, h)
+            return F.dense(y, self.attention_output_kernel, kshape=(nq * h, self.hidden_dim)), cache

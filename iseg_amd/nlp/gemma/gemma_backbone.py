@@ -4,8 +4,10 @@ floats holding integers, as the reference's Input declares), "padding_mask": [B,
 [B, T, hidden_dim] in the compute dtype.  Variable names are the reference's (:231-243): token_embedding/embeddings,
 decoder_block_{i}/..., final_normalization/scale.
 
-Out of scope: the KV cache, GemmaCausalLM and generation, the tokenizer and preprocessors, presets and their download, the reverse (logits) use
-of the tied embedding (`ReversibleEmbedding(reverse=True)`) and get_layout_map -- the last two raise NotImplementedError."""
+The reverse (logits) use of the tied embedding is `ReversibleEmbedding.logits(x)` (F.embedding_logits); the `reverse=True` keyword of its `call`
+raises NotImplementedError and names it.  The KV cache, GemmaCausalLM and generation are in gemma_causal.py.
+
+Out of scope: the tokenizer and preprocessors, presets and their download, and get_layout_map (raises NotImplementedError)."""
 import math
 
 import torch
@@ -25,7 +27,7 @@ def _embedding_init(name):
 
 
 class ReversibleEmbedding(Layer):
-    """the token table of :113-125; only the forward lookup is built"""
+    """the token table of :113-125: `call` is the lookup, `logits` the reverse use x @ embeddings^T (one parameter, both gradients add up on it)"""
 
     def __init__(self, input_dim, output_dim, name=None, **kwargs):
         super().__init__(name=name, **kwargs)
@@ -37,8 +39,14 @@ class ReversibleEmbedding(Layer):
 
     def call(self, token_ids, reverse=False, scale=1.0, training=None):
         if reverse:
-            raise NotImplementedError("ReversibleEmbedding: the reverse (logits) use of the tied embedding is not built")
+            raise NotImplementedError("ReversibleEmbedding: call() has no reverse use; the logits of the tied embedding are logits(x)")
         return F.embedding(token_ids, self.embeddings, scale)
+
+    def logits(self, x):
+        """x [B, T, output_dim] -> [B, T, input_dim] = x @ embeddings^T (ReversibleEmbedding(reverse=True), gemma_causal.py:158)"""
+        if not self.built:
+            self.build()
+        return F.embedding_logits(x, self.embeddings)
 
 
 class GemmaBackbone(Layer):

@@ -6,7 +6,10 @@ ffw_gating/kernel and ffw_gating_2/kernel are [d, intermediate_dim // 2], ffw_li
 product is iseg_glu_fwd / _bwd with ISEG_ACT_GELU_TANH.  Dropout (default 0): on the attention probabilities (gemma_attention.py:145-148) and on
 the attention output (:163-164); the reference also constructs `feedforward_dropout` (:68) and never calls it, and so it is here.
 
-Out of scope: the KV cache -- `cache=` / a non-zero `cache_update_index` raise NotImplementedError."""
+The KV cache has an entry point of its own, `call_with_cache(x, cache, cache_update_index)` (inference only); the `cache=` /
+`cache_update_index=` keywords of `call` raise NotImplementedError and name it."""
+import torch
+
 from ... import functional as F
 from ...nn import Layer
 from .gemma_attention import CachedGemmaAttention
@@ -47,7 +50,8 @@ class GemmaDecoderBlock(Layer):
 
     def call(self, x, padding_mask=None, cache=None, cache_update_index=0, training=None):
         if cache is not None or cache_update_index:
-            raise NotImplementedError("GemmaDecoderBlock: the KV cache (cache=, cache_update_index) is not built")
+            raise NotImplementedError("GemmaDecoderBlock: call() takes no KV cache (cache=, cache_update_index); use call_with_cache(x, cache, "
+                                      "cache_update_index)")
         x, skip = F.fork(x)
         attention = self.attention(self.pre_attention_norm(x), padding_mask=padding_mask, training=training)
         attention = F.dropout(attention, self.dropout, bool(training))
@@ -58,3 +62,17 @@ class GemmaDecoderBlock(Layer):
         x2 = F.dense(normalized_2, self.ffw_gating_2_kernel)
         y = F.dense(F.glu(x1, x2, "gelu_tanh"), self.ffw_linear_kernel)
         return F.add(y, skip)
+
+    def call_with_cache(self, x, cache, cache_update_index):
+        """GemmaDecoderBlock.call with a cache (:139-178): x [B, Tn, d] at positions cache_update_index .., cache [B, 2, S, nkv, h] -> (x, cache).
+        Inference only, no dropout, no padding mask.  The cache is updated IN PLACE and the same tensor is returned; the reference returns a new one."""
+        if not self.built:
+            raise RuntimeError("GemmaDecoderBlock.call_with_cache: build the layer first (one uncached call)")
+        with torch.no_grad():
+            attention, cache = self.attention.call_with_cache(self.pre_attention_norm(x), cache, cache_update_index)
+            attention_x = F.add(x, attention)
+            normalized = self.pre_ffw_norm(attention_x)
+            x1 = F.dense(normalized, self.ffw_gating_kernel)
+            x2 = F.dense(normalized, self.ffw_gating_2_kernel)
+            y = F.dense(F.glu(x1, x2, "gelu_tanh"), self.ffw_linear_kernel)
+            return F.add(y, attention_x), cache
