@@ -1255,6 +1255,39 @@ size_t iseg_gemma_decode_attention_scratch_bytes(int64_t batch, int pos0, int Tn
 int iseg_gemma_decode_attention(const void* q, int64_t ldq, const void* kcache, int64_t k_batch, int64_t ldk, const void* vcache, int64_t v_batch,
                                 int64_t ldv, void* out, int64_t ldo, void* ws, size_t ws_bytes, int64_t batch, int S, int pos0, int Tn, int nq,
                                 int nkv, int h, float scale, int splits, int dtype, iseg_stream_t stream);
+/* The samplers behind GemmaCausalLM.compile(sampler=) (nlp/gemma/gemma_causal.py class docstring: keras_nlp.samplers Random / TopK / TopP): one
+ * token id per row of logits [batch, V] (bf16 or fp32, row pitch ld >= V elements) from ONE uniform u[b] in [0, 1) per row that the caller
+ * draws; no random numbers are made here.  tokens int32 [batch].  Per row x, in exact arithmetic (the kernels work in fp32):
+ *   order      x descending, then index ascending; NaN above +inf above the finite values above -inf, -0 ties with +0.  The order is taken on
+ *              the STORED values (not on x / T), so ties are the input's.
+ *   non-finite if the first of the order is NaN, +inf or -inf (all masked) its index is the token -- the lowest index holding the top value,
+ *              torch.argmax's answer -- and u is not read.  Otherwise -inf entries weigh 0 and are never drawn.
+ *   weights    w_i = exp(x_i / T - max_j x_j / T), W = sum_i w_i, T = temperature > 0.
+ *   kept set   ISEG_SAMPLE_RANDOM: every index.  ISEG_SAMPLE_TOP_K: the first min(k, V) of the order.  ISEG_SAMPLE_TOP_P: among the first
+ *              k' = min(k, V) of the order (k = 0: V), position j iff the weights of the positions before it sum to <= p W (the full softmax
+ *              mass, not a renormalised one); the first is always kept.
+ *   draw       the kept ids in TOKEN-ID order, S = their weight: the token is the smallest kept id i whose cumulative kept weight up to and
+ *              including i exceeds u S; if rounding leaves none, the largest kept id with a weight > 0.  Ids with weight 0 are never returned.
+ * Pass 1, one workgroup per (row, chunk of whole 2048-element tiles): the chunk's top key (a monotone integer image of the stored value) with
+ * its lowest index, the chunk's weight sum relative to its own maximum and, for TOP_K / TOP_P, 256-bin histograms of counts and of mass over the
+ * top key digit, mass as fixed-point integers so that the sums do not depend on the order of the additions.  Pass 2, one workgroup per row,
+ * merges the partials in chunk order, finds the cut key by radix selection (the remaining digits from filtered sweeps of the row) and how many
+ * of the elements tied with it are kept, lowest index first, then draws with prefix sums over the row as stored.  No atomics across
+ * workgroups: a second call returns the same tokens.  128-bit loads when logits is 16-byte aligned and ld * element size is a multiple of 16,
+ * scalar loads otherwise.
+ * splits: 0 = the launcher's plan, a function of (batch, V) alone that iseg_token_sample_splits returns; a positive value is taken, clipped to
+ * the number of 2048-element tiles that hold an element.  The scratch buffer (8-byte aligned) holds iseg_token_sample_scratch_bytes (same
+ * `splits` argument); a smaller one returns ISEG_ERR_WORKSPACE.
+ * Supported (iseg_token_sample_supported): bf16 or fp32, 1 <= V <= 2^20, k >= 0, k >= 1 for TOP_K (k > V is V); anything else returns
+ * ISEG_ERR_UNSUPPORTED.  temperature <= 0 or not finite, p outside (0, 1] and ld < V return ISEG_ERR_ARG.  All before any memory is touched. */
+#define ISEG_SAMPLE_RANDOM 0
+#define ISEG_SAMPLE_TOP_K 1
+#define ISEG_SAMPLE_TOP_P 2
+int iseg_token_sample_supported(int64_t V, int mode, int k, int dtype);
+int iseg_token_sample_splits(int64_t batch, int64_t V);
+size_t iseg_token_sample_scratch_bytes(int64_t batch, int64_t V, int mode, int k, int splits);
+int iseg_token_sample(const void* logits, int64_t ld, const float* u, int32_t* tokens, void* ws, size_t ws_bytes, int64_t batch, int64_t V, int mode,
+                      int k, float p, float temperature, int splits, int dtype, iseg_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -12,6 +12,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libiseg_hip.so")
 
 F32, BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_GELU_GRAD, ACT_RELU_GRAD, ACT_MUL_AUX, ACT_SIGMOID, ACT_SWISH, ACT_GELU_TANH = 0, 1, 2, 3, 4, 5, 6, 7, 8
+SAMPLE_RANDOM, SAMPLE_TOP_K, SAMPLE_TOP_P = 0, 1, 2
 
 
 class HipLibraryMissing(RuntimeError):
@@ -303,6 +304,10 @@ SIGNATURES = {
     "iseg_gemma_decode_attention_splits": (_i, [_l, _i, _i, _i, _i, _i]),
     "iseg_gemma_decode_attention_scratch_bytes": (_z, [_l, _i, _i, _i, _i, _i, _i]),
     "iseg_gemma_decode_attention": (_i, [_p, _l, _p, _l, _l, _p, _l, _l, _p, _l, _p, _z, _l, _i, _i, _i, _i, _i, _i, _f, _i, _i, _p]),
+    "iseg_token_sample_supported": (_i, [_l, _i, _i, _i]),
+    "iseg_token_sample_splits": (_i, [_l, _l]),
+    "iseg_token_sample_scratch_bytes": (_z, [_l, _l, _i, _i, _i]),
+    "iseg_token_sample": (_i, [_p, _l, _p, _p, _p, _z, _l, _l, _i, _i, _f, _f, _i, _i, _p]),
     "iseg_sgd_momentum_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _f, _i, _p, _f, _p, _f, _l, _p]),
 }
 

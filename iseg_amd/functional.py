@@ -5,6 +5,7 @@ sequence of libiseg_hip.so calls.  Parameter gradients are written by the kernel
 (a view of the flat gradient buffer, see param_store.py) -- the Functions return None for parameters, so autograd
 never runs an accumulation kernel of its own for them.
 """
+import math
 import os
 
 import torch
@@ -3635,6 +3636,49 @@ def gemma_cached_attention_core(q, cache, pos0, nq, nkv, h, *, splits=0):
         if pos0 == 0 and Tn == S:
             return gemma_attention_core(packed, None, nq, nkv, h)
         return _c(_gemma_attention_composed(packed, None, int(nq), int(nkv), int(h), scale)[:, pos0:nvis])
+
+
+_SAMPLE_MODES = {"random": K.SAMPLE_RANDOM, "top_k": K.SAMPLE_TOP_K, "top_p": K.SAMPLE_TOP_P}
+SAMPLE_MAX_VOCAB = 1 << 20
+
+
+def sample_tokens(logits, u, *, mode, k=0, p=1.0, temperature=1.0, splits=0):
+    """logits [B, V] or a [B, 1, V] view (bf16 or fp32, rows of contiguous elements with any pitch), u fp32 [B] uniform in [0, 1) -> int32 [B]: one
+    token per row from softmax(logits / temperature) restricted to the kept set of `mode` (csrc/token_sample.hip, two launches):
+      "random"  every token;  "top_k"  the k largest logits;  "top_p"  among the k largest (k = 0: all), those whose preceding softmax mass is <= p.
+    Ties are ordered by index; the draw walks the kept tokens in token-id order to the first whose cumulative weight exceeds u times their sum;
+    a row whose largest entry is NaN, +inf or -inf returns torch.argmax's index (include/iseg_hip.h has the full statement).  The random number
+    is the caller's: the same u gives the same token.  Inference only; there is no torch route."""
+    if mode not in _SAMPLE_MODES:
+        raise ValueError(f"sample_tokens: mode is one of {sorted(_SAMPLE_MODES)}, got {mode!r}")
+    if logits.requires_grad:
+        raise RuntimeError("sample_tokens: sampling is inference only (the logits require grad)")
+    if logits.dim() == 3 and logits.shape[1] == 1:
+        logits = logits[:, 0]
+    if logits.dim() != 2 or u.dim() != 1 or u.shape[0] != logits.shape[0]:
+        raise ValueError(f"sample_tokens: logits is [B, V] or [B, 1, V] and u is [B], got {tuple(logits.shape)} and {tuple(u.shape)}")
+    B, V = logits.shape
+    k, p, temperature = int(k), float(p), float(temperature)
+    if logits.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError(f"sample_tokens: logits are bfloat16 or float32, got {logits.dtype}")
+    if u.dtype != torch.float32:
+        raise ValueError(f"sample_tokens: u is float32, got {u.dtype}")
+    if not 1 <= V <= SAMPLE_MAX_VOCAB:
+        raise ValueError(f"sample_tokens: the vocabulary is 1 .. {SAMPLE_MAX_VOCAB} entries, got {V}")
+    if k < 0 or (mode == "top_k" and k < 1):
+        raise ValueError(f"sample_tokens: k >= 0, and k >= 1 for top_k, got {k}")
+    if not (temperature > 0.0 and math.isfinite(temperature)):
+        raise ValueError(f"sample_tokens: temperature must be positive and finite, got {temperature}")
+    if not 0.0 < p <= 1.0:
+        raise ValueError(f"sample_tokens: p must lie in (0, 1], got {p}")
+    if nn.dry_run():
+        return _dry((B,), logits, torch.int32)
+    if B == 0:
+        return torch.empty((0,), dtype=torch.int32, device=logits.device)
+    if logits.stride(1) != 1 or (B > 1 and logits.stride(0) < V):
+        logits = logits.contiguous()
+    with torch.no_grad():
+        return K.token_sample(logits, _c(u), _SAMPLE_MODES[mode], k, p, temperature, splits)
 
 
 def embedding_logits(x, table):

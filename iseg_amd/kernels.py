@@ -2314,3 +2314,31 @@ def gemma_decode_attention(q, cache, pos0, nq, nkv, h, scale, splits=0):
                                              cache.shape[2], int(pos0), Tn, nq, nkv, h, float(scale), int(splits), dt(q), stream()),
                "iseg_gemma_decode_attention")
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------
+# token sampling (csrc/token_sample.hip)
+# ---------------------------------------------------------------------------------------------------------
+SAMPLE_RANDOM, SAMPLE_TOP_K, SAMPLE_TOP_P = _hip.SAMPLE_RANDOM, _hip.SAMPLE_TOP_K, _hip.SAMPLE_TOP_P
+
+
+def token_sample_supported(V, mode, k, dtype):
+    return dtype in _DT and bool(_hip.lib().iseg_token_sample_supported(int(V), int(mode), int(k), _DT[dtype]))
+
+
+def token_sample_splits(B, V):
+    """the chunk count iseg_token_sample plans for these arguments"""
+    return int(_hip.lib().iseg_token_sample_splits(int(B), int(V)))
+
+
+def token_sample(logits, u, mode, k, p, temperature, splits=0):
+    """one token id per row of logits [B, V] (rows of contiguous elements, any pitch >= V) from the uniforms u fp32 [B]: random, top-k or top-p
+    sampling as include/iseg_hip.h states it -> int32 [B]; splits = 0: the launcher's plan"""
+    _require_cuda(logits, u)
+    B, V = logits.shape
+    L = _hip.lib()
+    tokens = torch.empty((B,), dtype=torch.int32, device=logits.device)
+    ws, nbytes = workspace(L.iseg_token_sample_scratch_bytes(B, V, int(mode), int(k), int(splits)), logits.device)
+    _hip.check(L.iseg_token_sample(ptr(logits), logits.stride(0), ptr(u), ptr(tokens), ptr(ws), nbytes, B, V, int(mode), int(k), float(p),
+                                   float(temperature), int(splits), dt(logits), stream()), "iseg_token_sample")
+    return tokens

@@ -1,5 +1,5 @@
 """nlp/gemma/gemma_causal.py of the reference (GemmaCausalLM :19-444): the backbone with the tied embedding as the language-model head, the KV cache
-and greedy generation.
+and generation (greedy, or with a sampler of nlp/samplers.py).
 
     logits = model({"token_ids": [B, T], "padding_mask": [B, T]})                    (:156-158)  trainable: backbone + ReversibleEmbedding.logits
     logits, hidden_states, cache = model.call_with_cache(token_ids, cache, index)     (:186-226)  inference only
@@ -11,10 +11,11 @@ its [B, 2, S, nkv, h] view, which the layer updates IN PLACE (F.gemma_rope_cache
 copies into a new one.  Single-token steps run on the split-KV decode kernels of csrc/gemma_decode.hip; the seeding call (the whole prompt at
 index 0) on the training kernels of csrc/gemma.hip.  No padding mask is passed on the cached path (the reference passes none).
 
-The sampler restates keras_nlp's greedy Sampler.__call__ (`greedy_sample`): the only one built; compile(sampler=) with anything else raises
-NotImplementedError.
+compile(sampler=) takes "greedy" (the default: keras_nlp's greedy Sampler.__call__, `greedy_sample`) or an instance of nlp/samplers.py:
+GreedySampler, RandomSampler, TopKSampler, TopPSampler.  The random ones choose each token with the fused kernels of csrc/token_sample.hip from
+one uniform per row and step.  Every other string alias raises NotImplementedError naming the classes.
 
-Out of scope: the tokenizer and preprocessors (strings need a `preprocessor`, and none is built), presets, samplers other than greedy, training
+Out of scope: the tokenizer and preprocessors (strings need a `preprocessor`, and none is built), presets, beam and contrastive samplers, training
 through the cache, HIP-graph replay of the decode step (the cache index is a host argument), paged caches."""
 import math
 
@@ -23,6 +24,11 @@ import torch
 from ... import functional as F
 from ... import nn
 from ...nn import Layer
+from ..samplers import Sampler, sample_loop
+
+
+def _argmax(logits):
+    return torch.argmax(logits, dim=-1)
 
 
 def greedy_sample(next, prompt, cache, index, mask, end_token_id=None):
@@ -30,20 +36,7 @@ def greedy_sample(next, prompt, cache, index, mask, end_token_id=None):
     becomes the token at `index` unless mask[:, index] marks a user token, which is kept.  With an end_token_id the loop stops before a step
     once every row holds an end token at a position where `mask` is false; rows that are finished keep generating until all are.
     prompt [B, S] integers (a copy is returned), mask [B, S] bool, index: the first position to fill."""
-    prompt = prompt.clone()
-    mask = mask.to(torch.bool)
-    max_length = prompt.shape[1]
-    index = int(index)
-    while index < max_length:
-        if end_token_id is not None:
-            done = ((prompt == end_token_id) & ~mask).any(dim=-1)
-            if bool(done.all()):
-                break
-        logits, _, cache = next(prompt, cache, index)
-        token = torch.argmax(logits, dim=-1).to(prompt.dtype)
-        prompt[:, index] = torch.where(mask[:, index], prompt[:, index], token)
-        index += 1
-    return prompt
+    return sample_loop(_argmax, next, prompt, cache, index, mask, end_token_id=end_token_id)
 
 
 def generated_padding_mask(token_ids, padding_mask, end_token_id):
@@ -79,8 +72,14 @@ class GemmaCausalLM(Layer):
         self.built = True
 
     def compile(self, sampler="greedy", **unused):
-        if sampler != "greedy":
-            raise NotImplementedError(f"GemmaCausalLM.compile: only the greedy sampler is built, got {sampler!r}")
+        """sampler: "greedy", or an instance of iseg_amd.nlp.samplers (GreedySampler, RandomSampler, TopKSampler, TopPSampler or a Sampler subclass
+        of the caller's).  The other string aliases of keras_nlp.samplers.get are not built."""
+        if isinstance(sampler, str):
+            if sampler != "greedy":
+                raise NotImplementedError(f'GemmaCausalLM.compile: the only string alias is "greedy", got {sampler!r}; pass an instance of '
+                                          "iseg_amd.nlp.samplers.GreedySampler, RandomSampler, TopKSampler or TopPSampler instead")
+        elif not isinstance(sampler, Sampler):
+            raise ValueError(f'GemmaCausalLM.compile: sampler is "greedy" or an iseg_amd.nlp.samplers.Sampler instance, got {sampler!r}')
         self.sampler = sampler
 
     # ---- the trainable forward (:156-158) ------------------------------------------------------------------------------------------------------
@@ -114,7 +113,7 @@ class GemmaCausalLM(Layer):
 
     def generate_step(self, inputs, end_token_id=None):
         """one batch of {"token_ids" [B, S], "padding_mask" [B, S]} (true = user token) -> the same dictionary with the remaining positions filled
-        greedily (:241-314): generation starts at the shortest row's length; longer rows keep their own tokens there"""
+        by the compiled sampler, greedily by default (:241-314): generation starts at the shortest row's length; longer rows keep their own tokens there"""
         token_ids, padding_mask = inputs["token_ids"], inputs["padding_mask"].to(torch.bool)
         _, cache = self._build_cache(token_ids)
         index = int(padding_mask.to(torch.int32).sum(dim=-1).min().item())
@@ -125,7 +124,10 @@ class GemmaCausalLM(Layer):
             logits, hidden_states, cache = self.call_with_cache(prompt[:, cache_update_index:cache_update_index + 1], cache, cache_update_index)
             return logits[:, 0], hidden_states[:, 0], cache
 
-        token_ids = greedy_sample(next, token_ids, cache, index, padding_mask, end_token_id=end_token_id)
+        if isinstance(self.sampler, Sampler):
+            token_ids = self.sampler(next, token_ids, cache, index, padding_mask, end_token_id=end_token_id)
+        else:
+            token_ids = greedy_sample(next, token_ids, cache, index, padding_mask, end_token_id=end_token_id)
         return {"token_ids": token_ids, "padding_mask": generated_padding_mask(token_ids, padding_mask, end_token_id)}
 
     def generate(self, inputs, max_length=None):

@@ -1,0 +1,145 @@
+"""keras_nlp.samplers as GemmaCausalLM.compile(sampler=) takes them (the class docstring of nlp/gemma/gemma_causal.py in the reference): the decoding
+loop of Sampler.__call__ and the greedy, random, top-k and top-p rules for the next token.  Defaults are keras_nlp's.
+
+    sampler = TopKSampler(k=5, seed=7)
+    model.compile(sampler=sampler)
+    out = model.generate({"token_ids": ..., "padding_mask": ...})
+
+The loop (`sample_loop`) is the one greedy_sample of gemma_causal.py has always run; a subclass supplies get_next_token(logits) alone.  The random
+samplers draw one uniform per row and step from a torch.Generator they own (made on the logits' device at first use, seeded with `seed`, or
+from the library's seed stream when seed is None) and hand it with the logits to F.sample_tokens: the fused kernels of csrc/token_sample.hip.
+The same seed, prompt and weights give the same tokens; the random stream itself is torch's, not the reference's.
+
+Out of scope: BeamSampler, ContrastiveSampler, the string aliases ("top_k", ...) of keras_nlp.samplers.get."""
+import math
+
+import torch
+
+from .. import functional as F
+
+
+def sample_loop(get_next_token, next, prompt, cache, index, mask, end_token_id=None):
+    """keras_nlp Sampler.__call__: while index < max_length, logits = next(prompt, cache, index)[0]; get_next_token(logits) becomes the token at
+    `index` unless mask[:, index] marks a user token, which is kept.  With an end_token_id the loop stops before a step once every row holds an
+    end token at a position where `mask` is false; rows that are finished keep generating until all are.
+    prompt [B, S] integers (a copy is returned), mask [B, S] bool, index: the first position to fill."""
+    prompt = prompt.clone()
+    mask = mask.to(torch.bool)
+    max_length = prompt.shape[1]
+    index = int(index)
+    while index < max_length:
+        if end_token_id is not None:
+            done = ((prompt == end_token_id) & ~mask).any(dim=-1)
+            if bool(done.all()):
+                break
+        logits, _, cache = next(prompt, cache, index)
+        token = get_next_token(logits).to(prompt.dtype)
+        prompt[:, index] = torch.where(mask[:, index], prompt[:, index], token)
+        index += 1
+    return prompt
+
+
+def _check_temperature(temperature):
+    temperature = float(temperature)
+    if not (temperature > 0.0 and math.isfinite(temperature)):
+        raise ValueError(f"Sampler: temperature must be positive and finite, got {temperature}")
+    return temperature
+
+
+class Sampler:
+    """the base class: the loop, and the temperature every subclass carries.  get_next_token(logits [B, V]) -> token ids [B]"""
+
+    def __init__(self, temperature=1.0):
+        self.temperature = _check_temperature(temperature)
+
+    def __call__(self, next, prompt, cache=None, index=0, mask=None, end_token_id=None):
+        if mask is None:
+            mask = torch.zeros_like(prompt, dtype=torch.bool)
+        return sample_loop(self.get_next_token, next, prompt, cache, index, mask, end_token_id=end_token_id)
+
+    def get_next_token(self, logits):
+        raise NotImplementedError(f"{type(self).__name__}.get_next_token: a sampler defines how the next token is chosen")
+
+    def get_config(self):
+        return {"temperature": self.temperature}
+
+    @classmethod
+    def from_config(cls, config):
+        return cls(**config)
+
+
+class GreedySampler(Sampler):
+    """the most probable token: torch.argmax, the path GemmaCausalLM has always taken (the temperature does not change an argmax)"""
+
+    def get_next_token(self, logits):
+        return torch.argmax(logits, dim=-1)
+
+
+class _SeededSampler(Sampler):
+    mode = None
+
+    def __init__(self, seed=None, temperature=1.0):
+        super().__init__(temperature)
+        if seed is not None and (isinstance(seed, bool) or not isinstance(seed, int)):
+            raise ValueError(f"{type(self).__name__}: seed is an integer or None, got {seed!r}")
+        self.seed = seed
+        self._generator = None
+
+    def uniforms(self, logits):
+        """fp32 [B] in [0, 1): one draw per row from this sampler's own generator"""
+        if self._generator is None or self._generator.device != logits.device:
+            self._generator = torch.Generator(device=logits.device)
+            self._generator.manual_seed((self.seed if self.seed is not None else F.next_seed()) & 0x7FFFFFFFFFFFFFFF)
+        return torch.rand(logits.shape[0], generator=self._generator, device=logits.device, dtype=torch.float32)
+
+    def _kernel_args(self):
+        return {}
+
+    def get_next_token(self, logits):
+        return F.sample_tokens(logits, self.uniforms(logits), mode=self.mode, temperature=self.temperature, **self._kernel_args())
+
+    def get_config(self):
+        return {**super().get_config(), "seed": self.seed}
+
+
+class RandomSampler(_SeededSampler):
+    """a draw from softmax(logits / temperature) over the whole vocabulary"""
+    mode = "random"
+
+
+class TopKSampler(_SeededSampler):
+    """a draw from softmax(logits / temperature) over the k largest logits (ties by index)"""
+    mode = "top_k"
+
+    def __init__(self, k=5, seed=None, temperature=1.0):
+        super().__init__(seed, temperature)
+        if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+            raise ValueError(f"TopKSampler: k is an integer >= 1, got {k!r}")
+        self.k = k
+
+    def _kernel_args(self):
+        return {"k": self.k}
+
+    def get_config(self):
+        return {**super().get_config(), "k": self.k}
+
+
+class TopPSampler(_SeededSampler):
+    """a draw from softmax(logits / temperature) over the most probable tokens whose preceding probability mass is <= p, optionally looking at the
+    k largest alone (k = None: the whole vocabulary)"""
+    mode = "top_p"
+
+    def __init__(self, p=0.1, k=None, seed=None, temperature=1.0):
+        super().__init__(seed, temperature)
+        p = float(p)
+        if not 0.0 < p <= 1.0:
+            raise ValueError(f"TopPSampler: p must lie in (0, 1], got {p}")
+        if k is not None and (isinstance(k, bool) or not isinstance(k, int) or k < 1):
+            raise ValueError(f"TopPSampler: k is an integer >= 1 or None, got {k!r}")
+        self.p, self.k = p, k
+
+    def _kernel_args(self):
+        return {"p": self.p, "k": self.k or 0}
+
+    def get_config(self):
+        return {**super().get_config(), "p": self.p, "k": self.k}
