@@ -1288,6 +1288,56 @@ int iseg_token_sample_splits(int64_t batch, int64_t V);
 size_t iseg_token_sample_scratch_bytes(int64_t batch, int64_t V, int mode, int k, int splits);
 int iseg_token_sample(const void* logits, int64_t ld, const float* u, int32_t* tokens, void* ws, size_t ws_bytes, int64_t batch, int64_t V, int mode,
                       int k, float p, float temperature, int splits, int dtype, iseg_stream_t stream);
+/* The language-model head's loss without a [tokens, vocab] tensor: SparseCategoricalCrossentropy(from_logits=True) and
+ * SparseCategoricalAccuracy of nlp/gemma/gemma_causal.py:165-172 on the logits Z = X E^T (X [M, d] hidden states, E [V, d] the tied table).  The
+ * caller cuts the vocabulary into chunks [v0, v0 + w) of any width w >= 1, has iseg_gemm write Z_c = X E[v0 : v0 + w]^T [M, w] in FP32 (row pitch
+ * ld >= w elements; never rounded to bf16) and hands each chunk to the kernels below.  Rows are independent; t = targets[r] (int32).
+ *   state      per row, fp32 m, s, z_t and int32 argmax.  Before the first chunk the caller sets m = -inf, s = 0 (z_t and argmax: anything, 0
+ *              is a good choice).  After the chunks that cover [0, V) once each, in increasing v0:  m = max_v Z[r,v];  s = sum_v exp(Z[r,v] - m);
+ *              z_t = Z[r,t] if 0 <= t < V, else untouched;  argmax = the SMALLEST v with Z[r,v] = m (ties inside a chunk and across chunks).
+ *   chunk_fwd  merges one chunk into the state:  m' = max(m, max_j z_j);  s' = s exp(m - m') + sum_j exp(z_j - m');  z_t = z_{t - v0} when
+ *              v0 <= t < v0 + w;  argmax = v0 + (smallest j with z_j = max_j z_j) when that maximum is > m (strictly: an earlier chunk keeps a tie).
+ *              exp(-inf - x) is 0 and no difference of two -inf is formed: the empty state and -inf logits cost nothing.
+ *   non-finite NaN is never a maximum and never the argmax (comparisons with it are false), but it is summed: one NaN logit in a row makes
+ *              s, lse and the loss of THAT row NaN, and every entry of that row of G.  A +inf logit does the same (inf - inf), as softmax does.
+ *              A row of -inf alone has lse = -inf and a NaN loss.
+ *   finalise   lse[r] = m + log s;  valid = 0 <= t < V;  w_r = valid ? (weights ? weights[r] : 1) : 0;  loss[r] = scale w_r (lse - z_t), evaluated
+ *              from the fp32 state in fp64 as log s - (z_t - m) and rounded once (so is lse), and
+ *              exactly 0 where w_r = 0 whatever the row holds (the zero row of tf.one_hot, as iseg_softmax_ce_ignore treats a label outside the
+ *              classes).  scale is a constant factor of the loss (1, or 1 / tokens for Keras' sum_over_batch_size) that chunk_bwd is given too;
+ *              match[r] = valid and argmax = t.  sums[0..2] = sum_r loss[r], sum_r w_r match[r], sum_r w_r: wavefront and workgroup partial sums
+ *              in a fixed order, the per-workgroup records (scratch, iseg_lm_head_ce_scratch_bytes(M) bytes, 4-byte aligned; a smaller one
+ *              returns ISEG_ERR_WORKSPACE) summed in fp64 by one workgroup.  No atomics: a second call returns the same bits.
+ *   chunk_bwd  from the chunk's Z_c computed AGAIN (nothing [M, V] is saved) and the final state's m and s:
+ *                  G[r, j] = scale w_r up_r (exp(z_j - lse[r]) - [v0 + j == t]),   j < w,
+ *              evaluated as exp(z_j - m) (c_r / s) - [v0 + j == t] c_r with c_r = scale w_r up_r (the rounding of m + log s would move every
+ *              probability of the row by half an ulp of lse; z_j - m is exact for neighbouring magnitudes; c_r and c_r / s are rounded once
+ *              each), in fp32 and rounded once to `dtype`.  exp is v_exp_f32 on t log2 e = hi + lo with the product's rounding error kept
+ *              in lo: one ulp whatever |t| is, in chunk_fwd too (row pitch ldg >= w; columns j >= w are not written).  upstream NULL: up_r = 1.
+ *              Rows with w_r = 0 are written as zeros without reading their logits (not NaN * 0).  X^T G and G E[v0 : v0 + w] are iseg_gemm's.
+ * One wavefront per row and chunk, 16-byte loads along the row when the base is 16-byte aligned and the pitch a multiple of 16 bytes (both
+ * buffers for chunk_bwd), scalar accesses otherwise; the last, narrower chunk and any w that is no multiple of 4 take the scalar path at the
+ * row's end only.  Rows are taken in trips of at most 32768 per launch grid.  v0 + w must stay below 2^31 - 1024.  Bad arguments return
+ * ISEG_ERR_ARG before any memory is touched.  iseg_lm_head_ce_chunk_default: the chunk width the Python layer uses when none is forced, in
+ * [1, V] (0 for V < 1); profiles/lm_head_ce_kbench.md has the sweep behind it. */
+int iseg_lm_head_ce_chunk_default(int64_t M, int64_t V);
+size_t iseg_lm_head_ce_scratch_bytes(int64_t M);
+int iseg_lm_head_ce_chunk_fwd(const float* z, int64_t ld, const int32_t* targets, float* m, float* s, float* zt, int32_t* argmax, int64_t M,
+                              int64_t v0, int64_t w, iseg_stream_t stream);
+/* z_t[r] = x_r . E[t_r] once more for the rows with 0 <= t < V (the others are not touched): the d products summed in fp64 and rounded once to
+ * fp32, in place of the value chunk_fwd took from Z_c.  The loss sets ONE logit against lse, a softmax-weighted average of all of them that
+ * smooths the GEMM's accumulation error (d roundings per logit); the single logit carries it whole, and it is what separates the loss from the
+ * correctly rounded one at the fp32 compute type.  Call it after the chunks and before finalise; x [M, d] and table [V, d] in `dtype` with
+ * their row pitches in elements.  One wavefront per row, 16-byte loads when both bases are 16-byte aligned, both pitches multiples of 16 bytes
+ * and d a multiple of 8, scalar loads otherwise. */
+int iseg_lm_head_ce_target_logit(const void* x, int64_t ldx, const void* table, int64_t ldt, const int32_t* targets, float* zt, int64_t M, int64_t V,
+                                 int64_t d, int dtype, iseg_stream_t stream);
+int iseg_lm_head_ce_finalise(const float* m, const float* s, const float* zt, const int32_t* argmax, const int32_t* targets, const float* weights,
+                             float* loss, float* lse, int32_t* match, float* sums, void* scratch, size_t scratch_bytes, int64_t M, int64_t V,
+                             float scale, iseg_stream_t stream);
+int iseg_lm_head_ce_chunk_bwd(const float* z, int64_t ld, const float* m, const float* s, const int32_t* targets, const float* weights,
+                              const float* upstream, float scale, void* g, int64_t ldg, int64_t M, int64_t V, int64_t v0, int64_t w, int dtype,
+                              iseg_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -308,6 +308,12 @@ SIGNATURES = {
     "iseg_token_sample_splits": (_i, [_l, _l]),
     "iseg_token_sample_scratch_bytes": (_z, [_l, _l, _i, _i, _i]),
     "iseg_token_sample": (_i, [_p, _l, _p, _p, _p, _z, _l, _l, _i, _i, _f, _f, _i, _i, _p]),
+    "iseg_lm_head_ce_chunk_default": (_i, [_l, _l]),
+    "iseg_lm_head_ce_scratch_bytes": (_z, [_l]),
+    "iseg_lm_head_ce_chunk_fwd": (_i, [_p, _l, _p, _p, _p, _p, _p, _l, _l, _l, _p]),
+    "iseg_lm_head_ce_target_logit": (_i, [_p, _l, _p, _l, _p, _p, _l, _l, _l, _i, _p]),
+    "iseg_lm_head_ce_finalise": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _z, _l, _l, _f, _p]),
+    "iseg_lm_head_ce_chunk_bwd": (_i, [_p, _l, _p, _p, _p, _p, _p, _f, _p, _l, _l, _l, _l, _l, _i, _p]),
     "iseg_sgd_momentum_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _f, _i, _p, _f, _p, _f, _l, _p]),
 }
 

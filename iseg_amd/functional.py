@@ -3691,6 +3691,18 @@ def embedding_logits(x, table):
     return _DenseFn.apply(x, table, None, K.ACT_NONE, None, True)
 
 
+def lm_head_cross_entropy(hidden, table, target_ids, sample_weight=None, *, upstream_scale=1.0, chunk=0, with_accuracy=False):
+    """hidden [..., d] (compute dtype), table [V, d] parameter, target_ids [...] -> the per-token loss [...] in fp32,
+    upstream_scale * sample_weight * (logsumexp(hidden @ table^T) - its target's logit), without a [tokens, V] tensor: the table is walked in
+    chunks of `chunk` rows (0: the library's rule) and each chunk's fp32 logits are consumed by the kernels of csrc/lm_head_ce.hip; the backward
+    pass computes them again.  A target outside [0, V) counts as weight 0.  with_accuracy: also the first-maximal argmax [...] int32.
+    Differentiable in hidden and table; the tape node is iseg_amd/nlp/lm_loss.py's (its first lines say why).  There is no torch route."""
+    from .nlp import lm_loss
+
+    loss, argmax, _ = lm_loss.lm_head_cross_entropy(hidden, table, target_ids, sample_weight, upstream_scale=upstream_scale, chunk=chunk)
+    return (loss, argmax) if with_accuracy else loss
+
+
 _FLIP_CACHE = {}
 
 

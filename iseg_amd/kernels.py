@@ -2342,3 +2342,105 @@ def token_sample(logits, u, mode, k, p, temperature, splits=0):
     _hip.check(L.iseg_token_sample(ptr(logits), logits.stride(0), ptr(u), ptr(tokens), ptr(ws), nbytes, B, V, int(mode), int(k), float(p),
                                    float(temperature), int(splits), dt(logits), stream()), "iseg_token_sample")
     return tokens
+
+
+# ---------------------------------------------------------------------------------------------------------
+# chunked-vocabulary cross-entropy of the language-model head (csrc/lm_head_ce.hip)
+# ---------------------------------------------------------------------------------------------------------
+def lm_head_ce_chunk_default(M, V):
+    """the chunk width used when none is forced: in [1, V] (profiles/lm_head_ce_kbench.md)"""
+    return int(_hip.lib().iseg_lm_head_ce_chunk_default(int(M), int(V)))
+
+
+def lm_head_ce_pitch(w):
+    """row pitch of the chunk buffers Z_c (fp32) and G_c (compute dtype): whole 16-byte pieces in both"""
+    return (int(w) + 7) // 8 * 8
+
+
+def lm_head_ce_chunks(V, chunk):
+    """[(v0, w)] covering [0, V) once, in increasing order; the last chunk may be narrower"""
+    return [(v0, min(chunk, V - v0)) for v0 in range(0, V, chunk)]
+
+
+def lm_head_ce_logits(x2, table, z, v0, w):
+    """Z_c [M, w] fp32 (pitch z.stride(0)) = x2 [M, d] @ table[v0 : v0 + w]^T: the table's rows as they lie are the K-contiguous B operand"""
+    M, d = x2.shape
+    return gemm(x2, table[v0:v0 + w], z, M, w, d, lda=x2.stride(0), ldb=table.stride(0), ldd=z.stride(0), a_kcontig=1, b_kcontig=1)
+
+
+def lm_head_ce_state(M, device):
+    """the empty online-softmax state of M rows: (m = -inf, s = 0, z_t = 0, argmax = 0)"""
+    return (torch.full((M,), float("-inf"), dtype=torch.float32, device=device), torch.zeros((M,), dtype=torch.float32, device=device),
+            torch.zeros((M,), dtype=torch.float32, device=device), torch.zeros((M,), dtype=torch.int32, device=device))
+
+
+def lm_head_ce_chunk_fwd(z, targets, state, v0, w):
+    m, s, zt, arg = state
+    _hip.call("iseg_lm_head_ce_chunk_fwd", ptr(z), z.stride(0), ptr(targets), ptr(m), ptr(s), ptr(zt), ptr(arg), z.shape[0], int(v0), int(w), stream())
+
+
+def lm_head_ce_target_logit(x2, table, targets, state):
+    """the state's z_t again as the fp64 dot product x_r . table[t_r], rounded once: the one logit whose accumulation error the loss carries whole"""
+    _hip.call("iseg_lm_head_ce_target_logit", ptr(x2), x2.stride(0), ptr(table), table.stride(0), ptr(targets), ptr(state[2]), x2.shape[0],
+              table.shape[0], x2.shape[1], dt(x2), stream())
+
+
+def lm_head_ce_finalise(state, targets, weights, V, scale=1.0):
+    """-> (loss [M], lse [M], match [M] int32, sums [3] = sum loss, sum w match, sum w), all fp32 but match"""
+    m, s, zt, arg = state
+    M = m.shape[0]
+    L = _hip.lib()
+    loss = torch.empty((M,), dtype=torch.float32, device=m.device)
+    lse = torch.empty((M,), dtype=torch.float32, device=m.device)
+    match = torch.empty((M,), dtype=torch.int32, device=m.device)
+    sums = torch.empty((3,), dtype=torch.float32, device=m.device)
+    ws, nbytes = workspace(L.iseg_lm_head_ce_scratch_bytes(M), m.device)
+    _hip.check(L.iseg_lm_head_ce_finalise(ptr(m), ptr(s), ptr(zt), ptr(arg), ptr(targets), ptr(weights), ptr(loss), ptr(lse), ptr(match), ptr(sums),
+                                          ptr(ws), nbytes, M, int(V), float(scale), stream()), "iseg_lm_head_ce_finalise")
+    return loss, lse, match, sums
+
+
+def lm_head_ce_chunk_bwd(z, m, s, targets, weights, upstream, scale, g, V, v0, w):
+    _hip.call("iseg_lm_head_ce_chunk_bwd", ptr(z), z.stride(0), ptr(m), ptr(s), ptr(targets), ptr(weights), ptr(upstream), float(scale), ptr(g), g.stride(0),
+              z.shape[0], int(V), int(v0), int(w), dt(g), stream())
+
+
+def lm_head_ce_fwd(x2, table, targets, weights, chunk, scale=1.0):
+    """x2 [M, d] and table [V, d] in the compute dtype, targets int32 [M], weights fp32 [M] or None -> (loss, lse, argmax, match, sums, m, s) of
+    include/iseg_hip.h (m, s: the final state, what the backward pass needs); the only [M, chunk] tensor is the fp32 Z_c, written and consumed
+    once per chunk"""
+    _require_cuda(x2, table, targets, weights)
+    M, V = x2.shape[0], table.shape[0]
+    z = torch.empty((M, lm_head_ce_pitch(min(chunk, V))), dtype=torch.float32, device=x2.device)
+    state = lm_head_ce_state(M, x2.device)
+    for v0, w in lm_head_ce_chunks(V, chunk):
+        lm_head_ce_logits(x2, table, z, v0, w)
+        lm_head_ce_chunk_fwd(z, targets, state, v0, w)
+    lm_head_ce_target_logit(x2, table, targets, state)
+    loss, lse, match, sums = lm_head_ce_finalise(state, targets, weights, V, scale)
+    return loss, lse, state[3], match, sums, state[0], state[1]
+
+
+def lm_head_ce_bwd(x2, table, targets, weights, m, s, upstream, scale, chunk, dtable=None, want_dx=True):
+    """the gradients of sum_r upstream[r] loss[r]: per chunk Z_c again, G_c (rounded once), dX += G_c E[c] in ONE fp32 [M, d] buffer that is cast
+    at the end, and rows [v0, v0 + w) of dtable (fp32 [V, d], None: not wanted) += G_c^T X -- every row of dtable is written by one chunk only.
+    -> dX in the compute dtype, or None"""
+    _require_cuda(x2, table, targets, weights, m, s, upstream, dtable)
+    M, d = x2.shape
+    V = table.shape[0]
+    if dtable is None and not want_dx:
+        return None
+    ld = lm_head_ce_pitch(min(chunk, V))
+    z = torch.empty((M, ld), dtype=torch.float32, device=x2.device)
+    g = torch.empty((M, ld), dtype=x2.dtype, device=x2.device)
+    dx32 = torch.empty((M, d), dtype=torch.float32, device=x2.device) if want_dx else None
+    for i, (v0, w) in enumerate(lm_head_ce_chunks(V, chunk)):
+        lm_head_ce_logits(x2, table, z, v0, w)
+        lm_head_ce_chunk_bwd(z, m, s, targets, weights, upstream, scale, g, V, v0, w)
+        if want_dx:
+            gemm(g, table[v0:v0 + w], dx32, M, d, w, lda=ld, ldb=table.stride(0), ldd=d, a_kcontig=1, b_kcontig=0, accumulate=i > 0)
+        if dtable is not None:
+            dense_wgrad(g[:, :w], x2, dtable[v0:v0 + w])
+    if not want_dx:
+        return None
+    return dx32 if x2.dtype == torch.float32 else cast(dx32, x2.dtype)

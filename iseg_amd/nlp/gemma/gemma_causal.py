@@ -5,6 +5,8 @@ and generation (greedy, or with a sampler of nlp/samplers.py).
     logits, hidden_states, cache = model.call_with_cache(token_ids, cache, index)     (:186-226)  inference only
     out = model.generate_step({"token_ids", "padding_mask"}, end_token_id=None)        (:241-314)
     scores = model.score(token_ids, ..., scoring_mode="logits" | "loss")               (:316-444)
+    loss = model.compute_loss(inputs, y, sample_weight)                                (:165-172, :103-118)  the compiled loss and metric of fit(x, y,
+                                                                                       sample_weight) on the chunked head of nlp/lm_loss.py
 
 The cache has the reference's shape [B, num_layers, 2, S, num_key_value_heads, head_dim] in the compute dtype.  call_with_cache hands each layer
 its [B, 2, S, nkv, h] view, which the layer updates IN PLACE (F.gemma_rope_cache), and returns the same tensor; the reference stacks per-layer
@@ -18,6 +20,7 @@ one uniform per row and step.  Every other string alias raises NotImplementedErr
 Out of scope: the tokenizer and preprocessors (strings need a `preprocessor`, and none is built), presets, beam and contrastive samplers, training
 through the cache, HIP-graph replay of the decode step (the cache index is a host argument), paged caches."""
 import math
+import os
 
 import torch
 
@@ -25,6 +28,11 @@ from ... import functional as F
 from ... import nn
 from ...nn import Layer
 from ..samplers import Sampler, sample_loop
+
+
+def lm_head_fused():
+    """True where compute_loss takes the chunked head of nlp/lm_loss.py: ISEG_LMHEAD_FUSED unset or not "0" """
+    return os.environ.get("ISEG_LMHEAD_FUSED", "1") != "0"
 
 
 def _argmax(logits):
@@ -86,6 +94,50 @@ class GemmaCausalLM(Layer):
     def call(self, inputs, training=None):
         hidden_states = self.backbone(inputs, training=training)
         return self.backbone.token_embedding.logits(hidden_states)
+
+    # ---- the training loss (:165-172 compile(), :103-118 fit(x, y, sample_weight)) ------------------------------------------------------------------
+    def compute_loss(self, inputs, y, sample_weight=None, reduction="sum_over_batch_size", with_metrics=False, training=None):
+        """SparseCategoricalCrossentropy(from_logits=True) of the model's logits against y [B, T] with sample_weight [B, T] (None: ones), as the
+        reference's fit(x, y, sample_weight) computes it, on the chunked head of nlp/lm_loss.py: no [B, T, vocab] tensor exists.
+        reduction: "sum_over_batch_size" (Keras: sum w l / (B T), divided by the element count, not by sum w), "sum", or "none" ([B, T] fp32).
+        with_metrics: -> (loss, {"sparse_categorical_accuracy": sum w match / sum w}), SparseCategoricalAccuracy with sample weights (the argmax is
+        the first maximal logit).  A target outside [0, vocab) counts as weight 0 in both.  ISEG_LMHEAD_FUSED=0 runs the composed route:
+        embedding_logits, softmax_ce_per_pixel and torch's argmax on the stored logits; its loss kernel takes up to 256 classes and raises beyond."""
+        if reduction not in ("sum_over_batch_size", "sum", "none"):
+            raise ValueError(f'GemmaCausalLM.compute_loss: reduction is "sum_over_batch_size", "sum" or "none", got {reduction!r}')
+        token_ids = inputs["token_ids"]
+        if tuple(y.shape) != tuple(token_ids.shape):
+            raise ValueError(f"GemmaCausalLM.compute_loss: y has the shape of token_ids {tuple(token_ids.shape)}, got {tuple(y.shape)}")
+        if sample_weight is not None and tuple(sample_weight.shape) != tuple(y.shape):
+            raise ValueError(f"GemmaCausalLM.compute_loss: sample_weight has the shape of y {tuple(y.shape)}, got {tuple(sample_weight.shape)}")
+        hidden_states = self.backbone(inputs, training=training)
+        table = self.backbone.token_embedding.embeddings
+        vocab = table.shape[0]
+        scale = 1.0 / max(y.numel(), 1) if reduction == "sum_over_batch_size" else 1.0
+        if lm_head_fused():
+            from .. import lm_loss
+
+            loss, _, sums = lm_loss.lm_head_cross_entropy(hidden_states, table, y, sample_weight, upstream_scale=scale)
+            accuracy = sums[1] / sums[2] if with_metrics and not nn.dry_run() else None
+        else:
+            logits = self.backbone.token_embedding.logits(hidden_states)
+            if nn.dry_run():
+                loss, accuracy = torch.empty(tuple(y.shape), dtype=torch.float32, device=logits.device), None
+            else:
+                valid = ((y >= 0) & (y < vocab)).to(torch.float32)
+                w = valid if sample_weight is None else valid * sample_weight.to(torch.float32)
+                labels = torch.where(valid.bool(), y, torch.full_like(y, -1))
+                loss = F.softmax_ce_per_pixel(logits, labels, vocab, -1).reshape(y.shape) * (w * scale)
+                accuracy = None
+                if with_metrics:
+                    accuracy = (w * (torch.argmax(logits.detach(), dim=-1) == y).to(torch.float32)).sum() / w.sum()
+        if reduction != "none":
+            loss = loss.sum()
+        if not with_metrics:
+            return loss
+        if accuracy is None:
+            accuracy = torch.empty((), dtype=torch.float32, device=loss.device)
+        return loss, {"sparse_categorical_accuracy": accuracy}
 
     # ---- the cached forward (:186-226) ---------------------------------------------------------------------------------------------------------
     def call_with_cache(self, token_ids, cache, cache_update_index):
