@@ -1255,6 +1255,45 @@ size_t iseg_gemma_decode_attention_scratch_bytes(int64_t batch, int pos0, int Tn
 int iseg_gemma_decode_attention(const void* q, int64_t ldq, const void* kcache, int64_t k_batch, int64_t ldk, const void* vcache, int64_t v_batch,
                                 int64_t ldv, void* out, int64_t ldo, void* ws, size_t ws_bytes, int64_t batch, int S, int pos0, int Tn, int nq,
                                 int nkv, int h, float scale, int splits, int dtype, iseg_stream_t stream);
+/* The same two launchers with the position in DEVICE memory: pos_d is one int32, shared by the batch, that the kernels read when they run, so a
+ * captured graph of a decoding step can be replayed at every position (GemmaCausalLM.compile(graph_decode=True)).  All other arguments are those
+ * of iseg_gemma_rope_cache / iseg_gemma_decode_attention.
+ * iseg_gemma_rope_cache_at: for 0 <= *pos_d <= S - Tn, q_out and the cache rows are bit for bit iseg_gemma_rope_cache's at pos0 = *pos_d.
+ * iseg_gemma_decode_attention_at: the same supported set.  The grid cannot depend on the position, so it is the plan of the cache's capacity,
+ *   pos0 = S - Tn, and the workspace holds iseg_gemma_decode_attention_scratch_bytes(batch, S - Tn, Tn, nq, nkv, h, splits) bytes: the chunk
+ *   count and the scratch size never decrease with pos0, so what suffices at the capacity suffices at every position.  Every workgroup derives
+ *   from *pos_d the tile count and the effective chunk count that iseg_gemma_decode_attention plans on the host for that position (the same
+ *   functions, compiled for both sides); pass-1 workgroups whose chunk index is at or past the effective count return at once and pass 2
+ *   merges the effective chunks alone, in chunk order.  For 0 <= *pos_d <= S - Tn the output is therefore bit for bit
+ *   iseg_gemma_decode_attention(pos0 = *pos_d, same `splits`), splits = 0 included.  Keys past *pos_d + Tn - 1 are never loaded.
+ * The host cannot check a device value: with *pos_d outside [0, S - Tn] every workgroup of both launchers returns without reading or writing any
+ * memory other than *pos_d.  Everything the host can check is refused before any memory is touched with the codes above: pitches, alignment,
+ * the supported set (ISEG_ERR_UNSUPPORTED), a null or misaligned pos_d and Tn > S (ISEG_ERR_ARG), a short workspace (ISEG_ERR_WORKSPACE). */
+int iseg_gemma_rope_cache_at(const void* qkv, int64_t ld_in, void* q_out, int64_t ldq, void* kcache, int64_t k_batch, int64_t ldk, void* vcache,
+                             int64_t v_batch, int64_t ldv, const float* table, int64_t batch, int S, const int32_t* pos_d, int Tn, int nq, int nkv,
+                             int h, int dtype, iseg_stream_t stream);
+int iseg_gemma_decode_attention_at(const void* q, int64_t ldq, const void* kcache, int64_t k_batch, int64_t ldk, const void* vcache, int64_t v_batch,
+                                   int64_t ldv, void* out, int64_t ldo, void* ws, size_t ws_bytes, int64_t batch, int S, const int32_t* pos_d, int Tn,
+                                   int nq, int nkv, int h, float scale, int splits, int dtype, iseg_stream_t stream);
+/* The commit of one decoding step: the tail of the body of sample_loop (iseg_amd/nlp/samplers.py:21-39, keras_nlp Sampler.__call__) and the head of
+ * its next iteration, on state in device memory; one launch of one workgroup that loops over the rows (any batch).
+ *   prompt [batch, S] ids and cur_ids [batch] of type ids_dtype, tokens [batch] (the sampler's choice) of type tokens_dtype: ISEG_IDS_I32 or
+ *   ISEG_IDS_I64;  mask [batch, S] one byte per entry, non-zero = user token;  done [batch] bytes;  row pitches in elements;
+ *   pos_d one int32: the index of the previous token (generate_step's cache_update_index = index - 1);  end_token_id < 0: none.
+ * With p = *pos_d, read by every thread before a barrier:
+ *   freeze   if p + 1 is outside [0, S), or end_token_id >= 0 and every done[b] is set, nothing is written: samplers.py:30 (`while index <
+ *            max_length`) and :31-34 (the break once every row is done).  A replay after the generation has ended changes nothing.
+ *   commit   otherwise, per row:  t = mask[b, p+1] ? prompt[b, p+1] : tokens[b] converted to ids_dtype (:36-37);  prompt[b, p+1] = t;
+ *            cur_ids[b] = t (the token the next step embeds, :35 through generate_step's `next`);
+ *            done[b] |= (t == end_token_id && !mask[b, p+1]);  then, after a barrier, one thread writes *pos_d = p + 1 (:38).
+ * With the initial done[b] = any_s(prompt[b, s] == end_token_id && !mask[b, s]) computed by the caller (:32) this is sample_loop, provided an end
+ * token that a not-yet-generated, non-user position holds at the start is not the row's only one to be overwritten before the loop ends: `done`
+ * here only ever turns on, :32 is recomputed from the prompt (GemmaCausalLM.generate_step checks this on the host and otherwise runs the loop).
+ * The all-done reduction goes through LDS; plain loads and stores, no atomics. */
+#define ISEG_IDS_I32 0
+#define ISEG_IDS_I64 1
+int iseg_decode_commit(void* prompt, int64_t ld_prompt, const uint8_t* mask, int64_t ld_mask, int32_t* pos_d, void* cur_ids, uint8_t* done,
+                       const void* tokens, int64_t batch, int S, int64_t end_token_id, int ids_dtype, int tokens_dtype, iseg_stream_t stream);
 /* The samplers behind GemmaCausalLM.compile(sampler=) (nlp/gemma/gemma_causal.py class docstring: keras_nlp.samplers Random / TopK / TopP): one
  * token id per row of logits [batch, V] (bf16 or fp32, row pitch ld >= V elements) from ONE uniform u[b] in [0, 1) per row that the caller
  * draws; no random numbers are made here.  tokens int32 [batch].  Per row x, in exact arithmetic (the kernels work in fp32):

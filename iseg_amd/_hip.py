@@ -13,6 +13,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libiseg_hip.so")
 F32, BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_GELU_GRAD, ACT_RELU_GRAD, ACT_MUL_AUX, ACT_SIGMOID, ACT_SWISH, ACT_GELU_TANH = 0, 1, 2, 3, 4, 5, 6, 7, 8
 SAMPLE_RANDOM, SAMPLE_TOP_K, SAMPLE_TOP_P = 0, 1, 2
+IDS_I32, IDS_I64 = 0, 1
 
 
 class HipLibraryMissing(RuntimeError):
@@ -304,6 +305,9 @@ SIGNATURES = {
     "iseg_gemma_decode_attention_splits": (_i, [_l, _i, _i, _i, _i, _i]),
     "iseg_gemma_decode_attention_scratch_bytes": (_z, [_l, _i, _i, _i, _i, _i, _i]),
     "iseg_gemma_decode_attention": (_i, [_p, _l, _p, _l, _l, _p, _l, _l, _p, _l, _p, _z, _l, _i, _i, _i, _i, _i, _i, _f, _i, _i, _p]),
+    "iseg_gemma_rope_cache_at": (_i, [_p, _l, _p, _l, _p, _l, _l, _p, _l, _l, _p, _l, _i, _p, _i, _i, _i, _i, _i, _p]),
+    "iseg_gemma_decode_attention_at": (_i, [_p, _l, _p, _l, _l, _p, _l, _l, _p, _l, _p, _z, _l, _i, _p, _i, _i, _i, _i, _f, _i, _i, _p]),
+    "iseg_decode_commit": (_i, [_p, _l, _p, _l, _p, _p, _p, _p, _l, _i, _l, _i, _i, _p]),
     "iseg_token_sample_supported": (_i, [_l, _i, _i, _i]),
     "iseg_token_sample_splits": (_i, [_l, _l]),
     "iseg_token_sample_scratch_bytes": (_z, [_l, _l, _i, _i, _i]),

@@ -18,6 +18,13 @@
 // keeps m = -FLT_MAX and l = 0, and the merge gives such a partial the factor 0 without forming an exp2 of a difference of sentinels.  Keys
 // past pos0 + Tn - 1 are never loaded (zero fragments): the cache behind the write position may hold anything.  No atomics, fixed order: a second
 // call is bit-identical.
+//
+// The _at entry points (iseg_gemma_rope_cache_at, iseg_gemma_decode_attention_at) read the position from ONE int32 in device memory when the
+// kernels run, so that a captured graph of a decoding step can be replayed at every position.  The grid and the workspace are those of the
+// cache's capacity (the plan at pos0 = S - Tn); every workgroup derives the tile count and the effective chunk count of *pos_d with the
+// functions the host launcher plans with (visible_tiles, resolve_splits), workgroups of pass 1 past the effective count return at once and
+// pass 2 merges the effective chunks alone, in chunk order: the arithmetic is the host-position launcher's at pos0 = *pos_d, bit for bit.
+// A position outside [0, S - Tn] makes every workgroup return before it reads or writes anything else.
 #include "attn_tile.h"
 #include "iseg_hip.h"
 
@@ -32,6 +39,21 @@ constexpr int DH_MAX = 256;
 constexpr int DPART_HEAD = 2 * DROWS;      // floats in front of a partial's accumulators: m[16] | l[16]
 constexpr int SSTRIDE = AK + 4;            // row stride (floats) of the LDS score image [query row][key]: 272-B rows
 
+// ---- the split plan, on both sides: the host launchers size grids and workspaces with it, the _at kernels derive it from *pos_d ------------
+__host__ __device__ inline int visible_tiles(int pos0, int Tn) { return (int)(((int64_t)pos0 + Tn + AK - 1) / AK); }
+
+// chunks of the launcher's own plan: enough workgroups for two per CU of a 256-CU chip, at least two key tiles per chunk
+__host__ __device__ inline int plan_splits(int64_t batch, int pos0, int Tn, int nkv) {
+    const int64_t groups = batch * nkv, div = groups < 1 ? 1 : groups, want = (512 + div - 1) / div, most = visible_tiles(pos0, Tn) / 2;
+    return (int)(want < most ? want : most < 1 ? 1 : most);
+}
+
+__host__ __device__ inline int resolve_splits(int64_t batch, int pos0, int Tn, int nkv, int splits) {
+    if (splits <= 0) return plan_splits(batch, pos0, Tn, nkv);
+    const int tiles = visible_tiles(pos0, Tn);
+    return splits < tiles ? splits : tiles;
+}
+
 __device__ __forceinline__ bf16x8 qfrag(const bf16_t* __restrict__ base, int64_t off, int col) {
     if (off < 0) return zero8();
     return *reinterpret_cast<const bf16x8*>(base + off + col);
@@ -41,12 +63,23 @@ __device__ __forceinline__ bf16x8 qfrag(const bf16_t* __restrict__ base, int64_t
 // scores of the 16-key groups w, w + SLABS, .. of a tile over the whole head width and leaves them in LDS; after one barrier every wavefront
 // reads all 64 keys' scores back in the accumulator layout, repeats the (cheap) softmax and multiplies into ITS 64 value columns.  The score
 // buffer is double: the barrier of tile k + 1 orders the reads of tile k before the writes of tile k + 2.
-template <int SLABS>
+// AT: pos0 is *pos_d (in [0, max_pos], or every thread returns), `splits` is the grid's chunk count (the capacity's plan, also the stride of a
+// group's partials) and `splits_arg` the caller's argument, from which the effective count `nsplit` of this position is resolved.
+template <int SLABS, bool AT>
 __global__ __launch_bounds__(64 * SLABS) void gemma_decode_partial_kernel(const bf16_t* __restrict__ q, int64_t ldq, const bf16_t* __restrict__ kc,
                                                                           int64_t kbs, int64_t ldk, const bf16_t* __restrict__ vc, int64_t vbs,
                                                                           int64_t ldv, float* __restrict__ part, int Tn, int pos0, int nkv, int g,
-                                                                          int splits, int tiles, float scale) {
+                                                                          int splits, int tiles, float scale, const int32_t* __restrict__ pos_d,
+                                                                          int max_pos, int64_t batch, int splits_arg) {
     constexpr int H = SLABS * AD;
+    int nsplit = splits;
+    if constexpr (AT) {
+        pos0 = *pos_d;
+        if (pos0 < 0 || pos0 > max_pos) return;
+        tiles = visible_tiles(pos0, Tn);
+        nsplit = resolve_splits(batch, pos0, Tn, nkv, splits_arg);
+        if ((int)(blockIdx.x % splits) >= nsplit) return;
+    }
     constexpr int TJ = (4 + SLABS - 1) / SLABS;      // 16-key groups of a tile per wavefront
     __shared__ __attribute__((aligned(16))) bf16_t Vimg[SLABS][AK * ASTRIDE];
     __shared__ __attribute__((aligned(16))) float Simg[2][DROWS * SSTRIDE];
@@ -91,7 +124,7 @@ __global__ __launch_bounds__(64 * SLABS) void gemma_decode_partial_kernel(const 
 #pragma unroll
         for (int cc = 0; cc < 8; ++cc) vr[cc] = grow8(vb, ldv, k0 + vrow + 8 * cc, nvis, vcol);
     };
-    const int t0 = (int)((int64_t)split * tiles / splits), t1 = (int)((int64_t)(split + 1) * tiles / splits);
+    const int t0 = (int)((int64_t)split * tiles / nsplit), t1 = (int)((int64_t)(split + 1) * tiles / nsplit);
     fetch(t0 * AK);
     for (int kt = t0; kt < t1; ++kt) {
         const int k0 = kt * AK;
@@ -162,9 +195,18 @@ __global__ __launch_bounds__(64 * SLABS) void gemma_decode_partial_kernel(const 
     }
 }
 
-// blockIdx.x = ((b * nkv) + kvh) * GT + R: one stacked row, a thread per column; the partials are merged in chunk order
+// blockIdx.x = ((b * nkv) + kvh) * GT + R: one stacked row, a thread per column; the partials are merged in chunk order.
+// AT: `splits` is the stride of a group's partials (the capacity's plan); the chunks merged are the `nsplit` of the position *pos_d
+template <bool AT>
 __global__ __launch_bounds__(256) void gemma_decode_merge_kernel(const float* __restrict__ part, bf16_t* __restrict__ out, int64_t ldo, int Tn, int nkv,
-                                                                 int g, int h, int splits, float scale) {
+                                                                 int g, int h, int splits, float scale, const int32_t* __restrict__ pos_d,
+                                                                 int max_pos, int64_t batch, int splits_arg) {
+    int nsplit = splits;
+    if constexpr (AT) {
+        const int pos0 = *pos_d;
+        if (pos0 < 0 || pos0 > max_pos) return;
+        nsplit = resolve_splits(batch, pos0, Tn, nkv, splits_arg);
+    }
     const int GT = g * Tn;
     const int R = (int)(blockIdx.x % GT);
     const int64_t grp = blockIdx.x / GT;
@@ -174,12 +216,12 @@ __global__ __launch_bounds__(256) void gemma_decode_merge_kernel(const float* __
     const float* base = part + grp * splits * stride;
     const float c = scale * LOG2E;
     float M = -FLT_MAX;
-    for (int s = 0; s < splits; ++s) M = fmaxf(M, base[s * stride + R]);
+    for (int s = 0; s < nsplit; ++s) M = fmaxf(M, base[s * stride + R]);
     const int t = R / g;
     bf16_t* orow = out + (b * Tn + t) * ldo + ((int64_t)kvh * g + (R - t * g)) * h;
     for (int col = threadIdx.x; col < h; col += 256) {
         float num = 0.f, den = 0.f;
-        for (int s = 0; s < splits; ++s) {
+        for (int s = 0; s < nsplit; ++s) {
             const float* p = base + s * stride;
             const float ms = p[R];
             // a chunk in which the row saw nothing: the factor is the constant 0, no exp2 of a difference of sentinels
@@ -191,12 +233,17 @@ __global__ __launch_bounds__(256) void gemma_decode_merge_kernel(const float* __
     }
 }
 
-// One workgroup per new row (b, t): the rotated q heads go to q_out, the rotated k heads and the v heads to row pos0 + t of the caches
-template <class T>
+// One workgroup per new row (b, t): the rotated q heads go to q_out, the rotated k heads and the v heads to row pos0 + t of the caches.
+// AT: pos0 is *pos_d, in [0, max_pos] or every thread returns
+template <class T, bool AT>
 __global__ __launch_bounds__(256) void gemma_rope_cache_kernel(const T* __restrict__ qkv, int64_t ld_in, T* __restrict__ q_out, int64_t ldq,
                                                                T* __restrict__ kc, int64_t kbs, int64_t ldk, T* __restrict__ vc, int64_t vbs,
                                                                int64_t ldv, const float* __restrict__ table, int64_t rows, int Tn, int pos0, int nq,
-                                                               int nkv, int h) {
+                                                               int nkv, int h, const int32_t* __restrict__ pos_d, int max_pos) {
+    if constexpr (AT) {
+        pos0 = *pos_d;
+        if (pos0 < 0 || pos0 > max_pos) return;
+    }
     const int half = h / 2, pairs = (nq + nkv) * half, v_cols = nkv * h;
     for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
         const int64_t b = row / Tn;
@@ -221,20 +268,6 @@ __global__ __launch_bounds__(256) void gemma_rope_cache_kernel(const T* __restri
 
 bool pitch_ok(int64_t ld, int64_t width) { return ld >= width && ld % 8 == 0; }
 
-int visible_tiles(int pos0, int Tn) { return (int)(((int64_t)pos0 + Tn + AK - 1) / AK); }
-
-// chunks of the launcher's own plan: enough workgroups for two per CU of a 256-CU chip, at least two key tiles per chunk
-int plan_splits(int64_t batch, int pos0, int Tn, int nkv) {
-    const int64_t groups = batch * nkv, want = ceil_div64(512, groups < 1 ? 1 : groups), most = visible_tiles(pos0, Tn) / 2;
-    return (int)(want < most ? want : most < 1 ? 1 : most);
-}
-
-int resolve_splits(int64_t batch, int pos0, int Tn, int nkv, int splits) {
-    if (splits <= 0) return plan_splits(batch, pos0, Tn, nkv);
-    const int tiles = visible_tiles(pos0, Tn);
-    return splits < tiles ? splits : tiles;
-}
-
 bool geometry_ok(int64_t batch, int pos0, int Tn, int nq, int nkv, int h) {
     return batch > 0 && pos0 >= 0 && Tn > 0 && (int64_t)pos0 + Tn <= INT_MAX - AK && nq > 0 && nkv > 0 && h > 0;
 }
@@ -249,14 +282,20 @@ bool geometry_ok(int64_t batch, int pos0, int Tn, int nq, int nkv, int h) {
         }                                     \
     } while (0)
 
-extern "C" int iseg_gemma_rope_cache(const void* qkv, int64_t ld_in, void* q_out, int64_t ldq, void* kcache, int64_t k_batch, int64_t ldk,
-                                     void* vcache, int64_t v_batch, int64_t ldv, const float* table, int64_t batch, int S, int pos0, int Tn, int nq,
-                                     int nkv, int h, int dtype, hipStream_t stream) {
-    const char* who = "iseg_gemma_rope_cache";
+// both rope launchers: AT reads the position from pos_d when the kernel runs, pos0 is then unused
+template <bool AT>
+static int rope_cache_launch(const char* who, const void* qkv, int64_t ld_in, void* q_out, int64_t ldq, void* kcache, int64_t k_batch, int64_t ldk,
+                             void* vcache, int64_t v_batch, int64_t ldv, const float* table, int64_t batch, int S, int pos0,
+                             const int32_t* pos_d, int Tn, int nq, int nkv, int h, int dtype, hipStream_t stream) {
     ISEG_REQUIRE(qkv && q_out && kcache && vcache && table && batch > 0 && S > 0 && Tn > 0 && nq > 0 && nkv > 0 && h > 0 && h % 2 == 0,
                  "%s: bad arguments", who);
-    ISEG_REQUIRE(pos0 >= 0 && (int64_t)pos0 + Tn <= S, "%s: rows %d .. %lld do not lie inside a cache of %d rows", who, pos0,
-                 (long long)pos0 + Tn - 1, S);
+    if constexpr (AT) {
+        ISEG_REQUIRE(pos_d && (uintptr_t)pos_d % 4 == 0, "%s: the position is one aligned int32 in device memory", who);
+        ISEG_REQUIRE(Tn <= S, "%s: %d new rows do not fit a cache of %d rows", who, Tn, S);
+    } else {
+        ISEG_REQUIRE(pos0 >= 0 && (int64_t)pos0 + Tn <= S, "%s: rows %d .. %lld do not lie inside a cache of %d rows", who, pos0,
+                     (long long)pos0 + Tn - 1, S);
+    }
     const int64_t width = (int64_t)(nq + 2 * nkv) * h;
     ISEG_REQUIRE(width <= INT_MAX && ld_in >= width && ldq >= (int64_t)nq * h && ldk >= (int64_t)nkv * h && ldv >= (int64_t)nkv * h &&
                      k_batch >= 0 && v_batch >= 0,
@@ -264,10 +303,24 @@ extern "C" int iseg_gemma_rope_cache(const void* qkv, int64_t ld_in, void* q_out
     const int64_t rows = batch * Tn;
     return by_dtype(dtype, who, [&](auto t) {
         using E = decltype(t);
-        hipLaunchKernelGGL((gemma_rope_cache_kernel<E>), dim3(grid_cap(rows, 1, 65536)), dim3(256), 0, stream, (const E*)qkv, ld_in, (E*)q_out, ldq,
-                           (E*)kcache, k_batch, ldk, (E*)vcache, v_batch, ldv, table, rows, Tn, pos0, nq, nkv, h);
+        hipLaunchKernelGGL((gemma_rope_cache_kernel<E, AT>), dim3(grid_cap(rows, 1, 65536)), dim3(256), 0, stream, (const E*)qkv, ld_in, (E*)q_out,
+                           ldq, (E*)kcache, k_batch, ldk, (E*)vcache, v_batch, ldv, table, rows, Tn, pos0, nq, nkv, h, pos_d, S - Tn);
         return iseg_check_launch(who);
     });
+}
+
+extern "C" int iseg_gemma_rope_cache(const void* qkv, int64_t ld_in, void* q_out, int64_t ldq, void* kcache, int64_t k_batch, int64_t ldk,
+                                     void* vcache, int64_t v_batch, int64_t ldv, const float* table, int64_t batch, int S, int pos0, int Tn, int nq,
+                                     int nkv, int h, int dtype, hipStream_t stream) {
+    return rope_cache_launch<false>("iseg_gemma_rope_cache", qkv, ld_in, q_out, ldq, kcache, k_batch, ldk, vcache, v_batch, ldv, table, batch, S, pos0,
+                                    nullptr, Tn, nq, nkv, h, dtype, stream);
+}
+
+extern "C" int iseg_gemma_rope_cache_at(const void* qkv, int64_t ld_in, void* q_out, int64_t ldq, void* kcache, int64_t k_batch, int64_t ldk,
+                                        void* vcache, int64_t v_batch, int64_t ldv, const float* table, int64_t batch, int S, const int32_t* pos_d,
+                                        int Tn, int nq, int nkv, int h, int dtype, hipStream_t stream) {
+    return rope_cache_launch<true>("iseg_gemma_rope_cache_at", qkv, ld_in, q_out, ldq, kcache, k_batch, ldk, vcache, v_batch, ldv, table, batch, S, 0,
+                                   pos_d, Tn, nq, nkv, h, dtype, stream);
 }
 
 extern "C" int iseg_gemma_decode_attention_supported(int Tn, int nq, int nkv, int h, int dtype) {
@@ -288,10 +341,12 @@ extern "C" size_t iseg_gemma_decode_attention_scratch_bytes(int64_t batch, int p
     return (size_t)batch * nkv * resolve_splits(batch, pos0, Tn, nkv, splits) * partial * sizeof(float);
 }
 
-extern "C" int iseg_gemma_decode_attention(const void* q, int64_t ldq, const void* kcache, int64_t k_batch, int64_t ldk, const void* vcache,
-                                           int64_t v_batch, int64_t ldv, void* out, int64_t ldo, void* ws, size_t ws_bytes, int64_t batch, int S,
-                                           int pos0, int Tn, int nq, int nkv, int h, float scale, int splits, int dtype, hipStream_t stream) {
-    const char* who = "iseg_gemma_decode_attention";
+// both attention launchers.  AT: the position is read from pos_d when the kernels run; the grid and the workspace are planned for the
+// capacity, pos0 = S - Tn, and `splits` travels to the kernels, which resolve it again for the position they find
+template <bool AT>
+static int decode_attention_launch(const char* who, const void* q, int64_t ldq, const void* kcache, int64_t k_batch, int64_t ldk, const void* vcache,
+                                   int64_t v_batch, int64_t ldv, void* out, int64_t ldo, void* ws, size_t ws_bytes, int64_t batch, int S, int pos0,
+                                   const int32_t* pos_d, int Tn, int nq, int nkv, int h, float scale, int splits, int dtype, hipStream_t stream) {
     ISEG_REQUIRE(q && kcache && vcache && out && batch > 0 && S > 0 && Tn > 0, "%s: bad arguments", who);
     GEMMA_UNSUPPORTED(iseg_gemma_decode_attention_supported(Tn, nq, nkv, h, dtype),
                       "%s: needs bf16, a head width of 64, 128, 192 or 256, nq a multiple of nkv and (nq / nkv) * Tn <= 16 (got Tn %d, nq %d, nkv %d, h %d)",
@@ -303,8 +358,14 @@ extern "C" int iseg_gemma_decode_attention(const void* q, int64_t ldq, const voi
                       "%s: row pitches and batch strides must be multiples of 8 elements and the pitches cover their rows", who);
     GEMMA_UNSUPPORTED(((uintptr_t)q | (uintptr_t)kcache | (uintptr_t)vcache | (uintptr_t)out | (uintptr_t)ws) % 16 == 0,
                       "%s: operands must be 16-byte aligned", who);
-    ISEG_REQUIRE(pos0 >= 0 && (int64_t)pos0 + Tn <= S && S <= INT_MAX - AK, "%s: rows %d .. %lld do not lie inside a cache of %d rows", who, pos0,
-                 (long long)pos0 + Tn - 1, S);
+    if constexpr (AT) {
+        ISEG_REQUIRE(pos_d && (uintptr_t)pos_d % 4 == 0, "%s: the position is one aligned int32 in device memory", who);
+        ISEG_REQUIRE(Tn <= S && S <= INT_MAX - AK, "%s: %d new rows do not fit a cache of %d rows", who, Tn, S);
+        pos0 = S - Tn;
+    } else {
+        ISEG_REQUIRE(pos0 >= 0 && (int64_t)pos0 + Tn <= S && S <= INT_MAX - AK, "%s: rows %d .. %lld do not lie inside a cache of %d rows", who, pos0,
+                     (long long)pos0 + Tn - 1, S);
+    }
     const int g = nq / nkv, tiles = visible_tiles(pos0, Tn), nsplit = resolve_splits(batch, pos0, Tn, nkv, splits);
     const int64_t items = batch * nkv * nsplit, rows = batch * nkv * g * Tn;
     ISEG_REQUIRE(items <= INT_MAX && rows <= INT_MAX, "%s: too many work items", who);
@@ -312,8 +373,8 @@ extern "C" int iseg_gemma_decode_attention(const void* q, int64_t ldq, const voi
     const bf16_t *qp = (const bf16_t*)q, *kp = (const bf16_t*)kcache, *vp = (const bf16_t*)vcache;
     float* part = (float*)ws;
 #define DECODE_PASS1(SLABS)                                                                                                                         \
-    hipLaunchKernelGGL((gemma_decode_partial_kernel<SLABS>), dim3((unsigned)items), dim3(64 * SLABS), 0, stream, qp, ldq, kp, k_batch, ldk, vp, v_batch, \
-                       ldv, part, Tn, pos0, nkv, g, nsplit, tiles, scale)
+    hipLaunchKernelGGL((gemma_decode_partial_kernel<SLABS, AT>), dim3((unsigned)items), dim3(64 * SLABS), 0, stream, qp, ldq, kp, k_batch, ldk, vp,   \
+                       v_batch, ldv, part, Tn, pos0, nkv, g, nsplit, tiles, scale, pos_d, S - Tn, batch, splits)
     switch (h / AD) {
         case 1: DECODE_PASS1(1); break;
         case 2: DECODE_PASS1(2); break;
@@ -321,6 +382,22 @@ extern "C" int iseg_gemma_decode_attention(const void* q, int64_t ldq, const voi
         default: DECODE_PASS1(4); break;
     }
 #undef DECODE_PASS1
-    hipLaunchKernelGGL(gemma_decode_merge_kernel, dim3((unsigned)rows), dim3(256), 0, stream, part, (bf16_t*)out, ldo, Tn, nkv, g, h, nsplit, scale);
+    hipLaunchKernelGGL((gemma_decode_merge_kernel<AT>), dim3((unsigned)rows), dim3(256), 0, stream, part, (bf16_t*)out, ldo, Tn, nkv, g, h, nsplit, scale,
+                       pos_d, S - Tn, batch, splits);
     return iseg_check_launch(who);
+}
+
+extern "C" int iseg_gemma_decode_attention(const void* q, int64_t ldq, const void* kcache, int64_t k_batch, int64_t ldk, const void* vcache,
+                                           int64_t v_batch, int64_t ldv, void* out, int64_t ldo, void* ws, size_t ws_bytes, int64_t batch, int S,
+                                           int pos0, int Tn, int nq, int nkv, int h, float scale, int splits, int dtype, hipStream_t stream) {
+    return decode_attention_launch<false>("iseg_gemma_decode_attention", q, ldq, kcache, k_batch, ldk, vcache, v_batch, ldv, out, ldo, ws, ws_bytes,
+                                          batch, S, pos0, nullptr, Tn, nq, nkv, h, scale, splits, dtype, stream);
+}
+
+extern "C" int iseg_gemma_decode_attention_at(const void* q, int64_t ldq, const void* kcache, int64_t k_batch, int64_t ldk, const void* vcache,
+                                              int64_t v_batch, int64_t ldv, void* out, int64_t ldo, void* ws, size_t ws_bytes, int64_t batch, int S,
+                                              const int32_t* pos_d, int Tn, int nq, int nkv, int h, float scale, int splits, int dtype,
+                                              hipStream_t stream) {
+    return decode_attention_launch<true>("iseg_gemma_decode_attention_at", q, ldq, kcache, k_batch, ldk, vcache, v_batch, ldv, out, ldo, ws, ws_bytes,
+                                         batch, S, 0, pos_d, Tn, nq, nkv, h, scale, splits, dtype, stream);
 }

@@ -3572,6 +3572,13 @@ def _no_grad_inputs(who, *ts):
             raise RuntimeError(f"{who}: the cached path is inference only (an input requires grad); train through the uncached call")
 
 
+def _check_device_position(who, pos0, Tn, S):
+    if pos0.dtype != torch.int32 or pos0.numel() != 1:
+        raise ValueError(f"{who}: a tensor position is ONE int32 element in device memory, got {tuple(pos0.shape)} {pos0.dtype}")
+    if Tn > S:
+        raise ValueError(f"{who}: {Tn} new rows do not fit a cache of {S} rows")
+
+
 def _check_layer_cache(who, cache, B, nkv, h, dtype):
     if cache.dim() != 5 or cache.shape[0] != B or cache.shape[1] != 2 or cache.shape[3] != nkv or cache.shape[4] != h or cache.dtype != dtype:
         raise ValueError(f"{who}: a layer's cache is [{B}, 2, S, {nkv}, {h}] {dtype}, got {tuple(cache.shape)} {cache.dtype}")
@@ -3581,7 +3588,10 @@ def gemma_rope_cache(qkv, cache, pos0, nq, nkv, h):
     """qkv [B, Tn, (nq + 2 nkv) h]: packed projections of the tokens at positions pos0 .. pos0 + Tn - 1; cache: ONE layer's [B, 2, S, nkv, h] view of
     the [B, num_layers, 2, S, nkv, h] cache.  The rotary embedding at those positions (fp32 angles from gemma_rope_table(S, h)) and the
     dynamic_update_slice of nlp/gemma/gemma_attention.py:161-179 in one pass (csrc/gemma_decode.hip): rows pos0 .. of the cache receive the rotated
-    keys and the values IN PLACE, the rotated queries are returned [B, Tn, nq h]."""
+    keys and the values IN PLACE, the rotated queries are returned [B, Tn, nq h].
+    pos0 is an int, or a one-element int32 DEVICE tensor that the kernel reads when it runs (iseg_gemma_rope_cache_at: the same bits, and a
+    captured graph follows the tensor).  The host cannot range-check a device value and does not pretend to: outside [0, S - Tn] the kernel
+    touches nothing."""
     _check_act_dtype(qkv)
     _no_grad_inputs("gemma_rope_cache", qkv, cache)
     if qkv.dim() != 3 or qkv.shape[2] != (nq + 2 * nkv) * h or h % 2:
@@ -3591,6 +3601,10 @@ def gemma_rope_cache(qkv, cache, pos0, nq, nkv, h):
         return _dry((B, Tn, nq * h), qkv)
     _check_layer_cache("gemma_rope_cache", cache, B, nkv, h, qkv.dtype)
     S = cache.shape[2]
+    if torch.is_tensor(pos0):
+        _check_device_position("gemma_rope_cache", pos0, Tn, S)
+        with torch.no_grad():
+            return K.gemma_rope_cache_at(_c(qkv), cache, gemma_rope_table(S, h, qkv.device), pos0, int(nq), int(nkv), int(h))
     if pos0 < 0 or pos0 + Tn > S:
         raise ValueError(f"gemma_rope_cache: positions {pos0} .. {pos0 + Tn - 1} do not lie inside a cache of {S} rows")
     with torch.no_grad():
@@ -3612,16 +3626,27 @@ def gemma_cached_attention_core(q, cache, pos0, nq, nkv, h, *, splits=0):
     padding mask -- at index 0 with the whole cache the cached mask is the plain causal mask.
     Composed route (everything else, and the yardstick of the fused one): the new q rows at rows pos0 .. of a zeroed packed [B, S, .] buffer
     beside the cache's visible K and V rows, the composed route of gemma_attention_core, and the rows sliced out: the causal mask of row
-    pos0 + t is exactly the cached mask."""
+    pos0 + t is exactly the cached mask.
+    pos0 is an int, or a one-element int32 DEVICE tensor that the kernels read when they run (iseg_gemma_decode_attention_at: bit for bit the
+    int call at that position, from a grid and a workspace sized for the cache's capacity).  A tensor position takes the fused route alone: the
+    seeding and composed routes slice on the host and raise ValueError, and no host-side range check is made."""
     _check_act_dtype(q)
     _no_grad_inputs("gemma_cached_attention_core", q, cache)
     if q.dim() != 3 or q.shape[2] != nq * h or nq % nkv:
         raise ValueError(f"gemma_cached_attention_core: {tuple(q.shape)} is not [B, Tn, {nq} * {h}] with nq a multiple of nkv")
     B, Tn, _ = q.shape
+    if torch.is_tensor(pos0) and not gemma_cached_attention_fused(Tn, nq, nkv, h, q.dtype):
+        raise ValueError(f"gemma_cached_attention_core: a tensor position needs the fused decode kernels (bf16, head width 64 .. 256 in steps of "
+                         f'64, (nq / nkv) * Tn <= 16, ISEG_GEMMA_FUSED unset or not "0"), got Tn {Tn}, nq {nq}, nkv {nkv}, h {h}, {q.dtype}; the '
+                         "composed and seeding routes need the position on the host")
     if nn.dry_run():
         return _dry(q.shape, q)
     _check_layer_cache("gemma_cached_attention_core", cache, B, nkv, h, q.dtype)
     S = cache.shape[2]
+    if torch.is_tensor(pos0):
+        _check_device_position("gemma_cached_attention_core", pos0, Tn, S)
+        with torch.no_grad():
+            return K.gemma_decode_attention_at(_c(q), cache, pos0, int(nq), int(nkv), int(h), float(h) ** -0.5, splits)
     if pos0 < 0 or pos0 + Tn > S:
         raise ValueError(f"gemma_cached_attention_core: positions {pos0} .. {pos0 + Tn - 1} do not lie inside a cache of {S} rows")
     scale = float(h) ** -0.5
@@ -3679,6 +3704,20 @@ def sample_tokens(logits, u, *, mode, k=0, p=1.0, temperature=1.0, splits=0):
         logits = logits.contiguous()
     with torch.no_grad():
         return K.token_sample(logits, _c(u), _SAMPLE_MODES[mode], k, p, temperature, splits)
+
+
+def decode_commit(prompt, mask, pos_d, cur_ids, done, tokens, end_token_id=None):
+    """One step of nlp/samplers.py's sample_loop on state in device memory, IN PLACE (csrc/decode_commit.hip, one launch, no host read), with
+    p = pos_d[0], the index of the previous token:
+      frozen   p + 1 outside [0, S), or an end_token_id is given and every done[b] is set: nothing changes;
+      else     t = mask[b, p+1] ? prompt[b, p+1] : tokens[b];  prompt[b, p+1] = cur_ids[b] = t;  done[b] |= (t == end_token_id and not
+               mask[b, p+1]);  pos_d[0] = p + 1.
+    prompt [B, S] and cur_ids [B] int32 or int64, mask [B, S] and done [B] bool or uint8, pos_d int32 [1], tokens [B] int32 or int64 (the
+    sampler's choice).  The caller sets done = ((prompt == end_token_id) & ~mask).any(-1) before the first step.  Returns None."""
+    if end_token_id is not None and int(end_token_id) < 0:
+        raise ValueError(f"decode_commit: end_token_id is None or a token id >= 0, got {end_token_id}")
+    with torch.no_grad():
+        K.decode_commit(prompt, mask, pos_d, cur_ids, done, tokens, end_token_id)
 
 
 def embedding_logits(x, table):

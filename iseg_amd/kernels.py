@@ -2316,6 +2316,68 @@ def gemma_decode_attention(q, cache, pos0, nq, nkv, h, scale, splits=0):
     return out
 
 
+def _check_pos_d(pos_d):
+    if not (torch.is_tensor(pos_d) and pos_d.dtype == torch.int32 and pos_d.numel() == 1):
+        raise ValueError("a device position is ONE int32 element in device memory")
+    _require_cuda(pos_d)
+
+
+def gemma_rope_cache_at(qkv, cache, table, pos_d, nq, nkv, h):
+    """gemma_rope_cache at the position the int32 device tensor pos_d [1] holds when the kernel runs (outside [0, S - Tn]: nothing is touched)"""
+    _require_cuda(qkv, cache, table)
+    _check_pos_d(pos_d)
+    B, Tn, W = qkv.shape
+    kc, vc, bs, ld = _gemma_cache_views(cache, nkv, h)
+    q = torch.empty((B, Tn, nq * h), dtype=qkv.dtype, device=qkv.device)
+    _hip.call("iseg_gemma_rope_cache_at", ptr(qkv), W, ptr(q), nq * h, ptr(kc), bs, ld, ptr(vc), bs, ld, ptr(table), B, cache.shape[2], ptr(pos_d), Tn,
+              nq, nkv, h, dt(qkv), stream())
+    return q
+
+
+def gemma_decode_attention_at(q, cache, pos_d, nq, nkv, h, scale, splits=0):
+    """gemma_decode_attention at the position the int32 device tensor pos_d [1] holds when the kernels run: bit for bit the host-position call
+    there; the grid and the workspace are those of the cache's capacity (pos0 = S - Tn).  Outside [0, S - Tn] nothing is touched."""
+    _require_cuda(q, cache)
+    _check_pos_d(pos_d)
+    B, Tn, _ = q.shape
+    kc, vc, bs, ld = _gemma_cache_views(cache, nkv, h)
+    S = cache.shape[2]
+    L = _hip.lib()
+    out = torch.empty((B, Tn, nq * h), dtype=q.dtype, device=q.device)
+    ws, nbytes = workspace(L.iseg_gemma_decode_attention_scratch_bytes(B, S - Tn, Tn, nq, nkv, h, int(splits)), q.device)
+    _hip.check(L.iseg_gemma_decode_attention_at(ptr(q), q.stride(1), ptr(kc), bs, ld, ptr(vc), bs, ld, ptr(out), nq * h, ptr(ws), nbytes, B, S,
+                                                ptr(pos_d), Tn, nq, nkv, h, float(scale), int(splits), dt(q), stream()),
+               "iseg_gemma_decode_attention_at")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------
+# the commit of a decoding step (csrc/decode_commit.hip)
+# ---------------------------------------------------------------------------------------------------------
+_IDS = {torch.int32: _hip.IDS_I32, torch.int64: _hip.IDS_I64}
+
+
+def decode_commit(prompt, mask, pos_d, cur_ids, done, tokens, end_token_id):
+    """one step of nlp/samplers.py's sample_loop on device state, IN PLACE (include/iseg_hip.h has the statement): prompt [B, S] and cur_ids [B]
+    int32 or int64, mask [B, S] and done [B] bool or uint8, pos_d int32 [1], tokens [B] int32 or int64; end_token_id None or negative: none"""
+    _require_cuda(prompt, mask, pos_d, cur_ids, done, tokens)
+    _check_pos_d(pos_d)
+    if prompt.dim() != 2 or prompt.dtype not in _IDS or cur_ids.dtype != prompt.dtype or tokens.dtype not in _IDS:
+        raise ValueError(f"decode_commit: prompt [B, S] and cur_ids [B] share int32 or int64, tokens are int32 or int64, got {prompt.dtype}, "
+                         f"{cur_ids.dtype}, {tokens.dtype}")
+    B, S = prompt.shape
+    if tuple(mask.shape) != (B, S) or mask.element_size() != 1 or done.element_size() != 1:
+        raise ValueError(f"decode_commit: mask [{B}, {S}] and done [{B}] hold one byte per entry, got {tuple(mask.shape)} {mask.dtype}, {done.dtype}")
+    for name, t in (("cur_ids", cur_ids), ("done", done), ("tokens", tokens)):
+        if tuple(t.shape) != (B,) or not t.is_contiguous():
+            raise ValueError(f"decode_commit: {name} is a contiguous [{B}], got {tuple(t.shape)}")
+    if prompt.stride(1) != 1 or mask.stride(1) != 1:
+        raise ValueError("decode_commit: the rows of prompt and mask are contiguous")
+    end = -1 if end_token_id is None else int(end_token_id)
+    _hip.call("iseg_decode_commit", ptr(prompt), prompt.stride(0) if B > 1 else S, ptr(mask), mask.stride(0) if B > 1 else S, ptr(pos_d), ptr(cur_ids),
+              ptr(done), ptr(tokens), B, S, end if end >= 0 else -1, _IDS[prompt.dtype], _IDS[tokens.dtype], stream())
+
+
 # ---------------------------------------------------------------------------------------------------------
 # token sampling (csrc/token_sample.hip)
 # ---------------------------------------------------------------------------------------------------------

@@ -57,6 +57,9 @@ class CachedGemmaAttention(Layer):
         nq, nkv, h = self.num_query_heads, self.num_key_value_heads, self.head_dim
         with torch.no_grad():
             qkv = F.gemma_qkv(x, self.query_kernel, self.key_kernel, self.value_kernel)
-            q = F.gemma_rope_cache(qkv, cache, int(cache_update_index), nq, nkv, h)
-            y = F.gemma_cached_attention_core(q, cache, int(cache_update_index), nq, nkv, h)
+            # a one-element int32 device tensor (the replayed decode step) is passed through unchanged; anything else is a host integer, as ever
+            on_device = torch.is_tensor(cache_update_index) and cache_update_index.is_cuda and cache_update_index.dtype == torch.int32
+            index = cache_update_index if on_device else int(cache_update_index)
+            q = F.gemma_rope_cache(qkv, cache, index, nq, nkv, h)
+            y = F.gemma_cached_attention_core(q, cache, index, nq, nkv, h)
             return F.dense(y, self.attention_output_kernel, kshape=(nq * h, self.hidden_dim)), cache

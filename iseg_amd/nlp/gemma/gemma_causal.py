@@ -17,8 +17,22 @@ compile(sampler=) takes "greedy" (the default: keras_nlp's greedy Sampler.__call
 GreedySampler, RandomSampler, TopKSampler, TopPSampler.  The random ones choose each token with the fused kernels of csrc/token_sample.hip from
 one uniform per row and step.  Every other string alias raises NotImplementedError naming the classes.
 
+compile(graph_decode=True) (off by default; no counterpart in the reference, whose tf.function plays this role) makes one generated token one
+graph.replay().  The eager loop issues every launch of a step from Python and reads the stop condition on the host before each; here the loop's
+state lives in device memory: the prompt, the mask, the position (one int32 that the _at launchers of csrc/gemma_decode.hip read when they run),
+the token to embed and the per-row done flags, advanced by one launch of csrc/decode_commit.hip (F.decode_commit).  generate_step seeds the
+cache eagerly into a buffer the graph owns, captures on first use of a signature (B, S, compute dtype, sampler type and kernel arguments,
+prompt dtype; the end token is a frozen argument of the commit kernel, so each value has its graph) and replays S - index times.  The captured
+kernels compute bit for bit what the eager ones do, so the tokens are the eager loop's.  The seeded samplers' uniforms are drawn outside the
+graph, one launch in front of each replay, from the sampler's own generator: the eager loop's random stream for the same seed.  Without an end
+token the loop reads nothing back.  With one it reads `done` every `check_every` replays (generate_step's keyword, default 16); the commit
+kernel freezes once every row is done, so the result does not depend on check_every, but up to check_every - 1 frozen replays each draw
+uniforms that the eager loop would not have drawn: the generator of a sampler that is reused afterwards is that far ahead.  A Sampler subclass
+of the caller's keeps the eager loop (its get_next_token may read on the host); the fp32 compute dtype, ISEG_GEMMA_FUSED=0 and an unsupported
+head width raise ValueError (a captured step cannot take the composed route).  release_decode_graphs() drops graphs, caches and buffers.
+
 Out of scope: the tokenizer and preprocessors (strings need a `preprocessor`, and none is built), presets, beam and contrastive samplers, training
-through the cache, HIP-graph replay of the decode step (the cache index is a host argument), paged caches."""
+through the cache, paged caches."""
 import math
 import os
 
@@ -62,6 +76,8 @@ class GemmaCausalLM(Layer):
         self.backbone = backbone
         self.preprocessor = preprocessor
         self.sampler = "greedy"
+        self.graph_decode = False
+        self._decode_graphs = {}      # signature -> the captured step and the buffers it points into (_capture_decode_step)
 
     # ---- variables: the backbone's, the embedding is tied ---------------------------------------------------------------------------------
     @staticmethod
@@ -79,9 +95,12 @@ class GemmaCausalLM(Layer):
             self.backbone.build()
         self.built = True
 
-    def compile(self, sampler="greedy", **unused):
+    def compile(self, sampler="greedy", graph_decode=False, **unused):
         """sampler: "greedy", or an instance of iseg_amd.nlp.samplers (GreedySampler, RandomSampler, TopKSampler, TopPSampler or a Sampler subclass
-        of the caller's).  The other string aliases of keras_nlp.samplers.get are not built."""
+        of the caller's).  The other string aliases of keras_nlp.samplers.get are not built.
+        graph_decode=True: generate_step replays every decoding step from one captured HIP graph (the module docstring); off by default."""
+        if not isinstance(graph_decode, bool):
+            raise ValueError(f"GemmaCausalLM.compile: graph_decode is True or False, got {graph_decode!r}")
         if isinstance(sampler, str):
             if sampler != "greedy":
                 raise NotImplementedError(f'GemmaCausalLM.compile: the only string alias is "greedy", got {sampler!r}; pass an instance of '
@@ -89,6 +108,7 @@ class GemmaCausalLM(Layer):
         elif not isinstance(sampler, Sampler):
             raise ValueError(f'GemmaCausalLM.compile: sampler is "greedy" or an iseg_amd.nlp.samplers.Sampler instance, got {sampler!r}')
         self.sampler = sampler
+        self.graph_decode = graph_decode
 
     # ---- the trainable forward (:156-158) ------------------------------------------------------------------------------------------------------
     def call(self, inputs, training=None):
@@ -155,18 +175,166 @@ class GemmaCausalLM(Layer):
             hidden_states = bb.layer_norm(x)
             return bb.token_embedding.logits(hidden_states), hidden_states, cache
 
-    def _build_cache(self, token_ids):
-        """an empty cache for `token_ids` [B, S], seeded with one forward pass over the whole of it (:228-239) -> (hidden states, cache)"""
+    def _build_cache(self, token_ids, cache=None):
+        """an empty cache for `token_ids` [B, S], seeded with one forward pass over the whole of it (:228-239) -> (hidden states, cache).
+        cache: a buffer of the right shape to seed instead of a new one (every row of it is rewritten)"""
         bb = self.backbone
         B, S = token_ids.shape
-        cache = torch.zeros((B, bb.num_layers, 2, S, bb.num_key_value_heads, bb.head_dim), dtype=nn.compute_dtype(), device=token_ids.device)
+        if cache is None:
+            cache = torch.zeros((B, bb.num_layers, 2, S, bb.num_key_value_heads, bb.head_dim), dtype=nn.compute_dtype(), device=token_ids.device)
         _, hidden_states, cache = self.call_with_cache(token_ids, cache, 0)
         return hidden_states, cache
 
-    def generate_step(self, inputs, end_token_id=None):
+    # ---- the decode step as one replayed HIP graph (compile(graph_decode=True)) ---------------------------------------------------------------
+    def _graph_decode_sampler(self):
+        """the compiled sampler if a captured step may hold its token rule: "greedy" and the EXACT library classes.  A caller's subclass may read
+        on the host in get_next_token, so it keeps the eager loop -> (eligible, sampler object or None for the string)"""
+        from ..samplers import GreedySampler, RandomSampler, TopKSampler, TopPSampler
+
+        if isinstance(self.sampler, str):
+            return True, None
+        return type(self.sampler) in (GreedySampler, RandomSampler, TopKSampler, TopPSampler), self.sampler
+
+    def _require_fused_decode(self):
+        """a captured step has no host position, so it runs on the fused decode kernels or not at all"""
+        bb = self.backbone
+        nq, nkv, h, dtype = bb.num_query_heads, bb.num_key_value_heads, bb.head_dim, nn.compute_dtype()
+        if F.gemma_cached_attention_fused(1, nq, nkv, h, dtype):
+            return
+        if dtype != torch.bfloat16:
+            why = f"the compute dtype is {dtype}, the decode kernels are bfloat16"
+        elif os.environ.get("ISEG_GEMMA_FUSED", "1") == "0":
+            why = "ISEG_GEMMA_FUSED=0 selects the composed route"
+        else:
+            why = f"head width {h} with {nq} query heads on {nkv} key/value heads is outside the decode kernels' supported set"
+        raise ValueError(f"GemmaCausalLM.generate_step: graph_decode=True needs the fused decode kernels, but {why}; compile(graph_decode=False) "
+                         "runs the eager loop")
+
+    def _decode_entry(self, B, S, ids_dtype, sampler, device):
+        """the device state of one signature, which the captured step points into: the cache, the loop's state (prompt, mask, pos, cur_ids, done),
+        the uniform buffer of a seeded sampler and the sampler's token rule on it; `graphs` fills as end tokens are met (_decode_graph)"""
+        bb = self.backbone
+        e = dict(cache=torch.zeros((B, bb.num_layers, 2, S, bb.num_key_value_heads, bb.head_dim), dtype=nn.compute_dtype(), device=device),
+                 prompt=torch.zeros((B, S), dtype=ids_dtype, device=device), mask=torch.zeros((B, S), dtype=torch.bool, device=device),
+                 pos=torch.zeros(1, dtype=torch.int32, device=device), cur_ids=torch.zeros(B, dtype=ids_dtype, device=device),
+                 done=torch.zeros(B, dtype=torch.bool, device=device),
+                 uniforms=None if sampler is None or not hasattr(sampler, "uniforms_into") else torch.zeros(B, dtype=torch.float32, device=device),
+                 graphs={})
+        e["rule"] = _argmax if sampler is None else sampler.token_rule(e["uniforms"])
+        return e
+
+    def _decode_step(self, e, end_token_id):
+        """one step on the entry's state: embed cur_ids, all blocks at pos, the final norm, the logits, the token rule, F.decode_commit"""
+        logits, _, _ = self.call_with_cache(e["cur_ids"].view(-1, 1), e["cache"], e["pos"])
+        F.decode_commit(e["prompt"], e["mask"], e["pos"], e["cur_ids"], e["done"], e["rule"](logits[:, 0]), end_token_id)
+
+    def _decode_graph(self, e, end_token_id):
+        """the graph of entry e for this end token (a host argument of the commit kernel, frozen at capture: one graph per value), captured on
+        first use by GraphedCall's rules: a warm-up run on the capture stream (workspaces, keyed by stream, and lazy tables reach their final
+        size; the decode workspace is the capacity's at every position) and a single stream, so the graph has no parallel branches.  Captured
+        at position 0 on an all-zero state; generate_step overwrites the state before the first replay."""
+        from ...graphs import GraphedCall
+
+        key = -1 if end_token_id is None else int(end_token_id)
+        generation = GraphedCall._refresh_derived_weights()
+        if e["graphs"] and e["generation"] != generation:
+            e["graphs"].clear()      # the buffers the captured launches point into were re-allocated: capture again
+        graph = e["graphs"].get(key)
+        if graph is None:
+            for name in ("prompt", "mask", "pos", "cur_ids", "done"):
+                e[name].zero_()
+            side = torch.cuda.Stream(device=e["pos"].device)
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side), torch.no_grad():
+                self._decode_step(e, end_token_id)
+            side.synchronize()
+            e["pos"].zero_()
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.no_grad(), torch.cuda.graph(graph, stream=side):
+                self._decode_step(e, end_token_id)
+            torch.cuda.current_stream().wait_stream(side)
+            e["graphs"][key] = graph
+            e["generation"] = GraphedCall._refresh_derived_weights()
+        return graph
+
+    def release_decode_graphs(self):
+        """drop the captured decode graphs with their caches and state buffers; the next generate_step with graph_decode captures again"""
+        self._decode_graphs.clear()
+
+    @staticmethod
+    def _graph_decode_start(token_ids, padding_mask, end_token_id):
+        """(index, sticky) in ONE host read.  index: the first position to fill.  sticky: the commit kernel's `done`, which only ever turns on,
+        follows sample_loop's, which is recomputed from the prompt at every step.  They part only where a row's end token at a non-user position
+        is overwritten while the loop still runs; that cannot happen to a row that holds one in front of `index` (never rewritten) or at the
+        last position (rewritten by the last step).  Zero padding that equals the end token is such a row.  Other prompts keep the eager loop."""
+        S = token_ids.shape[1]
+        index = padding_mask.to(torch.int32).sum(dim=-1).min()
+        if end_token_id is None:
+            return int(index.item()), True
+        ends = (token_ids == end_token_id) & ~padding_mask
+        cols = torch.arange(S, device=token_ids.device)
+        ahead, behind = (ends & (cols >= index)).any(dim=-1), (ends & (cols < index)).any(dim=-1)
+        sticky = (~ahead | ends[:, -1] | behind).all()
+        index, sticky = torch.stack([index.to(torch.int64), sticky.to(torch.int64)]).tolist()
+        return int(index), bool(sticky)
+
+    def _generate_graphed(self, token_ids, padding_mask, index, end_token_id, sampler, check_every):
+        """sample_loop with one graph.replay() per token: the state of the loop lives in the entry's device buffers"""
+        B, S = token_ids.shape
+        sig = (B, S, nn.compute_dtype(), ("greedy",) if sampler is None else sampler.graph_signature(), token_ids.dtype)
+        e = self._decode_graphs.get(sig)
+        if e is None:
+            e = self._decode_graphs[sig] = self._decode_entry(B, S, token_ids.dtype, sampler, token_ids.device)
+        graph = self._decode_graph(e, end_token_id)
+        self._build_cache(token_ids, e["cache"])      # seeded eagerly, straight into the graph's own cache: no whole-cache copy
+        e["prompt"].copy_(token_ids)
+        e["mask"].copy_(padding_mask)
+        e["pos"].fill_(index - 1)
+        e["cur_ids"].copy_(token_ids[:, index - 1])
+        if end_token_id is None:
+            e["done"].zero_()
+        else:
+            e["done"].copy_(((token_ids == end_token_id) & ~padding_mask).any(dim=-1))
+        draw = None if e["uniforms"] is None else sampler.uniforms_into
+        self._replay_decode(graph, e, S - index, end_token_id is not None, draw, check_every)
+        return e["prompt"].clone()
+
+    @staticmethod
+    def _replay_decode(graph, e, steps, with_end, draw, check_every):
+        """`steps` replays, the step's uniforms drawn in front of each (one launch, outside the graph: the random stream is the eager loop's for
+        the same seed).  Without an end token nothing is read back.  With one, `done` is read once every check_every replays (the position
+        needs no read: it advances once per live replay and the host counts the replays) and the loop stops once every row is done; the
+        replays since the commit kernel froze have changed nothing."""
+        n = 0
+        while n < steps:
+            m = min(check_every, steps - n) if with_end else steps
+            for _ in range(m):
+                if draw is not None:
+                    draw(e["uniforms"])
+                graph.replay()
+            n += m
+            if with_end and n < steps and bool(e["done"].all()):
+                break
+
+    def generate_step(self, inputs, end_token_id=None, check_every=16):
         """one batch of {"token_ids" [B, S], "padding_mask" [B, S]} (true = user token) -> the same dictionary with the remaining positions filled
-        by the compiled sampler, greedily by default (:241-314): generation starts at the shortest row's length; longer rows keep their own tokens there"""
+        by the compiled sampler, greedily by default (:241-314): generation starts at the shortest row's length; longer rows keep their own tokens there.
+        check_every: with compile(graph_decode=True) and an end token, the number of replays between two host reads of the stop condition
+        (16 is a choice, not a measurement); the result does not depend on it."""
         token_ids, padding_mask = inputs["token_ids"], inputs["padding_mask"].to(torch.bool)
+        if self.graph_decode:
+            graphable, sampler = self._graph_decode_sampler()
+            if graphable:
+                if isinstance(check_every, bool) or not isinstance(check_every, int) or check_every < 1:
+                    raise ValueError(f"GemmaCausalLM.generate_step: check_every is an integer >= 1, got {check_every!r}")
+                if not self.built:
+                    self.build()
+                self._require_fused_decode()
+                index, sticky = self._graph_decode_start(token_ids, padding_mask, end_token_id)
+                if 1 <= index < token_ids.shape[1] and sticky:
+                    out = self._generate_graphed(token_ids, padding_mask, index, end_token_id, sampler, check_every)
+                    return {"token_ids": out, "padding_mask": generated_padding_mask(out, padding_mask, end_token_id)}
         _, cache = self._build_cache(token_ids)
         index = int(padding_mask.to(torch.int32).sum(dim=-1).min().item())
 

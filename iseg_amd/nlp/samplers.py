@@ -10,6 +10,11 @@ samplers draw one uniform per row and step from a torch.Generator they own (made
 from the library's seed stream when seed is None) and hand it with the logits to F.sample_tokens: the fused kernels of csrc/token_sample.hip.
 The same seed, prompt and weights give the same tokens; the random stream itself is torch's, not the reference's.
 
+For the decode step replayed from a captured graph (GemmaCausalLM.compile(graph_decode=True)) the library's own classes also give
+graph_signature() (what a capture freezes of the sampler: its type and kernel arguments), token_rule(uniforms) (get_next_token as a function of
+the logits alone, reading its uniforms from a static buffer) and, the seeded ones, uniforms_into(buf) (the step's draw of `uniforms`, written
+into that buffer in front of each replay).  sample_loop and the classes' behaviour are unchanged.
+
 Out of scope: BeamSampler, ContrastiveSampler, the string aliases ("top_k", ...) of keras_nlp.samplers.get."""
 import math
 
@@ -74,6 +79,13 @@ class GreedySampler(Sampler):
     def get_next_token(self, logits):
         return torch.argmax(logits, dim=-1)
 
+    def graph_signature(self):
+        return (type(self).__name__,)
+
+    def token_rule(self, uniforms=None):
+        """get_next_token as a function of the logits alone, free of this object's state: what a captured decode step records"""
+        return lambda logits: torch.argmax(logits, dim=-1)
+
 
 class _SeededSampler(Sampler):
     mode = None
@@ -85,15 +97,35 @@ class _SeededSampler(Sampler):
         self.seed = seed
         self._generator = None
 
+    def _generator_on(self, device):
+        if self._generator is None or self._generator.device != device:
+            self._generator = torch.Generator(device=device)
+            self._generator.manual_seed((self.seed if self.seed is not None else F.next_seed()) & 0x7FFFFFFFFFFFFFFF)
+        return self._generator
+
     def uniforms(self, logits):
         """fp32 [B] in [0, 1): one draw per row from this sampler's own generator"""
-        if self._generator is None or self._generator.device != logits.device:
-            self._generator = torch.Generator(device=logits.device)
-            self._generator.manual_seed((self.seed if self.seed is not None else F.next_seed()) & 0x7FFFFFFFFFFFFFFF)
-        return torch.rand(logits.shape[0], generator=self._generator, device=logits.device, dtype=torch.float32)
+        return torch.rand(logits.shape[0], generator=self._generator_on(logits.device), device=logits.device, dtype=torch.float32)
+
+    def uniforms_into(self, buf):
+        """this step's draw of `uniforms`, written into buf (fp32 [B], contiguous, on the device): the same generator and the same stream of numbers,
+        one launch, no allocation -- the buffer a captured decode step reads its uniforms from"""
+        if buf.dtype != torch.float32 or buf.dim() != 1 or not buf.is_contiguous():
+            raise ValueError(f"{type(self).__name__}.uniforms_into: the buffer is a contiguous float32 [B], got {tuple(buf.shape)} {buf.dtype}")
+        return torch.rand(buf.shape[0], generator=self._generator_on(buf.device), out=buf)
 
     def _kernel_args(self):
         return {}
+
+    def graph_signature(self):
+        """what a captured decode step freezes of this sampler: its type and the kernel's arguments (not the seed: the uniforms come from outside)"""
+        return (type(self).__name__, self.mode, self.temperature) + tuple(sorted(self._kernel_args().items()))
+
+    def token_rule(self, uniforms):
+        """get_next_token as a function of the logits alone, reading the step's uniforms from the static buffer `uniforms` (fp32 [B], filled by
+        uniforms_into in front of each step) and free of this object's state: what a captured decode step records"""
+        mode, temperature, args = self.mode, self.temperature, dict(self._kernel_args())
+        return lambda logits: F.sample_tokens(logits, uniforms, mode=mode, temperature=temperature, **args)
 
     def get_next_token(self, logits):
         return F.sample_tokens(logits, self.uniforms(logits), mode=self.mode, temperature=self.temperature, **self._kernel_args())
