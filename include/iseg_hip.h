@@ -1190,6 +1190,20 @@ int iseg_convnext_mlp_wgrad(const void* y, const float* mean, const float* rstd,
                             const float* W2, const float* b2, const float* gamma, float* dW1, float* db1, float* dW2, float* db2,
                             float* dgamma, int64_t M, int C, int dtype, void* ws, size_t ws_bytes, iseg_stream_t stream);
 
+/* The pair above in ONE pass over the rows at C = 96 (iseg_convnext_mlp_bwd_data_ln + iseg_convnext_mlp_wgrad recompute the [M, 4C] hidden
+ * tile twice; here a workgroup owns a chunk of rows and all 384 hidden units and forms it once): dy1 [M, C] = the gradient of the LayerNorm
+ * INPUT y1, dln_gamma / dln_beta += the LayerNorm parameter gradients, dW1 / db1 / dW2 / db2 / dgamma += the MLP parameter gradients -- the
+ * argument set and the semantics are the union of the two calls (LayerNorm on the row load is mandatory: mean, rstd, ln_gamma, ln_beta).
+ * dh feeds dy2 with the derivative of the sigmoid-form GELU (the chain kernel's polynomial differs by <= 8.7e-4 before the bf16 rounding).
+ * No atomics: per-chunk records in ws, fixed-order sums.  The workspace is sized by iseg_convnext_mlp_wgrad_workspace_bytes(M, 96): the two
+ * launchers leave the same chunk records and share one size function, which answers the larger need (this one's 256 chunks).  The LayerNorm
+ * partial rows are deferred when a reduction queue is open.  rowscale needs rows_per_group % 64 == 0. */
+int iseg_convnext_mlp_bwd_onepass(const void* y1, const float* mean, const float* rstd, const float* ln_gamma, const float* ln_beta,
+                                  const void* dout, const float* rowscale, int64_t rows_per_group, const void* bw_tiled, const float* b1,
+                                  const float* W2, const float* b2, const float* gamma, void* dy1, float* dln_gamma, float* dln_beta,
+                                  float* dW1, float* db1, float* dW2, float* db2, float* dgamma, int64_t M, int C, int dtype, void* ws,
+                                  size_t ws_bytes, iseg_stream_t stream);
+
 /* Gemma text backbone (nlp/gemma).
  * iseg_gemma_rope: rotary embedding of nlp/gemma/gemma_attention.py:96-114 on the packed projection rows qkv [rows = B * T][(nq + 2 nkv) h] =
  *   [q heads | k heads | v heads] (row pitches ld_in / ld_out in elements; out == qkv: in place).  Per q / k head, with x1 = x[0:h/2], x2 = x[h/2:h]:

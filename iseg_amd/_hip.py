@@ -294,6 +294,7 @@ SIGNATURES = {
     "iseg_convnext_mlp_fwd_ln": (_i, [_p, _p, _p, _f, _p, _p, _p, _p, _p, _p, _p, _l, _p, _p, _l, _i, _i, _p]),
     "iseg_convnext_mlp_wgrad_workspace_bytes": (_z, [_l, _i]),
     "iseg_convnext_mlp_wgrad": (_i, [_p, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _l, _i, _i, _p, _z, _p]),
+    "iseg_convnext_mlp_bwd_onepass": (_i, [_p] * 7 + [_l] + [_p] * 13 + [_l, _i, _i, _p, _z, _p]),
     "iseg_gemma_rope": (_i, [_p, _l, _p, _l, _p, _l, _i, _i, _i, _i, _i, _i, _p]),
     "iseg_gemma_attention_supported": (_i, [_i, _i, _i, _i]),
     "iseg_gemma_attention_lse_elems": (_z, [_l, _i, _i, _i]),

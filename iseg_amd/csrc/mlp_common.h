@@ -1,4 +1,4 @@
-// Helpers shared by the fused ConvNeXt MLP kernels (mlp_fused.hip, mlp_wgrad.hip).
+// Helpers shared by the fused ConvNeXt MLP kernels (mlp_fused.hip, mlp_wgrad.hip, mlp_bwd_onepass.hip).
 #pragma once
 #include "common.h"
 

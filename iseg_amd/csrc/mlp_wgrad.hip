@@ -25,10 +25,9 @@
 #include "common.h"
 #include "iseg_hip.h"
 #include "mlp_common.h"
+#include "mlp_wgrad_common.h"
 
 namespace {
-
-typedef __attribute__((address_space(3))) bf16x4* lds_bf16x4_ptr;
 
 template <int C> struct WgGeom {
     static constexpr int WAVES = 8, NT = 64 * WAVES, RT = C > 96 ? 32 : 64;      // rows per LDS tile (registers: C / 2 accumulators + C / 4 weights per lane)
@@ -46,26 +45,6 @@ template <int C> struct WgGeom {
     static constexpr int IMG = C * 64, SLAB = 3 * IMG;                   // tiled backward weight buffer of mlp_fused.hip: [slab][A1 | A3 | A4]
     static_assert(C % 32 == 0 && HID % (16 * WAVES) == 0 && NLOAD <= NT && RT % RG == 0 && LDS <= 160 * 1024, "geometry");
 };
-
-__device__ __forceinline__ f32x4 mfma16(const bf16x8& a, const bf16x8& b, const f32x4& c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
-// B fragment (lane = channel 16 cb + (lane & 15)) of the 32 tile rows at `rows` in the accumulator's row order: k slot (q, j) = row 4 q + j
-// (j < 4), 16 + 4 q + j - 4 (j >= 4)
-__device__ __forceinline__ bf16x8 tr_frag(const bf16_t* rows, int stride, int cb, int lane) {
-    const int q = lane >> 4, qq = (lane >> 2) & 3, p = lane & 3;
-    const bf16_t* a0 = rows + (4 * q + qq) * stride + 16 * cb + 4 * p;
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(a0));
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(a0 + 16 * stride));
-    bf16x8 f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        f[i] = lo[i];
-        f[4 + i] = hi[i];
-    }
-    return f;
-}
 
 template <int C>
 __global__ __launch_bounds__(512) void convnext_mlp_wgrad_kernel(const bf16_t* __restrict__ Y, const float* __restrict__ mean,
@@ -309,61 +288,6 @@ __global__ __launch_bounds__(512) void convnext_mlp_wgrad_kernel(const bf16_t* _
     }
 }
 
-// Book the parameter gradients from the chunk-summed record (accumulating into the flat gradient buffer):
-//     dW1[c][hid] += dW1T[hid][c]      db1[hid] += ..      dW2[hid][c] += Z[hid][c] gamma[c]      db2[c] += gamma[c] S[c]
-//     dgamma[c]   += sum_hid W2[hid][c] Z[hid][c] + b2[c] S[c]           (gamma == NULL: dW2 += Z, db2 += S)
-// Block = 8 hidden units x 32 channels (256 threads, one element each); dW1 leaves through an LDS transpose; the per-block column sums of
-// W2 o Z go to `gpart` [HID / 8][C] for the fixed-order second stage.  (Summing the 80 chunk records inside this kernel took 47-134 us in
-// three different shapes -- 144 workgroups cannot pull 24 MB, and the db1 / S sums were 80 dependent loads on a handful of threads; the
-// generic row reduction in front does it in 8.5 us.)
-constexpr int FIN_ROWS = 8;
-// `rec` = the chunk-summed record [Z | dW1T | db1 | S] (fp32, one fixed-order row reduction over the chunk records in front of this launch)
-__global__ __launch_bounds__(256) void convnext_mlp_wgrad_finish_kernel(const float* __restrict__ rec, const float* __restrict__ W2,
-                                                                        const float* __restrict__ b2, const float* __restrict__ gamma,
-                                                                        float* __restrict__ dW1, float* __restrict__ db1,
-                                                                        float* __restrict__ dW2, float* __restrict__ db2,
-                                                                        float* __restrict__ gpart, int C) {
-    __shared__ float tw[FIN_ROWS][33];
-    __shared__ float tg[8][32];
-    const int HID = 4 * C;
-    const int c0 = blockIdx.x * 32, h0 = blockIdx.y * FIN_ROWS;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;      // 32 x 8
-    const int c = c0 + tx;
-    const int64_t plane = (int64_t)HID * C;
-    const float gm = gamma ? gamma[c] : 1.f;
-    {
-        const int64_t o = (int64_t)(h0 + ty) * C + c;
-        const float z = rec[o], w = rec[plane + o];
-        dW2[o] += z * gm;
-        tg[ty][tx] = W2[o] * z;
-        tw[ty][tx] = w;
-    }
-    __syncthreads();
-    {      // dW1[c][hid]: thread -> (channel row, hidden unit): FIN_ROWS consecutive hidden units per channel
-        const int hx = threadIdx.x & (FIN_ROWS - 1), cc = threadIdx.x / FIN_ROWS;      // 8 x 32
-        dW1[(int64_t)(c0 + cc) * HID + h0 + hx] += tw[hx][cc];
-    }
-    if (ty == 0) {
-        float v = 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v += tg[j][tx];
-        if (blockIdx.y == 0) {
-            const float s = rec[2 * plane + HID + c];
-            if (gamma) {
-                v += b2[c] * s;
-                db2[c] += gm * s;
-            } else {
-                db2[c] += s;
-            }
-        }
-        if (gamma) gpart[(int64_t)blockIdx.y * C + c] = v;
-    }
-    if (blockIdx.x == 0 && threadIdx.x < FIN_ROWS) {
-        const int hid = h0 + threadIdx.x;
-        db1[hid] += rec[2 * plane + hid];
-    }
-}
-
 template <int C> int rows_per_chunk_for(int64_t M, int* nchunk) {
     using G = WgGeom<C>;
     // One workgroup per CU in ONE resident round: the kernel's ids go round the 8 XCDs (32 CUs each), so an XCD gets NHG * ceil(nchunk / 8)
@@ -407,7 +331,10 @@ size_t wgrad_ws_floats(int C, int64_t M, int* nchunk_out) {
 
 extern "C" size_t iseg_convnext_mlp_wgrad_workspace_bytes(int64_t M, int C) {
     if (!(C == 96 || C == 192) || M <= 0) return 0;
-    return wgrad_ws_floats(C, M, nullptr) * sizeof(float);
+    // C = 96: the one-pass kernel (mlp_bwd_onepass.hip) leaves the same records in 256 chunks and is sized by this function too: the larger need
+    size_t floats = wgrad_ws_floats(C, M, nullptr);
+    if (C == 96 && onepass_ws_floats(M, nullptr) > floats) floats = onepass_ws_floats(M, nullptr);
+    return floats * sizeof(float);
 }
 
 extern "C" int iseg_convnext_mlp_wgrad(const void* y, const float* mean, const float* rstd, const float* ln_gamma, const float* ln_beta,
@@ -423,7 +350,8 @@ extern "C" int iseg_convnext_mlp_wgrad(const void* y, const float* mean, const f
     ISEG_REQUIRE((((uintptr_t)y | (uintptr_t)dout | (uintptr_t)bw_tiled | (uintptr_t)ln_gamma | (uintptr_t)ln_beta) & 15) == 0,
                  "iseg_convnext_mlp_wgrad: operands must be 16-byte aligned");
     int nchunk;
-    const size_t need = wgrad_ws_floats(C, M, &nchunk) * sizeof(float);
+    wgrad_ws_floats(C, M, &nchunk);
+    const size_t need = iseg_convnext_mlp_wgrad_workspace_bytes(M, C);
     ISEG_NEED_WORKSPACE("iseg_convnext_mlp_wgrad", ws, ws_bytes, need);
     float* const wsf = (float*)ws;
     int rc = C == 96 ? launch_wgrad<96>(y, mean, rstd, ln_gamma, ln_beta, dout, rowscale, rows_per_group, bw_tiled, b1, wsf, M, stream)

@@ -318,6 +318,14 @@ class _LnMlpResidualFn(Function):
         do2 = _c(dout).reshape(M, C)
         ln = (mean, rstd, ln_gamma.data, ln_beta.data)
         dx = None
+        if K.convnext_mlp_bwd_onepass_supported(C, x2.dtype) and any(p.requires_grad for p in (W1, b1, W2, b2)):
+            # C = 96: one kernel forms the hidden tile once for the data gradient and every parameter gradient (csrc/mlp_bwd_onepass.hip)
+            dln = K.convnext_mlp_bwd_onepass(x2, do2, bw, b1.data, W2.data, b2.data, None, ln, _grad_out(ln_gamma), _grad_out(ln_beta),
+                                             _grad_out(W1), _grad_out(b1), _grad_out(W2), _grad_out(b2), None, rowscale, ctx.rpg)
+            if ctx.needs_input_grad[0]:
+                dx = K.axpby(do2, dln, 1.0, 1.0, out=dln).reshape(dout.shape)      # + the skip connection's share
+            dist.grads_ready(ln_gamma, ln_beta, W1, b1, W2, b2)
+            return (dx,) + (None,) * 8
         if ctx.needs_input_grad[0]:
             dln = K.convnext_mlp_bwd_data_ln(x2, do2, bw, b1.data, ln, _grad_out(ln_gamma), _grad_out(ln_beta), rowscale, ctx.rpg)
             dx = K.axpby(do2, dln, 1.0, 1.0, out=dln).reshape(dout.shape)      # + the skip connection's share
@@ -1778,9 +1786,17 @@ class _ConvNeXtBlockFn(Function):
             # chunk of rows) recomputes it again and contracts over the rows for every parameter gradient of the MLP; the drop-path row factor
             # and the column sums of dbr ride both (csrc/mlp_wgrad.hip) -- replaces rowscale + colsum + chain + two weight-gradient GEMMs + their
             # split-K sums + layerscale_grads
+            # At C = 96 the two are ONE kernel that forms the hidden tile once (csrc/mlp_bwd_onepass.hip); C = 192 keeps the pair.
             y1m, ln = y1.reshape(M, C), (mean, rstd, p.ln_gamma.data, p.ln_beta.data)
-            dy1 = K.convnext_mlp_bwd_data_ln(y1m, do2, h, p.b1.data, ln, _grad_out(p.ln_gamma), _grad_out(p.ln_beta), dp_mask, H * W)
-            if any(q is not None and q.requires_grad for q in (p.w1, p.b1, p.w2, p.b2, p.gamma)):
+            mlp_grads = any(q is not None and q.requires_grad for q in (p.w1, p.b1, p.w2, p.b2, p.gamma))
+            if mlp_grads and K.convnext_mlp_bwd_onepass_supported(C, cdt):
+                dy1 = K.convnext_mlp_bwd_onepass(y1m, do2, h, p.b1.data, p.w2.data, p.b2.data, p.gamma.data if p.gamma is not None else None, ln,
+                                                 _grad_out(p.ln_gamma), _grad_out(p.ln_beta), _grad_out(p.w1), _grad_out(p.b1), _grad_out(p.w2),
+                                                 _grad_out(p.b2), _grad_out(p.gamma) if p.gamma is not None else None, dp_mask, H * W)
+                mlp_grads = False
+            else:
+                dy1 = K.convnext_mlp_bwd_data_ln(y1m, do2, h, p.b1.data, ln, _grad_out(p.ln_gamma), _grad_out(p.ln_beta), dp_mask, H * W)
+            if mlp_grads:
                 K.convnext_mlp_wgrad(y1m, do2, h, p.b1.data, p.w2.data, p.b2.data, p.gamma.data if p.gamma is not None else None,
                                      _grad_out(p.w1), _grad_out(p.b1), _grad_out(p.w2), _grad_out(p.b2),
                                      _grad_out(p.gamma) if p.gamma is not None else None, dp_mask, H * W, ln=ln)

@@ -400,6 +400,27 @@ def convnext_mlp_wgrad(y, dout, bw_tiled, b1, W2, b2, gamma, dW1, db1, dW2, db2,
               wsb, stream())
 
 
+def convnext_mlp_bwd_onepass_supported(C, dtype):
+    """the one-pass backward kernel (csrc/mlp_bwd_onepass.hip) exists for bf16 rows of 96 channels"""
+    return C == 96 and dtype == torch.bfloat16
+
+
+def convnext_mlp_bwd_onepass(y1, dout, bw_tiled, b1, W2, b2, gamma, ln, dln_gamma, dln_beta, dW1, db1, dW2, db2, dgamma, rowscale=None,
+                             rows_per_group=0):
+    """convnext_mlp_bwd_data_ln + convnext_mlp_wgrad in one pass over the rows, the hidden tile formed once (csrc/mlp_bwd_onepass.hip, C = 96):
+    returns the gradient of the LayerNorm INPUT y1 and adds every parameter gradient to its buffer; ln = (mean, rstd, ln_gamma, ln_beta)"""
+    _require_cuda(y1, dout, bw_tiled, dln_gamma, dln_beta)
+    M, Cc = y1.shape
+    dy1 = torch.empty((M, Cc), dtype=y1.dtype, device=y1.device)
+    mean, rstd, lng, lnb = ln
+    need = _hip.lib().iseg_convnext_mlp_wgrad_workspace_bytes(M, Cc)      # one size function for both launchers of the chunk records
+    ws, wsb = workspace(need, y1.device)
+    _hip.call("iseg_convnext_mlp_bwd_onepass", ptr(y1), ptr(mean), ptr(rstd), ptr(lng), ptr(lnb), ptr(dout), ptr(rowscale), int(rows_per_group),
+              ptr(bw_tiled), ptr(b1), ptr(W2), ptr(b2), ptr(gamma), ptr(dy1), ptr(dln_gamma), ptr(dln_beta), ptr(dW1), ptr(db1), ptr(dW2),
+              ptr(db2), ptr(dgamma), M, Cc, dt(y1), ptr(ws), wsb, stream())
+    return dy1
+
+
 def layernorm_fwd(x2d, gamma, beta, eps, save_stats=True):
     _require_cuda(x2d)
     rows, Cc = x2d.shape
