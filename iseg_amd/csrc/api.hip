@@ -69,30 +69,14 @@ struct DefState {
     DefBatch batch{};
 } g_def;
 
-// same arithmetic as reduce_rows_kernel (16 columns x 16 row lanes, fixed order), one descriptor per run of workgroups
+// reduce_rows_kernel over a table: one descriptor per run of workgroups, the sum through the same reduce_rows_16x16 (common.h)
 __global__ __launch_bounds__(256) void reduce_rows_batched_kernel(DefBatch b) {
-    __shared__ float red[16][17];
     int i = 0;
     while (i + 1 < b.count && (int)blockIdx.x >= b.d[i + 1].block0) ++i;      // (uniform: the table sits in scalar registers)
     const DefDesc& q = b.d[i];
-    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-    const int64_t j = (int64_t)((int)blockIdx.x - q.block0) * 16 + tx;
-    float s = 0.f;
-    if (j < q.n) {
-        int p = ty;
-        for (; p + 48 < q.P; p += 64) {
-            const float a = q.partials[(int64_t)p * q.pstride + j], c = q.partials[(int64_t)(p + 16) * q.pstride + j];
-            const float e = q.partials[(int64_t)(p + 32) * q.pstride + j], f = q.partials[(int64_t)(p + 48) * q.pstride + j];
-            s += (a + c) + (e + f);
-        }
-        for (; p < q.P; p += 16) s += q.partials[(int64_t)p * q.pstride + j];
-    }
-    red[ty][tx] = s;
-    __syncthreads();
-    if (ty == 0 && j < q.n) {
-        float t = red[0][tx];
-#pragma unroll
-        for (int k = 1; k < 16; ++k) t += red[k][tx];
+    const int64_t j = (int64_t)((int)blockIdx.x - q.block0) * 16 + (threadIdx.x & 15);
+    float t = reduce_rows_16x16(q.partials, q.P, q.pstride, j, q.n);
+    if (threadIdx.x < 16 && j < q.n) {
         t *= q.scale;
         float* dst = j < q.n0 ? q.out0 + j : (q.out1 ? q.out1 + (j - q.n0) : nullptr);
         if (dst) *dst = t + *dst;      // (only accumulating reductions are deferred)
@@ -113,12 +97,14 @@ int def_flush(hipStream_t stream) {
 
 }  // namespace
 
-float* iseg_deferred_partials(size_t bytes, const float* out0, const float* out1, int accumulate, hipStream_t stream) {
-    if (!g_def.on || !accumulate || stream != g_def.stream || !out0) return nullptr;
+// an arena slice for the partials of `r` if it may be queued, else nullptr
+static float* def_partials(const RowReduce& r, hipStream_t stream) {
+    const float *out0 = r.out0, *out1 = r.out1;
+    if (!g_def.on || !r.accumulate || r.batch != 1 || stream != g_def.stream || !out0) return nullptr;
     const char* a = (const char*)out0;
     if (a < g_def.glo || a >= g_def.ghi) return nullptr;
     if (out1 && ((const char*)out1 < g_def.glo || (const char*)out1 >= g_def.ghi)) return nullptr;
-    bytes = (bytes + 255) / 256 * 256;
+    const size_t bytes = ((size_t)r.P * r.pstride * sizeof(float) + 255) / 256 * 256;
     if (bytes > g_def.cap) return nullptr;
     for (int i = 0; i < g_def.batch.count; ++i) {      // two queued reductions into the same gradient would race inside one launch
         const DefDesc& q = g_def.batch.d[i];
@@ -133,22 +119,19 @@ float* iseg_deferred_partials(size_t bytes, const float* out0, const float* out1
     return p;
 }
 
-void iseg_deferred_push(const float* partials, int P, int64_t pstride, int64_t n, float* out0, float* out1, int64_t n0, float scale,
-                        hipStream_t stream) {
+float* reduce_rows_begin(RowReduce& r, void* ws, hipStream_t stream, bool may_queue) {
+    float* const arena = may_queue ? def_partials(r, stream) : nullptr;
+    r.queued = arena != nullptr;
+    r.partials = arena ? arena : (float*)ws;
+    return const_cast<float*>(r.partials);
+}
+
+void reduce_rows_end(const RowReduce& r, hipStream_t stream) {
+    if (!r.queued) return launch_reduce_rows(r, stream);
     DefBatch& b = g_def.batch;
-    if (b.count == DEF_MAX) def_flush(stream);      // (cannot happen after iseg_deferred_partials, kept for safety)
-    DefDesc& q = b.d[b.count++];
-    q.partials = partials;
-    q.out0 = out0;
-    q.out1 = out1;
-    q.pstride = pstride;
-    q.n = n;
-    q.n0 = n0;
-    q.P = P;
-    q.scale = scale;
-    q.block0 = b.blocks;
-    q.pad = 0;
-    b.blocks += (int)((n + 15) / 16);
+    if (b.count == DEF_MAX) def_flush(stream);      // (cannot happen after reduce_rows_begin, kept for safety)
+    b.d[b.count++] = DefDesc{r.partials, r.out0, r.out1, r.pstride, r.n, r.n0, r.P, r.scale, /*block0*/ b.blocks, /*pad*/ 0};
+    b.blocks += (int)((r.n + 15) / 16);
 }
 
 extern "C" int iseg_deferred_begin(void* grad_base, size_t grad_bytes, void* arena, size_t arena_bytes, hipStream_t stream) {

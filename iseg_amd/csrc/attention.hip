@@ -430,7 +430,7 @@ extern "C" int iseg_colsum_wide(const void* x, int64_t ldx, int64_t rows, int64_
         hipLaunchKernelGGL((colsum_wide_partial_kernel<T>), grid, dim3(256), 0, stream, (const T*)x, ldx, rows, cols, (float*)ws);
     });
     if (rc != ISEG_OK) return rc;
-    launch_reduce_rows((const float*)ws, chunks, cols, 0, 1, cols, out, nullptr, cols, 0, 1.f, accumulate, stream);
+    launch_reduce_rows({.partials = (const float*)ws, .P = chunks, .pstride = cols, .n = cols, .out0 = out, .n0 = cols, .accumulate = accumulate}, stream);
     return iseg_check_launch("iseg_colsum_wide");
 }
 

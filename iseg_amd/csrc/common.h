@@ -159,34 +159,47 @@ __device__ __forceinline__ float group_sum(float v, int width) {
     return v;
 }
 
-// Deferred parameter-gradient reductions (api.hip).  Between iseg_deferred_begin() and iseg_deferred_end() a two-stage reduction whose
-// output lies inside the registered gradient buffer (and accumulates into it) is not launched: its partial sums go to the caller's arena and
-// a descriptor is queued; iseg_deferred_flush() runs ONE launch over all queued descriptors.  The ~70 five-microsecond reduce launches of a
-// training step (LayerNorm / depthwise / bias gradients) cost more at their kernel boundaries than in their work.
-//   iseg_deferred_partials(): arena slice for `bytes` of partials if this reduction may be deferred, else nullptr (launch it right away)
-float* iseg_deferred_partials(size_t bytes, const float* out0, const float* out1, int accumulate, hipStream_t stream);
-void iseg_deferred_push(const float* partials, int P, int64_t pstride, int64_t n, float* out0, float* out1, int64_t n0, float scale,
-                        hipStream_t stream);
-
 // Second stage of every two-stage reduction (LayerNorm / BatchNorm / colsum / depthwise-wgrad parameter gradients):
 //   out[b][j] (+)= scale * sum_{p<P} partials[b*bstride_in + p*pstride + j],  j < n,
-// written to out0 for j < n0 and to out1[j-n0] beyond (out1 may be null).  A block owns 16 columns; 16 row-lanes stride
-// over p and are combined through LDS in a fixed order, so the result is deterministic and the pass takes P/64 dependent
-// steps instead of P.  Template parameter only makes the symbol TU-local-safe.
-template <int TAG>
-__global__ __launch_bounds__(256) void reduce_rows_kernel(const float* __restrict__ partials, int P, int64_t pstride,
-                                                          int64_t bstride_in, int64_t n, float* __restrict__ out0,
-                                                          float* __restrict__ out1, int64_t n0, int64_t bstride_out, float scale,
-                                                          int accumulate) {
-    // 16 columns x 16 row-lanes per workgroup: P/16 dependent steps, 64-B coalesced segments
+// written to out0 for j < n0 and to out1[j-n0] beyond (out1 may be null).  One descriptor says it all, filled by name; the defaults are
+// "one problem, unscaled, overwriting, no second output".
+struct RowReduce {
+    const float* partials = nullptr;      // P rows of n floats, pstride apart (reduce_rows_begin fills it in)
+    int P = 0;
+    int64_t pstride = 0, n = 0;
+    float* out0 = nullptr;
+    float* out1 = nullptr;
+    int64_t n0 = 0;                       // columns that go to out0
+    float scale = 1.f;
+    int accumulate = 0;
+    int batch = 1;                        // independent problems, bstride_in / bstride_out floats apart
+    int64_t bstride_in = 0, bstride_out = 0;
+    bool queued = false;                  // set by reduce_rows_begin: reduce_rows_end queues this reduction instead of launching it
+};
+
+// Deferred parameter-gradient reductions (api.hip).  Between iseg_deferred_begin() and iseg_deferred_end() a two-stage reduction whose
+// output lies inside the registered gradient buffer (and accumulates into it) is not launched: its partial sums go to the caller's arena and
+// the descriptor is queued; iseg_deferred_flush() runs ONE launch over all queued descriptors.  The ~70 five-microsecond reduce launches of a
+// training step (LayerNorm / depthwise / bias gradients) cost more at their kernel boundaries than in their work.  A launcher states its
+// reduction once and brackets its producer launch with the pair:
+//   reduce_rows_begin(): the buffer the producer writes its partials to -- an arena slice when this reduction may be queued (queue open on
+//                        this stream, accumulating, outputs inside the gradient buffer, arena large enough; `may_queue` is the launcher's
+//                        own veto), else `ws`, the launcher's workspace
+//   reduce_rows_end():   after the producer launch: queues the descriptor, or launches the reduction right away
+float* reduce_rows_begin(RowReduce& r, void* ws, hipStream_t stream, bool may_queue = true);
+void reduce_rows_end(const RowReduce& r, hipStream_t stream);
+
+// The sum itself: a block owns 16 columns; 16 row-lanes stride over p (four independent loads in flight) and are combined through LDS in
+// a fixed order, so the result is deterministic and the pass takes P/64 dependent steps instead of P, in 64-B coalesced segments.  Returns
+// sum_{p<P} src[p*pstride + j] in the row-lane-0 thread of column j < n (0 elsewhere).  Both second-stage kernels (the one below and the
+// batched one of the deferred queue, api.hip) sum through this function: deferred and immediate gradients are bit-identical by construction.
+__device__ __forceinline__ float reduce_rows_16x16(const float* __restrict__ src, int P, int64_t pstride, int64_t j, int64_t n) {
     __shared__ float red[16][17];
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-    const int64_t j = (int64_t)blockIdx.x * 16 + tx;
-    const float* src = partials + (int64_t)blockIdx.y * bstride_in;
     float s = 0.f;
     if (j < n) {
         int p = ty;
-        for (; p + 48 < P; p += 64) {  // four independent loads in flight
+        for (; p + 48 < P; p += 64) {
             const float a = src[(int64_t)p * pstride + j], b = src[(int64_t)(p + 16) * pstride + j];
             const float c = src[(int64_t)(p + 32) * pstride + j], d = src[(int64_t)(p + 48) * pstride + j];
             s += (a + b) + (c + d);
@@ -195,10 +208,22 @@ __global__ __launch_bounds__(256) void reduce_rows_kernel(const float* __restric
     }
     red[ty][tx] = s;
     __syncthreads();
-    if (ty == 0 && j < n) {
-        float t = red[0][tx];
+    if (ty != 0 || j >= n) return 0.f;
+    float t = red[0][tx];
 #pragma unroll
-        for (int k = 1; k < 16; ++k) t += red[k][tx];
+    for (int k = 1; k < 16; ++k) t += red[k][tx];
+    return t;
+}
+
+// Template parameter only makes the symbol TU-local-safe.
+template <int TAG>
+__global__ __launch_bounds__(256) void reduce_rows_kernel(const float* __restrict__ partials, int P, int64_t pstride,
+                                                          int64_t bstride_in, int64_t n, float* __restrict__ out0,
+                                                          float* __restrict__ out1, int64_t n0, int64_t bstride_out, float scale,
+                                                          int accumulate) {
+    const int64_t j = (int64_t)blockIdx.x * 16 + (threadIdx.x & 15);
+    float t = reduce_rows_16x16(partials + (int64_t)blockIdx.y * bstride_in, P, pstride, j, n);
+    if (threadIdx.x < 16 && j < n) {
         t *= scale;
         float* dst = j < n0 ? out0 + (int64_t)blockIdx.y * bstride_out + j : (out1 ? out1 + (int64_t)blockIdx.y * bstride_out + (j - n0) : nullptr);
         if (dst) {
@@ -243,19 +268,17 @@ __global__ __launch_bounds__(256) void reduce_rows_wide_kernel(const float* __re
     *reinterpret_cast<float4*>(dst) = s;
 }
 
-static inline void launch_reduce_rows(const float* partials, int P, int64_t pstride, int64_t bstride_in, int batch, int64_t n,
-                                      float* out0, float* out1, int64_t n0, int64_t bstride_out, float scale, int accumulate,
-                                      hipStream_t stream) {
-    const bool aligned = (((uintptr_t)partials | (uintptr_t)out0 | (uintptr_t)out1) & 15) == 0;
+static inline void launch_reduce_rows(const RowReduce& r, hipStream_t stream) {
+    const bool aligned = (((uintptr_t)r.partials | (uintptr_t)r.out0 | (uintptr_t)r.out1) & 15) == 0;
     // (up to 128 partial rows: the chunk records of the fused-stage weight gradients are 40 / 80 rows of 0.3 M floats -- the 16 x 16 kernel below
     // reads them in 64-byte segments at 2.8 TB/s; flagship 8.91 -> 8.87 ms)
-    if (batch == 1 && P <= 128 && n >= 32768 && n % 4 == 0 && n0 % 4 == 0 && pstride % 4 == 0 && aligned) {
-        hipLaunchKernelGGL((reduce_rows_wide_kernel<0>), dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, stream, partials, P,
-                           pstride, n, out0, out1, n0, scale, accumulate);
+    if (r.batch == 1 && r.P <= 128 && r.n >= 32768 && r.n % 4 == 0 && r.n0 % 4 == 0 && r.pstride % 4 == 0 && aligned) {
+        hipLaunchKernelGGL((reduce_rows_wide_kernel<0>), dim3((unsigned)((r.n / 4 + 255) / 256)), dim3(256), 0, stream, r.partials, r.P,
+                           r.pstride, r.n, r.out0, r.out1, r.n0, r.scale, r.accumulate);
         return;
     }
-    hipLaunchKernelGGL((reduce_rows_kernel<0>), dim3((unsigned)((n + 15) / 16), batch), dim3(256), 0, stream, partials, P, pstride,
-                       bstride_in, n, out0, out1, n0, bstride_out, scale, accumulate);
+    hipLaunchKernelGGL((reduce_rows_kernel<0>), dim3((unsigned)((r.n + 15) / 16), r.batch), dim3(256), 0, stream, r.partials, r.P, r.pstride,
+                       r.bstride_in, r.n, r.out0, r.out1, r.n0, r.bstride_out, r.scale, r.accumulate);
 }
 
 // Fast Phi(x) = 0.5(1+erf(x/sqrt2)) for bf16-storage kernels: Abramowitz-Stegun 7.1.26 (|err| <= 1.5e-7, far below the

@@ -1048,7 +1048,7 @@ extern "C" int iseg_mul_colsum(const void* a, const void* b, int64_t rows, int C
                            stream, (const T*)a, (const T*)b, rows, C, (float*)ws);
     });
     if (rc != ISEG_OK) return rc;
-    launch_reduce_rows((const float*)ws, blocks, C, 0, 1, C, out, nullptr, C, 0, 1.f, accumulate, stream);
+    launch_reduce_rows({.partials = (const float*)ws, .P = blocks, .pstride = C, .n = C, .out0 = out, .n0 = C, .accumulate = accumulate}, stream);
     return iseg_check_launch("iseg_mul_colsum");
 }
 

@@ -1174,8 +1174,9 @@ extern "C" int iseg_dwconv2d_bwd_weight(const void* x, const void* dy, float* dw
     // what the header tells a caller to ask for is then also what is checked, whichever route a later change picks
     const size_t promised = iseg_dwconv2d_bwd_weight_workspace_bytes(N, H, W, C, K);
     ISEG_NEED_WORKSPACE("iseg_dwconv2d_bwd_weight", ws, ws_bytes, need > promised ? need : promised);
-    float* const arena = iseg_deferred_partials(need, dw, db, accumulate, stream);      // (see common.h: deferred reductions)
-    if (arena) ws = arena;
+    const int n = (K * K + 1) * C;
+    RowReduce red{.P = g.bx, .pstride = n, .n = n, .out0 = dw, .out1 = db, .n0 = K * K * C, .accumulate = accumulate};
+    ws = reduce_rows_begin(red, ws, stream);      // (see common.h: deferred reductions)
     if (bm) {
         if (!iseg_dwconv7_wgrad_mfma_launch(x, dy, (float*)ws, N, H, W, C, pad_t, pad_l, bm, stream)) {
             iseg_set_error("iseg_dwconv2d_bwd_weight: the matrix-core kernel could not be launched");
@@ -1198,8 +1199,6 @@ extern "C" int iseg_dwconv2d_bwd_weight(const void* x, const void* dy, float* dw
             launch(x, dy, (float*)ws, N, H, W, C, dil, pad_t, pad_l, g, stream);
         });
     }
-    const int n = (K * K + 1) * C;
-    if (arena) iseg_deferred_push((const float*)ws, g.bx, n, n, dw, db, K * K * C, 1.f, stream);
-    else launch_reduce_rows((const float*)ws, g.bx, n, 0, 1, n, dw, db, K * K * C, 0, 1.f, accumulate, stream);
+    reduce_rows_end(red, stream);
     return iseg_check_launch("iseg_dwconv2d_bwd_weight");
 }

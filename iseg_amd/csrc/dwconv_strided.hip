@@ -207,6 +207,7 @@ extern "C" int iseg_dwconv2d_strided_bwd_weight(const void* x, const void* dy, f
     });
     if (rc != ISEG_OK) return rc;
     const int n = (K * K + 1) * C;
-    launch_reduce_rows((const float*)ws, parts, n, 0, 1, n, dw, db, (int64_t)K * K * C, 0, 1.f, accumulate, stream);
+    launch_reduce_rows({.partials = (const float*)ws, .P = parts, .pstride = n, .n = n, .out0 = dw, .out1 = db, .n0 = (int64_t)K * K * C,
+                        .accumulate = accumulate}, stream);
     return iseg_check_launch("iseg_dwconv2d_strided_bwd_weight");
 }

@@ -304,6 +304,7 @@ extern "C" int iseg_dwconv2d7_bwd_weight_mfma(const void* x, const void* dy, flo
         return ISEG_ERR_UNSUPPORTED;
     }
     const int n = NT * C;
-    launch_reduce_rows((const float*)ws, blocks, n, 0, 1, n, dw, db, (int64_t)(NT - 1) * C, 0, 1.f, accumulate, stream);
+    launch_reduce_rows({.partials = (const float*)ws, .P = blocks, .pstride = n, .n = n, .out0 = dw, .out1 = db, .n0 = (int64_t)(NT - 1) * C,
+                        .accumulate = accumulate}, stream);
     return iseg_check_launch("iseg_dwconv2d7_bwd_weight_mfma");
 }

@@ -754,8 +754,9 @@ extern "C" int iseg_colsum(const void* x, int64_t ldx, int64_t batch_stride, int
     const int P = colsum_blocks(rows, C, V);
     const size_t need = (size_t)batch * P * C * sizeof(float);
     ISEG_NEED_WORKSPACE("iseg_colsum", ws, ws_bytes, need);
-    float* const arena = batch == 1 ? iseg_deferred_partials(need, out, nullptr, accumulate, stream) : nullptr;      // (see common.h: deferred reductions)
-    if (arena) ws = arena;
+    RowReduce red{.P = P, .pstride = C, .n = C, .out0 = out, .n0 = C, .scale = scale, .accumulate = accumulate, .batch = batch,
+                  .bstride_in = (int64_t)P * C, .bstride_out = C};
+    ws = reduce_rows_begin(red, ws, stream, batch == 1);      // (see common.h: deferred reductions; the queue holds single problems)
     const size_t lds = colsum_slab_bytes(C, V);
     const int rc = by_dtype(dtype, "iseg_colsum", [&](auto t) {
         using T = decltype(t);
@@ -763,8 +764,7 @@ extern "C" int iseg_colsum(const void* x, int64_t ldx, int64_t batch_stride, int
                            batch_stride, (float*)ws, rows, C);
     });
     if (rc != ISEG_OK) return rc;
-    if (arena) iseg_deferred_push((const float*)ws, P, C, C, out, nullptr, C, scale, stream);
-    else launch_reduce_rows((const float*)ws, P, C, (int64_t)P * C, batch, C, out, nullptr, C, C, scale, accumulate, stream);
+    reduce_rows_end(red, stream);
     return iseg_check_launch("iseg_colsum");
 }
 
@@ -869,12 +869,11 @@ extern "C" int iseg_layerscale_grads(const float* Z, const float* W2, const floa
     // (the caller is held to the query, which also covers the slab form's finer strips: one rule for both forms)
     const size_t promised = iseg_layerscale_grads_workspace_bytes(K, N);
     ISEG_NEED_WORKSPACE("iseg_layerscale_grads", ws, ws_bytes, need > promised ? need : promised);
-    float* const arena = iseg_deferred_partials(need, dgamma, nullptr, accumulate, stream);      // (see common.h: deferred reductions)
-    if (arena) ws = arena;
+    RowReduce red{.P = P, .pstride = N, .n = N, .out0 = dgamma, .n0 = N, .accumulate = accumulate};
+    ws = reduce_rows_begin(red, ws, stream);      // (see common.h: deferred reductions)
     hipLaunchKernelGGL(layerscale_stage1_kernel, dim3((N + 63) / 64, P), dim3(256), 0, stream, Z, W2, gamma, b2, S, dW2, db2, (float*)ws, K, N,
                        accumulate);
-    if (arena) iseg_deferred_push((const float*)ws, P, N, N, dgamma, nullptr, N, 1.f, stream);
-    else launch_reduce_rows((const float*)ws, P, N, 0, 1, N, dgamma, nullptr, N, 0, 1.f, accumulate, stream);
+    reduce_rows_end(red, stream);
     return iseg_check_launch("iseg_layerscale_grads");
 }
 
@@ -917,8 +916,8 @@ static int layerscale_grads_slabs_impl(const float* slabs, int nslabs, const flo
     // (a buffer smaller than the query answers is refused, not served with coarser strips)
     const size_t promised = iseg_layerscale_grads_workspace_bytes(K, N);
     ISEG_NEED_WORKSPACE("iseg_layerscale_grads_slabs", ws, ws_bytes, need > promised ? need : promised);
-    float* const arena = iseg_deferred_partials(need, dgamma, nullptr, accumulate, stream);
-    if (arena) ws = arena;
+    RowReduce red{.P = P, .pstride = N, .n = N, .out0 = dgamma, .n0 = N, .accumulate = accumulate};
+    ws = reduce_rows_begin(red, ws, stream);
     const int64_t slab_stride = (int64_t)(K + 1) * N;
     if (job) {
         const int gx = (N / 4 + 15) / 16;
@@ -929,8 +928,7 @@ static int layerscale_grads_slabs_impl(const float* slabs, int nslabs, const flo
         hipLaunchKernelGGL(layerscale_slabs_kernel, dim3((N / 4 + 15) / 16, P), dim3(256), 0, stream, slabs, nslabs, slab_stride, W2, gamma, b2,
                            dW2, db2, (float*)ws, K, N, accumulate);
     }
-    if (arena) iseg_deferred_push((const float*)ws, P, N, N, dgamma, nullptr, N, 1.f, stream);
-    else launch_reduce_rows((const float*)ws, P, N, 0, 1, N, dgamma, nullptr, N, 0, 1.f, accumulate, stream);
+    reduce_rows_end(red, stream);
     return iseg_check_launch("iseg_layerscale_grads_slabs");
 }
 

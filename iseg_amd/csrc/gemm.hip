@@ -272,7 +272,8 @@ int iseg_mm::gemm_reduce(const Epi& e, void* D, int64_t ldd, int out_dtype, int6
     const int64_t total = p.slab_rows * N;
     if (slabs && plain_epilogue) {
         // weight gradients: D (+)= alpha * sum_z slab[z] (and the ones-row -> colsum_out) with the 2-D parallel reducer
-        launch_reduce_rows(slabs, p.eff_split, total, 0, 1, total, (float*)D, e.colsum_out, M * N, 0, e.alpha, e.accumulate, stream);
+        launch_reduce_rows({.partials = slabs, .P = p.eff_split, .pstride = total, .n = total, .out0 = (float*)D, .out1 = e.colsum_out, .n0 = M * N,
+                            .scale = e.alpha, .accumulate = e.accumulate}, stream);
     } else if (slabs) {
         const int blocks = (int)(ceil_div64(total, 256) < 2048 ? ceil_div64(total, 256) : 2048);
         if (out_dtype == ISEG_BF16)

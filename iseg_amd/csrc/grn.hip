@@ -313,7 +313,8 @@ extern "C" int iseg_grn_fwd(const void* x, const float* gamma, const float* beta
         hipLaunchKernelGGL((grn_colsum_kernel<T, false>), dim3(P, (unsigned)N), dim3(256), 0, stream, (const T*)x, (const T*)nullptr, parts, HW, C);
     });
     if (rc != ISEG_OK) return rc;
-    launch_reduce_rows(parts, P, C, (int64_t)P * C, (int)N, C, sumsq, nullptr, C, C, 1.f, 0, stream);
+    launch_reduce_rows({.partials = parts, .P = P, .pstride = C, .n = C, .out0 = sumsq, .n0 = C, .batch = (int)N, .bstride_in = (int64_t)P * C,
+                        .bstride_out = C}, stream);
     hipLaunchKernelGGL(grn_stats_kernel, dim3((unsigned)N), dim3(256), 0, stream, (const float*)sumsq, nx, gx, C, eps);
     if (!y) return iseg_check_launch("iseg_grn_fwd");      // statistics only: the caller folds gamma*nx + 1 into the next layer's kernel
     const int64_t chunks = N * HW * (C / 8);
@@ -338,20 +339,20 @@ extern "C" int iseg_grn_bwd(const void* dy, const void* x, const float* gamma, c
     const size_t side = align256((size_t)N * 2 * C * sizeof(float));
     float* parts = (float*)ws;
     float* t = (float*)((char*)ws + align256((size_t)N * P * 2 * C * sizeof(float)));
-    float* buf = (float*)((char*)t + side);
+    const int64_t C2 = 2 * (int64_t)C;
     // per-sample rows (D*nx | sum dy) are the partials of the parameter gradients: they go to the trainer's arena when its queue is open
-    float* arena = iseg_deferred_partials((size_t)N * 2 * C * sizeof(float), dgamma, dbeta, accumulate, stream);
-    if (arena) buf = arena;
+    RowReduce red{.P = (int)N, .pstride = C2, .n = C2, .out0 = dgamma, .out1 = dbeta, .n0 = C, .accumulate = accumulate};
+    float* const buf = reduce_rows_begin(red, (char*)t + side, stream);
     const int rc = by_dtype(dtype, "iseg_grn_bwd", [&](auto t) {
         using T = decltype(t);
         hipLaunchKernelGGL((grn_colsum_kernel<T, true>), dim3(P, (unsigned)N), dim3(256), 0, stream, (const T*)x, (const T*)dy, parts, HW, C);
     });
     if (rc != ISEG_OK) return rc;
-    launch_reduce_rows(parts, P, 2 * (int64_t)C, (int64_t)P * 2 * C, (int)N, 2 * (int64_t)C, buf, nullptr, 2 * (int64_t)C, 2 * (int64_t)C, 1.f,
-                       0, stream);
-    hipLaunchKernelGGL(grn_bwd_stats_kernel, dim3((unsigned)N), dim3(256), 0, stream, buf, 2 * (int64_t)C, gamma, nx, gx, t, C, eps);
-    if (arena) iseg_deferred_push(buf, (int)N, 2 * (int64_t)C, 2 * (int64_t)C, dgamma, dbeta, C, 1.f, stream);
-    else launch_reduce_rows(buf, (int)N, 2 * (int64_t)C, 0, 1, 2 * (int64_t)C, dgamma, dbeta, C, 0, 1.f, accumulate, stream);
+    // first level, always at once: the partial rows of each sample -> its row of `buf`
+    launch_reduce_rows({.partials = parts, .P = P, .pstride = C2, .n = C2, .out0 = buf, .n0 = C2, .batch = (int)N, .bstride_in = P * C2,
+                        .bstride_out = C2}, stream);
+    hipLaunchKernelGGL(grn_bwd_stats_kernel, dim3((unsigned)N), dim3(256), 0, stream, buf, C2, gamma, nx, gx, t, C, eps);
+    reduce_rows_end(red, stream);
     const int64_t chunks = N * HW * (C / 8);
     const unsigned blocks = grid_cap(chunks, 256, 8192);
     return by_dtype(dtype, "iseg_grn_bwd", [&](auto st) {
@@ -404,7 +405,8 @@ extern "C" int iseg_grn_bwd_folded(const void* dy, const void* x, const float* g
     ISEG_NEED_WORKSPACE("iseg_grn_bwd_folded", ws, ws_bytes, iseg_grn_workspace_bytes(N, HW, C));
     float* t = (float*)ws;
     hipLaunchKernelGGL(grn_bwd_stats_kernel, dim3((unsigned)N), dim3(256), 0, stream, dstats, 2 * (int64_t)C, gamma, nx, gx, t, C, eps);
-    launch_reduce_rows(dstats, (int)N, 2 * (int64_t)C, 0, 1, 2 * (int64_t)C, dgamma, dbeta, C, 0, 1.f, accumulate, stream);
+    launch_reduce_rows({.partials = dstats, .P = (int)N, .pstride = 2 * (int64_t)C, .n = 2 * (int64_t)C, .out0 = dgamma, .out1 = dbeta, .n0 = C,
+                        .accumulate = accumulate}, stream);
     const int64_t chunks = N * HW * (C / 8);
     const unsigned blocks = grid_cap(chunks, 256, 8192);
     return by_dtype(dtype, "iseg_grn_bwd_folded", [&](auto st) {

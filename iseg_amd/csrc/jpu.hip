@@ -341,8 +341,8 @@ extern "C" int iseg_jpu_dwconv3x4_stats(const void* x, const float* w, const flo
     if (rc != ISEG_OK) return rc;
     // [part][4][2C] -> packed [4][2C+1]: one batch entry per rate, the count slot (written by the kernel) skipped by the output stride
     if (packed)
-        launch_reduce_rows(part, (int)jp_parts(g), JP_RATES * 2 * (int64_t)C, 2 * (int64_t)C, JP_RATES, 2 * (int64_t)C, packed, nullptr,
-                           2 * (int64_t)C, 2 * (int64_t)C + 1, 1.f, 0, stream);
+        launch_reduce_rows({.partials = part, .P = (int)jp_parts(g), .pstride = JP_RATES * 2 * (int64_t)C, .n = 2 * (int64_t)C, .out0 = packed,
+                            .n0 = 2 * (int64_t)C, .batch = JP_RATES, .bstride_in = 2 * (int64_t)C, .bstride_out = 2 * (int64_t)C + 1}, stream);
     return iseg_check_launch("iseg_jpu_dwconv3x4_stats");
 }
 
@@ -366,7 +366,9 @@ extern "C" int iseg_jpu_bnfold_dwconv3x4_bwd(const void* D, const void* z, const
     if (rc != ISEG_OK) return rc;
     // [part][4][10][C]: rows 0..8 of every rate -> dw [4][9][C], row 9 -> db [4][C]; one batch entry per rate
     const int64_t prow = JP_RATES * JP_BWD_ROWS * (int64_t)C, rrow = JP_BWD_ROWS * (int64_t)C;
-    launch_reduce_rows(part, (int)jp_parts(g), prow, rrow, JP_RATES, 9 * (int64_t)C, dw, nullptr, 9 * (int64_t)C, 9 * (int64_t)C, 1.f, 1, stream);
-    launch_reduce_rows(part + 9 * (int64_t)C, (int)jp_parts(g), prow, rrow, JP_RATES, (int64_t)C, db, nullptr, (int64_t)C, (int64_t)C, 1.f, 1, stream);
+    launch_reduce_rows({.partials = part, .P = (int)jp_parts(g), .pstride = prow, .n = 9 * (int64_t)C, .out0 = dw, .n0 = 9 * (int64_t)C, .accumulate = 1,
+                        .batch = JP_RATES, .bstride_in = rrow, .bstride_out = 9 * (int64_t)C}, stream);
+    launch_reduce_rows({.partials = part + 9 * (int64_t)C, .P = (int)jp_parts(g), .pstride = prow, .n = C, .out0 = db, .n0 = C, .accumulate = 1,
+                        .batch = JP_RATES, .bstride_in = rrow, .bstride_out = C}, stream);
     return iseg_check_launch("iseg_jpu_bnfold_dwconv3x4_bwd");
 }

@@ -493,8 +493,8 @@ extern "C" int iseg_groupnorm_bwd(const void* dy, const void* x, const float* ga
     });
     if (rc != ISEG_OK) return rc;
     if (dgamma || dbeta) {
-        if (dgamma) launch_reduce_rows((const float*)ws, N, 2 * C, 0, 1, C, dgamma, nullptr, C, 0, 1.f, accumulate_param_grads, stream);
-        if (dbeta) launch_reduce_rows((const float*)ws + C, N, 2 * C, 0, 1, C, dbeta, nullptr, C, 0, 1.f, accumulate_param_grads, stream);
+        if (dgamma) launch_reduce_rows({.partials = (const float*)ws, .P = N, .pstride = 2 * C, .n = C, .out0 = dgamma, .n0 = C, .accumulate = accumulate_param_grads}, stream);
+        if (dbeta) launch_reduce_rows({.partials = (const float*)ws + C, .P = N, .pstride = 2 * C, .n = C, .out0 = dbeta, .n0 = C, .accumulate = accumulate_param_grads}, stream);
     }
     return iseg_check_launch("iseg_groupnorm_bwd");
 }
@@ -527,7 +527,7 @@ extern "C" int iseg_rmsnorm_bwd(const void* dy, const void* x, const float* scal
                            rows, C);
     });
     if (rc != ISEG_OK) return rc;
-    launch_reduce_rows((const float*)ws, blocks, C, 0, 1, C, dscale, nullptr, C, 0, 1.f, accumulate_param_grads, stream);
+    launch_reduce_rows({.partials = (const float*)ws, .P = blocks, .pstride = C, .n = C, .out0 = dscale, .n0 = C, .accumulate = accumulate_param_grads}, stream);
     return iseg_check_launch("iseg_rmsnorm_bwd");
 }
 

@@ -51,7 +51,7 @@ struct OpGeom {
     static constexpr int OFF_LG = OFF_ST + 2 * RT * 2 * 4;
     static constexpr int LDS = OFF_LG + C * 4;
     static constexpr int IMG = C * 64, SLAB = 3 * IMG;             // tiled backward weight buffer of mlp_fused.hip: [slab][A1 | A3 | A4]
-    static constexpr int64_t REC = 2 * (int64_t)HID * C + HID + C; // chunk record [Z | dW1T | db1 | S]
+    static constexpr int64_t REC = mlp_record_floats(C);           // chunk record [Z | dW1T | db1 | S]
     static_assert(NG == 3 && NLOAD <= NT && RT * DSTR * 4 <= 2 * TILE * 2 && 3 * (NT / 32) * C * 4 <= RT * HSTR * 2 && LDS <= 160 * 1024,
                   "geometry");
 };
@@ -417,44 +417,26 @@ extern "C" int iseg_convnext_mlp_bwd_onepass(const void* y1, const float* mean, 
                  "iseg_convnext_mlp_bwd_onepass: the row factor must be constant inside 64-row tiles (rows_per_group = %lld)", (long long)rows_per_group);
     ISEG_REQUIRE((((uintptr_t)y1 | (uintptr_t)dout | (uintptr_t)bw_tiled | (uintptr_t)ln_gamma | (uintptr_t)ln_beta | (uintptr_t)dy1) & 15) == 0,
                  "iseg_convnext_mlp_bwd_onepass: operands must be 16-byte aligned");
-    int nchunk;
     // (sized by the weight-gradient pair's function: one answer for both launchers that leave these chunk records, mlp_wgrad_common.h)
     const size_t need = iseg_convnext_mlp_wgrad_workspace_bytes(M, C);
-    static_assert(G::REC == 2 * 4 * 96 * 96 + 4 * 96 + 96, "record of onepass_ws_floats");
     ISEG_NEED_WORKSPACE("iseg_convnext_mlp_bwd_onepass", ws, ws_bytes, need);
+    int nchunk;
     const int rpc = onepass_rows_per_chunk(M, &nchunk);
-    float* const part = (float*)ws;
-    float* const sum = part + (int64_t)nchunk * G::REC;
-    float* const gpart_ws = sum + G::REC;
-    float* lnpart = gpart_ws + (G::HID / FIN_ROWS) * G::C;
+    const MlpGradWs L = onepass_ws(M);
+    float* const wsf = (float*)ws;
     // dln_gamma | dln_beta: one partial row per chunk, summed in fixed order into the gradient buffers (queued when the caller defers reductions)
-    float* const ln_arena = iseg_deferred_partials((size_t)nchunk * 2 * G::C * sizeof(float), dln_gamma, dln_beta, 1, stream);
-    if (ln_arena) lnpart = ln_arena;
+    RowReduce ln_red{.P = nchunk, .pstride = 2 * G::C, .n = 2 * G::C, .out0 = dln_gamma, .out1 = dln_beta, .n0 = G::C, .accumulate = 1};
+    float* const lnpart = reduce_rows_begin(ln_red, L.lnpart(wsf), stream);
     static const bool raised = [] {
         return hipFuncSetAttribute(reinterpret_cast<const void*>(&convnext_mlp_bwd_onepass_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                    G::LDS) == hipSuccess;
     }();
     (void)raised;
     hipLaunchKernelGGL(convnext_mlp_bwd_onepass_kernel, dim3(nchunk), dim3(G::NT), G::LDS, stream, (const bf16_t*)y1, mean, rstd, ln_gamma, ln_beta,
-                       (const bf16_t*)dout, rowscale, rows_per_group, bw_tiled, b1, (bf16_t*)dy1, part, lnpart, M, (int64_t)rpc);
+                       (const bf16_t*)dout, rowscale, rows_per_group, bw_tiled, b1, (bf16_t*)dy1, L.records(wsf), lnpart, M, (int64_t)rpc);
     const int rc = iseg_check_launch("iseg_convnext_mlp_bwd_onepass");
     if (rc != ISEG_OK) return rc;
-    if (ln_arena) iseg_deferred_push(lnpart, nchunk, 2 * G::C, 2 * G::C, dln_gamma, dln_beta, G::C, 1.f, stream);
-    else launch_reduce_rows(lnpart, nchunk, 2 * G::C, 0, 1, 2 * G::C, dln_gamma, dln_beta, G::C, 0, 1.f, 1, stream);
-    // chunk records -> their sum -> the parameter gradients (mlp_wgrad.hip)
-    launch_reduce_rows(part, nchunk, G::REC, 0, 1, G::REC, sum, nullptr, G::REC, 0, 1.f, 0, stream);
-    const int P = G::HID / FIN_ROWS;
-    float* gpart = gpart_ws;
-    float* arena = nullptr;
-    if (gamma) {
-        arena = iseg_deferred_partials((size_t)P * G::C * sizeof(float), dgamma, nullptr, 1, stream);
-        if (arena) gpart = arena;
-    }
-    hipLaunchKernelGGL(convnext_mlp_wgrad_finish_kernel, dim3(G::C / 32, G::HID / FIN_ROWS), dim3(256), 0, stream, sum, W2, b2, gamma, dW1, db1, dW2,
-                       db2, gpart, G::C);
-    if (gamma) {
-        if (arena) iseg_deferred_push(gpart, P, G::C, G::C, dgamma, nullptr, G::C, 1.f, stream);
-        else launch_reduce_rows(gpart, P, G::C, 0, 1, G::C, dgamma, nullptr, G::C, 0, 1.f, 1, stream);
-    }
-    return iseg_check_launch("iseg_convnext_mlp_bwd_onepass_finish");
+    reduce_rows_end(ln_red, stream);
+    // chunk records -> their sum -> the parameter gradients (mlp_wgrad_common.h)
+    return mlp_grads_from_records(L, wsf, W2, b2, gamma, dW1, db1, dW2, db2, dgamma, "iseg_convnext_mlp_bwd_onepass_finish", stream);
 }

@@ -784,16 +784,13 @@ extern "C" int iseg_convnext_mlp_bwd_data_ln(const void* y1, const float* mean, 
     ISEG_NEED_WORKSPACE("iseg_convnext_mlp_bwd_data_ln", ws, ws_bytes, need);
     const MlpLayerNorm ln{ln_gamma, ln_beta, const_cast<float*>(mean), const_cast<float*>(rstd), 0.f};
     // dgamma | dbeta: the workgroups' partial rows, summed in fixed order into the gradient buffers (queued when the caller defers reductions)
-    float* partials = (float*)ws;
-    float* const arena = iseg_deferred_partials(need, dln_gamma, dln_beta, 1, stream);
-    if (arena) partials = arena;
+    RowReduce red{.P = (int)mlp_bwd_blocks(M, C), .pstride = 2 * C, .n = 2 * C, .out0 = dln_gamma, .out1 = dln_beta, .n0 = C, .accumulate = 1};
+    float* const partials = reduce_rows_begin(red, ws, stream);
     const int rc = C == 96 ? launch_mlp_bwd<96, 2, 8, 3, false, true>(y1, dout, rowscale, rows_per_group, bw_tiled, b1, nullptr, nullptr, dy1, M, ln,
                                                                        stream, partials)
                            : launch_mlp_bwd<192, 1, 4, 3, false, true>(y1, dout, rowscale, rows_per_group, bw_tiled, b1, nullptr, nullptr, dy1, M, ln,
                                                                         stream, partials);
     if (rc != ISEG_OK) return rc;
-    const int blocks = (int)mlp_bwd_blocks(M, C);
-    if (arena) iseg_deferred_push(partials, blocks, 2 * C, 2 * C, dln_gamma, dln_beta, C, 1.f, stream);
-    else launch_reduce_rows(partials, blocks, 2 * C, 0, 1, 2 * C, dln_gamma, dln_beta, C, 0, 1.f, 1, stream);
+    reduce_rows_end(red, stream);
     return iseg_check_launch("iseg_convnext_mlp_bwd_data_ln");
 }

@@ -250,7 +250,7 @@ __global__ __launch_bounds__(512) void convnext_mlp_wgrad_kernel(const bf16_t* _
 
     // ---- partial results of this (chunk, hidden group) ----
     // one record per chunk: [Z | dW1T | db1 | S], so that ONE fixed-order row reduction sums everything over the chunks
-    constexpr int64_t REC = 2 * (int64_t)HID * C + HID + C;
+    constexpr int64_t REC = mlp_record_floats(C);
     float* const pz = part + (int64_t)chunk * REC;
     float* const pw = pz + (int64_t)HID * C;
     float* const pb = pw + (int64_t)HID * C;
@@ -318,13 +318,11 @@ int launch_wgrad(const void* y, const float* mean, const float* rstd, const floa
     return iseg_check_launch("iseg_convnext_mlp_wgrad");
 }
 
-size_t wgrad_ws_floats(int C, int64_t M, int* nchunk_out) {
+MlpGradWs wgrad_ws(int C, int64_t M) {
     int nchunk;
     if (C == 96) rows_per_chunk_for<96>(M, &nchunk);
     else rows_per_chunk_for<192>(M, &nchunk);
-    if (nchunk_out) *nchunk_out = nchunk;
-    const size_t rec = 2 * 4 * (size_t)C * C + 4 * C + C;      // [Z | dW1T | db1 | S]
-    return (size_t)(nchunk + 1) * rec + (size_t)(4 * C / FIN_ROWS) * C;      // chunk records, their sum, the layer-scale partials
+    return {C, nchunk, false};
 }
 
 }  // namespace
@@ -332,8 +330,8 @@ size_t wgrad_ws_floats(int C, int64_t M, int* nchunk_out) {
 extern "C" size_t iseg_convnext_mlp_wgrad_workspace_bytes(int64_t M, int C) {
     if (!(C == 96 || C == 192) || M <= 0) return 0;
     // C = 96: the one-pass kernel (mlp_bwd_onepass.hip) leaves the same records in 256 chunks and is sized by this function too: the larger need
-    size_t floats = wgrad_ws_floats(C, M, nullptr);
-    if (C == 96 && onepass_ws_floats(M, nullptr) > floats) floats = onepass_ws_floats(M, nullptr);
+    size_t floats = wgrad_ws(C, M).floats();
+    if (C == 96 && onepass_ws(M).floats() > floats) floats = onepass_ws(M).floats();
     return floats * sizeof(float);
 }
 
@@ -349,33 +347,11 @@ extern "C" int iseg_convnext_mlp_wgrad(const void* y, const float* mean, const f
                  "iseg_convnext_mlp_wgrad: the row factor must be constant inside 64-row tiles (rows_per_group = %lld)", (long long)rows_per_group);
     ISEG_REQUIRE((((uintptr_t)y | (uintptr_t)dout | (uintptr_t)bw_tiled | (uintptr_t)ln_gamma | (uintptr_t)ln_beta) & 15) == 0,
                  "iseg_convnext_mlp_wgrad: operands must be 16-byte aligned");
-    int nchunk;
-    wgrad_ws_floats(C, M, &nchunk);
     const size_t need = iseg_convnext_mlp_wgrad_workspace_bytes(M, C);
     ISEG_NEED_WORKSPACE("iseg_convnext_mlp_wgrad", ws, ws_bytes, need);
     float* const wsf = (float*)ws;
     int rc = C == 96 ? launch_wgrad<96>(y, mean, rstd, ln_gamma, ln_beta, dout, rowscale, rows_per_group, bw_tiled, b1, wsf, M, stream)
                      : launch_wgrad<192>(y, mean, rstd, ln_gamma, ln_beta, dout, rowscale, rows_per_group, bw_tiled, b1, wsf, M, stream);
     if (rc != ISEG_OK) return rc;
-    const int HID = 4 * C;
-    const int64_t rec = 2 * (int64_t)HID * C + HID + C;
-    float* part = wsf;
-    float* sum = part + (int64_t)nchunk * rec;
-    float* gpart_ws = sum + rec;
-    // chunk records -> their sum: the fixed-order two-level row reduction every parameter gradient uses (common.h)
-    launch_reduce_rows(part, nchunk, rec, 0, 1, rec, sum, nullptr, rec, 0, 1.f, 0, stream);
-    const int P = HID / FIN_ROWS;
-    float* gpart = gpart_ws;
-    float* arena = nullptr;
-    if (gamma) {
-        arena = iseg_deferred_partials((size_t)P * C * sizeof(float), dgamma, nullptr, 1, stream);      // (common.h: deferred reductions)
-        if (arena) gpart = arena;
-    }
-    hipLaunchKernelGGL(convnext_mlp_wgrad_finish_kernel, dim3(C / 32, HID / FIN_ROWS), dim3(256), 0, stream, sum, W2, b2, gamma,
-                       dW1, db1, dW2, db2, gpart, C);
-    if (gamma) {
-        if (arena) iseg_deferred_push(gpart, P, C, C, dgamma, nullptr, C, 1.f, stream);
-        else launch_reduce_rows(gpart, P, C, 0, 1, C, dgamma, nullptr, C, 0, 1.f, 1, stream);
-    }
-    return iseg_check_launch("iseg_convnext_mlp_wgrad_finish");
+    return mlp_grads_from_records(wgrad_ws(C, M), wsf, W2, b2, gamma, dW1, db1, dW2, db2, dgamma, "iseg_convnext_mlp_wgrad_finish", stream);
 }

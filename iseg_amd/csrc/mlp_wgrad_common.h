@@ -1,5 +1,6 @@
 // Shared by the weight-gradient kernels of the fused ConvNeXt MLP (mlp_wgrad.hip, mlp_bwd_onepass.hip): the 16x16x32 MFMA wrapper, the
-// transposed B fragment of a row-major LDS tile, and the finish launch that books the parameter gradients from the chunk-summed record.
+// transposed B fragment of a row-major LDS tile, the layout of the chunk-record workspace, and the tail both launchers end on: records -> their
+// sum -> the finish launch that books the parameter gradients from the chunk-summed record -> the layer-scale gradient's second stage.
 #pragma once
 #include "common.h"
 
@@ -82,8 +83,41 @@ __global__ __launch_bounds__(256) void convnext_mlp_wgrad_finish_kernel(const fl
     }
 }
 
-// Row chunks and workspace of the one-pass kernel (mlp_bwd_onepass.hip, C = 96).  It leaves the same chunk records as convnext_mlp_wgrad_kernel,
-// only more of them, so ONE size function answers for both launchers at C = 96 (iseg_convnext_mlp_wgrad_workspace_bytes: the larger need).
+// floats of one chunk record [Z | dW1T | db1 | S]: what a producer workgroup leaves per row chunk, and what the finish kernel reads summed
+constexpr int64_t mlp_record_floats(int C) {
+    const int64_t HID = 4 * C;
+    return 2 * HID * C + HID + C;
+}
+
+// The producers' workspace: [records | sum | layer-scale partials | LayerNorm partial rows] (the last for the one-pass kernel only)
+struct MlpGradWs {
+    int C, nchunk;
+    bool with_ln;
+    int64_t rec() const { return mlp_record_floats(C); }
+    int gparts() const { return 4 * C / FIN_ROWS; }      // rows the finish launch leaves for the layer-scale gradient
+    float* records(float* ws) const { return ws; }
+    float* sum(float* ws) const { return ws + nchunk * rec(); }
+    float* gpart(float* ws) const { return sum(ws) + rec(); }
+    float* lnpart(float* ws) const { return gpart(ws) + (int64_t)gparts() * C; }
+    size_t floats() const { return (size_t)((nchunk + 1) * rec() + (int64_t)gparts() * C + (with_ln ? (int64_t)nchunk * 2 * C : 0)); }
+};
+
+// The tail of both producers: chunk records -> their sum (the fixed-order row reduction of common.h) -> the finish launch -> dgamma, queued
+// when the caller defers reductions.  `who` names the entry point in a launch error.
+inline int mlp_grads_from_records(const MlpGradWs& L, float* ws, const float* W2, const float* b2, const float* gamma, float* dW1, float* db1,
+                                  float* dW2, float* db2, float* dgamma, const char* who, hipStream_t stream) {
+    const int C = L.C, HID = 4 * C;
+    launch_reduce_rows({.partials = L.records(ws), .P = L.nchunk, .pstride = L.rec(), .n = L.rec(), .out0 = L.sum(ws), .n0 = L.rec()}, stream);
+    RowReduce red{.P = L.gparts(), .pstride = C, .n = C, .out0 = dgamma, .n0 = C, .accumulate = 1};
+    float* const gpart = reduce_rows_begin(red, L.gpart(ws), stream, gamma != nullptr);
+    hipLaunchKernelGGL(convnext_mlp_wgrad_finish_kernel, dim3(C / 32, HID / FIN_ROWS), dim3(256), 0, stream, L.sum(ws), W2, b2, gamma, dW1, db1, dW2,
+                       db2, gpart, C);
+    if (gamma) reduce_rows_end(red, stream);
+    return iseg_check_launch(who);
+}
+
+// Row chunks of the one-pass kernel (mlp_bwd_onepass.hip, C = 96).  It leaves the same chunk records as convnext_mlp_wgrad_kernel, only more
+// of them, so ONE size function answers for both launchers at C = 96 (iseg_convnext_mlp_wgrad_workspace_bytes: the larger need).
 // One workgroup per CU in ONE resident round (the rule of mlp_wgrad.hip with one hidden group): 256 chunks of whole 64-row tiles.
 inline int onepass_rows_per_chunk(int64_t M, int* nchunk) {
     int64_t rpc = (M + 255) / 256;
@@ -93,14 +127,10 @@ inline int onepass_rows_per_chunk(int64_t M, int* nchunk) {
     return (int)rpc;
 }
 
-// chunk records, their sum, the layer-scale partials of the finish launch, the LayerNorm partial rows
-inline size_t onepass_ws_floats(int64_t M, int* nchunk_out) {
-    constexpr int C = 96, HID = 4 * C;
-    constexpr size_t REC = 2 * (size_t)HID * C + HID + C;
+inline MlpGradWs onepass_ws(int64_t M) {
     int nchunk;
     onepass_rows_per_chunk(M, &nchunk);
-    if (nchunk_out) *nchunk_out = nchunk;
-    return (size_t)(nchunk + 1) * REC + (size_t)(HID / FIN_ROWS) * C + (size_t)nchunk * 2 * C;
+    return {96, nchunk, true};
 }
 
 }  // namespace

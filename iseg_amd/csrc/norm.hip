@@ -912,7 +912,8 @@ static int layernorm_bwd_launch(const void* dy, const int32_t* dy_index, const v
                                mean, rstd, (T*)dx, (const T*)dx_add, parts, rows, C);
         });
         if (rc != ISEG_OK) return rc;
-        launch_reduce_rows(parts, nb, 2 * C, 0, 1, 2 * C, dgamma, dbeta, C, 0, 1.f, accumulate_param_grads, stream);
+        launch_reduce_rows({.partials = parts, .P = nb, .pstride = 2 * C, .n = 2 * C, .out0 = dgamma, .out1 = dbeta, .n0 = C,
+                            .accumulate = accumulate_param_grads}, stream);
         return iseg_check_launch("iseg_layernorm_bwd");
     }
     const int lpr = ln_lanes_per_row(C);
@@ -921,9 +922,8 @@ static int layernorm_bwd_launch(const void* dy, const int32_t* dy_index, const v
     const bool posted = post.colscale || post.rowscale;      // the column sums need the finish kernel: summed here, not by the deferred queue
     const size_t need = (size_t)blocks * 2 * C * sizeof(float) + (posted ? (size_t)2 * C * sizeof(float) : 0);
     ISEG_NEED_WORKSPACE("iseg_layernorm_bwd", ws, ws_bytes, need);
-    float* partials = (float*)ws;
-    float* const arena = posted ? nullptr : iseg_deferred_partials(need, dgamma, dbeta, accumulate_param_grads, stream);      // (see common.h: deferred reductions)
-    if (arena) partials = arena;
+    RowReduce red{.P = blocks, .pstride = 2 * C, .n = 2 * C, .out0 = dgamma, .out1 = dbeta, .n0 = C, .accumulate = accumulate_param_grads};
+    float* const partials = reduce_rows_begin(red, ws, stream, !posted);      // (see common.h: deferred reductions)
     const size_t lds = 2 * (size_t)C * sizeof(float);
     const int cpl = (C / 8 + lpr - 1) / lpr;
     const int rc = by_dtype(dtype, "iseg_layernorm_bwd", [&](auto t) {
@@ -945,11 +945,10 @@ static int layernorm_bwd_launch(const void* dy, const int32_t* dy_index, const v
     if (rc != ISEG_OK) return rc;
     if (posted) {
         float* sums = partials + (size_t)blocks * 2 * C;
-        launch_reduce_rows(partials, blocks, 2 * C, 0, 1, 2 * C, sums, nullptr, 2 * C, 0, 1.f, 0, stream);
+        launch_reduce_rows({.partials = partials, .P = blocks, .pstride = 2 * C, .n = 2 * C, .out0 = sums, .n0 = 2 * C}, stream);
         hipLaunchKernelGGL(ln_post_finish_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, sums, post.colscale, gamma, beta, dgamma, dbeta,
                            dcolscale, C);
-    } else if (arena) iseg_deferred_push(partials, blocks, 2 * C, 2 * C, dgamma, dbeta, C, 1.f, stream);
-    else launch_reduce_rows(partials, blocks, 2 * C, 0, 1, 2 * C, dgamma, dbeta, C, 0, 1.f, accumulate_param_grads, stream);
+    } else reduce_rows_end(red, stream);
     return iseg_check_launch("iseg_layernorm_bwd");
 }
 
@@ -996,7 +995,7 @@ extern "C" int iseg_bn_stats(const void* x, int64_t ldx, float* packed, int64_t 
         hipLaunchKernelGGL((bn_stats_kernel<T>), dim3(blocks), dim3(256), lds, stream, (const T*)x, ldx, (float*)ws, rows, C, packed + 2 * C);
     });
     if (rc != ISEG_OK) return rc;
-    launch_reduce_rows((const float*)ws, blocks, 2 * C, 0, 1, 2 * C, packed, nullptr, 2 * C, 0, 1.f, 0, stream);
+    launch_reduce_rows({.partials = (const float*)ws, .P = blocks, .pstride = 2 * C, .n = 2 * C, .out0 = packed, .n0 = 2 * C}, stream);
     return iseg_check_launch("iseg_bn_stats");
 }
 
@@ -1070,7 +1069,7 @@ static int bn_bwd_reduce_launch(const void* dy, int64_t lddy, const void* x, int
                            mean, rstd, (float*)ws, rows, C, relu, re_gamma, re_beta);
     });
     if (rc != ISEG_OK) return rc;
-    launch_reduce_rows((const float*)ws, blocks, 2 * C, 0, 1, 2 * C, sums, nullptr, 2 * C, 0, 1.f, 0, stream);
+    launch_reduce_rows({.partials = (const float*)ws, .P = blocks, .pstride = 2 * C, .n = 2 * C, .out0 = sums, .n0 = 2 * C}, stream);
     return iseg_check_launch("iseg_bn_bwd_reduce");
 }
 

@@ -430,7 +430,7 @@ extern "C" int iseg_relu_dwconv3_stats(const void* x, const float* w, void* z, f
                            packed ? part : nullptr, packed ? packed + 2 * C : nullptr, g, t);
     });
     if (rc != ISEG_OK) return rc;
-    if (packed) launch_reduce_rows(part, (int)sc_parts(g, t), 2 * (int64_t)C, 0, 1, 2 * (int64_t)C, packed, nullptr, 2 * (int64_t)C, 0, 1.f, 0, stream);
+    if (packed) launch_reduce_rows({.partials = part, .P = (int)sc_parts(g, t), .pstride = 2 * (int64_t)C, .n = 2 * (int64_t)C, .out0 = packed, .n0 = 2 * (int64_t)C}, stream);
     return iseg_check_launch("iseg_relu_dwconv3_stats");
 }
 
@@ -483,6 +483,7 @@ extern "C" int iseg_bnfold_dwconv3_relu_bwd(const void* D, const void* z, const 
                            inv_n, train, (T*)dx, part, g, t);
     });
     if (rc != ISEG_OK) return rc;
-    launch_reduce_rows(part, (int)sc_parts(g, t), 9 * (int64_t)C, 0, 1, 9 * (int64_t)C, dw, nullptr, 9 * (int64_t)C, 0, 1.f, 1, stream);
+    launch_reduce_rows({.partials = part, .P = (int)sc_parts(g, t), .pstride = 9 * (int64_t)C, .n = 9 * (int64_t)C, .out0 = dw, .n0 = 9 * (int64_t)C,
+                        .accumulate = 1}, stream);
     return iseg_check_launch("iseg_bnfold_dwconv3_relu_bwd");
 }

@@ -411,6 +411,6 @@ extern "C" int iseg_window_attention_bwd(const void* qkv, const float* table, co
                        (bf16_t*)dqkv, (float*)ws, pairs, T, heads, table_windows, scale);
     // dbias[h][i][j] = sum over the waves / heads partial groups, in group order
     const int64_t n = (int64_t)heads * T * T;
-    launch_reduce_rows((const float*)ws, waves / heads, n, 0, 1, n, dbias, nullptr, n, 0, 1.f, 0, stream);
+    launch_reduce_rows({.partials = (const float*)ws, .P = waves / heads, .pstride = n, .n = n, .out0 = dbias, .n0 = n}, stream);
     return iseg_check_launch("iseg_window_attention_bwd");
 }

@@ -317,25 +317,32 @@ class _LnMlpResidualFn(Function):
         M, C = x2.shape
         do2 = _c(dout).reshape(M, C)
         ln = (mean, rstd, ln_gamma.data, ln_beta.data)
+        dln = _LnMlpResidualFn.mlp_ln_backward(x2, do2, bw, ln, (ln_gamma, ln_beta, W1, b1, W2, b2, None), rowscale, ctx.rpg)
         dx = None
-        if K.convnext_mlp_bwd_onepass_supported(C, x2.dtype) and any(p.requires_grad for p in (W1, b1, W2, b2)):
-            # C = 96: one kernel forms the hidden tile once for the data gradient and every parameter gradient (csrc/mlp_bwd_onepass.hip)
-            dln = K.convnext_mlp_bwd_onepass(x2, do2, bw, b1.data, W2.data, b2.data, None, ln, _grad_out(ln_gamma), _grad_out(ln_beta),
-                                             _grad_out(W1), _grad_out(b1), _grad_out(W2), _grad_out(b2), None, rowscale, ctx.rpg)
-            if ctx.needs_input_grad[0]:
-                dx = K.axpby(do2, dln, 1.0, 1.0, out=dln).reshape(dout.shape)      # + the skip connection's share
-            dist.grads_ready(ln_gamma, ln_beta, W1, b1, W2, b2)
-            return (dx,) + (None,) * 8
         if ctx.needs_input_grad[0]:
-            dln = K.convnext_mlp_bwd_data_ln(x2, do2, bw, b1.data, ln, _grad_out(ln_gamma), _grad_out(ln_beta), rowscale, ctx.rpg)
             dx = K.axpby(do2, dln, 1.0, 1.0, out=dln).reshape(dout.shape)      # + the skip connection's share
-        else:      # (the LayerNorm parameter gradients come out of the chain kernel's epilogue)
-            K.convnext_mlp_bwd_data_ln(x2, do2, bw, b1.data, ln, _grad_out(ln_gamma), _grad_out(ln_beta), rowscale, ctx.rpg)
-        if any(p.requires_grad for p in (W1, b1, W2, b2)):
-            K.convnext_mlp_wgrad(x2, do2, bw, b1.data, W2.data, b2.data, None, _grad_out(W1), _grad_out(b1), _grad_out(W2), _grad_out(b2), None, rowscale,
-                                 ctx.rpg, ln=ln)
         dist.grads_ready(ln_gamma, ln_beta, W1, b1, W2, b2)
         return (dx,) + (None,) * 8
+
+    @staticmethod
+    def mlp_ln_backward(rows, dout, bw, ln, params, rowscale, rows_per_group):
+        """Backward of Dense(gelu(Dense(LayerNorm(rows)))) (o gamma, o the row factor) on the fused kernels: returns the gradient of `rows` and
+        books the gradients of params = (ln_gamma, ln_beta, w1, b1, w2, b2, gamma), gamma possibly None; ln = (mean, rstd, ln_gamma, ln_beta) as
+        saved by the forward pass, `bw` the tiled weight images.  Nothing [M, 4C]-shaped reaches HBM: one kernel carries the data gradient
+        through the recomputed hidden tile and, in its epilogue, through the LayerNorm backward (which books dln_gamma / dln_beta); a second one
+        (csrc/mlp_wgrad.hip) recomputes the tile again and contracts over the rows for every parameter gradient of the MLP.  Where the one-pass
+        kernel exists (C = 96, csrc/mlp_bwd_onepass.hip) and an MLP parameter wants its gradient, the two are ONE kernel that forms the tile once."""
+        ln_gamma, ln_beta, w1, b1, w2, b2, gamma = params
+        gam, dgam = (gamma.data, _grad_out(gamma)) if gamma is not None else (None, None)
+        mlp_grads = any(q is not None and q.requires_grad for q in (w1, b1, w2, b2, gamma))
+        if mlp_grads and K.convnext_mlp_bwd_onepass_supported(rows.shape[1], rows.dtype):
+            return K.convnext_mlp_bwd_onepass(rows, dout, bw, b1.data, w2.data, b2.data, gam, ln, _grad_out(ln_gamma), _grad_out(ln_beta),
+                                              _grad_out(w1), _grad_out(b1), _grad_out(w2), _grad_out(b2), dgam, rowscale, rows_per_group)
+        drows = K.convnext_mlp_bwd_data_ln(rows, dout, bw, b1.data, ln, _grad_out(ln_gamma), _grad_out(ln_beta), rowscale, rows_per_group)
+        if mlp_grads:
+            K.convnext_mlp_wgrad(rows, dout, bw, b1.data, w2.data, b2.data, gam, _grad_out(w1), _grad_out(b1), _grad_out(w2), _grad_out(b2), dgam,
+                                 rowscale, rows_per_group, ln=ln)
+        return drows
 
 
 def ln_mlp_residual_supported(x, params, drop_path_mask=None):
@@ -1781,25 +1788,9 @@ class _ConvNeXtBlockFn(Function):
         do2 = _c(dout).reshape(M, C)
         cdt = xc.dtype
         if ctx.ln_on_load:
-            # round 3: nothing [M, 4C]-shaped reaches HBM in the backward pass either.  One kernel carries the data gradient through the
-            # recomputed hidden tile and, in its epilogue, through the LayerNorm backward; a second one (workgroups own 128 hidden units and a
-            # chunk of rows) recomputes it again and contracts over the rows for every parameter gradient of the MLP; the drop-path row factor
-            # and the column sums of dbr ride both (csrc/mlp_wgrad.hip) -- replaces rowscale + colsum + chain + two weight-gradient GEMMs + their
-            # split-K sums + layerscale_grads
-            # At C = 96 the two are ONE kernel that forms the hidden tile once (csrc/mlp_bwd_onepass.hip); C = 192 keeps the pair.
-            y1m, ln = y1.reshape(M, C), (mean, rstd, p.ln_gamma.data, p.ln_beta.data)
-            mlp_grads = any(q is not None and q.requires_grad for q in (p.w1, p.b1, p.w2, p.b2, p.gamma))
-            if mlp_grads and K.convnext_mlp_bwd_onepass_supported(C, cdt):
-                dy1 = K.convnext_mlp_bwd_onepass(y1m, do2, h, p.b1.data, p.w2.data, p.b2.data, p.gamma.data if p.gamma is not None else None, ln,
-                                                 _grad_out(p.ln_gamma), _grad_out(p.ln_beta), _grad_out(p.w1), _grad_out(p.b1), _grad_out(p.w2),
-                                                 _grad_out(p.b2), _grad_out(p.gamma) if p.gamma is not None else None, dp_mask, H * W)
-                mlp_grads = False
-            else:
-                dy1 = K.convnext_mlp_bwd_data_ln(y1m, do2, h, p.b1.data, ln, _grad_out(p.ln_gamma), _grad_out(p.ln_beta), dp_mask, H * W)
-            if mlp_grads:
-                K.convnext_mlp_wgrad(y1m, do2, h, p.b1.data, p.w2.data, p.b2.data, p.gamma.data if p.gamma is not None else None,
-                                     _grad_out(p.w1), _grad_out(p.b1), _grad_out(p.w2), _grad_out(p.b2),
-                                     _grad_out(p.gamma) if p.gamma is not None else None, dp_mask, H * W, ln=ln)
+            ln = (mean, rstd, p.ln_gamma.data, p.ln_beta.data)
+            dy1 = _LnMlpResidualFn.mlp_ln_backward(y1.reshape(M, C), do2, h, ln, (p.ln_gamma, p.ln_beta, p.w1, p.b1, p.w2, p.b2, p.gamma), dp_mask,
+                                                    H * W)
             del h
         else:
             dy2 = _ConvNeXtBlockFn._mlp_backward_with_hidden(ctx, p, do2, y2, h, g, dp_mask, H, W, C, M, cdt, xc)

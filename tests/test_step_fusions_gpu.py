@@ -103,11 +103,13 @@ def test_bias_gradient_on_the_weight_gradient_gemm(cuda, M, Kd, N):
 def test_deferred_gradient_reductions_match_immediate_ones(cuda):
     """K.deferred_reductions: LayerNorm / depthwise / bias gradient reductions queued and run by one launch give the same gradients (same
     summation order inside and across workgroups: BIT-identical), also
-    when two reductions hit the same gradient (conflict -> early flush) and when the arena is small"""
+    when two reductions hit the same gradient (conflict -> early flush) and when the arena is small.  Every launcher that can queue its
+    second stage is driven here (GRN: test_grn_parameter_gradients_through_the_deferred_queue): the layer-scale gradients in both forms at
+    (4C, C) = (384, 96), and the fused MLP backward kernels at C = 96 over 520 rows (three row chunks, the last one 8 rows: a ragged tile)"""
     from iseg_amd import kernels as K
 
     torch.manual_seed(0)
-    flat = torch.zeros(200000, device="cuda")
+    flat = torch.zeros(320000, device="cuda")
     views = {"lng": flat[0:384], "lnb": flat[512:896], "dw": flat[1024:1024 + 49 * 96], "db": flat[8192:8192 + 96], "cb": flat[9000:9000 + 192],
              "lng2": flat[10240:10240 + 96], "lnb2": flat[10496:10496 + 96]}
     x = torch.randn(3000, 384, device="cuda").to(torch.bfloat16)
@@ -123,6 +125,30 @@ def test_deferred_gradient_reductions_match_immediate_ones(cuda):
     di = torch.randn(2, 32, 32, 96, device="cuda").to(torch.bfloat16)
     cs = torch.randn(5000, 192, device="cuda").to(torch.bfloat16)
     outside = torch.zeros(192, device="cuda")
+    Cm, Hm, Mm = 96, 384, 520
+    sizes = {"dln_gamma": Cm, "dln_beta": Cm, "dW1": Cm * Hm, "db1": Hm, "dW2": Hm * Cm, "db2": Cm, "dgamma": Cm}
+    used = [12288]
+
+    def take(*names):      # the next views of the flat buffer, 256-byte aligned
+        out = []
+        for n in names:
+            out.append(flat[used[0]:used[0] + sizes[n]])
+            used[0] += (sizes[n] + 63) // 64 * 64
+        return out
+
+    ls_t, ls_s = take("dW2", "dgamma", "db2"), take("dW2", "dgamma", "db2")
+    chain, wg = take("dln_gamma", "dln_beta"), take("dW1", "db1", "dW2", "db2", "dgamma")
+    op = take("dln_gamma", "dln_beta", "dW1", "db1", "dW2", "db2", "dgamma")
+    assert used[0] <= flat.numel()
+    Z, slabs = torch.randn(Hm, Cm, device="cuda"), torch.randn(3, Hm + 1, Cm, device="cuda") * 0.5
+    W1, W2 = torch.randn(Cm, Hm, device="cuda") * 0.05, torch.randn(Hm, Cm, device="cuda") * 0.05
+    b1, b2, S = torch.randn(Hm, device="cuda") * 0.1, torch.randn(Cm, device="cuda") * 0.1, torch.randn(Cm, device="cuda")
+    gam, lng, lnb = torch.rand(Cm, device="cuda") + 0.5, torch.rand(Cm, device="cuda") + 0.5, torch.randn(Cm, device="cuda") * 0.2
+    y1 = torch.randn(Mm, Cm, device="cuda").to(torch.bfloat16)
+    do = (torch.randn(Mm, Cm, device="cuda") * 0.1).to(torch.bfloat16)
+    _, mean1, rstd1 = K.layernorm_fwd(y1, lng, lnb, 1e-6)
+    ln = (mean1, rstd1, lng, lnb)
+    _, bw = K.convnext_mlp_prep(W1, W2, gam, backward=True)
 
     def run():
         flat.zero_()
@@ -134,6 +160,11 @@ def test_deferred_gradient_reductions_match_immediate_ones(cuda):
         K.layernorm_bwd(dys, xs, gs, means, rstds, views["lng2"], views["lnb2"])
         K.layernorm_bwd(dys, xs, gs, means, rstds, views["lng2"], views["lnb2"])    # same outputs again: conflict with the queued one
         K.colsum(cs, 192, 0, 1, 5000, 192, views["cb"], accumulate=True)
+        K.layerscale_grads(Z, W2, b2, gam, S, ls_t[0].view(Hm, Cm), ls_t[1], ls_t[2])
+        K.layerscale_grads_slabs(slabs, 3, W2, b2, gam, ls_s[0].view(Hm, Cm), ls_s[1], ls_s[2])
+        K.convnext_mlp_bwd_data_ln(y1, do, bw, b1, ln, chain[0], chain[1])
+        K.convnext_mlp_wgrad(y1, do, bw, b1, W2, b2, gam, wg[0].view(Cm, Hm), wg[1], wg[2].view(Hm, Cm), wg[3], wg[4], ln=ln)
+        K.convnext_mlp_bwd_onepass(y1, do, bw, b1, W2, b2, gam, ln, op[0], op[1], op[2].view(Cm, Hm), op[3], op[4].view(Hm, Cm), op[5], op[6])
         return flat.clone(), outside.clone()
 
     ref, ref_out = run()

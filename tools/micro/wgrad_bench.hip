@@ -5,8 +5,9 @@
 #include <stdarg.h>
 extern "C" void iseg_set_error(const char* fmt, ...) { va_list a; va_start(a, fmt); vfprintf(stderr, fmt, a); va_end(a); fputc('\n', stderr); }
 int iseg_check_launch(const char* what) { hipError_t e = hipGetLastError(); if (e != hipSuccess) { fprintf(stderr, "%s: %s\n", what, hipGetErrorString(e)); return -2; } return 0; }
-float* iseg_deferred_partials(size_t, const float*, const float*, int, hipStream_t) { return nullptr; }
-void iseg_deferred_push(const float*, int, int64_t, int64_t, float*, float*, int64_t, float, hipStream_t) {}
+#include "../../iseg_amd/csrc/common.h"
+float* reduce_rows_begin(RowReduce& r, void* ws, hipStream_t, bool) { r.partials = (float*)ws; return (float*)ws; }      // (no deferred queue here)
+void reduce_rows_end(const RowReduce& r, hipStream_t s) { launch_reduce_rows(r, s); }
 #include "../../iseg_amd/csrc/mlp_wgrad.hip"
 
 int main(int argc, char** argv) {
