@@ -1341,6 +1341,57 @@ int iseg_token_sample_splits(int64_t batch, int64_t V);
 size_t iseg_token_sample_scratch_bytes(int64_t batch, int64_t V, int mode, int k, int splits);
 int iseg_token_sample(const void* logits, int64_t ld, const float* u, int32_t* tokens, void* ws, size_t ws_bytes, int64_t batch, int64_t V, int mode,
                       int k, float p, float temperature, int splits, int dtype, iseg_stream_t stream);
+/* One step of keras_nlp.samplers.BeamSampler (GemmaCausalLM.compile(sampler=BeamSampler(num_beams=2)) in the class docstring of
+ * nlp/gemma/gemma_causal.py) without a [rows, V] intermediate and without a second cache.  rows = groups * nb: row g * nb + j is beam j of batch
+ * row g, 1 <= nb <= 16.
+ *
+ * iseg_beam_select: logits [rows, V] (bf16 or fp32, row pitch ld >= V elements), log_probs fp32 [rows] (the running scores), T = temperature > 0.
+ *   score      of (beam j, token v) of a group, in exact arithmetic:  (x[j, v] - max_u x[j, u]) / T - log sum_u exp((x[j, u] - max x[j]) / T)
+ *              + log_probs[j], evaluated directly (not as log(softmax)): a candidate whose fp32 softmax underflows to 0 keeps its true score
+ *              and its place in the order, where the reference gets -inf and an arbitrary one.
+ *   selection  per group the nb best of the nb * V candidates with flat index j * V + v:  parents[g nb + r] = j, tokens[g nb + r] = v,
+ *              new_log_probs[g nb + r] = the score, r = 0 .. nb - 1 sorted by score descending, ties by flat index ascending.  Within one row the
+ *              score order is the order of the STORED logits (value descending, then index ascending: order_keys.h), and a row's candidates
+ *              are its nb first in that order; the rows' candidates are then ranked by their rounded fp32 scores.
+ *   non-finite a -inf logit scores -inf.  A row that holds a NaN or a +inf logit, or -inf alone, scores NaN throughout (as log_softmax does), and so
+ *              does a row whose log_probs is NaN; NaN ranks above every number, as in torch.topk, so such a row's candidates are its tokens
+ *              0 .. min(nb, V) - 1.  Whatever the input, 0 <= parents < nb and 0 <= tokens < V, and the nb pairs of a group are distinct.
+ *   accuracy   the exponent (x - m) log2(e) / T is formed in fp64 and split into an fp32 head and tail, v_exp_f32 takes the head and the tail
+ *              enters linearly: a weight is off by at most 2 * 2^-23 of itself whatever its exponent.  Weights are summed in fp64 in a fixed
+ *              order; the score is formed in fp64 and rounded once.  |score error| <= 2 * 2^-23 + 2^-24 |score|.
+ * Pass 1, one workgroup per (row, chunk of whole 2048-element tiles), reads the logits ONCE: the chunk's nb first entries of the order with
+ * their indices and, relative to the chunk's own maximum, the sum of the weights.  Pass 2, one workgroup per group and one wavefront per row:
+ * merges the row's chunk records in a fixed order (each sum scaled by exp((m_chunk - m_row) / T), as the decode merge), takes the row's nb first
+ * entries, forms their scores, and the first wavefront selects nb of the <= nb * nb candidates.  No atomics across workgroups: a second call
+ * returns the same bits.  128-bit loads when logits is 16-byte aligned and ld * element size is a multiple of 16, scalar loads otherwise.
+ * splits: 0 = the launcher's plan, a function of (rows, V) alone that iseg_beam_select_splits returns; a positive value is taken, clipped to
+ * the number of 2048-element tiles that hold an element.  The scratch buffer (8-byte aligned) holds iseg_beam_select_scratch_bytes (same
+ * `splits` argument); a smaller one returns ISEG_ERR_WORKSPACE.  Supported (iseg_beam_select_supported): bf16 or fp32, 1 <= V <= 2^20,
+ * 1 <= nb <= 16; anything else returns ISEG_ERR_UNSUPPORTED.  rows that are no multiple of nb, a temperature <= 0 or not finite and ld < V
+ * return ISEG_ERR_ARG.  All before any memory is touched.
+ *
+ * iseg_beam_reorder: keras_nlp's gather_beams by `parents` (int32 [groups * nb], device memory) IN PLACE, on the cache and on the prompt.
+ *   cache      [groups * nb, planes, Sc, row_bytes] bytes, contiguous (planes = num_layers * 2, Sc positions of its own, which need not be
+ *              the prompt's S; row_bytes = nkv * head_dim * element size, a multiple of 16; base 16-byte aligned):  cache[g nb + j, p, s] = old cache[g nb + parents[g nb + j], p, s] for s < len only;
+ *              positions >= len are neither read nor written.  The gather moves data between the beams of one group at identical
+ *              coordinates, so one thread owns a 16-byte column across the nb beams: it loads the source of every j with parents[j] != j, then
+ *              stores them.  No other thread touches those addresses: no second cache, no barrier, any mapping (several children of one
+ *              parent included).  A group of identity parents costs no access to the cache at all.  cache NULL or len 0: skipped.
+ *   prompt     [groups * nb, S] ids (int32 or int64, row pitch ld_prompt elements), mask [groups * nb, S] bytes (row pitch ld_mask), tokens
+ *              int32 [groups * nb]:  prompt[g nb + j, :] = old prompt[g nb + parents[g nb + j], :], then prompt[r, index] = tokens[r] unless
+ *              mask[r, index] marks a user token (the mask is not gathered: the beams of a group share it).  One thread owns a column of
+ *              the group here too.  prompt NULL: skipped.
+ * A group with a parent outside [0, nb) is left untouched, cache and prompt.  Grid-stride launches; no host read.  nb outside 1 .. 16, a
+ * row_bytes that is no multiple of 16, a misaligned cache, len outside [0, Sc], index outside [0, S) and a row pitch below S return
+ * ISEG_ERR_ARG, before any memory is touched. */
+int iseg_beam_select_supported(int64_t V, int nb, int dtype);
+int iseg_beam_select_splits(int64_t rows, int64_t V);
+size_t iseg_beam_select_scratch_bytes(int64_t rows, int64_t V, int nb, int splits);
+int iseg_beam_select(const void* logits, int64_t ld, const float* log_probs, int32_t* parents, int32_t* tokens, float* new_log_probs, void* ws,
+                     size_t ws_bytes, int64_t rows, int64_t V, int nb, float temperature, int splits, int dtype, iseg_stream_t stream);
+int iseg_beam_reorder(void* cache, int64_t planes, int64_t Sc, int64_t row_bytes, int64_t len, void* prompt, int64_t S, int64_t ld_prompt,
+                      const uint8_t* mask, int64_t ld_mask, const int32_t* tokens, int64_t index, int ids_dtype, const int32_t* parents, int64_t groups,
+                      int nb, iseg_stream_t stream);
 /* The language-model head's loss without a [tokens, vocab] tensor: SparseCategoricalCrossentropy(from_logits=True) and
  * SparseCategoricalAccuracy of nlp/gemma/gemma_causal.py:165-172 on the logits Z = X E^T (X [M, d] hidden states, E [V, d] the tied table).  The
  * caller cuts the vocabulary into chunks [v0, v0 + w) of any width w >= 1, has iseg_gemm write Z_c = X E[v0 : v0 + w]^T [M, w] in FP32 (row pitch

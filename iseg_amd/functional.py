@@ -3713,6 +3713,120 @@ def sample_tokens(logits, u, *, mode, k=0, p=1.0, temperature=1.0, splits=0):
         return K.token_sample(logits, _c(u), _SAMPLE_MODES[mode], k, p, temperature, splits)
 
 
+BEAM_MAX_BEAMS = 16
+
+
+def beam_fused():
+    """True where a beam step on device tensors takes the kernels of csrc/beam_search.hip: ISEG_BEAM_FUSED unset or not "0" """
+    return os.environ.get("ISEG_BEAM_FUSED", "1") != "0"
+
+
+def _beam_select_composed(logits, log_probs, nb, temperature):
+    """keras_nlp's op sequence in plain torch: the fp32 log-softmax of logits / T plus the running score, [B, nb V], top-k.  The order is pinned
+    down as the kernel's: score descending, ties by flat index ascending, NaN above every number"""
+    R, V = logits.shape
+    B, N = R // nb, nb * V
+    scores = (torch.log_softmax(logits.to(torch.float32) / temperature, dim=-1) + log_probs[:, None]).reshape(B, N)
+    key = torch.nan_to_num(scores, nan=math.inf, posinf=math.inf, neginf=-math.inf)
+    nth = torch.topk(key, nb, dim=-1).values[:, -1:]
+    # everything above the nb-th value, then that value's ties, each by index: all ranks are distinct, so this top-k is a set
+    rank = (key > nth).to(torch.int64) * (2 * N) + (key == nth).to(torch.int64) * N + (N - 1 - torch.arange(N, device=logits.device))
+    flat = torch.topk(rank, nb, dim=-1).indices
+    flat = flat.gather(-1, torch.sort(key.gather(-1, flat), dim=-1, descending=True, stable=True).indices)
+    return ((flat // V).to(torch.int32).reshape(R), (flat % V).to(torch.int32).reshape(R), scores.gather(-1, flat).reshape(R))
+
+
+def beam_select(logits, log_probs, num_beams, temperature=1.0, splits=0):
+    """One selection of keras_nlp.samplers.BeamSampler.  logits [B nb, V] or a [B nb, 1, V] view (row b nb + j is beam j of batch row b), log_probs
+    fp32 [B nb] the beams' running scores -> (parents int32, tokens int32, new log_probs fp32), each [B nb]: per batch row the nb best of the
+    nb V candidates (beam j, token v) with score log_softmax(logits[j] / temperature)[v] + log_probs[j], sorted by score descending, ties by
+    flat index j V + v ascending; parents are beam indices inside the batch row.  NaN ranks above every number; a row with a NaN or +inf logit
+    scores NaN throughout; a -inf logit scores -inf (include/iseg_hip.h has the full statement).
+    Device tensors in bf16 or fp32 with V <= 2^20 take the kernels of csrc/beam_search.hip (two launches, the logits read once, no [B nb, V]
+    intermediate); CPU tensors, other dtypes and ISEG_BEAM_FUSED=0 the composed route, the reference's op sequence in torch.  Inference only."""
+    if logits.requires_grad:
+        raise RuntimeError("beam_select: beam search is inference only (the logits require grad)")
+    if logits.dim() == 3 and logits.shape[1] == 1:
+        logits = logits[:, 0]
+    if isinstance(num_beams, bool) or not isinstance(num_beams, int) or not 1 <= num_beams <= BEAM_MAX_BEAMS:
+        raise ValueError(f"beam_select: num_beams is an integer in 1 .. {BEAM_MAX_BEAMS}, got {num_beams!r}")
+    if logits.dim() != 2 or log_probs.dim() != 1 or log_probs.shape[0] != logits.shape[0] or logits.shape[0] % num_beams:
+        raise ValueError(f"beam_select: logits is [B * {num_beams}, V] or [B * {num_beams}, 1, V] and log_probs is [B * {num_beams}], got "
+                         f"{tuple(logits.shape)} and {tuple(log_probs.shape)}")
+    R, V = logits.shape
+    temperature = float(temperature)
+    if not logits.dtype.is_floating_point:
+        raise ValueError(f"beam_select: logits are floating point, got {logits.dtype}")
+    if log_probs.dtype != torch.float32:
+        raise ValueError(f"beam_select: log_probs is float32, got {log_probs.dtype}")
+    if V < 1:
+        raise ValueError("beam_select: the vocabulary is empty")
+    if not (temperature > 0.0 and math.isfinite(temperature)):
+        raise ValueError(f"beam_select: temperature must be positive and finite, got {temperature}")
+    if nn.dry_run():
+        return _dry((R,), logits, torch.int32), _dry((R,), logits, torch.int32), _dry((R,), logits, torch.float32)
+    with torch.no_grad():
+        if R == 0:
+            return (torch.empty((0,), dtype=torch.int32, device=logits.device), torch.empty((0,), dtype=torch.int32, device=logits.device),
+                    torch.empty((0,), dtype=torch.float32, device=logits.device))
+        if logits.is_cuda and beam_fused() and logits.dtype in (torch.bfloat16, torch.float32) and V <= SAMPLE_MAX_VOCAB:
+            if logits.stride(1) != 1 or (R > 1 and logits.stride(0) < V):
+                logits = logits.contiguous()
+            return K.beam_select(logits, _c(log_probs), num_beams, temperature, splits)
+        return _beam_select_composed(logits, log_probs, num_beams, temperature)
+
+
+def beam_reorder(cache, prompt, mask, parents, tokens, index, num_beams, length=None):
+    """keras_nlp's gather_beams after a selection, and the step's token write -> (cache, prompt).  cache [B nb, L, 2, Sc, nkv, h] or None (Sc: the
+    cache's own number of positions, which need not be the prompt's S), prompt [B nb, S] int32 or int64, mask [B nb, S] bool (true = a user token), parents and tokens int32 [B nb] as beam_select returns them:
+        cache[b nb + j] = cache[b nb + parents[b nb + j]];  prompt likewise;  prompt[:, index] = mask[:, index] ? prompt[:, index] : tokens.
+    length: the number of filled cache positions (default `index`: call_with_cache's step `index` writes position index - 1).
+    On device tensors (csrc/beam_search.hip) both are updated IN PLACE and returned: only the positions < length of the cache move, a beam
+    that is its own parent moves nothing, and no second cache exists; this relies on the positions >= length being equal among the beams of
+    a batch row, as they are when the cache was repeated from one row.  A group with a parent outside [0, nb) is left untouched.  CPU tensors,
+    a cache that is not contiguous or whose [nkv, h] rows are no multiple of 16 bytes, a prompt or mask whose rows overlap (an expanded
+    view) and ISEG_BEAM_FUSED=0 take the composed route: new tensors, the whole cache gathered, as the reference does.  All tensors lie on
+    one device."""
+    nb, index = int(num_beams), int(index)
+    if prompt.dim() != 2 or prompt.dtype not in (torch.int32, torch.int64) or tuple(mask.shape) != tuple(prompt.shape) or mask.dtype != torch.bool:
+        raise ValueError(f"beam_reorder: prompt is an int32 or int64 [B * nb, S] and mask a bool tensor of its shape, got {tuple(prompt.shape)} "
+                         f"{prompt.dtype} and {tuple(mask.shape)} {mask.dtype}")
+    R, S = prompt.shape
+    if not 1 <= nb <= BEAM_MAX_BEAMS or R % nb:
+        raise ValueError(f"beam_reorder: {R} rows are no whole number of groups of {nb} beams (1 .. {BEAM_MAX_BEAMS})")
+    for name, t in (("parents", parents), ("tokens", tokens)):
+        if tuple(t.shape) != (R,) or t.dtype != torch.int32:
+            raise ValueError(f"beam_reorder: {name} is an int32 [{R}], got {tuple(t.shape)} {t.dtype}")
+    if not 0 <= index < S:
+        raise ValueError(f"beam_reorder: position {index} does not lie inside a prompt of {S}")
+    if cache is None:
+        length = 0
+    else:
+        if not torch.is_tensor(cache) or cache.dim() != 6 or cache.shape[0] != R:
+            raise ValueError(f"beam_reorder: the cache is a [{R}, L, 2, S, nkv, h] tensor or None, got {tuple(cache.shape) if torch.is_tensor(cache) else cache!r}")
+        length = index if length is None else int(length)
+        if not 0 <= length <= cache.shape[3]:
+            raise ValueError(f"beam_reorder: {length} filled positions do not lie inside a cache of {cache.shape[3]}")
+    for name, t in (("mask", mask), ("parents", parents), ("tokens", tokens), ("cache", cache)):
+        if t is not None and t.device != prompt.device:
+            raise ValueError(f"beam_reorder: {name} lies on {t.device}, the prompt on {prompt.device}")
+    if nn.dry_run() or R == 0:
+        return cache, prompt
+    with torch.no_grad():
+        fused = (prompt.is_cuda and beam_fused() and prompt.stride(1) == 1 and mask.stride(1) == 1
+                 and (R == 1 or (prompt.stride(0) >= S and mask.stride(0) >= S)))
+        if fused and cache is not None:
+            fused = (cache.is_cuda and cache.is_contiguous() and cache.data_ptr() % 16 == 0
+                     and (cache.shape[4] * cache.shape[5] * cache.element_size()) % 16 == 0)
+        if fused:
+            K.beam_reorder(cache, length, prompt, mask, _c(tokens), index, _c(parents), nb)
+            return cache, prompt
+        rows = (torch.arange(R, device=prompt.device) // nb * nb + parents).to(torch.int64)
+        prompt = prompt.index_select(0, rows)
+        prompt[:, index] = torch.where(mask[:, index], prompt[:, index], tokens.to(prompt.dtype))
+        return (None if cache is None else cache.index_select(0, rows)), prompt
+
+
 def decode_commit(prompt, mask, pos_d, cur_ids, done, tokens, end_token_id=None):
     """One step of nlp/samplers.py's sample_loop on state in device memory, IN PLACE (csrc/decode_commit.hip, one launch, no host read), with
     p = pos_d[0], the index of the previous token:

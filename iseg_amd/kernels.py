@@ -2428,6 +2428,58 @@ def token_sample(logits, u, mode, k, p, temperature, splits=0):
 
 
 # ---------------------------------------------------------------------------------------------------------
+# beam search (csrc/beam_search.hip)
+# ---------------------------------------------------------------------------------------------------------
+def beam_select_supported(V, num_beams, dtype):
+    return dtype in _DT and bool(_hip.lib().iseg_beam_select_supported(int(V), int(num_beams), _DT[dtype]))
+
+
+def beam_select_splits(rows, V):
+    """the chunk count iseg_beam_select plans for these arguments"""
+    return int(_hip.lib().iseg_beam_select_splits(int(rows), int(V)))
+
+
+def beam_select(logits, log_probs, num_beams, temperature, splits=0):
+    """the num_beams best of each group's num_beams * V candidates, as include/iseg_hip.h states it: logits [B * nb, V] (rows of contiguous
+    elements, any pitch >= V), log_probs fp32 [B * nb] -> (parents int32, tokens int32, new log_probs fp32), each [B * nb]; splits = 0: the
+    launcher's plan"""
+    _require_cuda(logits, log_probs)
+    R, V = logits.shape
+    L = _hip.lib()
+    parents = torch.empty((R,), dtype=torch.int32, device=logits.device)
+    tokens = torch.empty((R,), dtype=torch.int32, device=logits.device)
+    scores = torch.empty((R,), dtype=torch.float32, device=logits.device)
+    ws, nbytes = workspace(L.iseg_beam_select_scratch_bytes(R, V, int(num_beams), int(splits)), logits.device)
+    _hip.check(L.iseg_beam_select(ptr(logits), logits.stride(0), ptr(log_probs), ptr(parents), ptr(tokens), ptr(scores), ptr(ws), nbytes, R, V,
+                                  int(num_beams), float(temperature), int(splits), dt(logits), stream()), "iseg_beam_select")
+    return parents, tokens, scores
+
+
+def beam_reorder(cache, length, prompt, mask, tokens, index, parents, num_beams):
+    """keras_nlp's gather_beams by parents int32 [B * nb], IN PLACE: the first `length` positions of cache [B * nb, L, 2, Sc, nkv, h] (contiguous;
+    Sc need not be the prompt's S; None: no cache) and prompt [B * nb, S] (int32 or int64; None: no prompt), whose position `index` then takes
+    tokens int32 [B * nb] where mask [B * nb, S] (one byte per entry) is false"""
+    _require_cuda(cache, prompt, mask, tokens, parents)
+    R = parents.shape[0]
+    planes = Sc = row_bytes = 0
+    if cache is not None:
+        if cache.dim() != 6 or cache.shape[0] != R or not cache.is_contiguous():
+            raise ValueError(f"beam_reorder: the cache is a contiguous [{R}, L, 2, Sc, nkv, h], got {tuple(cache.shape)} with strides {cache.stride()}")
+        planes, Sc, row_bytes = cache.shape[1] * cache.shape[2], cache.shape[3], cache.shape[4] * cache.shape[5] * cache.element_size()
+    S = ld_prompt = ld_mask = ids = 0
+    if prompt is not None:
+        if prompt.dim() != 2 or prompt.shape[0] != R or tuple(mask.shape) != tuple(prompt.shape) or mask.element_size() != 1 or tuple(tokens.shape) != (R,):
+            raise ValueError(f"beam_reorder: prompt [{R}, S], a one-byte mask of its shape and tokens [{R}], got {tuple(prompt.shape)}, "
+                             f"{tuple(mask.shape)} {mask.dtype}, {tuple(tokens.shape)}")
+        if prompt.stride(1) != 1 or mask.stride(1) != 1:
+            raise ValueError("beam_reorder: the rows of prompt and mask are contiguous")
+        S, ids = prompt.shape[1], _IDS[prompt.dtype]
+        ld_prompt, ld_mask = (prompt.stride(0), mask.stride(0)) if R > 1 else (S, S)
+    _hip.call("iseg_beam_reorder", ptr(cache), planes, Sc, row_bytes, int(length), ptr(prompt), S, ld_prompt, ptr(mask), ld_mask, ptr(tokens),
+              int(index), ids, ptr(parents), R // int(num_beams), int(num_beams), stream())
+
+
+# ---------------------------------------------------------------------------------------------------------
 # chunked-vocabulary cross-entropy of the language-model head (csrc/lm_head_ce.hip)
 # ---------------------------------------------------------------------------------------------------------
 def lm_head_ce_chunk_default(M, V):

@@ -14,8 +14,13 @@ copies into a new one.  Single-token steps run on the split-KV decode kernels of
 index 0) on the training kernels of csrc/gemma.hip.  No padding mask is passed on the cached path (the reference passes none).
 
 compile(sampler=) takes "greedy" (the default: keras_nlp's greedy Sampler.__call__, `greedy_sample`) or an instance of nlp/samplers.py:
-GreedySampler, RandomSampler, TopKSampler, TopPSampler.  The random ones choose each token with the fused kernels of csrc/token_sample.hip from
-one uniform per row and step.  Every other string alias raises NotImplementedError naming the classes.
+GreedySampler, RandomSampler, TopKSampler, TopPSampler, BeamSampler.  The random ones choose each token with the fused kernels of
+csrc/token_sample.hip from one uniform per row and step.  BeamSampler(num_beams=nb) expands the seeded [B, ...] cache to [B nb, ...] once
+(call_with_cache does not care how large the batch is) and runs every step on the kernels of csrc/beam_search.hip: the selection reads the
+logits once, the cache is reordered in place over its filled prefix (ISEG_BEAM_FUSED=0: the composed route in torch; nlp/samplers.py has the
+algorithm and what it pins down beyond the reference).  generate_step returns the best beam; with return_all_beams=True it raises, because
+the {"token_ids", "padding_mask"} contract has no beam axis: call the sampler directly.  Every other string alias, "beam" included, raises
+NotImplementedError naming the classes.
 
 compile(graph_decode=True) (off by default; no counterpart in the reference, whose tf.function plays this role) makes one generated token one
 graph.replay().  The eager loop issues every launch of a step from Python and reads the stop condition on the host before each; here the loop's
@@ -28,10 +33,11 @@ graph, one launch in front of each replay, from the sampler's own generator: the
 token the loop reads nothing back.  With one it reads `done` every `check_every` replays (generate_step's keyword, default 16); the commit
 kernel freezes once every row is done, so the result does not depend on check_every, but up to check_every - 1 frozen replays each draw
 uniforms that the eager loop would not have drawn: the generator of a sampler that is reused afterwards is that far ahead.  A Sampler subclass
-of the caller's keeps the eager loop (its get_next_token may read on the host); the fp32 compute dtype, ISEG_GEMMA_FUSED=0 and an unsupported
+of the caller's keeps the eager loop (its get_next_token may read on the host), and so does BeamSampler (a captured beam step would need the
+filled length in device memory); the fp32 compute dtype, ISEG_GEMMA_FUSED=0 and an unsupported
 head width raise ValueError (a captured step cannot take the composed route).  release_decode_graphs() drops graphs, caches and buffers.
 
-Out of scope: the tokenizer and preprocessors (strings need a `preprocessor`, and none is built), presets, beam and contrastive samplers, training
+Out of scope: the tokenizer and preprocessors (strings need a `preprocessor`, and none is built), presets, the contrastive sampler, training
 through the cache, paged caches."""
 import math
 import os
@@ -41,7 +47,7 @@ import torch
 from ... import functional as F
 from ... import nn
 from ...nn import Layer
-from ..samplers import Sampler, sample_loop
+from ..samplers import BeamSampler, Sampler, sample_loop
 
 
 def lm_head_fused():
@@ -96,15 +102,15 @@ class GemmaCausalLM(Layer):
         self.built = True
 
     def compile(self, sampler="greedy", graph_decode=False, **unused):
-        """sampler: "greedy", or an instance of iseg_amd.nlp.samplers (GreedySampler, RandomSampler, TopKSampler, TopPSampler or a Sampler subclass
-        of the caller's).  The other string aliases of keras_nlp.samplers.get are not built.
+        """sampler: "greedy", or an instance of iseg_amd.nlp.samplers (GreedySampler, RandomSampler, TopKSampler, TopPSampler, BeamSampler or a
+        Sampler subclass of the caller's).  The other string aliases of keras_nlp.samplers.get are not built.
         graph_decode=True: generate_step replays every decoding step from one captured HIP graph (the module docstring); off by default."""
         if not isinstance(graph_decode, bool):
             raise ValueError(f"GemmaCausalLM.compile: graph_decode is True or False, got {graph_decode!r}")
         if isinstance(sampler, str):
             if sampler != "greedy":
                 raise NotImplementedError(f'GemmaCausalLM.compile: the only string alias is "greedy", got {sampler!r}; pass an instance of '
-                                          "iseg_amd.nlp.samplers.GreedySampler, RandomSampler, TopKSampler or TopPSampler instead")
+                                          "iseg_amd.nlp.samplers.GreedySampler, RandomSampler, TopKSampler, TopPSampler or BeamSampler instead")
         elif not isinstance(sampler, Sampler):
             raise ValueError(f'GemmaCausalLM.compile: sampler is "greedy" or an iseg_amd.nlp.samplers.Sampler instance, got {sampler!r}')
         self.sampler = sampler
@@ -323,6 +329,9 @@ class GemmaCausalLM(Layer):
         check_every: with compile(graph_decode=True) and an end token, the number of replays between two host reads of the stop condition
         (16 is a choice, not a measurement); the result does not depend on it."""
         token_ids, padding_mask = inputs["token_ids"], inputs["padding_mask"].to(torch.bool)
+        if isinstance(self.sampler, BeamSampler) and self.sampler.return_all_beams:
+            raise ValueError('GemmaCausalLM.generate_step: the {"token_ids", "padding_mask"} result has no beam axis; with '
+                             "BeamSampler(return_all_beams=True) call the sampler directly")
         if self.graph_decode:
             graphable, sampler = self._graph_decode_sampler()
             if graphable:

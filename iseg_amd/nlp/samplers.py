@@ -1,5 +1,5 @@
 """keras_nlp.samplers as GemmaCausalLM.compile(sampler=) takes them (the class docstring of nlp/gemma/gemma_causal.py in the reference): the decoding
-loop of Sampler.__call__ and the greedy, random, top-k and top-p rules for the next token.  Defaults are keras_nlp's.
+loop of Sampler.__call__, the greedy, random, top-k and top-p rules for the next token, and beam search.  Defaults are keras_nlp's.
 
     sampler = TopKSampler(k=5, seed=7)
     model.compile(sampler=sampler)
@@ -15,7 +15,22 @@ graph_signature() (what a capture freezes of the sampler: its type and kernel ar
 the logits alone, reading its uniforms from a static buffer) and, the seeded ones, uniforms_into(buf) (the step's draw of `uniforms`, written
 into that buffer in front of each replay).  sample_loop and the classes' behaviour are unchanged.
 
-Out of scope: BeamSampler, ContrastiveSampler, the string aliases ("top_k", ...) of keras_nlp.samplers.get."""
+BeamSampler(num_beams=5, return_all_beams=False, temperature=1.0) restates keras_nlp's BeamSampler.__call__; it is no get_next_token rule, because a
+beam step carries running scores and reorders the cache.  Every prompt row becomes num_beams rows (row b nb + j is beam j of batch row b) with
+fp32 running scores [0, -1e9, ..., -1e9], so that the first step extends beam 0 alone.  A step scores every (beam, token) pair with
+log softmax(logits / temperature) + the beam's running score, keeps the nb best per batch row (F.beam_select), gathers prompt and cache by
+the chosen parents and writes the chosen tokens except over user tokens (F.beam_reorder); the running score keeps the selected candidate's
+value even where a user token overrides its token, as in the reference.  The loop stops as sample_loop does, over all B nb rows.  On device
+tensors both halves are kernels of csrc/beam_search.hip: the logits are read once and no [B nb, V] tensor is made, and the cache is reordered
+in place over its filled prefix only; CPU tensors and ISEG_BEAM_FUSED=0 take the composed route, the reference's op sequence in torch.
+Where the reference leaves the result open it is pinned down (include/iseg_hip.h has the full statement):
+  order      the selected beams come out sorted by score descending, ties by flat index (beam V + token) ascending;
+  scores     (x - max) / T - log sum exp is evaluated directly: where an fp32 softmax underflows to 0 the reference gets -inf and an
+             arbitrary order, here such candidates keep their true value and place;
+  non-finite a -inf logit scores -inf; a NaN or +inf logit makes its row's scores NaN; NaN ranks above every number, as in torch.topk;
+             0 <= parent < nb and 0 <= token < V always.
+
+Out of scope: ContrastiveSampler, the string aliases ("top_k", ...) of keras_nlp.samplers.get."""
 import math
 
 import torch
@@ -175,3 +190,58 @@ class TopPSampler(_SeededSampler):
 
     def get_config(self):
         return {**super().get_config(), "p": self.p, "k": self.k}
+
+
+class BeamSampler(Sampler):
+    """beam search: num_beams hypotheses per prompt row, extended jointly; the result is the hypothesis with the largest sum of token
+    log-probabilities (the first of equals), or with return_all_beams=True the pair (prompts [B, nb, S], log_probs [B, nb]) sorted by score
+    descending.  num_beams is an integer in 1 .. 16; num_beams=1 is greedy search on logits without ties.  The module docstring has the
+    algorithm, the two routes and what is pinned down beyond the reference."""
+
+    def __init__(self, num_beams=5, return_all_beams=False, temperature=1.0):
+        super().__init__(temperature)
+        if isinstance(num_beams, bool) or not isinstance(num_beams, int) or not 1 <= num_beams <= F.BEAM_MAX_BEAMS:
+            raise ValueError(f"BeamSampler: num_beams is an integer in 1 .. {F.BEAM_MAX_BEAMS}, got {num_beams!r}")
+        if not isinstance(return_all_beams, bool):
+            raise ValueError(f"BeamSampler: return_all_beams is True or False, got {return_all_beams!r}")
+        self.num_beams, self.return_all_beams = num_beams, return_all_beams
+
+    def __call__(self, next, prompt, cache=None, index=0, mask=None, end_token_id=None):
+        """next(prompt [B nb, S], cache, index) -> (logits [B nb, V], hidden states, cache), as sample_loop calls it.  cache: None or a tensor
+        whose axis 0 is the batch, in call_with_cache's convention [B, L, 2, S, nkv, h] with step `index` writing position index - 1."""
+        nb = self.num_beams
+        if prompt.dim() != 2:
+            raise ValueError(f"BeamSampler: prompt is [B, S], got {tuple(prompt.shape)}")
+        if mask is None:
+            mask = torch.zeros_like(prompt, dtype=torch.bool)
+        if cache is not None and not torch.is_tensor(cache):
+            raise ValueError(f"BeamSampler: the cache is a tensor with the batch on axis 0 or None, got {type(cache).__name__}")
+        B, S = prompt.shape
+        # copies, num_beams to a row: the caller's tensors are never written
+        prompt = torch.repeat_interleave(prompt, nb, dim=0)
+        mask = torch.repeat_interleave(mask.to(torch.bool), nb, dim=0)
+        if cache is not None:
+            cache = torch.repeat_interleave(cache, nb, dim=0)
+        log_probs = torch.tensor([0.0] + [-1e9] * (nb - 1), dtype=torch.float32, device=prompt.device).repeat(B)
+        index = int(index)
+        while index < S:
+            if end_token_id is not None:
+                done = ((prompt == end_token_id) & ~mask).any(dim=-1)
+                if bool(done.all()):
+                    break
+            logits, _, cache = next(prompt, cache, index)
+            parents, tokens, log_probs = F.beam_select(logits, log_probs, nb, self.temperature)
+            cache, prompt = F.beam_reorder(cache, prompt, mask, parents, tokens, index, nb)
+            index += 1
+        prompts, log_probs = prompt.view(B, nb, S), log_probs.view(B, nb)
+        if self.return_all_beams:
+            order = torch.sort(log_probs, dim=-1, descending=True, stable=True).indices
+            return prompts.gather(1, order[:, :, None].expand(-1, -1, S)), log_probs.gather(1, order)
+        best = torch.argmax(log_probs, dim=-1)      # the first of equal maxima
+        return prompts[torch.arange(B, device=prompt.device), best]
+
+    def get_next_token(self, logits):
+        raise NotImplementedError("BeamSampler.get_next_token: a beam step needs the running scores and reorders the cache; call the sampler")
+
+    def get_config(self):
+        return {**super().get_config(), "num_beams": self.num_beams, "return_all_beams": self.return_all_beams}
