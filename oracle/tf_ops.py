@@ -609,9 +609,11 @@ def dcnv2(x, offset_in, kernel, bias, offset_kernel, offset_bias, dilation=1):
     hi = torch.tensor([H + 1, W + 1], dtype=x.dtype)
     lo = torch.zeros(2, dtype=x.dtype)
     f = torch.floor(g)
-    i1 = torch.minimum(torch.maximum(f + 1, lo), hi)                                         # :150-156
-    i0 = torch.minimum(torch.maximum(f, lo), hi)                                             # :160
-    gc = torch.minimum(torch.maximum(g, lo), hi)                                             # :164
+    # tf.clip_by_value passes the whole gradient where the input lies inside [lo, hi], bounds included; so does torch.clamp, while
+    # torch.minimum / torch.maximum split it 1/2 : 1/2 at a tie (a tap exactly on the bound: tests/test_sampling_kinks_host.py)
+    i1 = torch.clamp(f + 1, lo, hi)                                                          # :150-156
+    i0 = torch.clamp(f, lo, hi)                                                              # :160
+    gc = torch.clamp(g, lo, hi)                                                              # :164
     d0, d1 = gc - i0, i1 - gc                                                                # :182-183
     wts = torch.stack([d0[..., 0] * d0[..., 1], d0[..., 0] * d1[..., 1], d1[..., 0] * d0[..., 1], d1[..., 0] * d1[..., 1]], dim=-1)      # :185-199
     xp = torch.nn.functional.pad(x, (0, 0, pw, pw, ph, ph))                                  # :201

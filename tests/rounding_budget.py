@@ -25,6 +25,7 @@ comment as `# iseg_amd/csrc/<file>:<line>`.  DESIGN.md ("Rounding points") lists
 BUDGET[family] is the share the fp32 restatement reaches over the family's cases (pooled), measured once and written down;
 test_every_budget_entry_is_backed_by_the_restatement keeps it honest.  The device floor is derived from it (share_floor).
 """
+import functools
 import inspect
 import math
 from typing import NamedTuple
@@ -32,6 +33,7 @@ from typing import NamedTuple
 import torch
 
 from oracle import tf_ops as O
+from tests import sampling_kinks as SK
 from tests.test_kernels_gpu import rnd
 
 BF, F32, F64 = torch.bfloat16, torch.float32, torch.float64
@@ -68,7 +70,21 @@ BUDGET = {
     "attention_self_bwd": 0.99895,      # 0.999163
     "gelu_approx": 0.9982,          # 0.998562: the degree-6 / degree-7 polynomials cancel, so their fp32 value depends on the evaluation order
     "gelu_approx_act": 0.999905,    # 0.999924
+    "dcnv3": 0.99727,               # 0.997819: see FP32_COORDINATES
+    "dcnv3_bwd": 0.99807,           # 0.998456 (mask gradient and the interior elements of the offset gradient)
+    "dcnv2_sample": 0.999976,       # 0.999981 (the coordinate is one addition)
+    "dcnv2_sample_bwd": 0.999952,   # 0.999961 (logit gradients and the interior elements of the offset gradients)
+    "defattn": 0.99852,             # 0.998817
+    "defattn_bwd": 0.99869,         # 0.998950 (value / attention gradients and the interior elements of the offset gradient)
 }
+
+# Tier-1 families whose fp32 restatement is NOT within 1e-3 ulp of a perfect store, and why: the sampling coordinate is computed in fp32 (as the
+# kernels do: iseg_amd/csrc/dcnv3.hip:14-15, iseg_amd/csrc/defattn.hip:11-12) through a chain of 7 to 10 roundings at the magnitude of the image
+# size, and a bilinear weight is that coordinate minus its floor: an absolute error of up to TAU / 4 ~ 1e-5 (tests/sampling_kinks.py) in a weight of
+# order 1 is ~1e-5 of the output, 2.5e-3 of a bf16 ulp per tap and up to ~10 times that where the taps of an output cancel.  The restatement's
+# measured max |e| (0.512 / 0.526 / 0.513 / 0.502 ulp) is held below the figure written here, and condition 2 of the device test scales its
+# excess as everywhere.  DCNv2's coordinate is one addition: its families meet the 1e-3 of every other tier-1 family.
+FP32_COORDINATES = {"dcnv3": 0.53, "dcnv3_bwd": 0.53, "defattn": 0.53, "defattn_bwd": 0.53}
 
 # Families whose kernel rounds an intermediate to bf16 that never leaves the CU (the probabilities of the attention cores, G / dH of the fused MLP
 # forward and data-gradient kernels).  One element of that intermediate which fp32 and fp64 round differently moves an output by the
@@ -278,6 +294,15 @@ class Case:
         to the reference as the side under test stored it (the device's on the device, the restatement's on the host).  Otherwise one element
         of the intermediate that fp32 and fp64 round differently moves an output behind it by several of its ulps, in the restatement too."""
         return {inp: outputs[out].detach().cpu().to(BF) for inp, out in self.p.get("feed", {}).items()}
+
+    def selected(self, outputs):
+        """the cases with `select=` (a function -> {output: boolean mask}) enter with the masked elements of those outputs only, as flat CPU
+        tensors: the offset gradients of the sampling kernels are discontinuous at cell borders, where fp32 and fp64 may stand on different
+        sides, and only their interior elements are a statement about rounding (the others: tests/test_sampling_kinks_gpu.py)"""
+        if "select" not in self.p:
+            return outputs
+        masks = self.p["select"]()
+        return {k: (v.detach().cpu()[masks[k]] if k in masks else v) for k, v in outputs.items()}
 
     def outputs(self, dtype, fed=None):
         """{output name: tensor in `dtype`}: torch.float64 = the reference, torch.float32 = the restatement"""
@@ -865,6 +890,40 @@ case("resize", "up_12_to_20", "resize", make_resize, resize_compute, shape=(2, 1
 case("resize_x2", "exact_x2", "resize", make_resize, resize_compute, shape=(2, 16, 16, 96), out=(32, 32))
 
 
+# ---- the sampling kernels: DCNv3, DCNv2's sampling half, deformable attention ---------------------------------------------------------
+# The operands are the `budget` cases of tests/sampling_kinks.py (the recipes of the core tests at 2 x 40 x 36 x 32), the formula is the oracle itself
+# (oracle/tf_ops.dcnv3_op, oracle/tf_ops.dcnv2 with identity products, tests/deformable_mhsa_ref.core): fp64 is the reference, torch.float32 the
+# restatement.  Only bf16-STORED outputs are cases: the fp32 input gradients of iseg_dcnv3_bwd / iseg_dcnv2_sample_bwd keep their parity tolerance.
+def _kink_case(op):
+    return next(c for c in SK.CASES if c.op == op and c.kind == "budget")
+
+
+def make_sampling(op):
+    return dict(SK.operands(_kink_case(op), BF))
+
+
+def sampling_compute(i, op, keep):
+    out = SK.OPS[op].run(i, _kink_case(op).p, dtype=i["offset"].dtype)
+    if op == "dcnv2":      # the kernel writes ONE [N, H, W, 27] gradient: 18 offsets, 9 modulation logits
+        out["doff"] = torch.cat([out["doffset"], out["dlogit"]], dim=-1)
+    return {k: out[k] for k in keep}
+
+
+def sampling_interior(op):
+    """-> {name of the offset gradient: its interior elements} (DCNv2: and every logit element)"""
+    cls = SK.classes(_kink_case(op), BF)
+    if op == "dcnv2":
+        return {"doff": torch.cat([cls.interior, torch.ones(cls.interior.shape[:3] + (9,), dtype=torch.bool)], dim=-1)}
+    return {"doffset": cls.interior}
+
+
+for _op, _fwd, _bwd in (("dcnv3", ("y",), ("dmask", "doffset")), ("dcnv2", ("col",), ("doff",)), ("defattn", ("out",), ("dvalue", "dattn", "doffset"))):
+    _fam = "dcnv2_sample" if _op == "dcnv2" else _op
+    case(_fam, "40x36", _fam, make_sampling, sampling_compute, op=_op, keep=_fwd)
+    case(_fam + "_bwd", "40x36", _fam + "_bwd", make_sampling, sampling_compute, op=_op, keep=_bwd, select=functools.partial(sampling_interior, _op))
+del _op, _fwd, _bwd, _fam
+
+
 FAMILIES = sorted({c.family for c in CASES})
 assert set(FAMILIES) == set(BUDGET), (FAMILIES, sorted(BUDGET))
 
@@ -880,7 +939,8 @@ def restated(c):
     """-> {output: (bf16 of the fp32 restatement, fp64 reference, fp32 restatement)}; computed once per case and shared, never modified"""
     if c.id not in _RESTATED:
         r32 = c.outputs(F32)
-        ref = c.outputs(F64, c.fed(r32))
+        ref = c.selected(c.outputs(F64, c.fed(r32)))
+        r32 = c.selected(r32)
         _RESTATED[c.id] = {k: (r32[k].to(F32).to(BF), ref[k], r32[k].to(F32)) for k in ref}
     return _RESTATED[c.id]
 

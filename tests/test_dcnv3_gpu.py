@@ -38,9 +38,11 @@ def test_dcnv3_core_forward_backward(cuda, dtype, shape, G, scale):
         if dtype == torch.float32:
             close(off.grad, offr.grad, dtype, "dcnv3 doffset", f32_tol=5e-5)
         else:
-            # bf16 offsets are multiples of 2^-8 or coarser: some sampling coordinates land exactly on a cell border, where
-            # floor() in fp32 (kernel) and fp64 (oracle) may pick different cells and the offset gradient is discontinuous;
-            # bound the relative L2 error instead of the max-norm
+            # the offset gradient jumps where a coordinate crosses an integer, and within TAU ~ 1e-4 of one fp32 (kernel) and fp64 (oracle) may
+            # stand on different sides.  Measured (test_sampling_kinks_gpu.py): at most 0.12 % of the elements of these recipes are that
+            # close; where none takes the other side the relative L2 error is the bf16 store's, 1.5e-3 to 1.9e-3, and 7 such elements of 12 960
+            # make it 2.6e-2.  The band below holds that and no more: each element is judged by its class -- interior, exactly on a kink, next to
+            # one -- in test_sampling_kinks_gpu.py, which fails kernels this band passes (test_sampling_kinks_host.py: the mutants)
             d = off.grad.cpu().double() - offr.grad
             assert d.norm().item() / offr.grad.norm().item() < 5e-2
     finally:
@@ -201,7 +203,9 @@ def test_dcnv3_input_gradient_keeps_its_precision_for_tiny_gradients(cuda, dtype
 def test_dcnv2_layer_forward_and_gradients(cuda, dtype, N, H, W, C, Fo, custom):
     """DCNv2 (modulated deformable sampling kernels + offset convolution + one GEMM) against the op-for-op restatement of layers/dcn_v2.py:110-262:
     offsets large enough to leave the image (the clipped-corner weights and the zero border take part), output, input / offset-input gradients and
-    every parameter gradient.  bf16: offsets land on cell borders where the offset gradient is discontinuous -- direction / size band only."""
+    every parameter gradient.  bf16: the offset convolution's output is rounded to bf16 on the kernel side only, which moves coordinates across cell borders,
+    where the offset gradient is discontinuous -- direction / size band only; the sampling kernels themselves are held element by element, on operands
+    rounded on both sides, in test_sampling_kinks_gpu.py (border share of such operands: under 0.1 %)."""
     from iseg_amd import nn
     from iseg_amd.layers.dcn_v2 import DCNv2
     from iseg_amd.param_store import ParamStore

@@ -67,8 +67,11 @@ def test_deformable_attention_core_forward_backward(cuda, dtype, case):
         if dtype == torch.float32:
             close(o.grad, do, dtype, "defattn doffset", f32_tol=5e-5)
         else:
-            # bf16 logits put a few per mille of the coordinates within 1e-4 of a cell border, where floor() in fp32 (kernel) and fp64
-            # (restatement) may pick different cells and the offset gradient is discontinuous: relative L2 instead of the max-norm
+            # the offset gradient jumps where a coordinate crosses an integer or a clip bound, and within TAU ~ 4e-5 of one fp32 (kernel) and fp64
+            # (restatement) may stand on different sides.  Measured on these cases (test_sampling_kinks_gpu.py): 0.2 % of the elements
+            # of the bf16 case (1, 12, 12, 64) are that close, under 0.07 % elsewhere, and the relative L2 error on the device is the bf16 store's,
+            # 1.5e-3 to 1.7e-3.  This band is kept as it was; every element is judged by its class -- interior, exactly on a kink, next to one -- in
+            # test_sampling_kinks_gpu.py, which fails kernels this band passes (a strict clip bound, the other side at an integer)
             assert (o.grad.cpu().double() - do).norm().item() / do.norm().item() < 5e-2
     finally:
         nn.set_compute_dtype(torch.float32)
@@ -132,7 +135,8 @@ def test_deformable_attention_refuses_more_points_than_the_kernels_hold(cuda):
 @pytest.mark.parametrize("dense", [False, True], ids=["conv", "dense"])
 def test_deformable_mhsa_layer_forward_and_gradients(cuda, dtype, apply_linear, dense):
     """output, the gradients of the input and of a separate value= input, and every parameter gradient; offset_proj is scaled up so that the samples
-    leave their cell.  bf16: the relative L2 band of the DCNv2 layer test, for its reason -- the offset gradient is discontinuous at cell borders.
+    leave their cell.  bf16: the relative L2 band of the DCNv2 layer test, for its reason -- the offset gradient is discontinuous at cell borders (the core
+    itself, on operands rounded on both sides: test_sampling_kinks_gpu.py).
     Conditioning of the inputs: under bf16 the kernel side computes the offset logits from bf16 weights and rounds them to bf16, the restatement
     from the fp32 masters in fp64, so a logit of size 2 differs by about 2 * 2^-8 = 0.008 and a coordinate by that times (1 - t^2) * H / factor.  A
     sample whose coordinate moves across a cell border has an offset gradient that is wrong by its own size, so the relative L2 error of every

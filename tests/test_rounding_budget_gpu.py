@@ -270,7 +270,43 @@ def run_broadcast_rows(k, d, p):
     return {"y": y}
 
 
+def _sampling(p):
+    from tests import sampling_kinks as SK
+
+    return next(c for c in SK.CASES if c.op == p["op"] and c.kind == "budget").p
+
+
+def run_dcnv3(k, d, p):
+    q = _sampling(p)
+    G = q["G"]
+    return {"y": k.dcnv3_fwd(d["x"], d["offset"], d["mask"], G, d["x"].shape[3] // G, 3, 3, 1, 1, 1, 1.0)}
+
+
+def run_dcnv3_bwd(k, d, p):
+    q = _sampling(p)
+    G = q["G"]
+    _, doff, dmask = k.dcnv3_bwd(d["x"], d["offset"], d["mask"], d["dout"], G, d["x"].shape[3] // G, 3, 3, 1, 1, 1, 1.0)      # (dx: fp32, not a case)
+    return {"dmask": dmask, "doffset": doff}
+
+
+def run_defattn(k, d, p):
+    q = _sampling(p)
+    return {"out": k.defattn_fwd(d["value"], d["offset"], d["attn"], q["heads"], q["P"], q["orf"])}
+
+
+def run_defattn_bwd(k, d, p):
+    q = _sampling(p)
+    dvalue, doff, dattn = k.defattn_bwd(d["value"], d["offset"], d["attn"], d["dout"], q["heads"], q["P"], q["orf"])
+    return {"dvalue": dvalue, "dattn": dattn, "doffset": doff}
+
+
 RUN = {
+    "dcnv3": run_dcnv3,
+    "dcnv3_bwd": run_dcnv3_bwd,
+    "dcnv2_sample": lambda k, d, p: {"col": k.dcnv2_sample_fwd(d["x"], d["offset"])},
+    "dcnv2_sample_bwd": lambda k, d, p: {"doff": k.dcnv2_sample_bwd(d["x"], d["offset"], d["dout"])[1]},
+    "defattn": run_defattn,
+    "defattn_bwd": run_defattn_bwd,
     "cast": lambda k, d, p: {"y": k.cast(d["x"], BF)},
     "axpby": lambda k, d, p: {"y": k.axpby(d["a"], d["b"], p["alpha"], p["beta"])},
     "add_relu": lambda k, d, p: {"y": k.add_relu(d["a"], d["b"])},
@@ -314,6 +350,7 @@ def check(c):
     d = {name: (v.cuda() if torch.is_tensor(v) else v) for name, v in c.inputs().items()}
     got = RUN[c.kind](k, d, c.p)
     torch.cuda.synchronize()
+    got = c.selected(got)
     fed = c.fed(got)
     want = c.outputs(torch.float64, fed) if fed else {name: ref for name, (_, ref, _) in R.restated(c).items()}
     assert {name.split("@")[0] for name in got} == set(want)

@@ -40,7 +40,8 @@ def test_restatement_meets_the_device_conditions(c):
         st = R.rounding_stats(b16, ref)
         bad = R.failures(st, ref.numel(), c.family, R.family_max_e(c.family), c.independent())
         assert not bad, R.report(f"{c.id}:{name} (fp32 restatement)", b16, ref, st) + "\n" + "; ".join(bad)
-        assert c.tier == 2 or st.max_abs_e <= 0.5 + 1e-3, f"{c.id}:{name}: the restatement itself is {st.max_abs_e:.4f} ulp off"
+        # (tier 1 with fp32 sampling coordinates: the written figure of R.FP32_COORDINATES instead of 1e-3, for the reason given there)
+        assert c.tier == 2 or st.max_abs_e <= R.FP32_COORDINATES.get(c.family, 0.5 + 1e-3), f"{c.id}:{name}: the restatement itself is {st.max_abs_e:.4f} ulp off"
 
 
 @pytest.mark.parametrize("c", R.CASES, ids=lambda c: c.id)
@@ -88,6 +89,13 @@ def test_unstored_max_e_is_backed_by_the_restatement():
         assert measured > 0.75, f"{family}: the restatement is faithfully rounded ({measured:.3f}); the family does not belong in UNSTORED_MAX_E"
         assert measured <= written <= 0.5 + 1.5 * (measured - 0.5), f"{family}: written {written}, the restatement shows {measured:.4f}"
         assert all(c.tier == 2 for c in R.family_cases(family))
+
+
+def test_fp32_coordinate_families_are_the_sampling_kernels_and_need_their_allowance():
+    assert set(R.FP32_COORDINATES) <= {"dcnv3", "dcnv3_bwd", "defattn", "defattn_bwd"} and all(0.5 < v <= 0.53 for v in R.FP32_COORDINATES.values())
+    for family in R.FP32_COORDINATES:
+        assert R.measured_max_e(family) > 0.5 + 1e-3, f"{family}: the restatement meets the 1e-3 of the other tier-1 families; drop the entry"
+        assert all(c.tier == 1 for c in R.family_cases(family))
 
 
 def test_every_family_is_tiered_and_every_skip_is_explained():
