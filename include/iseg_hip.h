@@ -1392,6 +1392,73 @@ int iseg_beam_select(const void* logits, int64_t ld, const float* log_probs, int
 int iseg_beam_reorder(void* cache, int64_t planes, int64_t Sc, int64_t row_bytes, int64_t len, void* prompt, int64_t S, int64_t ld_prompt,
                       const uint8_t* mask, int64_t ld_mask, const int32_t* tokens, int64_t index, int ids_dtype, const int32_t* parents, int64_t groups,
                       int nb, iseg_stream_t stream);
+/* One step of keras_nlp.samplers.ContrastiveSampler (contrastive search) without a [B, V] probability tensor, without a [B k, T] similarity
+ * matrix and without copying or gathering a cache.  Row b * k + j is candidate j of batch row b (groups = B), 1 <= k <= 16.
+ *
+ * iseg_contrastive_candidates: logits [R, V] (bf16 or fp32, row pitch ld >= V elements), T = temperature > 0 -> probs fp32 [rows, k] and tokens
+ * int32 [rows, k]: the k largest of p = softmax(x / T) of every output row and their token ids.
+ *   row map    row_map NULL: R = rows and output row r reads logits row r.  Otherwise int32 [rows] in device memory and R = rows * group: output
+ *              row r reads logits row r * group + row_map[r] (clamped into [0, group)), so a step reads the previous step's winner out of its
+ *              [B k, V] logits and never gathers it.
+ *   order      probability descending, ties by token id ascending: the order of the STORED logits (value descending, then index ascending;
+ *              order_keys.h), which is the probabilities' order wherever two of them differ.  The reference's top_k(sorted=False) has none.
+ *   precision  p = exp((x - max) / T) / sum_u exp((x_u - max) / T): the weights as iseg_beam_select forms them (each within 2 * 2^-23 of itself),
+ *              summed in fp64 in a fixed order; the candidate's own weight and the quotient in fp64, rounded once to fp32:
+ *              |error| <= 2.5 * 2^-23 p.  The reference rounds the probabilities to the logits' dtype; here they stay fp32.
+ *   non-finite a -inf logit has p = 0.  A row whose largest entry is NaN or +inf, or that holds -inf alone, has p = NaN throughout (as softmax
+ *              has) and, every token tying, the tokens 0 .. k - 1.  Whatever the input, 0 <= token < V and a row's k tokens are distinct.
+ * Pass 1 is iseg_beam_select's (one workgroup per (row, chunk of whole 2048-element tiles), the logits read ONCE); pass 2, one wavefront per
+ * output row, merges the chunk records.  No atomics: a second call returns the same bits.  splits, the scratch buffer (8-byte aligned,
+ * iseg_contrastive_candidates_scratch_bytes with the same `splits`; smaller: ISEG_ERR_WORKSPACE) and the plan
+ * (iseg_contrastive_candidates_splits(rows, V)) are iseg_beam_select's.  Supported (iseg_contrastive_candidates_supported): bf16 or fp32,
+ * 1 <= V <= 2^20, 1 <= k <= min(16, V); anything else returns ISEG_ERR_UNSUPPORTED.  A temperature <= 0 or not finite, ld < V and a row map
+ * with group < 1 return ISEG_ERR_ARG.  All before any memory is touched.
+ *
+ * iseg_contrastive_select: hist [groups, S, D] the hidden states of the positions so far (bf16 or fp32; batch stride hs_b and position stride
+ * hs_t in elements), index the number of filled positions, cand [groups * k, D] the candidates' hidden states (row pitch ldc), probs fp32
+ * [groups * k], 0 <= alpha <= 1 -> max_sim fp32 [groups * k], scores fp32 [groups * k], winner int32 [groups]:
+ *   max_sim[b k + j] = max over t < index of  <hist[b, t], cand[b k + j]> / (|hist[b, t]| * |cand[b k + j]|),
+ *   scores[b k + j]  = (1 - alpha) * probs[b k + j] - alpha * max_sim[b k + j],      winner[b] = the first j with the maximal score.
+ *   arithmetic the dot product and the two squared norms are fp32 FMA chains over the stored elements (8 consecutive elements per lane and
+ *              512-element trip, then a 64-lane butterfly), square roots, one product and one division in fp32.  No epsilon: a zero vector in
+ *              the history or as a candidate gives 0 / 0 = NaN, as in the reference.  |error of max_sim| <= (2 D + 8) * 2^-24.
+ *   NaN        ranks above every number, as torch.max and torch.argmax have it: one NaN similarity makes max_sim NaN, a NaN score wins.
+ *              0 <= winner < k always.
+ *   positions  >= index are never read.  1 <= index <= S.
+ * Pass 1, one workgroup per (batch row, chunk of positions, group of candidates): the candidates stay in LDS (all k of them where k * D
+ * elements fit 128 KB, else groups of equal size and the history is read once per group) while the chunk's positions stream by once; the
+ * record is the largest order key of sim per candidate.  Pass 2, one wavefront per batch row, takes the maxima over the chunks and forms scores
+ * and winner.  A similarity does not depend on the chunk its position falls into and a maximum does not depend on the grouping: every output
+ * is bit-identical for every `splits`, and from call to call.  No atomics.  splits: 0 = the launcher's plan, a function of (groups, index, D, k,
+ * dtype) that iseg_contrastive_select_splits returns; a positive value is taken, clipped to `index`.  The scratch buffer (4-byte aligned)
+ * holds iseg_contrastive_select_scratch_bytes (same `splits`); smaller: ISEG_ERR_WORKSPACE.  Supported (iseg_contrastive_select_supported):
+ * bf16 or fp32, D a multiple of 8 in 8 .. 16384, 1 <= k <= 16; anything else returns ISEG_ERR_UNSUPPORTED.  index outside 1 .. S, alpha
+ * outside [0, 1], bases that are not 16-byte aligned, pitches below D or no multiple of 8 elements return ISEG_ERR_ARG, before any memory is
+ * touched.
+ *
+ * iseg_contrastive_commit: the winner's state becomes its group's, IN PLACE, one launch, with w = winner[b] (int32 [groups], device memory):
+ *   cache      [groups * k, planes, Sc, row_bytes] bytes, contiguous, as iseg_beam_reorder takes it:  cache[b k + j, p, pos] = cache[b k + w, p,
+ *              pos] for every plane p and every j; no other position is read or written.  The rows of a group are equal below pos (the cache
+ *              was repeated k times once), so one position per step is all that ever moves.  cache NULL: skipped.
+ *   prompt     [groups * k, S] ids (int32 or int64, row pitch ld_prompt):  prompt[b k + j, index] = prompt[b k + w, index].  NULL: skipped.
+ *   hist       [groups, Sh, D] as above:  hist[b, index] = cand[b k + w].  NULL: skipped.
+ * A thread owns a 16-byte column: it reads the winner's and writes the others'.  A group whose winner lies outside [0, k) is left untouched.
+ * Grid-stride launch; no host read.  k outside 1 .. 16, a row_bytes or D * element size that is no multiple of 16, misaligned bases, pos
+ * outside [0, Sc), index outside [0, S) or [0, Sh) and a row pitch below the row return ISEG_ERR_ARG, before any memory is touched. */
+int iseg_contrastive_candidates_supported(int64_t V, int k, int dtype);
+int iseg_contrastive_candidates_splits(int64_t rows, int64_t V);
+size_t iseg_contrastive_candidates_scratch_bytes(int64_t rows, int64_t V, int k, int splits);
+int iseg_contrastive_candidates(const void* logits, int64_t ld, const int32_t* row_map, int group, float* probs, int32_t* tokens, void* ws,
+                                size_t ws_bytes, int64_t rows, int64_t V, int k, float temperature, int splits, int dtype, iseg_stream_t stream);
+int iseg_contrastive_select_supported(int64_t D, int k, int dtype);
+int iseg_contrastive_select_splits(int64_t groups, int64_t index, int64_t D, int k, int dtype);
+size_t iseg_contrastive_select_scratch_bytes(int64_t groups, int64_t index, int64_t D, int k, int splits, int dtype);
+int iseg_contrastive_select(const void* hist, int64_t hs_b, int64_t hs_t, int64_t S, int64_t index, const void* cand, int64_t ldc,
+                            const float* probs, int32_t* winner, float* scores, float* max_sim, void* ws, size_t ws_bytes, int64_t groups, int64_t D,
+                            int k, float alpha, int splits, int dtype, iseg_stream_t stream);
+int iseg_contrastive_commit(void* cache, int64_t planes, int64_t Sc, int64_t row_bytes, int64_t pos, void* prompt, int64_t S, int64_t ld_prompt,
+                            int64_t index, int ids_dtype, void* hist, int64_t hs_b, int64_t hs_t, int64_t Sh, const void* cand, int64_t ldc, int64_t D,
+                            int dtype, const int32_t* winner, int64_t groups, int k, iseg_stream_t stream);
 /* The language-model head's loss without a [tokens, vocab] tensor: SparseCategoricalCrossentropy(from_logits=True) and
  * SparseCategoricalAccuracy of nlp/gemma/gemma_causal.py:165-172 on the logits Z = X E^T (X [M, d] hidden states, E [V, d] the tied table).  The
  * caller cuts the vocabulary into chunks [v0, v0 + w) of any width w >= 1, has iseg_gemm write Z_c = X E[v0 : v0 + w]^T [M, w] in FP32 (row pitch

@@ -318,6 +318,15 @@ SIGNATURES = {
     "iseg_beam_select_scratch_bytes": (_z, [_l, _l, _i, _i]),
     "iseg_beam_select": (_i, [_p, _l, _p, _p, _p, _p, _p, _z, _l, _l, _i, _f, _i, _i, _p]),
     "iseg_beam_reorder": (_i, [_p, _l, _l, _l, _l, _p, _l, _l, _p, _l, _p, _l, _i, _p, _l, _i, _p]),
+    "iseg_contrastive_candidates_supported": (_i, [_l, _i, _i]),
+    "iseg_contrastive_candidates_splits": (_i, [_l, _l]),
+    "iseg_contrastive_candidates_scratch_bytes": (_z, [_l, _l, _i, _i]),
+    "iseg_contrastive_candidates": (_i, [_p, _l, _p, _i, _p, _p, _p, _z, _l, _l, _i, _f, _i, _i, _p]),
+    "iseg_contrastive_select_supported": (_i, [_l, _i, _i]),
+    "iseg_contrastive_select_splits": (_i, [_l, _l, _l, _i, _i]),
+    "iseg_contrastive_select_scratch_bytes": (_z, [_l, _l, _l, _i, _i, _i]),
+    "iseg_contrastive_select": (_i, [_p, _l, _l, _l, _l, _p, _l, _p, _p, _p, _p, _p, _z, _l, _l, _i, _f, _i, _i, _p]),
+    "iseg_contrastive_commit": (_i, [_p, _l, _l, _l, _l, _p, _l, _l, _l, _i, _p, _l, _l, _l, _p, _l, _l, _i, _p, _l, _i, _p]),
     "iseg_lm_head_ce_chunk_default": (_i, [_l, _l]),
     "iseg_lm_head_ce_scratch_bytes": (_z, [_l]),
     "iseg_lm_head_ce_chunk_fwd": (_i, [_p, _l, _p, _p, _p, _p, _p, _l, _l, _l, _p]),

@@ -9,7 +9,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libiseg_hip.so")
-SOURCES = ["api.hip", "gemm.hip", "gemm_nn.hip", "gemm_nt.hip", "gemm_tn.hip", "norm.hip", "dwconv.hip", "dwconv_mfma.hip", "dwconv_wgrad_mfma.hip", "dwconv_strided.hip", "elementwise.hip", "resize.hip", "loss.hip", "confusion.hip", "ohem.hip", "mask_loss.hip", "sod_metrics.hip", "sod_fmv2.hip", "ccl.hip", "optim.hip", "misc.hip", "attention.hip", "dcnv3.hip", "defattn.hip", "winattn.hip", "flashattn.hip", "selfattn.hip", "mlp_fused.hip", "mlp_wgrad.hip", "mlp_bwd_onepass.hip", "conv_igemm.hip", "conv_patchify.hip", "augment.hip", "projective.hip", "grn.hip", "eva.hip", "comm.hip", "mbconv.hip", "sepconv.hip", "jpu.hip", "resblock.hip", "gemma.hip", "gemma_decode.hip", "decode_commit.hip", "token_sample.hip", "beam_search.hip", "lm_head_ce.hip"]
+SOURCES = ["api.hip", "gemm.hip", "gemm_nn.hip", "gemm_nt.hip", "gemm_tn.hip", "norm.hip", "dwconv.hip", "dwconv_mfma.hip", "dwconv_wgrad_mfma.hip", "dwconv_strided.hip", "elementwise.hip", "resize.hip", "loss.hip", "confusion.hip", "ohem.hip", "mask_loss.hip", "sod_metrics.hip", "sod_fmv2.hip", "ccl.hip", "optim.hip", "misc.hip", "attention.hip", "dcnv3.hip", "defattn.hip", "winattn.hip", "flashattn.hip", "selfattn.hip", "mlp_fused.hip", "mlp_wgrad.hip", "mlp_bwd_onepass.hip", "conv_igemm.hip", "conv_patchify.hip", "augment.hip", "projective.hip", "grn.hip", "eva.hip", "comm.hip", "mbconv.hip", "sepconv.hip", "jpu.hip", "resblock.hip", "gemma.hip", "gemma_decode.hip", "decode_commit.hip", "token_sample.hip", "beam_search.hip", "contrastive.hip", "lm_head_ce.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
          "-Wno-unused-result"] + [f"-D{d}" for d in os.environ.get("ISEG_BUILD_DEFINES", "").split() if d]
 

@@ -4,7 +4,7 @@
 //
 // Select.  Within one row the score (x - max) / T - log sum exp + log_probs[j] is a monotone function of x, so a row's candidates are its nb
 // first entries in the order of order_keys.h (stored value descending, then index ascending), and the logits are read once:
-//   pass 1  one workgroup per (row, chunk of whole 2048-element tiles), four tiles in flight per trip.  Per trip: the trip's top key (wave
+//   pass 1  (topk_chunks.h, shared with contrastive.hip) one workgroup per (row, chunk of whole 2048-element tiles), four tiles in flight per trip.  Per trip: the trip's top key (wave
 //           maxima through LDS); the running maximum moves to it and every thread rescales its own fp64 weight sum by exp2 in fp64 (once per
 //           trip at most); the weights of the trip's 32 elements per thread, relative to the running maximum, are added in fp64; each wavefront
 //           then extracts, by up to nb maxima over its lanes' packed (key, index) pairs, those of its entries that beat the workgroup's current
@@ -22,6 +22,7 @@
 #include "common.h"
 #include "iseg_hip.h"
 #include "order_keys.h"
+#include "topk_chunks.h"
 
 #include <limits.h>
 #include <math.h>
@@ -29,150 +30,10 @@
 
 namespace {
 
-constexpr int BS_TILE = 2048;            // elements per tile: 256 threads x 8
-constexpr int BS_P1_THREADS = 256;
-constexpr int BS_P1_WAVES = BS_P1_THREADS / 64;
-constexpr int BS_VPL = 4;                // 8-element vectors (tiles) a thread loads before it works on them
-constexpr int BS_MAX_NB = 16;
-constexpr int BS_P2_THREADS = BS_MAX_NB * 64;      // a wavefront per beam row
-constexpr int64_t BS_VMAX = 1 << 20;
 constexpr int BS_RE_THREADS = 256;
 constexpr int64_t BS_RE_GRID_CAP = 16384;
 
 typedef __attribute__((ext_vector_type(4))) unsigned int bs_u32x4;      // one 16-byte column of the cache
-
-static_assert(BS_P1_WAVES * BS_MAX_NB == 64, "the pass-1 merge gives one wavefront entry to each lane of the first wavefront");
-
-// c is earlier in the order than nothing yet (`first`) or strictly later than `prev`, the entry taken last: the next to take is the largest such
-__device__ __forceinline__ bool bs_open(u64 c, u64 prev, bool first) { return first || c < prev; }
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-// exp2((x - m) c), c = log2(e) / T in fp64: the exponent is exact to 2^-53, hi is its fp32 head and lo the rest (|lo| <= 2^-24 |hi|), so
-// exp2(hi + lo) = exp2(hi) (1 + lo ln 2) up to (lo ln 2)^2 / 2 < 2^-34 where exp2(hi) is not flushed to 0.  x = -inf weighs 0.
-__device__ __forceinline__ float bs_weight(float x, float m, double c) {
-    const double e = ((double)x - (double)m) * c;
-    const float hi = (float)e;
-    const float lo = fabsf(hi) <= FLT_MAX ? (float)(e - (double)hi) : 0.f;
-    return __builtin_amdgcn_exp2f(hi) * fmaf(lo, 0.6931471805599453f, 1.f);
-}
-
-// blockIdx.x = row * splits + split.  Record of pstride u64: the bits of the fp64 weight sum relative to the chunk's own maximum (the value of
-// the first pair's key; 0 unless that is finite), then nb packed (key, index) pairs in the row's order, 0 where the chunk has fewer elements.
-template <class T>
-__global__ __launch_bounds__(BS_P1_THREADS) void beam_select_partial_kernel(const T* __restrict__ logits, int64_t ld, u64* __restrict__ part, int pstride,
-                                                                            int V, int splits, int tiles, int nb, double cexp, int vec) {
-    constexpr int KB = KeyBits<T>::value;
-    __shared__ u64 top[BS_MAX_NB];
-    __shared__ u64 wtop[BS_P1_WAVES][BS_MAX_NB];
-    __shared__ u64 wmax[BS_P1_WAVES];
-    __shared__ double wsum[BS_P1_WAVES];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t rowi = blockIdx.x / splits;
-    const int split = (int)(blockIdx.x % splits);
-    const T* row = logits + rowi * ld;
-    const int t0 = (int)((int64_t)split * tiles / splits), t1 = (int)((int64_t)(split + 1) * tiles / splits);
-    const int begin = t0 * BS_TILE, end = t1 * BS_TILE < V ? t1 * BS_TILE : V;
-
-    if (tid < BS_MAX_NB) top[tid] = 0;
-    __syncthreads();
-    uint32_t runkey = 0;      // the top key so far (every key of an element is > 0)
-    double s = 0.0;           // this thread's weights relative to value_of(runkey)
-    float x[BS_VPL][8];
-    int n[BS_VPL];
-    u64 pk[BS_VPL][8];
-    for (int b0 = begin; b0 < end; b0 += BS_VPL * BS_TILE) {      // the same trips for every thread: there are barriers inside
-        const int i0 = b0 + tid * 8;
-#pragma unroll
-        for (int v = 0; v < BS_VPL; ++v) n[v] = load8(row, i0 + v * BS_TILE, end, vec, x[v]);
-        u64 lm = 0;
-#pragma unroll
-        for (int v = 0; v < BS_VPL; ++v)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                pk[v][j] = j < n[v] ? pack_top(key_of<KB>(x[v][j]), i0 + v * BS_TILE + j) : 0;
-                lm = pk[v][j] > lm ? pk[v][j] : lm;
-            }
-        const u64 wm = wave_max_u64(lm);
-        if (lane == 0) wmax[wave] = wm;
-        __syncthreads();
-        u64 bm = wmax[0];
-#pragma unroll
-        for (int w = 1; w < BS_P1_WAVES; ++w) bm = wmax[w] > bm ? wmax[w] : bm;
-        const u64 tau = top[nb - 1];      // an entry has to beat the current nb-th to enter the list
-
-        // ---- the running maximum and this thread's share of the weight sum ----
-        const uint32_t bkey = (uint32_t)(bm >> 32);
-        if (bkey > runkey) {
-            s = key_finite<KB>(runkey) && key_finite<KB>(bkey) ? s * exp2(((double)value_of<KB>(runkey) - (double)value_of<KB>(bkey)) * cexp) : 0.0;
-            runkey = bkey;
-        }
-        if (key_finite<KB>(runkey)) {
-            const float m = value_of<KB>(runkey);
-#pragma unroll
-            for (int v = 0; v < BS_VPL; ++v)
-#pragma unroll
-                for (int j = 0; j < 8; ++j)
-                    if (j < n[v]) s += (double)bs_weight(x[v][j], m, cexp);
-        }
-
-        // ---- this wavefront's entries that beat tau, in order ----
-        bool live = wm > tau;
-        u64 prev = 0;
-        for (int r = 0; r < nb; ++r) {
-            u64 res = 0;
-            if (live) {
-                u64 l = 0;
-#pragma unroll
-                for (int v = 0; v < BS_VPL; ++v)
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const u64 c = pk[v][j];
-                        l = (bs_open(c, prev, r == 0) && c > l) ? c : l;
-                    }
-                res = wave_max_u64(l);
-                if (res <= tau) res = 0, live = false;
-                prev = res;
-            }
-            if (lane == 0) wtop[wave][r] = res;
-        }
-        __syncthreads();
-        // ---- the first wavefront merges them with the list (lane l: entry l & 15 of wavefront l >> 4, and entry l of the list) ----
-        if (wave == 0 && bm > tau) {
-            const u64 c0 = (lane & 15) < nb ? wtop[lane >> 4][lane & 15] : 0;
-            const u64 c1 = lane < nb ? top[lane] : 0;
-            u64 mine = 0;
-            prev = 0;
-            for (int r = 0; r < nb; ++r) {
-                u64 l = bs_open(c0, prev, r == 0) ? c0 : 0;
-                l = (bs_open(c1, prev, r == 0) && c1 > l) ? c1 : l;
-                const u64 res = wave_max_u64(l);
-                if (lane == r) mine = res;
-                prev = res;
-                if (res == 0) break;
-            }
-            if (lane < nb) top[lane] = mine;
-        }
-        // (no barrier here: the next trip's first one orders these writes in front of every read of `top`, and wmax / wtop are rewritten only
-        // after a barrier that their readers reach after reading)
-    }
-    __syncthreads();
-    s = wave_sum_f64(s);
-    if (lane == 0) wsum[wave] = s;
-    __syncthreads();
-    u64* p = part + (size_t)blockIdx.x * pstride;
-    if (tid == 0) {
-        double total = wsum[0];
-#pragma unroll
-        for (int w = 1; w < BS_P1_WAVES; ++w) total += wsum[w];
-        p[0] = (u64)__double_as_longlong(key_finite<KB>(runkey) ? total : 0.0);
-    }
-    if (tid < nb) p[1 + tid] = top[tid];
-}
 
 // blockIdx.x = group; wavefront j owns beam row j
 template <class T>
@@ -187,36 +48,14 @@ __global__ __launch_bounds__(BS_P2_THREADS) void beam_select_merge_kernel(const 
     u64 mine = 0;      // lane r < nb of wavefront j < nb: candidate r of row j as (key of the fp32 score, flat index j V + token)
     if (j < nb) {
         const u64* prow = part + (size_t)(g * nb + j) * splits * pstride;
-        u64 best = 0;
-        for (int sp = lane; sp < splits; sp += 64) {
-            const u64 e = prow[(size_t)sp * pstride + 1];
-            best = e > best ? e : best;
-        }
-        const uint32_t topkey = (uint32_t)(wave_max_u64(best) >> 32);
+        const uint32_t topkey = bs_row_top(prow, pstride, splits, lane);
         const float lp = log_probs[g * nb + j];
         if (!key_finite<KB>(topkey) || lp != lp) {      // the row's scores are all NaN: its first tokens
             if (lane < nb && lane < V) mine = pack_top(key_of<32>(NAN), j * V + lane);
         } else {
             const float M = value_of<KB>(topkey);
-            double acc = 0.0;      // a lane adds its chunks in chunk order; chunks of -inf alone weigh nothing
-            for (int sp = lane; sp < splits; sp += 64) {
-                const uint32_t mk = (uint32_t)(prow[(size_t)sp * pstride + 1] >> 32);
-                if (key_finite<KB>(mk))
-                    acc += exp2(((double)value_of<KB>(mk) - (double)M) * cexp) * __longlong_as_double((long long)prow[(size_t)sp * pstride]);
-            }
-            const double lse = log(wave_sum_f64(acc));
-            u64 prev = 0, entry = 0;
-            for (int r = 0; r < nb; ++r) {      // the row's r-th entry over all records
-                u64 l = 0;
-                for (int i = lane; i < splits * nb; i += 64) {
-                    const u64 c = prow[(size_t)(i / nb) * pstride + 1 + i % nb];
-                    l = (bs_open(c, prev, r == 0) && c > l) ? c : l;
-                }
-                const u64 res = wave_max_u64(l);
-                if (lane == r) entry = res;
-                prev = res;
-                if (res == 0) break;
-            }
+            const double lse = log(bs_row_sum<KB>(prow, pstride, splits, lane, M, cexp));
+            const u64 entry = bs_row_entries(prow, pstride, splits, nb, lane);
             if (lane < nb && entry) {
                 const float xv = value_of<KB>((uint32_t)(entry >> 32));
                 const int idx = (int)(0xFFFFFFFFu - (uint32_t)(entry & 0xFFFFFFFFu));
@@ -314,20 +153,6 @@ __global__ __launch_bounds__(BS_RE_THREADS) void beam_reorder_prompt_kernel(I* p
     }
 }
 
-int bs_tiles(int64_t V) { return (int)ceil_div64(V, BS_TILE); }
-
-// chunks of the launcher's own plan: enough workgroups for two per CU of a 256-CU chip, at least two tiles per chunk
-int bs_plan(int64_t rows, int64_t V) {
-    const int64_t want = ceil_div64(512, rows < 1 ? 1 : rows), most = bs_tiles(V) / 2;
-    return (int)(want < most ? want : most < 1 ? 1 : most);
-}
-
-int bs_resolve(int64_t rows, int64_t V, int splits) {
-    if (splits <= 0) return bs_plan(rows, V);
-    const int tiles = bs_tiles(V);
-    return splits < tiles ? splits : tiles;
-}
-
 // the template's beam capacity: nb rounded up to 2, 4, 8 or 16
 template <class F> int by_beams(int nb, F&& f) {
     if (nb <= 2) return f(IntC<2>{});
@@ -374,7 +199,7 @@ extern "C" int iseg_beam_select(const void* logits, int64_t ld, const float* log
     return by_dtype(dtype, who, [&](auto t) {
         using E = decltype(t);
         hipLaunchKernelGGL((beam_select_partial_kernel<E>), dim3((unsigned)(rows * nsplit)), dim3(BS_P1_THREADS), 0, stream, (const E*)logits, ld, part,
-                           1 + nb, (int)V, nsplit, tiles, nb, cexp, vec);
+                           1 + nb, (int)V, nsplit, tiles, nb, cexp, vec, (const int32_t*)nullptr, 1);
         hipLaunchKernelGGL((beam_select_merge_kernel<E>), dim3((unsigned)(rows / nb)), dim3(BS_P2_THREADS), 0, stream, log_probs, parents, tokens,
                            new_log_probs, (const u64*)part, 1 + nb, (int)V, nsplit, nb, cexp, (double)temperature);
         return iseg_check_launch(who);

@@ -1,6 +1,6 @@
-// The total order of a logits row that token_sample.hip and beam_search.hip share: value descending, then index ascending; NaN above +inf above
+// The total order of a logits row that token_sample.hip, beam_search.hip and contrastive.hip share: value descending, then index ascending; NaN above +inf above
 // the finite values above -inf; -0 ties with +0.  Every element gets a monotone integer key of its STORED value (16 bits for bf16, 32 for fp32;
-// all NaNs share the top key), so ties are exactly the input's.  With the 8-element row loads and the 64-bit wavefront reductions both files use.
+// all NaNs share the top key), so ties are exactly the input's.  With the 8-element row loads and the 64-bit wavefront reductions these files use.
 #pragma once
 #include "common.h"
 

@@ -3721,19 +3721,26 @@ def beam_fused():
     return os.environ.get("ISEG_BEAM_FUSED", "1") != "0"
 
 
+def _topk_ordered(values, k):
+    """the k first entries of every row in the order value descending, then index ascending, NaN above every number -> (values, indices)"""
+    N = values.shape[-1]
+    key = torch.nan_to_num(values, nan=math.inf, posinf=math.inf, neginf=-math.inf)
+    nth = torch.topk(key, k, dim=-1).values[:, -1:]
+    # everything above the k-th value, then that value's ties, each by index: all ranks are distinct, so this top-k is a set
+    rank = (key > nth).to(torch.int64) * (2 * N) + (key == nth).to(torch.int64) * N + (N - 1 - torch.arange(N, device=values.device))
+    idx = torch.topk(rank, k, dim=-1).indices
+    idx = idx.gather(-1, torch.sort(key.gather(-1, idx), dim=-1, descending=True, stable=True).indices)
+    return values.gather(-1, idx), idx
+
+
 def _beam_select_composed(logits, log_probs, nb, temperature):
     """keras_nlp's op sequence in plain torch: the fp32 log-softmax of logits / T plus the running score, [B, nb V], top-k.  The order is pinned
     down as the kernel's: score descending, ties by flat index ascending, NaN above every number"""
     R, V = logits.shape
     B, N = R // nb, nb * V
     scores = (torch.log_softmax(logits.to(torch.float32) / temperature, dim=-1) + log_probs[:, None]).reshape(B, N)
-    key = torch.nan_to_num(scores, nan=math.inf, posinf=math.inf, neginf=-math.inf)
-    nth = torch.topk(key, nb, dim=-1).values[:, -1:]
-    # everything above the nb-th value, then that value's ties, each by index: all ranks are distinct, so this top-k is a set
-    rank = (key > nth).to(torch.int64) * (2 * N) + (key == nth).to(torch.int64) * N + (N - 1 - torch.arange(N, device=logits.device))
-    flat = torch.topk(rank, nb, dim=-1).indices
-    flat = flat.gather(-1, torch.sort(key.gather(-1, flat), dim=-1, descending=True, stable=True).indices)
-    return ((flat // V).to(torch.int32).reshape(R), (flat % V).to(torch.int32).reshape(R), scores.gather(-1, flat).reshape(R))
+    best, flat = _topk_ordered(scores, nb)
+    return ((flat // V).to(torch.int32).reshape(R), (flat % V).to(torch.int32).reshape(R), best.reshape(R))
 
 
 def beam_select(logits, log_probs, num_beams, temperature=1.0, splits=0):
@@ -3825,6 +3832,199 @@ def beam_reorder(cache, prompt, mask, parents, tokens, index, num_beams, length=
         prompt = prompt.index_select(0, rows)
         prompt[:, index] = torch.where(mask[:, index], prompt[:, index], tokens.to(prompt.dtype))
         return (None if cache is None else cache.index_select(0, rows)), prompt
+
+
+CONTRASTIVE_MAX_K = 16
+
+
+def contrastive_fused():
+    """True where a contrastive step on device tensors takes the kernels of csrc/contrastive.hip: ISEG_CONTRASTIVE_FUSED unset or not "0" """
+    return os.environ.get("ISEG_CONTRASTIVE_FUSED", "1") != "0"
+
+
+def _check_contrastive_k(who, k):
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= CONTRASTIVE_MAX_K:
+        raise ValueError(f"{who}: k is an integer in 1 .. {CONTRASTIVE_MAX_K}, got {k!r}")
+
+
+def contrastive_candidates(logits, k, temperature=1.0, row_map=None, splits=0):
+    """The candidates of one step of keras_nlp.samplers.ContrastiveSampler.  logits [R, V] or a [R, 1, V] view -> (probs fp32 [B, k], tokens int32
+    [B, k]): the k largest of softmax(logits / temperature) per output row, in fp32, probability descending, ties by token id ascending.
+    row_map None: B = R.  row_map int32 [B] with R = B g: output row b reads logits row b g + row_map[b] (values in [0, g)), which is how a step
+    reads the previous step's winners out of its [B k, V] logits.  A row whose largest logit is NaN or +inf has NaN probabilities and the
+    tokens 0 .. k - 1 (include/iseg_hip.h has the full statement).
+    Device tensors in bf16 or fp32 with V <= 2^20 take the kernels of csrc/contrastive.hip (two launches, the logits read once, no [B, V]
+    tensor, no gather); CPU tensors, other dtypes and ISEG_CONTRASTIVE_FUSED=0 the composed route, the reference's op sequence in torch in
+    fp32.  Inference only."""
+    if logits.requires_grad:
+        raise RuntimeError("contrastive_candidates: contrastive search is inference only (the logits require grad)")
+    if logits.dim() == 3 and logits.shape[1] == 1:
+        logits = logits[:, 0]
+    _check_contrastive_k("contrastive_candidates", k)
+    if logits.dim() != 2:
+        raise ValueError(f"contrastive_candidates: logits is [R, V] or [R, 1, V], got {tuple(logits.shape)}")
+    R, V = logits.shape
+    temperature = float(temperature)
+    if not logits.dtype.is_floating_point:
+        raise ValueError(f"contrastive_candidates: logits are floating point, got {logits.dtype}")
+    if V < 1 or k > V:
+        raise ValueError(f"contrastive_candidates: k = {k} candidates need a vocabulary of at least k entries, got {V}")
+    if not (temperature > 0.0 and math.isfinite(temperature)):
+        raise ValueError(f"contrastive_candidates: temperature must be positive and finite, got {temperature}")
+    B = R
+    if row_map is not None:
+        if row_map.dim() != 1 or row_map.dtype != torch.int32 or row_map.device != logits.device:
+            raise ValueError(f"contrastive_candidates: row_map is an int32 [B] on the logits' device, got {tuple(row_map.shape)} {row_map.dtype} on "
+                             f"{row_map.device}")
+        B = row_map.shape[0]
+        if (B == 0 and R != 0) or (B > 0 and R % B):
+            raise ValueError(f"contrastive_candidates: {R} logits rows are no whole number of groups for {B} output rows")
+    if nn.dry_run():
+        return _dry((B, k), logits, torch.float32), _dry((B, k), logits, torch.int32)
+    with torch.no_grad():
+        if B == 0:
+            return (torch.empty((0, k), dtype=torch.float32, device=logits.device), torch.empty((0, k), dtype=torch.int32, device=logits.device))
+        if logits.is_cuda and contrastive_fused() and logits.dtype in (torch.bfloat16, torch.float32) and V <= SAMPLE_MAX_VOCAB:
+            if logits.stride(1) != 1 or (R > 1 and logits.stride(0) < V):
+                logits = logits.contiguous()
+            return K.contrastive_candidates(logits, k, temperature, None if row_map is None else _c(row_map), splits)
+        if row_map is not None:
+            g = R // B
+            logits = logits.index_select(0, torch.arange(B, device=logits.device) * g + row_map.clamp(0, g - 1).to(torch.int64))
+        probs, tokens = _topk_ordered(torch.softmax(logits.to(torch.float32) / temperature, dim=-1), k)
+        dead = torch.isnan(probs).any(dim=-1, keepdim=True)      # a NaN row: every token ties, the first k ids
+        tokens = torch.where(dead, torch.arange(k, device=logits.device).expand(B, k), tokens)
+        return torch.where(dead, torch.full_like(probs, math.nan), probs), tokens.to(torch.int32)
+
+
+def _contrastive_select_composed(hidden_states, index, cand_hidden, probs, alpha, k):
+    """keras_nlp's op sequence in plain torch, in fp32: the history repeated k times, one batched matmul, the norms, the division, max, the score,
+    argmax (the first maximal score; NaN above every number)"""
+    B = hidden_states.shape[0]
+    h1 = torch.repeat_interleave(hidden_states[:, :index].to(torch.float32), k, dim=0)      # [B k, index, D]
+    h2 = cand_hidden.to(torch.float32)[:, :, None]                                            # [B k, D, 1]
+    sim = torch.matmul(h1, h2)[:, :, 0] / (torch.linalg.vector_norm(h1, dim=-1) * torch.linalg.vector_norm(h2, dim=-2))
+    max_sim = torch.max(sim, dim=-1).values
+    scores = (1.0 - alpha) * probs - alpha * max_sim
+    return torch.argmax(scores.view(B, k), dim=-1).to(torch.int32), scores, max_sim
+
+
+def contrastive_select(hidden_states, index, cand_hidden, probs, alpha, splits=0):
+    """The selection of one step of keras_nlp.samplers.ContrastiveSampler.  hidden_states [B, S, D] (its first `index` positions hold the hidden
+    states of the tokens so far; later positions are never read), cand_hidden [B k, D] (row b k + j: the hidden state of candidate j of batch
+    row b), probs fp32 [B k] the candidates' probabilities, 0 <= alpha <= 1 -> (winner int32 [B], scores fp32 [B k], max_sim fp32 [B k]):
+        max_sim = max over t < index of the cosine similarity of hidden_states[b, t] and the candidate (fp32, no epsilon: a zero vector gives NaN),
+        scores = (1 - alpha) probs - alpha max_sim,   winner[b] = the first maximal score of the row's k (NaN ranks above every number).
+    Device tensors in bf16 or fp32 with D a multiple of 8 (up to 16384) take the kernels of csrc/contrastive.hip: one pass over the filled
+    prefix, the row's candidates resident in LDS, no [B k, index] similarity matrix, results bit-identical for every `splits`.  CPU tensors,
+    other shapes and dtypes and ISEG_CONTRASTIVE_FUSED=0 take the composed route, the reference's op sequence in torch in fp32.  Inference
+    only."""
+    who = "contrastive_select"
+    for t in (hidden_states, cand_hidden, probs):
+        if t.requires_grad:
+            raise RuntimeError(f"{who}: contrastive search is inference only (an input requires grad)")
+    if hidden_states.dim() != 3 or cand_hidden.dim() != 2 or cand_hidden.shape[1] != hidden_states.shape[2]:
+        raise ValueError(f"{who}: hidden_states is [B, S, D] and cand_hidden [B * k, D], got {tuple(hidden_states.shape)} and {tuple(cand_hidden.shape)}")
+    B, S, D = hidden_states.shape
+    R = cand_hidden.shape[0]
+    if (B == 0 and R != 0) or (B > 0 and (R % B or not 1 <= R // B <= CONTRASTIVE_MAX_K)):
+        raise ValueError(f"{who}: {R} candidate rows are no whole number of groups of 1 .. {CONTRASTIVE_MAX_K} for {B} batch rows")
+    k = R // B if B else 1
+    if not hidden_states.dtype.is_floating_point or cand_hidden.dtype != hidden_states.dtype:
+        raise ValueError(f"{who}: hidden_states and cand_hidden share a floating-point dtype, got {hidden_states.dtype} and {cand_hidden.dtype}")
+    if tuple(probs.shape) != (R,) or probs.dtype != torch.float32:
+        raise ValueError(f"{who}: probs is a float32 [{R}], got {tuple(probs.shape)} {probs.dtype}")
+    index, alpha = int(index), float(alpha)
+    if not 1 <= index <= S:
+        raise ValueError(f"{who}: 1 <= index <= S = {S} filled positions, got {index}")
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"{who}: 0 <= alpha <= 1, got {alpha}")
+    for name, t in (("cand_hidden", cand_hidden), ("probs", probs)):
+        if t.device != hidden_states.device:
+            raise ValueError(f"{who}: {name} lies on {t.device}, the hidden states on {hidden_states.device}")
+    if nn.dry_run():
+        return _dry((B,), probs, torch.int32), _dry((R,), probs, torch.float32), _dry((R,), probs, torch.float32)
+    with torch.no_grad():
+        if B == 0:
+            return (torch.empty((0,), dtype=torch.int32, device=probs.device), torch.empty((0,), dtype=torch.float32, device=probs.device),
+                    torch.empty((0,), dtype=torch.float32, device=probs.device))
+        if (hidden_states.is_cuda and contrastive_fused() and hidden_states.dtype in (torch.bfloat16, torch.float32)
+                and K.contrastive_select_supported(D, k, hidden_states.dtype)):
+            if (hidden_states.stride(2) != 1 or hidden_states.stride(1) % 8 or hidden_states.stride(1) < D or hidden_states.data_ptr() % 16
+                    or (B > 1 and (hidden_states.stride(0) % 8 or hidden_states.stride(0) < S * hidden_states.stride(1)))):
+                hidden_states = hidden_states.contiguous()
+            if cand_hidden.stride(1) != 1 or cand_hidden.data_ptr() % 16 or (R > 1 and (cand_hidden.stride(0) % 8 or cand_hidden.stride(0) < D)):
+                cand_hidden = cand_hidden.contiguous()
+            return K.contrastive_select(hidden_states, index, cand_hidden, _c(probs), alpha, splits)
+        return _contrastive_select_composed(hidden_states, index, cand_hidden, probs, alpha, k)
+
+
+def contrastive_commit(cache, prompt, hidden_states, cand_hidden, winner, index, k, position=None):
+    """The end of one step of keras_nlp.samplers.ContrastiveSampler -> (cache, prompt, hidden_states) with, for w = winner[b] and every j < k:
+        cache[b k + j, :, :, position] = cache[b k + w, :, :, position];  prompt[b k + j, index] = prompt[b k + w, index];
+        hidden_states[b, index] = cand_hidden[b k + w].
+    cache [B k, L, 2, Sc, nkv, h] or None (Sc: the cache's own number of positions), prompt [B k, S] int32 or int64, hidden_states [B, Sh, D],
+    cand_hidden [B k, D], winner int32 [B] as contrastive_select returns it; position: the cache position the candidates' step wrote (default
+    `index`: call_with_cache's step index + 1 writes position index).
+    On device tensors (csrc/contrastive.hip, one launch) all three are updated IN PLACE and returned, and only that one position moves: this
+    relies on the k rows of a group being equal at every other position, as they are when the cache was repeated k times once and every step
+    was committed.  A group whose winner lies outside [0, k) is left untouched.  CPU tensors, a cache that is not contiguous or whose
+    [nkv, h] rows are no multiple of 16 bytes, hidden states whose rows are no multiple of 16 bytes and ISEG_CONTRASTIVE_FUSED=0 take the
+    composed route, the reference's: new tensors, the whole cache gathered by the winners and repeated k times."""
+    who = "contrastive_commit"
+    _check_contrastive_k(who, k)
+    index = int(index)
+    if prompt.dim() != 2 or prompt.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{who}: prompt is an int32 or int64 [B * k, S], got {tuple(prompt.shape)} {prompt.dtype}")
+    R, S = prompt.shape
+    if R % k:
+        raise ValueError(f"{who}: {R} rows are no whole number of groups of {k} candidates")
+    B = R // k
+    if tuple(winner.shape) != (B,) or winner.dtype != torch.int32:
+        raise ValueError(f"{who}: winner is an int32 [{B}], got {tuple(winner.shape)} {winner.dtype}")
+    if (hidden_states.dim() != 3 or hidden_states.shape[0] != B or tuple(cand_hidden.shape) != (R, hidden_states.shape[2])
+            or cand_hidden.dtype != hidden_states.dtype):
+        raise ValueError(f"{who}: hidden_states is [{B}, Sh, D] and cand_hidden [{R}, D] of its dtype, got {tuple(hidden_states.shape)} "
+                         f"{hidden_states.dtype} and {tuple(cand_hidden.shape)} {cand_hidden.dtype}")
+    if not 0 <= index < S or index >= hidden_states.shape[1]:
+        raise ValueError(f"{who}: position {index} does not lie inside a prompt of {S} and a history of {hidden_states.shape[1]}")
+    if cache is None:
+        position = 0
+    else:
+        if not torch.is_tensor(cache) or cache.dim() != 6 or cache.shape[0] != R:
+            raise ValueError(f"{who}: the cache is a [{R}, L, 2, S, nkv, h] tensor or None, got {tuple(cache.shape) if torch.is_tensor(cache) else cache!r}")
+        position = index if position is None else int(position)
+        if not 0 <= position < cache.shape[3]:
+            raise ValueError(f"{who}: position {position} does not lie inside a cache of {cache.shape[3]}")
+    for name, t in (("hidden_states", hidden_states), ("cand_hidden", cand_hidden), ("winner", winner), ("cache", cache)):
+        if t is not None and t.device != prompt.device:
+            raise ValueError(f"{who}: {name} lies on {t.device}, the prompt on {prompt.device}")
+        if t is not None and t.requires_grad:
+            raise RuntimeError(f"{who}: contrastive search is inference only ({name} requires grad)")
+    if nn.dry_run() or R == 0:
+        return cache, prompt, hidden_states
+    with torch.no_grad():
+        es, D = hidden_states.element_size(), hidden_states.shape[2]
+        fused = (prompt.is_cuda and contrastive_fused() and prompt.stride(1) == 1 and (R == 1 or prompt.stride(0) >= S)
+                 and hidden_states.dtype in (torch.bfloat16, torch.float32) and (D * es) % 16 == 0 and hidden_states.stride(2) == 1
+                 and cand_hidden.stride(1) == 1 and hidden_states.data_ptr() % 16 == 0 and cand_hidden.data_ptr() % 16 == 0
+                 and (hidden_states.stride(1) * es) % 16 == 0 and hidden_states.stride(1) >= D
+                 and (B == 1 or ((hidden_states.stride(0) * es) % 16 == 0 and hidden_states.stride(0) >= hidden_states.shape[1] * hidden_states.stride(1)))
+                 and (R == 1 or ((cand_hidden.stride(0) * es) % 16 == 0 and cand_hidden.stride(0) >= D)))
+        if fused and cache is not None:
+            fused = (cache.is_cuda and cache.is_contiguous() and cache.data_ptr() % 16 == 0
+                     and (cache.shape[4] * cache.shape[5] * cache.element_size()) % 16 == 0)
+        if fused:
+            K.contrastive_commit(cache, position, prompt, index, hidden_states, cand_hidden, _c(winner), k)
+            return cache, prompt, hidden_states
+        w = winner.clamp(0, k - 1).to(torch.int64)
+        rows = torch.arange(B, device=prompt.device) * k + w
+        prompt = torch.repeat_interleave(prompt.index_select(0, rows), k, dim=0)
+        hidden_states = hidden_states.clone()
+        hidden_states[:, index] = cand_hidden.index_select(0, rows)
+        if cache is not None:
+            cache = torch.repeat_interleave(cache.index_select(0, rows), k, dim=0)
+        return cache, prompt, hidden_states
 
 
 def decode_commit(prompt, mask, pos_d, cur_ids, done, tokens, end_token_id=None):

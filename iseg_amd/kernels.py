@@ -2480,6 +2480,109 @@ def beam_reorder(cache, length, prompt, mask, tokens, index, parents, num_beams)
 
 
 # ---------------------------------------------------------------------------------------------------------
+# contrastive search (csrc/contrastive.hip)
+# ---------------------------------------------------------------------------------------------------------
+def contrastive_candidates_supported(V, k, dtype):
+    return dtype in _DT and bool(_hip.lib().iseg_contrastive_candidates_supported(int(V), int(k), _DT[dtype]))
+
+
+def contrastive_candidates_splits(rows, V):
+    """the chunk count iseg_contrastive_candidates plans for these arguments"""
+    return int(_hip.lib().iseg_contrastive_candidates_splits(int(rows), int(V)))
+
+
+def contrastive_candidates(logits, k, temperature, row_map=None, splits=0):
+    """the k most probable tokens of every output row, as include/iseg_hip.h states it: logits [R, V] (rows of contiguous elements, any pitch >=
+    V); row_map None: R output rows; int32 [B]: output row b reads logits row b * (R // B) + row_map[b] -> (probs fp32 [B, k], tokens int32
+    [B, k]); splits = 0: the launcher's plan"""
+    _require_cuda(logits, row_map)
+    R, V = logits.shape
+    B = R if row_map is None else row_map.shape[0]
+    group = 1
+    if row_map is not None:
+        if row_map.dtype != torch.int32 or row_map.dim() != 1 or not row_map.is_contiguous() or B < 1 or R % B:
+            raise ValueError(f"contrastive_candidates: row_map is a contiguous int32 [B] with B dividing the {R} logits rows, got {tuple(row_map.shape)} "
+                             f"{row_map.dtype}")
+        group = R // B
+    L = _hip.lib()
+    probs = torch.empty((B, int(k)), dtype=torch.float32, device=logits.device)
+    tokens = torch.empty((B, int(k)), dtype=torch.int32, device=logits.device)
+    ws, nbytes = workspace(L.iseg_contrastive_candidates_scratch_bytes(B, V, int(k), int(splits)), logits.device)
+    _hip.check(L.iseg_contrastive_candidates(ptr(logits), logits.stride(0) if R > 1 else V, ptr(row_map), group, ptr(probs), ptr(tokens), ptr(ws), nbytes,
+                                             B, V, int(k), float(temperature), int(splits), dt(logits), stream()), "iseg_contrastive_candidates")
+    return probs, tokens
+
+
+def contrastive_select_supported(D, k, dtype):
+    return dtype in _DT and bool(_hip.lib().iseg_contrastive_select_supported(int(D), int(k), _DT[dtype]))
+
+
+def contrastive_select_splits(B, index, D, k, dtype):
+    """the number of position chunks iseg_contrastive_select plans for these arguments"""
+    return int(_hip.lib().iseg_contrastive_select_splits(int(B), int(index), int(D), int(k), _DT[dtype]))
+
+
+def contrastive_select(hidden_states, index, cand_hidden, probs, alpha, splits=0):
+    """hidden_states [B, S, D] (contiguous along D), its first `index` positions filled, cand_hidden [B * k, D] of the same dtype, probs fp32
+    [B * k] -> (winner int32 [B], scores fp32 [B * k], max_sim fp32 [B * k]) as include/iseg_hip.h states it; splits = 0: the launcher's plan"""
+    _require_cuda(hidden_states, cand_hidden, probs)
+    B, S, D = hidden_states.shape
+    R = cand_hidden.shape[0]
+    k = R // B
+    if cand_hidden.dim() != 2 or cand_hidden.shape[1] != D or R != B * k or cand_hidden.dtype != hidden_states.dtype or tuple(probs.shape) != (R,):
+        raise ValueError(f"contrastive_select: cand_hidden [B * k, {D}] of {hidden_states.dtype} and probs [B * k], got {tuple(cand_hidden.shape)} "
+                         f"{cand_hidden.dtype} and {tuple(probs.shape)}")
+    if hidden_states.stride(2) != 1 or cand_hidden.stride(1) != 1 or not probs.is_contiguous():
+        raise ValueError("contrastive_select: the hidden states are contiguous along D and probs is contiguous")
+    L = _hip.lib()
+    winner = torch.empty((B,), dtype=torch.int32, device=probs.device)
+    scores = torch.empty((R,), dtype=torch.float32, device=probs.device)
+    max_sim = torch.empty((R,), dtype=torch.float32, device=probs.device)
+    ws, nbytes = workspace(L.iseg_contrastive_select_scratch_bytes(B, int(index), D, k, int(splits), dt(hidden_states)), probs.device)
+    _hip.check(L.iseg_contrastive_select(ptr(hidden_states), hidden_states.stride(0) if B > 1 else S * hidden_states.stride(1), hidden_states.stride(1),
+                                         S, int(index), ptr(cand_hidden), cand_hidden.stride(0) if R > 1 else D, ptr(probs), ptr(winner), ptr(scores),
+                                         ptr(max_sim), ptr(ws), nbytes, B, D, k, float(alpha), int(splits), dt(hidden_states), stream()),
+               "iseg_contrastive_select")
+    return winner, scores, max_sim
+
+
+def contrastive_commit(cache, pos, prompt, index, hidden_states, cand_hidden, winner, k):
+    """the winner's state becomes its group's, IN PLACE (include/iseg_hip.h): position `pos` of cache [B * k, L, 2, Sc, nkv, h] (contiguous; None:
+    no cache), position `index` of prompt [B * k, S] (int32 or int64; None: none) and hidden_states[b, index] = cand_hidden[b * k + winner[b]]
+    (hidden_states [B, Sh, D]; None: none); winner int32 [B]"""
+    _require_cuda(cache, prompt, hidden_states, cand_hidden, winner)
+    B, k = winner.shape[0], int(k)
+    R = B * k
+    if winner.dtype != torch.int32 or winner.dim() != 1 or not winner.is_contiguous():
+        raise ValueError(f"contrastive_commit: winner is a contiguous int32 [B], got {tuple(winner.shape)} {winner.dtype}")
+    planes = Sc = row_bytes = 0
+    if cache is not None:
+        if cache.dim() != 6 or cache.shape[0] != R or not cache.is_contiguous():
+            raise ValueError(f"contrastive_commit: the cache is a contiguous [{R}, L, 2, Sc, nkv, h], got {tuple(cache.shape)} with strides {cache.stride()}")
+        planes, Sc, row_bytes = cache.shape[1] * cache.shape[2], cache.shape[3], cache.shape[4] * cache.shape[5] * cache.element_size()
+    S = ld_prompt = ids = 0
+    if prompt is not None:
+        if prompt.dim() != 2 or prompt.shape[0] != R or prompt.stride(1) != 1:
+            raise ValueError(f"contrastive_commit: prompt is [{R}, S] with contiguous rows, got {tuple(prompt.shape)}")
+        S, ids = prompt.shape[1], _IDS[prompt.dtype]
+        ld_prompt = prompt.stride(0) if R > 1 else S
+    hs_b = hs_t = Sh = ldc = D = 0
+    dtype = _DT[torch.float32]
+    if hidden_states is not None:
+        if (hidden_states.dim() != 3 or hidden_states.shape[0] != B or cand_hidden is None or tuple(cand_hidden.shape) != (R, hidden_states.shape[2])
+                or cand_hidden.dtype != hidden_states.dtype or hidden_states.stride(2) != 1 or cand_hidden.stride(1) != 1):
+            raise ValueError(f"contrastive_commit: hidden_states [{B}, Sh, D] and cand_hidden [{R}, D] share a dtype and are contiguous along D, got "
+                             f"{tuple(hidden_states.shape)} and {None if cand_hidden is None else tuple(cand_hidden.shape)}")
+        Sh, D = hidden_states.shape[1], hidden_states.shape[2]
+        hs_t = hidden_states.stride(1)
+        hs_b = hidden_states.stride(0) if B > 1 else Sh * hs_t
+        ldc = cand_hidden.stride(0) if R > 1 else D
+        dtype = dt(hidden_states)
+    _hip.call("iseg_contrastive_commit", ptr(cache), planes, Sc, row_bytes, int(pos), ptr(prompt), S, ld_prompt, int(index), ids, ptr(hidden_states), hs_b,
+              hs_t, Sh, ptr(cand_hidden), ldc, D, dtype, ptr(winner), B, k, stream())
+
+
+# ---------------------------------------------------------------------------------------------------------
 # chunked-vocabulary cross-entropy of the language-model head (csrc/lm_head_ce.hip)
 # ---------------------------------------------------------------------------------------------------------
 def lm_head_ce_chunk_default(M, V):

@@ -14,12 +14,15 @@ copies into a new one.  Single-token steps run on the split-KV decode kernels of
 index 0) on the training kernels of csrc/gemma.hip.  No padding mask is passed on the cached path (the reference passes none).
 
 compile(sampler=) takes "greedy" (the default: keras_nlp's greedy Sampler.__call__, `greedy_sample`) or an instance of nlp/samplers.py:
-GreedySampler, RandomSampler, TopKSampler, TopPSampler, BeamSampler.  The random ones choose each token with the fused kernels of
+GreedySampler, RandomSampler, TopKSampler, TopPSampler, BeamSampler, ContrastiveSampler.  The random ones choose each token with the fused kernels of
 csrc/token_sample.hip from one uniform per row and step.  BeamSampler(num_beams=nb) expands the seeded [B, ...] cache to [B nb, ...] once
 (call_with_cache does not care how large the batch is) and runs every step on the kernels of csrc/beam_search.hip: the selection reads the
 logits once, the cache is reordered in place over its filled prefix (ISEG_BEAM_FUSED=0: the composed route in torch; nlp/samplers.py has the
 algorithm and what it pins down beyond the reference).  generate_step returns the best beam; with return_all_beams=True it raises, because
-the {"token_ids", "padding_mask"} contract has no beam axis: call the sampler directly.  Every other string alias, "beam" included, raises
+the {"token_ids", "padding_mask"} contract has no beam axis: call the sampler directly.  ContrastiveSampler(k, alpha) is the one sampler that
+reads hidden states: generate_step hands it the hidden states of the seeding pass (hidden_states=, which no other sampler is passed), and a
+step runs on the kernels of csrc/contrastive.hip (ISEG_CONTRASTIVE_FUSED=0: the composed route; nlp/samplers.py has the algorithm): the cache
+is repeated k times once and one position per step moves, so k caches stay resident for the loop.  Every other string alias, "beam" included, raises
 NotImplementedError naming the classes.
 
 compile(graph_decode=True) (off by default; no counterpart in the reference, whose tf.function plays this role) makes one generated token one
@@ -33,11 +36,11 @@ graph, one launch in front of each replay, from the sampler's own generator: the
 token the loop reads nothing back.  With one it reads `done` every `check_every` replays (generate_step's keyword, default 16); the commit
 kernel freezes once every row is done, so the result does not depend on check_every, but up to check_every - 1 frozen replays each draw
 uniforms that the eager loop would not have drawn: the generator of a sampler that is reused afterwards is that far ahead.  A Sampler subclass
-of the caller's keeps the eager loop (its get_next_token may read on the host), and so does BeamSampler (a captured beam step would need the
-filled length in device memory); the fp32 compute dtype, ISEG_GEMMA_FUSED=0 and an unsupported
+of the caller's keeps the eager loop (its get_next_token may read on the host), and so do BeamSampler (a captured beam step would need the
+filled length in device memory) and ContrastiveSampler (likewise); the fp32 compute dtype, ISEG_GEMMA_FUSED=0 and an unsupported
 head width raise ValueError (a captured step cannot take the composed route).  release_decode_graphs() drops graphs, caches and buffers.
 
-Out of scope: the tokenizer and preprocessors (strings need a `preprocessor`, and none is built), presets, the contrastive sampler, training
+Out of scope: the tokenizer and preprocessors (strings need a `preprocessor`, and none is built), presets, training
 through the cache, paged caches."""
 import math
 import os
@@ -47,7 +50,7 @@ import torch
 from ... import functional as F
 from ... import nn
 from ...nn import Layer
-from ..samplers import BeamSampler, Sampler, sample_loop
+from ..samplers import BeamSampler, ContrastiveSampler, Sampler, sample_loop
 
 
 def lm_head_fused():
@@ -102,15 +105,16 @@ class GemmaCausalLM(Layer):
         self.built = True
 
     def compile(self, sampler="greedy", graph_decode=False, **unused):
-        """sampler: "greedy", or an instance of iseg_amd.nlp.samplers (GreedySampler, RandomSampler, TopKSampler, TopPSampler, BeamSampler or a
-        Sampler subclass of the caller's).  The other string aliases of keras_nlp.samplers.get are not built.
+        """sampler: "greedy", or an instance of iseg_amd.nlp.samplers (GreedySampler, RandomSampler, TopKSampler, TopPSampler, BeamSampler, ContrastiveSampler
+        or a Sampler subclass of the caller's).  The other string aliases of keras_nlp.samplers.get are not built.
         graph_decode=True: generate_step replays every decoding step from one captured HIP graph (the module docstring); off by default."""
         if not isinstance(graph_decode, bool):
             raise ValueError(f"GemmaCausalLM.compile: graph_decode is True or False, got {graph_decode!r}")
         if isinstance(sampler, str):
             if sampler != "greedy":
                 raise NotImplementedError(f'GemmaCausalLM.compile: the only string alias is "greedy", got {sampler!r}; pass an instance of '
-                                          "iseg_amd.nlp.samplers.GreedySampler, RandomSampler, TopKSampler, TopPSampler or BeamSampler instead")
+                                          "iseg_amd.nlp.samplers.GreedySampler, RandomSampler, TopKSampler, TopPSampler or BeamSampler instead "
+                                          "(or ContrastiveSampler)")
         elif not isinstance(sampler, Sampler):
             raise ValueError(f'GemmaCausalLM.compile: sampler is "greedy" or an iseg_amd.nlp.samplers.Sampler instance, got {sampler!r}')
         self.sampler = sampler
@@ -344,7 +348,7 @@ class GemmaCausalLM(Layer):
                 if 1 <= index < token_ids.shape[1] and sticky:
                     out = self._generate_graphed(token_ids, padding_mask, index, end_token_id, sampler, check_every)
                     return {"token_ids": out, "padding_mask": generated_padding_mask(out, padding_mask, end_token_id)}
-        _, cache = self._build_cache(token_ids)
+        hidden_states, cache = self._build_cache(token_ids)
         index = int(padding_mask.to(torch.int32).sum(dim=-1).min().item())
 
         def next(prompt, cache, index):
@@ -353,7 +357,9 @@ class GemmaCausalLM(Layer):
             logits, hidden_states, cache = self.call_with_cache(prompt[:, cache_update_index:cache_update_index + 1], cache, cache_update_index)
             return logits[:, 0], hidden_states[:, 0], cache
 
-        if isinstance(self.sampler, Sampler):
+        if isinstance(self.sampler, ContrastiveSampler):      # the one sampler that reads hidden states; no other is passed them
+            token_ids = self.sampler(next, token_ids, cache, index, padding_mask, end_token_id=end_token_id, hidden_states=hidden_states)
+        elif isinstance(self.sampler, Sampler):
             token_ids = self.sampler(next, token_ids, cache, index, padding_mask, end_token_id=end_token_id)
         else:
             token_ids = greedy_sample(next, token_ids, cache, index, padding_mask, end_token_id=end_token_id)

@@ -1,5 +1,6 @@
 """keras_nlp.samplers as GemmaCausalLM.compile(sampler=) takes them (the class docstring of nlp/gemma/gemma_causal.py in the reference): the decoding
-loop of Sampler.__call__, the greedy, random, top-k and top-p rules for the next token, and beam search.  Defaults are keras_nlp's.
+loop of Sampler.__call__, the greedy, random, top-k and top-p rules for the next token, beam search and contrastive search.  Defaults are
+keras_nlp's.
 
     sampler = TopKSampler(k=5, seed=7)
     model.compile(sampler=sampler)
@@ -30,7 +31,29 @@ Where the reference leaves the result open it is pinned down (include/iseg_hip.h
   non-finite a -inf logit scores -inf; a NaN or +inf logit makes its row's scores NaN; NaN ranks above every number, as in torch.topk;
              0 <= parent < nb and 0 <= token < V always.
 
-Out of scope: ContrastiveSampler, the string aliases ("top_k", ...) of keras_nlp.samplers.get."""
+ContrastiveSampler(k=5, alpha=0.5, temperature=1.0) restates keras_nlp's ContrastiveSampler.__call__ (contrastive search: the token that is
+probable AND whose hidden state is unlike every earlier one, which is what stops the repetition loops of greedy and beam search).  It is the
+one sampler that reads hidden states: it is called with hidden_states=[B, S, D], the final-norm output of every prompt position, and uses
+the second result of next().  One call of next on the B rows gives the first logits; then the cache is repeated k times ONCE (row b k + j is
+candidate j of batch row b) and every step
+  takes the k most probable tokens of softmax(logits / temperature) as candidates (F.contrastive_candidates; a user token at `index` replaces
+  all k), writes them at `index` of the B k rows and calls next at index + 1 on them: the candidates' logits, hidden states and cache rows;
+  scores candidate j with (1 - alpha) p_j - alpha max_t cos(hidden_states[b, t], its hidden state), t < index, and picks the first maximal
+  score (F.contrastive_select);
+  makes the winner's token, hidden state and cache position the group's (F.contrastive_commit) and reads the winner's row of the candidates'
+  logits as the next step's logits (the row map of F.contrastive_candidates).
+The loop stops as sample_loop does.  On device tensors the three halves are kernels of csrc/contrastive.hip: no [B, V] probability tensor, no
+[B k, index] similarity matrix, and after the first repeat only ONE cache position per step moves, where the reference copies the whole cache
+k times and gathers it back every step.  The price is that k caches stay resident for the whole loop; the reference holds the same amount
+transiently in every step.  CPU tensors, unsupported shapes and ISEG_CONTRASTIVE_FUSED=0 take the composed route, the reference's op sequence
+in torch.  Pinned down beyond the reference (include/iseg_hip.h has the full statement):
+  candidates probability descending, ties by token id ascending (the reference's top_k(sorted=False) has no order);
+  winner     the first maximal score in that order; NaN ranks above every number, as in torch.argmax;
+  precision  probabilities and scores are fp32 (the reference rounds the probabilities to the logits' dtype); dot products and norms
+             accumulate in fp32; no epsilon: a zero hidden state gives NaN, as in the reference;
+  range      0 <= token < V and 0 <= winner < k always.
+
+Out of scope: the string aliases ("top_k", ...) of keras_nlp.samplers.get."""
 import math
 
 import torch
@@ -245,3 +268,72 @@ class BeamSampler(Sampler):
 
     def get_config(self):
         return {**super().get_config(), "num_beams": self.num_beams, "return_all_beams": self.return_all_beams}
+
+
+class ContrastiveSampler(Sampler):
+    """contrastive search: per step the k most probable tokens are candidates, and the one with the largest
+    (1 - alpha) probability - alpha (largest cosine similarity of its hidden state to an earlier position's) becomes the token.  k is an integer
+    in 1 .. 16 (k = 1 is greedy search), 0 <= alpha <= 1 (alpha = 0 is greedy search on logits without ties).  k caches stay resident for the
+    whole loop (the reference holds as much transiently in every step).  The module docstring has the algorithm, the two routes and what is
+    pinned down beyond the reference."""
+
+    def __init__(self, k=5, alpha=0.5, temperature=1.0):
+        super().__init__(temperature)
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= F.CONTRASTIVE_MAX_K:
+            raise ValueError(f"ContrastiveSampler: k is an integer in 1 .. {F.CONTRASTIVE_MAX_K}, got {k!r}")
+        if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not 0.0 <= float(alpha) <= 1.0:
+            raise ValueError(f"ContrastiveSampler: 0 <= alpha <= 1, got {alpha!r}")
+        self.k, self.alpha = k, float(alpha)
+
+    def __call__(self, next, prompt, cache=None, index=0, mask=None, end_token_id=None, hidden_states=None):
+        """next(prompt [rows, S], cache, index) -> (logits [rows, V], hidden states [rows, D], cache) for the token at index - 1, as sample_loop
+        calls it, on B or B k rows.  hidden_states [B, S, D]: the hidden states of the prompt's positions (those below `index` are read).
+        cache: None or a tensor whose axis 0 is the batch, in call_with_cache's convention [B, L, 2, S, nkv, h] with step `index` writing
+        position index - 1.  The caller's prompt, cache and hidden_states are never written."""
+        k = self.k
+        if hidden_states is None:
+            raise ValueError("ContrastiveSampler: contrastive search compares hidden states; pass hidden_states=[B, S, D], the hidden state of "
+                             "every prompt position (GemmaCausalLM.generate_step does)")
+        if prompt.dim() != 2:
+            raise ValueError(f"ContrastiveSampler: prompt is [B, S], got {tuple(prompt.shape)}")
+        B, S = prompt.shape
+        if hidden_states.dim() != 3 or hidden_states.shape[0] != B or hidden_states.shape[1] < S:
+            raise ValueError(f"ContrastiveSampler: hidden_states is [{B}, {S}, D], got {tuple(hidden_states.shape)}")
+        if mask is None:
+            mask = torch.zeros_like(prompt, dtype=torch.bool)
+        if cache is not None and not torch.is_tensor(cache):
+            raise ValueError(f"ContrastiveSampler: the cache is a tensor with the batch on axis 0 or None, got {type(cache).__name__}")
+        mask = mask.to(torch.bool)
+        index = int(index)
+        if index >= S:
+            return prompt.clone()
+        if index < 1:
+            raise ValueError("ContrastiveSampler: the first step needs a previous position (index >= 1)")
+        history = hidden_states.detach().clone()
+        # the one step on B rows, on a copy of the cache; then k rows to a row, once
+        logits, _, cache = next(prompt, None if cache is None else cache.clone(), index)
+        prompt = torch.repeat_interleave(prompt, k, dim=0)
+        if cache is not None:
+            cache = torch.repeat_interleave(cache, k, dim=0)
+        row_map = None
+        while index < S:
+            if end_token_id is not None:
+                done = ((prompt[::k] == end_token_id) & ~mask).any(dim=-1)
+                if bool(done.all()):
+                    break
+            probs, tokens = F.contrastive_candidates(logits, k, self.temperature, row_map)
+            user = mask[:, index, None]
+            tokens = torch.where(user, prompt[::k, index, None], tokens.to(prompt.dtype))
+            prompt[:, index] = tokens.reshape(-1)
+            next_logits, cand_hidden, cache = next(prompt, cache, index + 1)
+            winner, _, _ = F.contrastive_select(history, index, cand_hidden, probs.reshape(-1), self.alpha)
+            cache, prompt, history = F.contrastive_commit(cache, prompt, history, cand_hidden, winner, index, k)
+            logits, row_map = next_logits, winner
+            index += 1
+        return prompt[::k].clone()
+
+    def get_next_token(self, logits):
+        raise NotImplementedError("ContrastiveSampler.get_next_token: a contrastive step reads the candidates' hidden states; call the sampler")
+
+    def get_config(self):
+        return {**super().get_config(), "k": self.k, "alpha": self.alpha}
